@@ -11,8 +11,10 @@ exist); inputs resident in HBM before the timed region.  N > 1: one process per 
 (`python bench.py --gpus 8` re-executes itself under torch.distributed.run with a free rendezvous port);
 utterances sharded (8 per rank, weak scaling), weights broadcast once over RCCL, no data-path collective.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
-Rank 0 prints ONE JSON line (see DESIGN.md section "Measurement" for every field).
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+Rank 0 prints ONE JSON line (see DESIGN.md section "Measurement" for every field).  A plain run sets up, warms up, times the K
+steps and prints the headline (`value`, `ms_per_step`, ...); `--full` adds everything else the line can carry: the roofline,
+kernel-class, power and clock figures of the timed region, fp32_exact, c1, c2, c5 and cpu_baseline.
 """
 import argparse
 import json
@@ -448,22 +450,40 @@ def fp32_exact(dev, rank, world, steps: int = 2):
             "dtype": "f32 (v_mfma_f32_32x32x2_f32 GEMM / attention / vocoder)", **pw}
 
 
+def dump_outputs(path, outs, rank):
+    """--dump-outputs: what the timed path handed its caller in the LAST timed step, every batch of that step in order - the mel of
+    the 32-NFE solve [8 n, T, 80] as mel.npy and the int16 PCM [8 n, 160 T + 32] (as float32: exact) as pcm.npy, n = batches per
+    step; rank r > 0 writes mel_rank<r>.npy / pcm_rank<r>.npy.  7.7 MB per batch of 8: at most 61 MB over all ranks (8 batches)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    sfx = f"_rank{rank}" if rank else ""
+    np.save(os.path.join(path, f"mel{sfx}.npy"), torch.cat([m for m, _ in outs]).float().cpu().numpy())
+    np.save(os.path.join(path, f"pcm{sfx}.npy"), torch.cat([p for _, p in outs]).float().cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=3)
-    ap.add_argument("--warmup", type=int, default=1)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-fp32-exact", action="store_true")
-    ap.add_argument("--no-c2", action="store_true", help="skip the BASELINE config-2 figure (extra key `c2`, N = 1 only)")
-    ap.add_argument("--no-c1", action="store_true", help="skip the BASELINE config-1 figure (extra key `c1`, N = 1 only)")
-    ap.add_argument("--no-c5", action="store_true", help="skip the BASELINE config-5 figure (extra key `c5`, N = 1 only)")
+    ap.add_argument("--steps", type=int, default=3, help="timed steps")
+    ap.add_argument("--warmup", type=int, default=1, help="untimed steps before them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the mel and PCM of the last timed step as DIR/mel.npy, DIR/pcm.npy (float32)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the figures beyond the headline: roofline / kernel classes / power / clocks of the timed region, "
+                         "fp32_exact, c1, c2, c5, cpu_baseline (each N = 1 only and each switched off by its --no-* option)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip `cpu_baseline`")
+    ap.add_argument("--no-fp32-exact", action="store_true", help="with --full: skip `fp32_exact`")
+    ap.add_argument("--no-c2", action="store_true", help="with --full: skip the BASELINE config-2 figure (extra key `c2`, N = 1 only)")
+    ap.add_argument("--no-c1", action="store_true", help="with --full: skip the BASELINE config-1 figure (extra key `c1`, N = 1 only)")
+    ap.add_argument("--no-c5", action="store_true", help="with --full: skip the BASELINE config-5 figure (extra key `c5`, N = 1 only)")
     ap.add_argument("--scaling", choices=["weak", "strong"], default="weak",
                     help="weak (default): 8 utterances per GPU per step.  strong: BASELINE config 4 literally - 64 utterances per step "
                          "dealt over the N ranks (N must divide 8), i.e. 64/N per GPU in batches of 8")
     ap.add_argument("--precision", choices=["f16x3", "f16", "fp32"], default=None,
                     help="default f16x3 (fp32-class); f16 = opt-in single-term fp16 operands (<= 1e-3 rel-L2 budget)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     from covomix_amd import dp, ops
     import covomix_amd.synthetic as syn
@@ -499,12 +519,15 @@ def main():
     def one_batch():
         y0 = torch.randn(B, T, 80, device=dev, generator=noise)
         mel = model.synthesis_sample(ids, cond, mask, COND_SCALE, y0=y0)
+        if not args.full:
+            wav = gen(mel.permute(0, 2, 1).contiguous())
+            return mel, ops.wav_to_int16(wav.squeeze(1).contiguous())
         ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
         ev[0].record()
         wav = gen(mel.permute(0, 2, 1).contiguous())
         ev[1].record()
         voc_events.append(ev)
-        return ops.wav_to_int16(wav.squeeze(1).contiguous())
+        return mel, ops.wav_to_int16(wav.squeeze(1).contiguous())
 
     strong = args.scaling == "strong"
     if strong and (64 // B) % world != 0:
@@ -512,9 +535,7 @@ def main():
     batches_per_step = (64 // B) // world if strong else 1
 
     def step():
-        for _ in range(batches_per_step):
-            pcm_ = one_batch()
-        return pcm_
+        return [one_batch() for _ in range(batches_per_step)]          # (mel, pcm) of every batch of the step
 
     def barrier():
         torch.cuda.synchronize()
@@ -524,34 +545,40 @@ def main():
 
     for _ in range(args.warmup):
         step()
-    timer = GemmTimer(split=(model.precision in ("f16x3", "f16")), every=int(os.environ.get("CVX_BENCH_TIMER_EVERY", "7")))
-    timer.install(ops)
-    every = int(os.environ.get("CVX_BENCH_TIMER_EVERY", "7"))
-    classes = {"attention": ClassTimer(ops, "attention_f16x3" if model.precision != "fp32" else "attention", every),
-               "adarmsnorm": ClassTimer(ops, "adarmsnorm", every)}
-    voc_events.clear()
-    power = PowerSampler(device_index=local) if rank == 0 else None
-    if power:
-        power.start()
+    timer, classes, power = None, {}, None
+    if args.full:                                        # event brackets, power sampler and clock stamps: the --full figures only
+        timer = GemmTimer(split=(model.precision in ("f16x3", "f16")), every=int(os.environ.get("CVX_BENCH_TIMER_EVERY", "7")))
+        timer.install(ops)
+        every = int(os.environ.get("CVX_BENCH_TIMER_EVERY", "7"))
+        classes = {"attention": ClassTimer(ops, "attention_f16x3" if model.precision != "fp32" else "attention", every),
+                   "adarmsnorm": ClassTimer(ops, "adarmsnorm", every)}
+        voc_events.clear()
+        power = PowerSampler(device_index=local) if rank == 0 else None
+        if power:
+            power.start()
     barrier()
-    clk0 = ops.clock_stamps()
+    clk0 = ops.clock_stamps() if args.full else None
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     cpu0 = time.process_time()                           # CPU seconds of this process, all its threads
     for _ in range(args.steps):
-        pcm = step()
+        outs = step()
     barrier()
     t1 = time.perf_counter()
-    clk1 = ops.clock_stamps()
+    clk1 = ops.clock_stamps() if args.full else None
     torch.cuda.synchronize()
     host_cpu = time.process_time() - cpu0
     elapsed = t1 - t0
-    timer.remove()
+    if timer:
+        timer.remove()
     for c in classes.values():
         c.remove()
     power_info = power.stop(t0, t1) if power else {}
     my_elapsed = elapsed
+    pcm = outs[-1][1]
     assert pcm.shape == (B, 160 * T + 32) and pcm.dtype == torch.int16
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, outs, rank)
     frames, elapsed = dp.reduce_metric(float(B * T * args.steps * batches_per_step), elapsed, dev)
     per_rank = [my_elapsed]
     loads = [t_load]
@@ -564,24 +591,6 @@ def main():
 
     if rank == 0:
         value = frames / elapsed
-        flops, gemm_s, launches, all_launches = timer.result()
-        achieved = flops / gemm_s / 1e12
-        split = model.precision in ("f16x3", "f16")
-        terms = {"f16x3": 3, "f16": 1, "fp32": 1}[model.precision]
-        p8 = model.precision == "f16x3" and ops._GEMM_FLAGS == 0
-        kname = ("gemm_f16x3_p8s_kernel" if p8 else "gemm_f16x3_dma_kernel") if split else "gemm_f32_glds_kernel"
-        mfma = "v_mfma_f32_16x16x32_f16" if p8 else "v_mfma_f32_32x32x16_f16"
-        peak = PEAK_F16_MFMA if split else PEAK_F32_MFMA
-        traffic = None
-        traffic_source = None
-        pmc = os.path.join(ROOT, "profiles", "pmc_summary.json")
-        if os.path.isfile(pmc) and model.precision == "f16x3":      # the committed PMC passes profile the default precision
-            try:
-                traffic = json.load(open(pmc)).get(kname, {}).get("hbm_bytes_per_launch")
-                # NOT measured by this run: PMC counters need their own rocprofv3 --pmc passes (tools/archive/collect_profiles.sh)
-                traffic_source = "profiles/pmc_summary.json (committed rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command, not this run)"
-            except Exception:
-                traffic = None
         out = {
             "metric": "mel-frames/sec (VoMix 32-step + HiFi-GAN, Bx1000x80)",
             "value": round(value, 2), "unit": "mel-frames/s", "n_gpus": world, "steps": args.steps,
@@ -597,23 +606,42 @@ def main():
                        "utterances_per_step": B * batches_per_step * world},
             "path_flop_per_frame": FLOP_PER_FRAME,
             "path_frac_of_f32_mfma_peak": round(value / world * FLOP_PER_FRAME / PEAK_F32_MFMA, 4),
+        }
+        if args.full:
+            flops, gemm_s, launches, all_launches = timer.result()
+            achieved = flops / gemm_s / 1e12
+            split = model.precision in ("f16x3", "f16")
+            terms = {"f16x3": 3, "f16": 1, "fp32": 1}[model.precision]
+            p8 = model.precision == "f16x3" and ops._GEMM_FLAGS == 0
+            kname = ("gemm_f16x3_p8s_kernel" if p8 else "gemm_f16x3_dma_kernel") if split else "gemm_f32_glds_kernel"
+            mfma = "v_mfma_f32_16x16x32_f16" if p8 else "v_mfma_f32_32x32x16_f16"
+            peak = PEAK_F16_MFMA if split else PEAK_F32_MFMA
+            traffic = None
+            traffic_source = None
+            pmc = os.path.join(ROOT, "profiles", "pmc_summary.json")
+            if os.path.isfile(pmc) and model.precision == "f16x3":      # the committed PMC passes profile the default precision
+                try:
+                    traffic = json.load(open(pmc)).get(kname, {}).get("hbm_bytes_per_launch")
+                    # NOT measured by this run: PMC counters need their own rocprofv3 --pmc passes (tools/archive/collect_profiles.sh)
+                    traffic_source = "profiles/pmc_summary.json (committed rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command, not this run)"
+                except Exception:
+                    traffic = None
             # dominant kernel.  achieved = ALGORITHMIC flops (2*M*N*K per launch) / HIP-event time of the launches;
             # the split kernel executes 3 MFMA products per algorithmic product, so its matrix-pipe work is 3x that.
-            "roofline": {"bound": "mfma",
-                         "kernel": kname + ((" (%s x%d)" % (mfma, terms)) if split else " (v_mfma_f32_32x32x2_f32)"),
-                         "achieved": round(achieved, 2), "peak": peak / 1e12, "unit": "TFLOP/s",
-                         "frac": round(achieved / (peak / 1e12), 4), "traffic": traffic, "traffic_source": traffic_source,
-                         "executed_mfma_frac": round(achieved * terms / (peak / 1e12), 4),
-                         "vs_f32_mfma_peak": round(achieved / (PEAK_F32_MFMA / 1e12), 4),
-                         "launches": all_launches, "timed_launches": launches,
-                         "avg_launch_ms": round(gemm_s / launches * 1e3, 4),
-                         "time_share_of_step": round(gemm_s / launches * all_launches / elapsed, 4),
-                         "ms_per_step": round(gemm_s / launches * all_launches / args.steps * 1e3, 3)},
-        }
-        out["roofline"].update(power_info)          # power_w, sclk_mhz, power_cap_w of the timed region (rank 0's GPU)
-        out["roofline"].update(effective_clock(clk0, clk1))
-        # host budget: a rank drives ~10k launches/s from Python; `busy_cores` = CPU seconds of the process (all threads, the power
-        # sampler included) per second of the timed region.  A rank whose share of the cgroup quota is below what it needs is
+            out["roofline"] = {"bound": "mfma",
+                               "kernel": kname + ((" (%s x%d)" % (mfma, terms)) if split else " (v_mfma_f32_32x32x2_f32)"),
+                               "achieved": round(achieved, 2), "peak": peak / 1e12, "unit": "TFLOP/s",
+                               "frac": round(achieved / (peak / 1e12), 4), "traffic": traffic, "traffic_source": traffic_source,
+                               "executed_mfma_frac": round(achieved * terms / (peak / 1e12), 4),
+                               "vs_f32_mfma_peak": round(achieved / (PEAK_F32_MFMA / 1e12), 4),
+                               "launches": all_launches, "timed_launches": launches,
+                               "avg_launch_ms": round(gemm_s / launches * 1e3, 4),
+                               "time_share_of_step": round(gemm_s / launches * all_launches / elapsed, 4),
+                               "ms_per_step": round(gemm_s / launches * all_launches / args.steps * 1e3, 3)}
+            out["roofline"].update(power_info)          # power_w, sclk_mhz, power_cap_w of the timed region (rank 0's GPU)
+            out["roofline"].update(effective_clock(clk0, clk1))
+        # host budget: a rank drives ~10k launches/s from Python; `busy_cores` = CPU seconds of the process (all threads, with --full
+        # the power sampler included) per second of the timed region.  A rank whose share of the cgroup quota is below what it needs is
         # host-bound however fast the GPU is - the first thing to rule out when an N > 1 line comes in low.
         busy = [c / max(e, 1e-9) for c, e in zip(cpus, per_rank)]
         need = max(1.5, -(-busy[0] // 0.5) * 0.5)     # cores a rank needs: what rank 0 used here (launching thread + event brackets + sampler), rounded up
@@ -621,31 +649,33 @@ def main():
         out["host"] = {"cpu_s_per_step": round(host_cpu / args.steps, 4), "busy_cores": [round(b, 3) for b in busy],
                        "cores_needed_per_rank": need, "host_cores_quota": host_cores(), "host_threads_per_rank": share,
                        "warning": (f"only {share} host thread(s) per rank for {need} needed: the ranks are host-bound" if share < need else None)}
-        out["kernel_classes_ms_per_step"] = {k: c.result(args.steps) for k, c in classes.items()}
-        voc_ms = sum(a.elapsed_time(b) for a, b in voc_events) / max(len(voc_events), 1)
-        out["kernel_classes_ms_per_step"]["vocoder"] = {"launches_per_step": 1, "timed": len(voc_events), "avg_launch_ms": round(voc_ms, 4),
-                                                        "ms_per_step": round(voc_ms, 3), "note": "whole Generator call incl. its saturation-flag read"}
+        if args.full:
+            out["kernel_classes_ms_per_step"] = {k: c.result(args.steps) for k, c in classes.items()}
+            voc_ms = sum(a.elapsed_time(b) for a, b in voc_events) / max(len(voc_events), 1)
+            out["kernel_classes_ms_per_step"]["vocoder"] = {"launches_per_step": 1, "timed": len(voc_events), "avg_launch_ms": round(voc_ms, 4),
+                                                            "ms_per_step": round(voc_ms, 3), "note": "whole Generator call incl. its saturation-flag read"}
         if world > 1:
             out["ranks"] = {"elapsed_s": [round(x, 4) for x in per_rank], "skew_max_over_min": round(max(per_rank) / max(min(per_rank), 1e-9), 4),
                             "load_and_broadcast_s": [round(x, 3) for x in loads]}
             out["ranks"].update({k: v for k, v in dp.INFO.items()})       # transports, RCCL version, IPC mode, a fallback's reason
         model_precision = model.precision
-        if world == 1 and not args.no_fp32_exact and model.precision == "f16x3":
+        extras = args.full and world == 1                # the figures beyond the headline: --full, N = 1 only
+        if extras and not args.no_fp32_exact and model.precision == "f16x3":
             del model, gen
             torch.cuda.empty_cache()
             with contextlib.redirect_stdout(sys.stderr):
                 out["fp32_exact"] = fp32_exact(dev, rank, world)
-        if world == 1 and not args.no_c2 and model_precision == "f16x3":
+        if extras and not args.no_c2 and model_precision == "f16x3":
             with contextlib.redirect_stdout(sys.stderr):
                 out["c2"] = config2(dev)
-        if world == 1 and not args.no_c1 and model_precision == "f16x3":
+        if extras and not args.no_c1 and model_precision == "f16x3":
             with contextlib.redirect_stdout(sys.stderr):
                 out["c1"] = config1(dev)
-        if world == 1 and not args.no_c5 and model_precision == "f16x3":
+        if extras and not args.no_c5 and model_precision == "f16x3":
             torch.cuda.empty_cache()
             with contextlib.redirect_stdout(sys.stderr):
                 out["c5"] = config5(dev)
-        if world == 1 and not args.no_cpu_baseline:
+        if extras and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(cpu_sd)
         sys.stdout.flush()
         os.write(json_fd, (json.dumps(out) + "\n").encode())

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Round-4 profile collection on the GPU box (run through gpurun from the repo root).  Outputs under gpurun_out/prof4/; the summaries
 # judged live under profiles/r04_* (copied by hand after a look).  PMC passes are their own runs with --kernel-trace only.
-#   1. bench.py (default): JSON line with roofline (+ power / sclk), kernel classes, c2, fp32_exact, cpu_baseline
+#   1. bench.py --full: JSON line with roofline (+ power / sclk), kernel classes, c2, fp32_exact, cpu_baseline
 #   2. rocprofv3 --kernel-trace --stats of bench.py (2 timed steps + 1 warm-up = 3 passes) and of tools/bench_c2.py
 #   3. --pmc SQ pass (GRBM_GUI_ACTIVE SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES) of both
 #   4. --pmc FETCH_SIZE / WRITE_SIZE passes of bench.py (separate)
@@ -10,9 +10,9 @@ set -u
 REPO=$(pwd)
 OUT=$REPO/gpurun_out/prof4
 rm -rf $OUT; mkdir -p $OUT
-python bench.py > $OUT/bench_n1.json 2> $OUT/bench_n1.err
+python bench.py --full > $OUT/bench_n1.json 2> $OUT/bench_n1.err
 cd /tmp && export TMPDIR=/tmp
-B="python $REPO/bench.py --no-cpu-baseline --no-fp32-exact --no-c2"
+B="python $REPO/bench.py --full --no-cpu-baseline --no-fp32-exact --no-c2"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- $B --steps 2 --warmup 1 > $OUT/stats.log 2>&1
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/c2_stats -- python $REPO/tools/bench_c2.py > $OUT/c2_stats.log 2>&1
 rocprofv3 --kernel-trace --pmc GRBM_GUI_ACTIVE SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES --output-format csv -d $OUT/pmc_sq -- $B --steps 1 --warmup 1 > $OUT/pmc_sq.log 2>&1

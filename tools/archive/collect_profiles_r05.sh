@@ -1,7 +1,7 @@
 #!/bin/bash
 # Round-5 profile collection on the GPU box (run through gpurun from the repo root).  Outputs under gpurun_out/prof5/; the summaries
 # judged live under profiles/r05_* (copied after a look).  PMC passes are their own runs with --kernel-trace only.
-#   1. bench.py (default): JSON line with roofline (+ power / sclk), kernel classes, c2, c5, fp32_exact, cpu_baseline
+#   1. bench.py --full: JSON line with roofline (+ power / sclk), kernel classes, c2, c5, fp32_exact, cpu_baseline
 #   2. rocprofv3 --kernel-trace --stats of bench.py (2 timed steps + 1 warm-up), of tools/bench_c2.py and of the config-5 pipeline
 #      (tools/bench_pipeline.py: serial / alternate / pipelined schedules in one trace; the overlap of the two stages is in its own
 #      HIP-event device timeline, c5_pipeline.txt - a profiler's trace slows the decode chain and merges the three schedules)
@@ -12,13 +12,13 @@ set -u
 REPO=$(pwd)
 OUT=$REPO/gpurun_out/prof5
 rm -rf $OUT; mkdir -p $OUT
-python bench.py > $OUT/bench_n1.json 2> $OUT/bench_n1.err
+python bench.py --full > $OUT/bench_n1.json 2> $OUT/bench_n1.err
 DIALOGUES=56 python tools/bench_pipeline.py > $OUT/c5_pipeline.txt 2>&1
 PASSES=3 python tools/ragged_dir.py > $OUT/ragged_dir.txt 2>&1
 cd /tmp && export TMPDIR=/tmp
 PASSES=1 rocprofv3 --kernel-trace --output-format csv -d $OUT/ragged -- python $REPO/tools/ragged_dir.py > $OUT/ragged_trace.log 2>&1
 f=$(find $OUT/ragged -name "*kernel_trace.csv" | head -1); [ -n "$f" ] && python $REPO/tools/gap_summary.py $f 12 -$(grep -o "[0-9.]* ms = files" $OUT/ragged_trace.log | head -1 | cut -d" " -f1) > $OUT/ragged_gaps.txt 2>&1
-B="python $REPO/bench.py --no-cpu-baseline --no-fp32-exact --no-c2 --no-c5"
+B="python $REPO/bench.py --full --no-cpu-baseline --no-fp32-exact --no-c2 --no-c5"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- $B --steps 2 --warmup 1 > $OUT/stats.log 2>&1
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/c2_stats -- python $REPO/tools/bench_c2.py > $OUT/c2_stats.log 2>&1
 DIALOGUES=28 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/c5_stats -- python $REPO/tools/bench_pipeline.py > $OUT/c5_stats.log 2>&1

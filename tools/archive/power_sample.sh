@@ -4,7 +4,7 @@
 OUT=gpurun_out/power_sample.log
 mkdir -p gpurun_out
 : > $OUT
-python bench.py --steps 12 --warmup 2 --no-cpu-baseline --no-fp32-exact > gpurun_out/power_bench.json 2> gpurun_out/power_bench.err &
+python bench.py --full --steps 12 --warmup 2 --no-cpu-baseline --no-fp32-exact > ${OUT%/*}/power_bench.json 2> ${OUT%/*}/power_bench.err &
 BP=$!
 i=0
 while kill -0 $BP 2>/dev/null; do

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Round-6 profile collection on the GPU box (run through gpurun from the repo root).  Outputs under gpurun_out/prof6/; the summaries
 # judged live under profiles/r06_* (copied after a look).  PMC passes are their own runs with --kernel-trace only.
-#   1. bench.py (default): JSON line with roofline (+ power / sclk), kernel classes, c1, c2, c5 (best schedule, ragged_eos), fp32_exact,
+#   1. bench.py --full: JSON line with roofline (+ power / sclk), kernel classes, c1, c2, c5 (best schedule, ragged_eos), fp32_exact,
 #      host, cpu_baseline
 #   2. config 5 under every schedule (tools/bench_pipeline.py, 56 dialogues), the text2semantic decode at 1 ... 64 slots and its
 #      continuous batching (tools/bench_t2s.py), the ragged test directory
@@ -12,12 +12,12 @@ set -u
 REPO=$(pwd)
 OUT=$REPO/gpurun_out/prof6
 rm -rf $OUT; mkdir -p $OUT
-python bench.py > $OUT/bench_n1.json 2> $OUT/bench_n1.err
+python bench.py --full > $OUT/bench_n1.json 2> $OUT/bench_n1.err
 DIALOGUES=56 python tools/bench_pipeline.py > $OUT/c5_schedules.txt 2>&1
 BATCHES=1,8,16,32,64 python tools/bench_t2s.py comix > $OUT/t2s_decode.txt 2>&1
 PASSES=3 python tools/ragged_dir.py > $OUT/ragged_dir.txt 2>&1
 cd /tmp && export TMPDIR=/tmp
-B="python $REPO/bench.py --no-cpu-baseline --no-fp32-exact --no-c1 --no-c2 --no-c5"
+B="python $REPO/bench.py --full --no-cpu-baseline --no-fp32-exact --no-c1 --no-c2 --no-c5"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- $B --steps 2 --warmup 1 > $OUT/stats.log 2>&1
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/c2_stats -- python $REPO/tools/bench_c2.py > $OUT/c2_stats.log 2>&1
 for nb in 8 64; do
