@@ -140,7 +140,9 @@ class TextToSemanticDecoder:
     def _ensure(self, slots: int, dialogues: int, steps: int) -> None:
         """Decode buffers for `slots` decode slots (x, q, att, h, logits, slot records, the self-attention caches), `dialogues`
         utterances in flight or queued (context k/v, token rows, dialogue records) and `steps` uniform draws per dialogue.  They only
-        grow; growing re-allocates (and drops the captured graphs, which hold the old addresses)."""
+        grow; growing re-allocates (and drops the captured graphs, which hold the old addresses).  The uniform draws per dialogue
+        are rounded up to whole chunks of CHUNK steps: a lock-step decode (_decode_chunks) runs whole chunks, and its sampling kernel
+        reads the draws of every position it reaches (up to the model's max_length, whatever the call's max_length)."""
         d, dev = self.d, self.device
         S, V, I = d["streams"], d["vocab"], d["inner"]
         f32 = lambda *s: torch.zeros(*s, dtype=torch.float32, device=dev)
@@ -162,8 +164,9 @@ class TextToSemanticDecoder:
                             dialogues=torch.zeros(dialogues, SR, dtype=torch.int32, device=dev),
                             queue=torch.zeros(2, dtype=torch.int32, device=dev))
             self._dialogues, grown = dialogues, True
+        steps = (max(steps, 1) + CHUNK - 1) // CHUNK * CHUNK
         if steps > self._steps or "uniforms" not in self.buf or self.buf["uniforms"].numel() < self._dialogues * self._steps * S * V:
-            self._steps = max(self._steps, steps, 1)
+            self._steps = max(self._steps, steps)
             self.buf["uniforms"] = f32(self._dialogues * self._steps * S * V)
             grown = True
         if grown:
@@ -400,7 +403,8 @@ class TextToSemanticDecoder:
             if S != 1:
                 raise NotImplementedError("guidance (cond_scale > 1) on a two-output model: the reference feeds the full-width hidden "
                                           "state to the half-width logit head there (text2semantic.py:783-785) and cannot run")
-            return self._generate_guided(sources, uniforms, max_length, temperature, generator, collect_logits, float(cond_scale))
+            return self._generate_guided(sources, uniforms, max_length, temperature, generator, collect_logits, float(cond_scale),
+                                         ignore_eos)
         nb = len(sources)
         if not 1 <= nb <= MAX_BATCH:
             raise ValueError(f"1..{MAX_BATCH} utterances per decode batch, got {nb}")
@@ -439,7 +443,7 @@ class TextToSemanticDecoder:
             out.append(self._cut(i, length, torch.stack([lg[i] for lg in logits]) if collect_logits and logits else None))
         return out
 
-    def _generate_guided(self, sources, uniforms, max_length, temperature, generator, collect_logits, cond_scale):
+    def _generate_guided(self, sources, uniforms, max_length, temperature, generator, collect_logits, cond_scale, ignore_eos=False):
         """generate_batch with cond_scale > 1: slots 2u (text context) / 2u + 1 (null context) per utterance u."""
         V, nu = self.d["vocab"], len(sources)
         nb = 2 * nu
@@ -475,14 +479,14 @@ class TextToSemanticDecoder:
                 lg = b["logits"][:nb].clone()
                 logits.append(lg[1::2] + (lg[0::2] - lg[1::2]) * cond_scale)
                 st = self._read_state(nb)
-                if all(st[2 * u_][1] for u_ in range(nu)):
+                if all(st[2 * u_][1] for u_ in range(nu)) and not ignore_eos:
                     break
         elif max_len > 0:
-            st = self._decode_chunks(float(temperature), nb, max_len, cond_scale, [2 * u_ for u_ in range(nu)])
+            st = self._decode_chunks(float(temperature), nb, max_len, cond_scale, [2 * u_ for u_ in range(nu)], ignore_eos)
         out = []
         for u_ in range(nu):
             i = 2 * u_
-            length = min(st[i][2] if st[i][1] and st[i][2] <= max_len else max_len, max_len)
+            length = min(st[i][2] if st[i][1] and st[i][2] <= max_len and not ignore_eos else max_len, max_len)
             out.append(self._cut(i, length, torch.stack([lg[u_] for lg in logits]) if collect_logits and logits else None))
         return out
 

@@ -27,6 +27,7 @@ import torch
 import torch.nn.functional as F
 
 SD = Dict[str, torch.Tensor]
+QBLOCK = 1024                  # query rows per attention block
 
 
 def t2s_dims(sd: SD) -> dict:
@@ -46,16 +47,19 @@ def rmsnorm(x, gamma):
 
 
 def rotate_interleaved(t, positions, freqs):
-    """t [..., n, 64]; positions [n] float; pairs (2i, 2i+1) rotate by positions * freqs[i]."""
-    ang = positions[:, None] * freqs[None, :]
-    ang = ang.repeat_interleave(2, dim=-1)
+    """t [..., n, 64]; positions [n] float; pairs (2i, 2i+1) rotate by positions * freqs[i].  The angle is formed in fp32 as the
+    reference forms it (fp32 positions times the fp32 freqs buffer); cos / sin and the rotation run in t's dtype."""
+    ang = positions.float()[:, None] * freqs.float()[None, :]
+    ang = ang.to(t.dtype).repeat_interleave(2, dim=-1)
     x = t.reshape(*t.shape[:-1], -1, 2)
     rot = torch.stack((-x[..., 1], x[..., 0]), dim=-1).reshape(t.shape)
     return t * ang.cos() + rot * ang.sin()
 
 
-def attention(sd: SD, p: str, x, heads: int, freqs=None, context=None, mask=None, causal=False, cache=None):
-    """One Attention.forward.  Returns (out, new_cache) with new_cache = (k, v) UN-rotated, [B, H, n, 64]."""
+def attention(sd: SD, p: str, x, heads: int, freqs=None, context=None, mask=None, causal=False, cache=None, stats=None):
+    """One Attention.forward.  Returns (out, new_cache) with new_cache = (k, v) UN-rotated, [B, H, n, 64].
+    Queries run in blocks of QBLOCK rows (row-wise softmax: the same result, bounded memory for long teacher-forced passes).
+    stats: optional list; gets the mean over query rows of the largest softmax probability (how peaked the attention is)."""
     B = x.shape[0]
     xn = rmsnorm(x, sd[p + ".norm.gamma"])
     ctx = xn if context is None else context
@@ -77,17 +81,21 @@ def attention(sd: SD, p: str, x, heads: int, freqs=None, context=None, mask=None
         v = torch.cat((nv[None].expand(B, -1, -1, -1), v), dim=-2)
         if mask is not None:
             mask = F.pad(mask, (1, 0), value=True)
-    sim = (q @ k.transpose(-1, -2)) * (64 ** -0.5)
-    neg = -torch.finfo(sim.dtype).max
-    if mask is not None:
-        sim = sim.masked_fill(~mask[:, None, None, :], neg)
-    if causal:
-        i, j = sim.shape[-2:]
-        n = max(i, j)
-        cm = torch.ones((n, n), dtype=torch.bool).triu(1)[-i:, :]
-        sim = sim.masked_fill(cm, neg)
-    out = sim.softmax(dim=-1) @ v
-    out = out.transpose(1, 2).reshape(B, -1, heads * 64)
+    neg = -torch.finfo(q.dtype).max
+    i, j = q.shape[-2], k.shape[-2]
+    outs = []
+    for r0 in range(0, i, QBLOCK):
+        sim = (q[..., r0:r0 + QBLOCK, :] @ k.transpose(-1, -2)) * (64 ** -0.5)
+        if mask is not None:
+            sim = sim.masked_fill(~mask[:, None, None, :], neg)
+        if causal:                      # query row r (of i) sees keys 0 .. j - i + r
+            rows = torch.arange(r0, r0 + sim.shape[-2])[:, None]
+            sim = sim.masked_fill(torch.arange(j)[None, :] > rows + (j - i), neg)
+        prob = sim.softmax(dim=-1)
+        if stats is not None:
+            stats.append(float(prob.amax(dim=-1).mean()))
+        outs.append(prob @ v)
+    out = torch.cat(outs, dim=-2).transpose(1, 2).reshape(B, -1, heads * 64)
     return out @ sd[p + ".to_out.weight"].T, new_cache
 
 
@@ -98,7 +106,7 @@ def feedforward(sd: SD, p: str, x):
 
 
 def transformer(sd: SD, pre: str, x, d: dict, depth: int, mask=None, context=None, context_mask=None, causal=False,
-                cache: Optional[List] = None):
+                cache: Optional[List] = None, stats=None):
     """Transformer.forward with return_cache semantics: x holds ALL positions; with a cache only the new ones run."""
     freqs = sd[pre + ".layers.0.0.rotary_emb.freqs"]
     if cache is not None:
@@ -107,11 +115,11 @@ def transformer(sd: SD, pre: str, x, d: dict, depth: int, mask=None, context=Non
     for i in range(depth):
         p = f"{pre}.layers.{i}"
         a, kv = attention(sd, p + ".0", x, d["heads"], freqs=freqs, mask=mask, causal=causal,
-                          cache=None if cache is None else cache[i])
+                          cache=None if cache is None else cache[i], stats=stats)
         x = a + x
         new_cache.append(kv)
         if context is not None:
-            c, _ = attention(sd, p + ".1", x, d["heads"], context=context, mask=context_mask)
+            c, _ = attention(sd, p + ".1", x, d["heads"], context=context, mask=context_mask, stats=stats)
             x = c + x
         x = feedforward(sd, p + ".2", x) + x
     return rmsnorm(x, sd[pre + ".final_norm.gamma"]), new_cache
@@ -205,3 +213,75 @@ def generate(sd: SD, source_ids: torch.Tensor, uniforms: torch.Tensor, max_lengt
         targets = [mask_after_eos(tt, d["eos_id"], -1) for tt in targets]
     flat = torch.cat(targets, dim=1)
     return dict(tokens=flat[flat != -1], streams=raw, logits=torch.stack(all_logits))
+
+
+# ---------------------------------------------------------------- long-decode checks (tests/test_t2s_long_gpu.py)
+DELTA = 1e-3                   # reference_choice: a step is decidable when no fp32-sized change of the logits can flip it
+LONG_LOGIT_TOL = 1.5e-5        # per-position rel-L2 bound of the long GPU checks: 10x the largest one measured (1.4e-6, tests/test_t2s_long_gpu.py)
+
+
+def teacher_forced_logits(sd: SD, source_ids: torch.Tensor, streams: torch.Tensor, cond_scale: float = 1.0,
+                          dtype=torch.float64, self_mask: Optional[torch.Tensor] = None,
+                          context_mask: Optional[torch.Tensor] = None, stats: Optional[list] = None) -> torch.Tensor:
+    """The decode's pre-filter logits [L, S, V] for the given tokens, from ONE causal full-sequence pass of the target
+    transformer over [start, E[tokens[:-1]]] (what `generate(forced=...)` computes step by step), in `dtype`.
+    source_ids [n] / [1, n]; streams [S, L] (the decoded tokens, stream-major).  cond_scale > 1: the null-context pass as well,
+    and the COMBINED logits null + (cond - null) * cond_scale.  The rotary angles stay fp32 products (rotate_interleaved).
+    self_mask [L] / context_mask [n + 1] (sensitivity checks only): keys kept by every self- / cross-attention row (default:
+    all; context_mask replaces the text mask, the learned null key is always kept).  stats: see `attention`."""
+    sd = {k: v.to(dtype) if v.is_floating_point() else v for k, v in sd.items()}
+    d = t2s_dims(sd)
+    src = source_ids.reshape(1, -1).long()
+    streams = streams.reshape(-1, streams.shape[-1]).long().cpu()
+    S, L = streams.shape
+    assert S == (2 if d["two_output"] else 1)
+    assert cond_scale >= 1.0 and (cond_scale == 1.0 or S == 1), "guidance: one-output models only"
+    enc, smask = encode(sd, src)
+    if context_mask is not None:
+        smask = context_mask.reshape(1, -1).bool()
+    E = sd["semantic_token_emb.weight"]
+    x = torch.cat([E[streams[s, :-1]] for s in range(S)], dim=-1)
+    x = torch.cat((sd["start_token.speech"][None, :], x), dim=0)[None]
+    sm = None if self_mask is None else self_mask.reshape(1, -1).bool()
+    run = lambda cm: transformer(sd, "target_transformer", x, d, d["target_depth"], mask=sm, context=enc, context_mask=cm,
+                                 causal=True, stats=stats)[0][0]
+    att = run(smask)
+    half = att.shape[-1] // S
+    logits = torch.stack([att[:, s * half:(s + 1) * half] @ E.T for s in range(S)], dim=1)      # [L, S, V]
+    if cond_scale > 1.0:
+        null = (run(torch.zeros_like(smask)) @ E.T)[:, None, :]
+        logits = null + (logits - null) * cond_scale
+    return logits
+
+
+def per_position_rel_l2(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+    """[L] rel-L2 of a against b at every position (the rest of the dimensions flattened)"""
+    a, b = a.double().cpu().reshape(a.shape[0], -1), b.double().cpu().reshape(b.shape[0], -1)
+    return (a - b).norm(dim=-1) / b.norm(dim=-1).clamp_min(1e-30)
+
+
+def reference_choice(logits: torch.Tensor, uniforms: torch.Tensor, temperature: float = 1.0, top_k: Optional[int] = None,
+                     delta: float = DELTA):
+    """The reference's token for every step and stream from `logits` [L, S, V] and the uniform draws [L, S, V]: top_k_filter,
+    then argmax of filtered / temperature + gumbel_from_uniform (text2semantic.py:105-132, 800), in fp64.
+    Returns (tokens [L, S], decidable [L, S] bool).  A step is decidable when a change of every logit by less than `delta` / 2
+    cannot change the token: the winner's perturbed score beats the runner-up in the top-k set by more than delta, the winner is
+    not within delta of the k-th / (k+1)-th boundary, and no entry within delta of that boundary scores within delta of it."""
+    lg = logits.double().cpu()
+    L, S, V = lg.shape
+    k = math.ceil(0.1 * V) if top_k is None else int(top_k)
+    u = uniforms.double().cpu().reshape(L, S, V)
+    val, ind = torch.topk(lg, k, dim=-1)
+    score = torch.full_like(lg, float("-inf")).scatter(-1, ind, val) / max(temperature, 1e-10) + gumbel_from_uniform(u)
+    top2 = score.topk(2, dim=-1)
+    tokens = score.argmax(dim=-1)
+    best = top2.values[..., 0]
+    margin_ok = (best - top2.values[..., 1]) > delta
+    srt = lg.sort(dim=-1, descending=True).values
+    boundary = 0.5 * (srt[..., k - 1] + srt[..., k])                        # between the k-th and the (k+1)-th logit
+    near = (lg - boundary[..., None]).abs() < delta                          # entries a small change could move across it
+    raw = lg / max(temperature, 1e-10) + gumbel_from_uniform(u)             # their score if they were in the set
+    winner_near = near.gather(-1, tokens[..., None])[..., 0]
+    rival = (near & (raw > best[..., None] - delta)).scatter(-1, tokens[..., None], False).any(dim=-1)
+    return tokens, margin_ok & ~winner_near & ~rival
+

@@ -458,3 +458,25 @@ def test_capture_gate_shared_entries_overlap_and_a_capture_is_alone():
     assert not any(t.is_alive() for t in ts), "deadlock"
     assert state["bad"] == 0 and state["captures"] == 16 and state["max_shared"] >= 2, state
     assert gate._readers == 0 and not gate._writer and gate._waiting == 0
+
+
+@pytest.mark.parametrize("nb", [8, 64])
+def test_t2s_uniform_buffer_covers_every_position_a_chunked_decode_reads(nb):
+    """text2semantic host sizing (no kernel runs): a lock-step decode replays whole chunks of CHUNK steps and its sampling kernel
+    reads the uniform draws of every position it reaches (up to the decoder's max_length); with the dialogue capacity equal to the
+    batch, the last dialogue's last read must stay inside the buffer whatever the call's max_length."""
+    import numpy as np
+    from conftest import GOLDEN
+    from covomix_amd.t2s import CHUNK, TextToSemanticDecoder
+    g = np.load(os.path.join(GOLDEN, "t2s_cosingle_small.npz"))
+    sd = {k[3:]: torch.from_numpy(g[k]) for k in g.files if k.startswith("w::")}
+    model = TextToSemanticDecoder(sd, torch.device("cpu"), max_length=2048)
+    S, V = model.d["streams"], model.d["vocab"]
+    for m in (1, 15, 17, 20, 33, 2047):
+        model._ensure(nb, nb, m)
+        steps = model._descriptor(1.0, nb).uniform_steps
+        last = min(-(-m // CHUNK) * CHUNK, model.max_length) - 1                 # the last position the chunks reach
+        assert model._dialogues == nb and steps >= -(-m // CHUNK) * CHUNK, (m, steps)
+        assert model.buf["uniforms"].numel() >= model._dialogues * steps * S * V
+        assert (((nb - 1) * steps + last) * S + S - 1) * V + V - 1 < model.buf["uniforms"].numel()
+        assert model._uniform_view(nb).shape == (nb, steps, S, V)
