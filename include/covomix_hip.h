@@ -59,8 +59,10 @@ typedef const cvx_ctx* cvx_stream_t;
  * decode of up to 64 slots at independent positions with an on-device dialogue queue (continuous batching): cvx_t2s_decoder grew
  * uniform_steps / queue / dialogues / start, slot records are int32[8], uniforms and tokens are indexed by dialogue; every entry point
  * takes a LAUNCH CONTEXT (cvx_ctx: stream + caller-owned saturation flag + CU count) instead of a bare stream - REMOVED: the library's
- * (device, stream) table and cvx_saturation_flag_bind / cvx_stream_set_cus / cvx_stream_cus. */
-#define CVX_ABI_VERSION 107
+ * (device, stream) table and cvx_saturation_flag_bind / cvx_stream_set_cus / cvx_stream_cus.  108: cvx_t2s_decoder loses its
+ * last two fields, the tuning hints group_loop and pairs_per_wave (the decode takes one row pair per wavefront and one group of
+ * slots per thread block). */
+#define CVX_ABI_VERSION 108
 int         cvx_version(void);
 const char* cvx_last_error_string(void);
 
@@ -172,8 +174,7 @@ typedef struct {
      * (pre-split A, M >= 2048, N >= 512). */
     int32_t w_interleaved;
     /* Kernel selection for A/B measurements (0 = default): CVX_GEMM_FLAG_* below.  Results of the kernels agree to fp32
-     * rounding.  (Bits 8.. are timing experiments that exist only in -DCVX_DEV_FLAGS builds of the library; the shipped
-     * library ignores them.) */
+     * rounding.  Other bits are ignored. */
     int32_t flags;
     /* Activation scales: DEVICE pointers to one float each (NULL = 1.0), powers of two.  a_scale_dev = the factor the
      * producer of A_hi/A_lo (and of A2_*: both operands must share it) multiplied the values by before splitting - the
@@ -621,9 +622,6 @@ typedef struct {
     int32_t* queue;                              /* NULL: slot b decodes dialogue b until the caller stops.  Else continuous batching (above) */
     int32_t* dialogues;
     const float* start;                          /* [dim] start token: the input of a slot that takes a new dialogue (queue != NULL) */
-    int32_t group_loop;                          /* tuning hint, 0 = the library's choice: groups of 8 slots one thread block walks with its
-                                                  * weight rows in registers (1, 2, 4, 8); the other groups run as blocks of their own */
-    int32_t pairs_per_wave;                      /* tuning hint, 0 = the library's choice: output row pairs per wavefront (1 or 2) */
 } cvx_t2s_decoder;
 
 int cvx_t2s_decode_steps(const cvx_t2s_decoder* dec, int32_t n_steps, cvx_stream_t stream);

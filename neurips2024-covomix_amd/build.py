@@ -21,10 +21,6 @@ OBJ_DIR = os.path.join(HERE, "csrc", ".obj")
 BASE_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result"]
 
 
-def _flags() -> list:
-    return BASE_FLAGS + os.environ.get("CVX_HIPCC_FLAGS", "").split()          # dev A/B builds (extra -D flags)
-
-
 def _digest(paths, extra=()) -> str:
     h = hashlib.sha256()
     for p in paths:
@@ -38,7 +34,7 @@ def _digest(paths, extra=()) -> str:
 
 def source_hash() -> str:
     """Hash of every source, header and compile flag that goes into the library."""
-    return _digest(SOURCES + HEADERS, _flags())
+    return _digest(SOURCES + HEADERS, BASE_FLAGS)
 
 
 def needs_build() -> bool:
@@ -55,7 +51,7 @@ def build_library(force: bool = False, verbose: bool = False) -> str:
     if not os.path.exists(hipcc):
         raise RuntimeError("hipcc not found: cannot build libcovomix_hip.so")
     os.makedirs(OBJ_DIR, exist_ok=True)
-    flags = _flags()
+    flags = BASE_FLAGS
 
     def compile_one(src: str) -> str:
         key = _digest([src] + HEADERS, flags)

@@ -27,7 +27,7 @@ typedef _Float16 f16;
 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
-constexpr int HD = 64, KT = 32;             // queries per block: 32 per wave, NW waves (128 or 256)
+constexpr int HD = 64, KT = 32;             // queries per block: 32 per wave, NW waves (128, or 64 when key-split)
 constexpr int TILE = KT * HD;                 // halves per operand tile (4 KiB)
 constexpr int STAGE = 4 * TILE;               // Khi | Klo | Vthi | Vtlo
 
@@ -61,21 +61,9 @@ __device__ __forceinline__ void store_split4(f16* hi, f16* lo, int64_t off, cons
 }
 
 // NT = 3: split operands, three products.  NT = 1: hi halves only (plain fp16 operands, fp32 accumulate and softmax).
-#ifndef CVX_ATT_WAVES
-#define CVX_ATT_WAVES 2
-#endif
-// ENERGY ABLATIONS (dev builds only, results are WRONG by construction; tools/archive/attn_ablate.py): which part of the loop the
-// power-capped launch pays for.  bit 0: no L2 -> LDS DMA after the first tile (tiles stay resident); bit 1: no LDS fragment
-// reads after the first tile (K / V^T fragments stay in registers); bit 2: no v_exp_f32 (p = its argument); bit 3: no P.V
-// MFMAs; bit 4: no K.Q MFMAs.
-#ifndef CVX_ATT_ABLATE
-#define CVX_ATT_ABLATE 0
-#endif
-#ifndef CVX_ATT_SHORT_NW2
-#define CVX_ATT_SHORT_NW2 1
-#endif
-// NW = waves per block (4 or 8), 32 queries each.  The K / V^T tiles a block streams through LDS are shared by its waves:
-// with 8 waves (256 queries) the L2 -> LDS DMA bytes per score halve.  Round-3 ablations (tools/archive/attn_ablate.py, Bt = 16,
+constexpr int ATT_WAVES = 2;                       // blocks per CU asked of the compiler (launch bounds) for the one-group form
+// NW = waves per block (4, or 2 in the key-split form), 32 queries each.  The K / V^T tiles a block streams through LDS are
+// shared by its waves.  Round-3 ablations (tools/archive/attn_ablate.py, Bt = 16,
 // T = 1000, H = 16, NW = 4): DMA switched off after the first tile 177 instead of 211 us and 0.233
 // instead of 0.286 J (on zero operands, i.e. at full clock, 130 instead of 159 us); no LDS fragment reads -7 %; no
 // v_exp_f32 -1 %; no P.V MFMAs 140 us; no K.Q MFMAs 134 us.  Halving the DMA BYTES (NW = 8) does not buy the DMA-off time.
@@ -86,7 +74,7 @@ __device__ __forceinline__ void store_split4(f16* hi, f16* lo, int64_t off, cons
 // through LDS in the fixed order 0, 1, 2 (the flash-decoding combine: O = sum O_s 2^(m_s - m), l likewise) before it normalises
 // and stores.  The chain shortens KS-fold and every SIMD holds KS waves to overlap.
 template <int NT, int NW, int KS = 1>
-__global__ __launch_bounds__(64 * NW * KS, (KS > 1 ? (NW * KS + 3) / 4 : CVX_ATT_WAVES)) void attention_f16x3_kernel(const f16* __restrict__ qk_hi, const f16* __restrict__ qk_lo,
+__global__ __launch_bounds__(64 * NW * KS, (KS > 1 ? (NW * KS + 3) / 4 : ATT_WAVES)) void attention_f16x3_kernel(const f16* __restrict__ qk_hi, const f16* __restrict__ qk_lo,
                                                                 const f16* __restrict__ vt_hi, const f16* __restrict__ vt_lo,
                                                                 float* __restrict__ out, f16* __restrict__ out_hi, f16* __restrict__ out_lo,
                                                                 int T, int Tp, int H, int n_groups, int n_qt, float scale_log2e,
@@ -138,11 +126,9 @@ __global__ __launch_bounds__(64 * NW * KS, (KS > 1 ? (NW * KS + 3) / 4 : CVX_ATT
     }
 
     // ---- DMA sources.  NW = 4: wave w fetches K rows [8w, 8w+8) (hi, lo) and V^T rows [16w, 16w+16) (hi, lo): 4 pieces per
-    // tile and wave.  NW = 8: waves 0-3 fetch the K pieces, waves 4-7 the V^T pieces (2 per tile and wave).
-    // NW = 2 (64-query blocks of the key-split form): every wave fetches two of the four row groups of K and of V^T.
+    // tile and wave.  NW = 2 (64-query blocks of the key-split form): every wave fetches two of the four row groups of K and of V^T.
     constexpr int PW = NW == 2 ? 2 : 1;                                     // row groups per wave
     const int wq = NW == 2 ? 2 * wid : (wid & 3);
-    const bool dma_k = NW <= 4 || wid < 4, dma_v = NW <= 4 || wid >= 4;
     int k_r[PW], k_c[PW], v_r[PW], v_c[PW];
     int64_t k_col[PW], v_row[PW];
 #pragma unroll
@@ -158,41 +144,16 @@ __global__ __launch_bounds__(64 * NW * KS, (KS > 1 ? (NW * KS + 3) / 4 : CVX_ATT
         f16* S = smem + stage * STAGE;
 #pragma unroll
         for (int pp = 0; pp < PW; ++pp) {
-            if (dma_k) {                                                    // (wave-uniform)
-                const int key = min(max(key0 + k_r[pp], kc0), kc1 - 1);
-                const int64_t ko = (roff + key) * ldqk + k_col[pp];
-                glds16(qk_hi + ko, S + 8 * (wq + pp) * HD);
-                if constexpr (NT == 3) glds16(qk_lo + ko, S + TILE + 8 * (wq + pp) * HD);
-            }
-            if (dma_v) {
-                const int64_t vo = v_row[pp] + key0;
-                glds16(vt_hi + vo, S + 2 * TILE + 16 * (wq + pp) * KT);
-                if constexpr (NT == 3) glds16(vt_lo + vo, S + 3 * TILE + 16 * (wq + pp) * KT);
-            }
+            const int key = min(max(key0 + k_r[pp], kc0), kc1 - 1);
+            const int64_t ko = (roff + key) * ldqk + k_col[pp];
+            glds16(qk_hi + ko, S + 8 * (wq + pp) * HD);
+            if constexpr (NT == 3) glds16(qk_lo + ko, S + TILE + 8 * (wq + pp) * HD);
+            const int64_t vo = v_row[pp] + key0;
+            glds16(vt_hi + vo, S + 2 * TILE + 16 * (wq + pp) * KT);
+            if constexpr (NT == 3) glds16(vt_lo + vo, S + 3 * TILE + 16 * (wq + pp) * KT);
         }
     };
 
-#ifdef CVX_ATT_REGSTAGE
-    // A/B variant (T14 of the guide, "issue early / write late"): the next tile goes global -> VGPR while the current one is
-    // computed and VGPR -> LDS (same swizzled layout) behind its last MFMA, instead of by LDS-DMA.  NW = 4 only.
-    f16x8 st_kh, st_kl, st_vh, st_vl;
-    auto fetch = [&](int key0) {
-        const int key = min(max(key0 + k_r[0], kc0), kc1 - 1);
-        const int64_t ko = (roff + key) * ldqk + k_col[0];
-        st_kh = gload8h(qk_hi + ko);
-        if constexpr (NT == 3) st_kl = gload8h(qk_lo + ko);
-        const int64_t vo = v_row[0] + key0;
-        st_vh = gload8h(vt_hi + vo);
-        if constexpr (NT == 3) st_vl = gload8h(vt_lo + vo);
-    };
-    auto commit = [&](int stage) {
-        f16* S = smem + stage * STAGE;
-        *reinterpret_cast<f16x8*>(S + 8 * wq * HD + lane * 8) = st_kh;
-        if constexpr (NT == 3) *reinterpret_cast<f16x8*>(S + TILE + 8 * wq * HD + lane * 8) = st_kl;
-        *reinterpret_cast<f16x8*>(S + 2 * TILE + 16 * wq * KT + lane * 8) = st_vh;
-        if constexpr (NT == 3) *reinterpret_cast<f16x8*>(S + 3 * TILE + 16 * wq * KT + lane * 8) = st_vl;
-    };
-#endif
     // ---- fragment offsets (halves)
     int koff[4];                                   // K rows are 64 halves; chunk (2s+g) ^ ((row>>1)&7)
 #pragma unroll
@@ -214,19 +175,7 @@ __global__ __launch_bounds__(64 * NW * KS, (KS > 1 ? (NW * KS + 3) / 4 : CVX_ATT
     //  from 3 to 2 blocks per CU)
     // (a 3-stage ring - tiles requested two ahead - measured the same: the loop is not DMA-latency bound)
     const int tile0 = kc0 / KT, ntiles = (kc1 + KT - 1) / KT - tile0;
-#ifdef CVX_ATT_REGSTAGE
-    fetch(tile0 * KT);
-    commit(0);
-#else
     if (KS == 1 || ks == 0) issue(tile0 * KT, 0);
-#endif
-#ifdef CVX_ATT_TRACE
-    unsigned long long tr[5] = {0, 0, 0, 0, 0};
-#define TSTAMP(i) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); const unsigned long long now_ = __builtin_readcyclecounter(); tr[i] += now_ - tlast_; tlast_ = now_; }
-    unsigned long long tlast_ = __builtin_readcyclecounter();
-#else
-#define TSTAMP(i)
-#endif
     f16x8 kfh[4], kfl[4];                         // K fragments of the running tile
     f16x8 vfh[2][2], vfl[2][2];                   // V^T fragments [s][dt]
     if (KS > 1 && ks > 0 && ks < ntiles) issue((tile0 + ks) * KT, 0);      // (group 0's first tile was requested above)
@@ -240,15 +189,9 @@ __global__ __launch_bounds__(64 * NW * KS, (KS > 1 ? (NW * KS + 3) / 4 : CVX_ATT
             if (it + KS < ntiles) issue(key0 + KS * KT, cur ^ 1);
             if (it >= ntiles) continue;                     // (group-uniform: a group past its last tile only keeps the barriers company)
         } else {
-#ifdef CVX_ATT_REGSTAGE
-        __syncthreads();                                    // every wave's ds_writes of tile `it` are visible; stage cur^1 is free
-        if (it + 1 < ntiles) fetch(key0 + KT);
-#else
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();                       // tile `it` landed everywhere; stage cur^1 is free
-        TSTAMP(0)
-        if (it + 1 < ntiles && !((CVX_ATT_ABLATE & 1) && it > 0)) issue(key0 + KT, cur ^ 1);
-#endif
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __builtin_amdgcn_s_barrier();                   // tile `it` landed everywhere; stage cur^1 is free
+            if (it + 1 < ntiles) issue(key0 + KT, cur ^ 1);
         }
         const f16* S = smem + cur * STAGE;
 
@@ -257,17 +200,11 @@ __global__ __launch_bounds__(64 * NW * KS, (KS > 1 ? (NW * KS + 3) / 4 : CVX_ATT
         // per-term accumulators disappear (measured: 1 accumulator 260 us, 3 accumulators 272 us, 2: 285 us).
         // The first MFMA of the chain takes its C operand from a zero register block kept live over the loop.
         f32x16 sacc;
-        if (!((CVX_ATT_ABLATE & 2) && it > 0)) {  // all K fragments first (8 reads in flight), then the MFMA chain
-#pragma unroll
-            for (int s = 0; s < 4; ++s) {
-                kfh[s] = *reinterpret_cast<const f16x8*>(S + koff[s]);
-                if constexpr (NT == 3) kfl[s] = *reinterpret_cast<const f16x8*>(S + TILE + koff[s]);
-            }
+#pragma unroll                                     // all K fragments first (8 reads in flight), then the MFMA chain
+        for (int s = 0; s < 4; ++s) {
+            kfh[s] = *reinterpret_cast<const f16x8*>(S + koff[s]);
+            if constexpr (NT == 3) kfl[s] = *reinterpret_cast<const f16x8*>(S + TILE + koff[s]);
         }
-        if (CVX_ATT_ABLATE & 16) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) sacc[r] = (float)(r + it) * 0.01f;
-        } else
 #pragma unroll
         for (int s = 0; s < 4; ++s) {
             if constexpr (NT == 3) {
@@ -279,11 +216,6 @@ __global__ __launch_bounds__(64 * NW * KS, (KS > 1 ? (NW * KS + 3) / 4 : CVX_ATT
             }
         }
 
-#ifdef CVX_ATT_TRACE
-        asm volatile("" : "+v"(sacc));
-        { float t_ = sacc[0]; asm volatile("s_nop 0" : "+v"(t_)); }
-#endif
-        TSTAMP(1)
         // ---- online softmax (this lane: 16 keys of query l31; partner lane^32 holds the other 16).
         // The running max m_run is kept in the scaled log2 domain; scores stay raw and the scale is folded into one
         // fma per element: p = exp2(s*c - m).  Only the last tile (ragged batches: and the first) can contain keys outside the sequence (wave-uniform branch), and
@@ -315,8 +247,7 @@ __global__ __launch_bounds__(64 * NW * KS, (KS > 1 ? (NW * KS + 3) / 4 : CVX_ATT
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
                 const float a0 = fmaf(sacc[2 * j], scale_log2e, -m_new), a1 = fmaf(sacc[2 * j + 1], scale_log2e, -m_new);
-                const float p0 = (CVX_ATT_ABLATE & 4) ? a0 : __builtin_amdgcn_exp2f(a0);
-                const float p1 = (CVX_ATT_ABLATE & 4) ? a1 : __builtin_amdgcn_exp2f(a1);
+                const float p0 = __builtin_amdgcn_exp2f(a0), p1 = __builtin_amdgcn_exp2f(a1);
                 psum += p0 + p1;                 // (pairs first: 8 dependent adds instead of 16)
                 const f16x2 h2 = __builtin_convertvector(f32x2{p0, p1}, f16x2);
                 const unsigned int hb = __builtin_bit_cast(unsigned int, h2);
@@ -338,7 +269,6 @@ __global__ __launch_bounds__(64 * NW * KS, (KS > 1 ? (NW * KS + 3) / 4 : CVX_ATT
             for (int r = 0; r < 16; ++r) { o0[r] *= alpha; o1[r] *= alpha; }
         }
 
-        TSTAMP(2)
         // ---- O^T += V^T . P^T
         const f16* Vh = S + 2 * TILE;
         const f16* Vl = S + 3 * TILE;
@@ -346,14 +276,11 @@ __global__ __launch_bounds__(64 * NW * KS, (KS > 1 ? (NW * KS + 3) / 4 : CVX_ATT
         for (int s = 0; s < 2; ++s) {
             f16x8 (&vhh)[2] = vfh[s];
             f16x8 (&vll)[2] = vfl[s];
-            if (!((CVX_ATT_ABLATE & 2) && it > 0)) {
 #pragma unroll
-                for (int dt = 0; dt < 2; ++dt) {
-                    vhh[dt] = *reinterpret_cast<const f16x8*>(Vh + dt * 32 * KT + voff[s]);
-                    if constexpr (NT == 3) vll[dt] = *reinterpret_cast<const f16x8*>(Vl + dt * 32 * KT + voff[s]);
-                }
+            for (int dt = 0; dt < 2; ++dt) {
+                vhh[dt] = *reinterpret_cast<const f16x8*>(Vh + dt * 32 * KT + voff[s]);
+                if constexpr (NT == 3) vll[dt] = *reinterpret_cast<const f16x8*>(Vl + dt * 32 * KT + voff[s]);
             }
-            if (CVX_ATT_ABLATE & 8) continue;
             // interleave the two O^T tiles: consecutive MFMAs alternate accumulators
             if constexpr (NT == 3) {
                 o0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(vll[0], ph[s], o0, 0, 0, 0);
@@ -364,22 +291,7 @@ __global__ __launch_bounds__(64 * NW * KS, (KS > 1 ? (NW * KS + 3) / 4 : CVX_ATT
             o0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(vhh[0], ph[s], o0, 0, 0, 0);
             o1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(vhh[1], ph[s], o1, 0, 0, 0);
         }
-#ifdef CVX_ATT_REGSTAGE
-        if (it + 1 < ntiles) commit(cur ^ 1);
-#endif
-#ifdef CVX_ATT_TRACE
-        asm volatile("" : "+v"(o0), "+v"(o1));
-        { float t_ = o0[0] + o1[0]; asm volatile("s_nop 0" : "+v"(t_)); }
-#endif
-        TSTAMP(3)
     }
-#ifdef CVX_ATT_TRACE
-    if (out && lane == 0) {
-        unsigned long long* tb = reinterpret_cast<unsigned long long*>(out) + ((size_t)blockIdx.x * 4 + wid) * 8;
-        tb[0] = tr[0]; tb[1] = tr[1]; tb[2] = tr[2]; tb[3] = tr[3]; tb[4] = ntiles;
-    }
-    out = nullptr;
-#endif
 
     if constexpr (KS > 1) {
         // merge the key groups' states: groups 1 .. KS-1 park (m, l, O) in LDS (the rings are dead), group 0 folds them in order
@@ -461,14 +373,9 @@ static int launch_attention_f16x3(const uint16_t* qk_hi, const uint16_t* qk_lo, 
                 "attention_f16x3: inputs must be 16-byte aligned");
     if (Bt == 0) return CVX_OK;
     // 128-query blocks (4 waves, three blocks per CU).  256-query blocks (8 waves: half the L2 -> LDS tile traffic per score,
-    // one block per CU) are built and correct but measured 3 % SLOWER (218.6 vs 212.5 us, same joules; on zero operands
-    // 182 vs 159 us: the schedule loses what the traffic saves) - opt-in for A/B runs: -DCVX_ATT_QB256.
-#ifdef CVX_ATT_QB256
-    const int nw = T >= 384 ? 8 : 4;
-#else
-    const int nw = 4;
-#endif
-    int qb = 32 * nw;
+    // one block per CU) measured 3 % SLOWER (218.6 vs 212.5 us, same joules; on zero operands 182 vs 159 us: the schedule
+    // loses what the traffic saves).
+    int qb = 128;
     int n_qt = (T + qb - 1) / qb;
     const int n_groups = Bt * H;
     dim3 grid((unsigned)(((n_groups + 7) / 8) * 8 * n_qt));
@@ -478,23 +385,15 @@ static int launch_attention_f16x3(const uint16_t* qk_hi, const uint16_t* qk_lo, 
     // LDS with three groups).
     int ksplit = 1, nwk = 4;
     const int64_t q_rows = cu_seqlens_dev ? cols : (int64_t)Bt * T;             // query rows of the launch
-    if (nw == 4 && T >= 4 * KT && q_rows < 2048) {
+    if (T >= 4 * KT && q_rows < 2048) {
         ksplit = 3;
-#if CVX_ATT_SHORT_NW2
         // half of the chip's SIMDs hold no wave at all when the 128-query blocks number fewer than 128: 64-query blocks (two query waves,
         // four key groups: 8 waves per block) put a wave on every SIMD
         if (grid.x <= 128) {
             nwk = 2; ksplit = 4; qb = 64; n_qt = (T + qb - 1) / qb;
             grid = dim3((unsigned)(((n_groups + 7) / 8) * 8 * n_qt));
         }
-#endif
     }
-#define CVX_ATT_LAUNCH(NT_, NW_)                                                                                                          \
-    hipLaunchKernelGGL((attention_f16x3_kernel<NT_, NW_>), grid, dim3(64 * NW_), 0, cvx_hip_stream(s),                       \
-                       reinterpret_cast<const f16*>(qk_hi), reinterpret_cast<const f16*>(qk_lo),                                          \
-                       reinterpret_cast<const f16*>(vt_hi), reinterpret_cast<const f16*>(vt_lo),                                          \
-                       out, reinterpret_cast<f16*>(out_hi), reinterpret_cast<f16*>(out_lo),                                               \
-                       T, Tp, H, n_groups, n_qt, scale * 1.44269504088896340736f, qk_scale_dev, v_scale_dev, out_scale_dev, cu_seqlens_dev, sat)
 #define CVX_ATT_LAUNCH_KS(NT_, KS_) CVX_ATT_LAUNCH_KW(NT_, 4, KS_)
 #define CVX_ATT_LAUNCH_KW(NT_, NW_, KS_)                                                                                                  \
     hipLaunchKernelGGL((attention_f16x3_kernel<NT_, NW_, KS_>), grid, dim3(64 * NW_ * KS_), 0, cvx_hip_stream(s),              \
@@ -504,11 +403,10 @@ static int launch_attention_f16x3(const uint16_t* qk_hi, const uint16_t* qk_lo, 
                        T, Tp, H, n_groups, n_qt, scale * 1.44269504088896340736f, qk_scale_dev, v_scale_dev, out_scale_dev, cu_seqlens_dev, sat)
     if (nwk == 2) { if (single) CVX_ATT_LAUNCH_KW(1, 2, 4); else CVX_ATT_LAUNCH_KW(3, 2, 4); }
     else if (ksplit == 3) { if (single) CVX_ATT_LAUNCH_KS(1, 3); else CVX_ATT_LAUNCH_KS(3, 3); }
-    else if (single) { if (nw == 8) CVX_ATT_LAUNCH(1, 8); else CVX_ATT_LAUNCH(1, 4); }
-    else { if (nw == 8) CVX_ATT_LAUNCH(3, 8); else CVX_ATT_LAUNCH(3, 4); }
+    else if (single) CVX_ATT_LAUNCH_KS(1, 1);
+    else CVX_ATT_LAUNCH_KS(3, 1);
 #undef CVX_ATT_LAUNCH_KS
 #undef CVX_ATT_LAUNCH_KW
-#undef CVX_ATT_LAUNCH
     CVX_CHECK_LAUNCH("cvx_attention_f16x3");
     return CVX_OK;
 }

@@ -64,7 +64,7 @@ __device__ __forceinline__ int cvx_item_len(const cvx_item_lengths& it, int b, i
 
 // Saturation bookkeeping of the values a lane stores as split pairs: the running max |v| and a NaN bit.  The clamps
 // (v_med3 / fmin(fmax)) turn a NaN into -65504 and v_max3 skips NaN operands, so NaN needs its own predicate: one v_cmp_u_f32
-// per two values into a scalar mask (no vector register).  -DCVX_NO_NAN_TRACK: dev A/B of what that costs.
+// per two values into a scalar mask (no vector register).
 struct CvxSat {
     float m; bool bad;
     __device__ __forceinline__ CvxSat() : m(0.f), bad(false) {}
@@ -73,12 +73,8 @@ struct CvxSat {
 // GEMM epilogues, enough live values to spill)
 __device__ __forceinline__ void cvx_amax3(CvxSat& s, const float a, const float b)
 {
-#ifndef CVX_NO_SAT_TRACK                      // (dev A/B: what the bookkeeping costs)
     asm("v_max3_f32 %0, %0, |%1|, |%2|" : "+v"(s.m) : "v"(a), "v"(b));
-#ifndef CVX_NO_NAN_TRACK
     s.bad |= __builtin_isunordered(a, b);
-#endif
-#endif
 }
 __device__ __forceinline__ void cvx_amax4(CvxSat& s, const f32x4 v)
 {
@@ -89,14 +85,10 @@ __device__ __forceinline__ void cvx_amax4(CvxSat& s, const f32x4 v)
 // optimiser) made the compiler keep a 576-byte copy of the accumulator block in scratch in every kernel that carries the generic
 // epilogue (round 3: the opt-in f16 mode lost 22 % to it before this was found).  A value that is not <= 65504 in magnitude
 // (too large, infinite or NaN) makes the running maximum infinite.
-#ifndef CVX_NO_SAT_TRACK
 __device__ __forceinline__ float cvx_amax3_c(float m, const float a, const float b)
 {
     return (fabsf(a) <= 65504.f && fabsf(b) <= 65504.f) ? m : __builtin_inff();
 }
-#else
-__device__ __forceinline__ float cvx_amax3_c(float m, const float, const float) { return m; }
-#endif
 // the commit: one atomic, only when saturated (a NaN maximum counts: "not <=", so a direct cvx_sat_commit(flag, |v|) is covered too)
 __device__ __forceinline__ void cvx_sat_commit(uint32_t* flag, float amax)
 {

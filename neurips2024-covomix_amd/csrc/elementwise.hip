@@ -126,9 +126,6 @@ __device__ __forceinline__ float wave_sum(float v)
 }
 
 typedef _Float16 f16x4_t __attribute__((ext_vector_type(4)));
-#ifndef CVX_NORM_NT
-#define CVX_NORM_NT 0          // dev A/B: bit 0 = non-temporal loads of x, bit 1 = non-temporal stores of the split pair (AdaRMSNorm)
-#endif
 // split 4 floats into fp16 (hi, lo) and store 8 bytes each (for GEMMs that take their A operand pre-split)
 __device__ __forceinline__ void store_split4(_Float16* hi, _Float16* lo, int64_t off, const f32x4 o, CvxSat& amax)
 {
@@ -142,11 +139,6 @@ __device__ __forceinline__ void store_split4(_Float16* hi, _Float16* lo, int64_t
         const float x = fminf(fmaxf(o[e], -65504.f), 65504.f);
         h[e] = (_Float16)x;
         l[e] = (_Float16)(x - (float)h[e]);
-    }
-    if (CVX_NORM_NT & 2) {
-        __builtin_nontemporal_store(h, reinterpret_cast<f16x4_t*>(hi + off));
-        if (lo) __builtin_nontemporal_store(l, reinterpret_cast<f16x4_t*>(lo + off));
-        return;
     }
     *reinterpret_cast<f16x4_t*>(hi + off) = h;
     if (lo) *reinterpret_cast<f16x4_t*>(lo + off) = l;      // lo == NULL: hi halves only
@@ -179,7 +171,7 @@ __global__ __launch_bounds__(256) void adarmsnorm_kernel(const float* __restrict
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
         const int j = lane + 64 * i;
-        if (j < nvec) v[i] = (CVX_NORM_NT & 1) ? __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(xr + 4 * j)) : gload4(xr + 4 * j);
+        if (j < nvec) v[i] = gload4(xr + 4 * j);
     }
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
@@ -258,14 +250,7 @@ __global__ __launch_bounds__(256) void adarmsnorm_generic_kernel(const float* __
 // ---------------------------------------------------------------- depthwise conv k=31 + GELU + residual
 // channels-last [Bt,T,C]: a thread owns one channel and TT consecutive frames; every global
 // access is a 256-byte coalesced row segment across the block's 64 channels x 4... (one wave = 64 channels).
-#ifndef CVX_DWCONV_ERFF
-#define CVX_DWCONV_ERFF 0
-#endif
-constexpr int DW_K = 31;
-#ifndef CVX_DW_TT
-#define CVX_DW_TT 16
-#endif
-constexpr int DW_TT = CVX_DW_TT;
+constexpr int DW_K = 31, DW_TT = 16;
 __global__ __launch_bounds__(256) void dwconv31_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                       const float* __restrict__ bias, float* __restrict__ y,
                                                       int T, int C, const int* __restrict__ cu_seqlens)
@@ -292,17 +277,13 @@ __global__ __launch_bounds__(256) void dwconv31_kernel(const float* __restrict__
     }
     const float bc = bias[c];
     // two outputs at a time through the branch-free GELU of the GEMM epilogues (1-ulp erf, packed fp32): the library erff was
-    // two thirds of this kernel's VALU work (CVX_DWCONV_ERFF=1 in a dev build: the library form)
+    // two thirds of this kernel's VALU work
 #pragma unroll
     for (int o = 0; o < DW_TT; o += 2) {
         float a0 = bc, a1 = bc;
 #pragma unroll
         for (int k = 0; k < DW_K; ++k) { a0 = fmaf(wk[k], xs[o + k], a0); a1 = fmaf(wk[k], xs[o + 1 + k], a1); }
-#if CVX_DWCONV_ERFF
-        const f32x2 g2 = f32x2{gelu_erf(a0), gelu_erf(a1)};
-#else
         const f32x2 g2 = gelu_fast2(f32x2{a0, a1});
-#endif
         const int t = t0 + o;
         if (t < T) y[base + (int64_t)t * C + c] = g2[0] + xs[o + DW_K / 2];
         if (t + 1 < T) y[base + (int64_t)(t + 1) * C + c] = g2[1] + xs[o + 1 + DW_K / 2];

@@ -53,7 +53,10 @@ struct SplitOut { _Float16* hi; _Float16* lo; int64_t ldc_h; int write_f32;
                   // K-split operand pairs with DIFFERENT pre-scales (EPI_BIAS_TW on the large-problem kernel only): A holds x * *a_scale,
                   // A2 holds x2 * *a2_scale; the accumulators are multiplied by *a2_scale / *a_scale (a power of two) where the K loop
                   // switches operands, and divided by *a2_scale at the end
-                  const float* a2_scale; };      // sticky saturation flag of the device (cvx_common.h), NULL = no bookkeeping   // trace (dbg bit 2): per-block s_memtime stamps (dev only)          // dbg: timing experiments only (bit 0: skip the epilogue) - cvx_gemm_split_io.flags >> 8
+                  const float* a2_scale; };
+// sat: sticky saturation flag of the device (cvx_common.h), NULL = no bookkeeping.  dbg: kernel-choice bits from the public
+// cvx_gemm_split_io.flags (8 one tile per block, 16 / 32 / 64 192-row / 256-row / mixed tiles: bit-identical results).  The host
+// sets no other dbg bit and no trace (what bit 0 / trace still guard in the 16x16x32 kernels is a former timing experiment).
 
 // accumulator factor: 1 / (weight pre-scale) / (activation pre-scale); both powers of two, so the division is exact
 __device__ __forceinline__ float total_acc_scale(float acc_scale, const SplitOut& so)

@@ -673,11 +673,7 @@ static int gemm_f16x3_impl(const cvx_gemm_args* a, const uint16_t* W_hi, const u
         so.tw_gamma = io->c_gamma_dev; so.rowsq = io->c_rowsq; so.rowsq_ld = (int)io->c_rowsq_ld; so.row_scale = io->a_row_scale_dev;
         so.res_hi = reinterpret_cast<const f16*>(io->R_hi); so.res_lo = reinterpret_cast<const f16*>(io->R_lo); so.res_ld = io->ldr_h;
         so.res_scale = io->r_scale_dev; so.a2_scale = io->a2_scale_dev;
-#ifdef CVX_DEV_FLAGS          // timing experiments (tools/): epilogue skipping, per-block stamps, one tile per block - never in the shipped library
-        so.dbg = io->flags >> 8; so.trace = (so.dbg & 4) ? reinterpret_cast<unsigned long long*>(io->workspace) : nullptr;
-#else
         so.dbg = 0; so.trace = nullptr;
-#endif
         if (io->flags & CVX_GEMM_FLAG_ONE_TILE) so.dbg |= 8;      // scheduling only: same arithmetic, bit-identical results
         if (io->flags & CVX_GEMM_FLAG_TILE192) so.dbg |= 16;      // tile height of the large-problem kernel pinned (same bits either way)
         if (io->flags & CVX_GEMM_FLAG_TILE256) so.dbg |= 32;
@@ -751,12 +747,6 @@ static int gemm_f16x3_impl(const cvx_gemm_args* a, const uint16_t* W_hi, const u
             const int f = splitk_factor_p8m(a->M, a->N, a->K, a->K1, a->A2 != nullptr);
             if (f > 1 && io->workspace_floats >= (int64_t)f * a->M * a->N) ksplit = f;
         }
-#ifdef CVX_DEV_FLAGS
-        if (io->flags & 0x10000) ksplit = 1;               // (dev A/B: no K slices; 0x20000: two)
-        if ((io->flags & 0x20000) && ksplit > 2) ksplit = 2;
-        if ((so.dbg & 4) && io->workspace)                 // stamps behind the split-K partials (tools/archive/gemm_small_trace.py)
-            so.trace = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(io->workspace) + ((size_t)100 << 20));
-#endif
         CVX_REQUIRE(cvxg::launch_gemm_f16x3_p8m(*a, A, wh, acc_scale, so, ksplit, ksplit > 1 ? io->workspace : nullptr, st),
                     "gemm_f16x3: interleaved operands below 2048 rows need N %% 16 == 0 (N %% 64 == 0 with RoPE), 16-byte aligned C / residual / "
                     "bias / RoPE tables and rope_cols %% 128 == 0 (M=%d N=%d K=%d)", a->M, a->N, a->K);

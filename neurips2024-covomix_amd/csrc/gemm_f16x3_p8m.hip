@@ -34,17 +34,6 @@ constexpr int MBUF_B = 2 * MT_B;                   // A | W
 constexpr int NBUF = 5;
 constexpr int MLDS_B = NBUF * MBUF_B;              // 160 KiB
 
-#ifdef CVX_DEV_FLAGS          // per-block s_memtime stamps of waves 0 and 4 (tools/archive/gemm_small_trace.py; never in the shipped library)
-#define CVX_P8M_STAMP(i) do { if (tr) { tr[i] = __builtin_readcyclecounter(); } } while (0)
-#else
-#define CVX_P8M_STAMP(i) do { } while (0)
-#endif
-#ifndef CVX_P8M_DMA_FIRST
-#define CVX_P8M_DMA_FIRST 0         // dev A/B: the load segment requests K-tile t + 4 before (1) or after (0) its 16 fragment reads
-#endif
-#ifndef CVX_P8M_PERM
-#define CVX_P8M_PERM 1              // dev A/B: 0 = 8-byte pair stores in the to_qkv / ff1 epilogues (rounds 1-4 before the permutation)
-#endif
 #define CVX_P8M_BARRIER() asm volatile("s_barrier" ::: "memory")
 #define CVX_P8M_WAIT_DMA() asm volatile("s_waitcnt vmcnt(8)" ::: "memory")
 #define CVX_P8M_WAIT_LDS() asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory")
@@ -55,7 +44,7 @@ constexpr int MLDS_B = NBUF * MBUF_B;              // 160 KiB
 template <bool HAS_A2, bool SWAP, bool PERM = false>
 __device__ __forceinline__ void tile_mainloop_m(const cvx_gemm_args& p, const PreSplitA& A, const f16* __restrict__ W, char* smem,
                                                 int m0, int n0, int kt0, int nk, int lane, int grp, int w4, int wr, int wc,
-                                                f32x4 (&acc)[4][4], unsigned long long* tr)
+                                                f32x4 (&acc)[4][4])
 {
     const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
     // DMA: wave w4 of a group moves rows [32 w4, 32 w4 + 32) of the A tile and of the W tile, 8 rows x 128 bytes per piece
@@ -110,7 +99,6 @@ __device__ __forceinline__ void tile_mainloop_m(const cvx_gemm_args& p, const Pr
     issue(grp + 2, grp + 2);
     CVX_P8M_WAIT_DMA();
     CVX_P8M_BARRIER();
-    CVX_P8M_STAMP(1);
     if (grp == 1) CVX_P8M_BARRIER();                    // group 1 runs one interval behind group 0
 
 #define CVX_P8M_MM(x, y, c) (SWAP ? __builtin_amdgcn_mfma_f32_16x16x32_f16(y, x, c, 0, 0, 0) : __builtin_amdgcn_mfma_f32_16x16x32_f16(x, y, c, 0, 0, 0))
@@ -120,9 +108,6 @@ __device__ __forceinline__ void tile_mainloop_m(const cvx_gemm_args& p, const Pr
         // ---- load segment (the other group multiplies): fragments of K-tile t, request K-tile t + 4
         const char* sb = smem + bi * MBUF_B;
         const int bn = bi + 4 >= NBUF ? bi + 4 - NBUF : bi + 4;
-#if CVX_P8M_DMA_FIRST
-        issue(t + 4, bn);
-#endif
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             fbh[i] = *reinterpret_cast<const f16x8*>(sb + i * 16 * 128 + boh);
@@ -133,9 +118,7 @@ __device__ __forceinline__ void tile_mainloop_m(const cvx_gemm_args& p, const Pr
             fah[i] = *reinterpret_cast<const f16x8*>(sb + i * 16 * 128 + aoh);
             fal[i] = *reinterpret_cast<const f16x8*>(sb + i * 16 * 128 + aol);
         }
-#if !CVX_P8M_DMA_FIRST
-        issue(t + 4, bn);
-#endif
+        issue(t + 4, bn);                               // (behind the 16 fragment reads)
         CVX_P8M_WAIT_LDS();
         CVX_P8M_BARRIER();
         // ---- compute segment: 4 x 4 tiles x three terms = 48 MFMAs, term-major (consecutive MFMAs hit different accumulators)
@@ -164,7 +147,6 @@ __device__ __forceinline__ void tile_mainloop_m(const cvx_gemm_args& p, const Pr
 #undef CVX_P8M_MM
     if (grp == 0) CVX_P8M_BARRIER();                    // pairs with group 1's last barrier
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");    // drain the tail's dummy pieces before LDS is reused
-    CVX_P8M_STAMP(2);
 }
 
 // PERM (round 4, the pair-writing epilogues EPI_QKV / EPI_GELU_SPLIT on whole 64-column wave tiles): 16-byte pair stores, see perm32
@@ -197,14 +179,6 @@ __global__ __launch_bounds__(512, 2) void gemm_f16x3_p8m_kernel(
         p.bias = nullptr;
     }
 
-    unsigned long long* tr = nullptr;
-#ifdef CVX_DEV_FLAGS
-    if ((so.dbg & 4) && so.trace && lane == 0 && w4 == 0) {
-        tr = so.trace + ((int64_t)blockIdx.x * 2 + grp) * 8;
-        unsigned long long rt; asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(rt));
-        tr[5] = rt; tr[0] = __builtin_readcyclecounter();
-    }
-#endif
     f32x4 acc[4][4];
 #pragma unroll
     for (int mi = 0; mi < 4; ++mi)
@@ -217,8 +191,8 @@ __global__ __launch_bounds__(512, 2) void gemm_f16x3_p8m_kernel(
     const int row0 = m0 + wr * 64 + grp * 32, col0 = n0 + wc * 64;
     EpiPre<2> pre;
     epilogue_prefetch<EPI, 2, PERM>(p, so, row0, col0, lane, v_block, pre);
-    if (v_block) tile_mainloop_m<HAS_A2, false, PERM>(p, A, W, smem_p8m, m0, n0, kt0, nk, lane, grp, w4, wr, wc, acc, tr);
-    else tile_mainloop_m<HAS_A2, true, PERM>(p, A, W, smem_p8m, m0, n0, kt0, nk, lane, grp, w4, wr, wc, acc, tr);
+    if (v_block) tile_mainloop_m<HAS_A2, false, PERM>(p, A, W, smem_p8m, m0, n0, kt0, nk, lane, grp, w4, wr, wc, acc);
+    else tile_mainloop_m<HAS_A2, true, PERM>(p, A, W, smem_p8m, m0, n0, kt0, nk, lane, grp, w4, wr, wc, acc);
 
     // ---- exchange: group 0 keeps rows 0-31 of every wave tile (blocks mi = 0, 1), group 1 rows 32-63 (mi = 2, 3)
     CVX_P8M_BARRIER();                                  // every wave is past its last fragment read and its last DMA piece
@@ -249,18 +223,9 @@ __global__ __launch_bounds__(512, 2) void gemm_f16x3_p8m_kernel(
 #pragma unroll
             for (int j = 0; j < 4; ++j) e[i][j] = X[theirs + (i * 4 + j) * 64] + acc[2 + i][j];
     }
-    CVX_P8M_STAMP(3);
     if (so.dbg & 1) return;                             // (dev: main loop only, timing)
     if (v_block) epilogue_vt<2, true, false, PERM>(p, e, row0, col0, lane, so, acc_scale, &pre);
     else epilogue_rows<EPI, 2, true, PERM ? 1 : 0>(p, e, row0, col0, lane, so, acc_scale, &pre);
-#ifdef CVX_DEV_FLAGS
-    if (tr) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        tr[4] = __builtin_readcyclecounter();
-        unsigned long long rt; asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(rt));
-        tr[6] = rt;
-    }
-#endif
 }
 
 }  // namespace
@@ -301,8 +266,8 @@ bool launch_gemm_f16x3_p8m(const cvx_gemm_args& a, const PreSplitA& A, const f16
     if (epi == EPI_QKV && a2.bias) epi = EPI_GENERIC;
     if (epi == EPI_GENERIC && s2.vt_hi) return false;
     const int ks = ksplit > 1 ? ksplit : 1;
-    // the pair-writing epilogues on whole wave tiles: permuted W tile rows, 16-byte pair stores (CVX_P8M_PERM=0 in a dev build: off)
-    const bool perm = CVX_P8M_PERM && ksplit <= 1 && !A.hi2 && (epi == EPI_QKV || epi == EPI_GELU_SPLIT) && a.N % 64 == 0 && s2.hi &&
+    // the pair-writing epilogues on whole wave tiles: permuted W tile rows, 16-byte pair stores
+    const bool perm = ksplit <= 1 && !A.hi2 && (epi == EPI_QKV || epi == EPI_GELU_SPLIT) && a.N % 64 == 0 && s2.hi &&
                       (((uintptr_t)s2.hi | (uintptr_t)s2.lo) & 15) == 0 && (s2.ldc_h & 7) == 0;
 #define CVX_P8M_LAUNCH_P(E)                                                                                              \
     do {                                                                                                                \

@@ -33,25 +33,13 @@ __device__ __forceinline__ void dma2(uint32_t voff0, uint32_t voff1, uint32_t m0
 // Column permutation of the pair-moving instances (the deferred-norm forms and to_qkv / ff1 of the large-problem kernel; the medium
 // kernel passes its own switch).  LDS row rho = 16 h + 4 g + e of a 32-row group of
 // the W tile holds weight row 8 g + 4 h + e, so accumulator tile ni = 2 t + h of lane group g (lane >> 4) holds the output columns
-// 32 t + 8 g + 4 h + (0..3): the tile pair (2 t, 2 t + 1) is 8 CONSECUTIVE columns per lane.
-#ifndef CVX_P8S_PERM
-#define CVX_P8S_PERM 1                         // dev A/B: 0 = the deferred-norm instances without the permutation (8-byte pair accesses)
-#endif
-// (and the large-problem kernel's plain to_qkv / ff1 instances: the same 16-byte pair stores)
-#ifndef CVX_P8S_PERM_PLAIN
-#define CVX_P8S_PERM_PLAIN 1                   // dev A/B: 0 = only the deferred-norm instances
-#endif
-__host__ __device__ constexpr bool epi_perm(int epi) { return CVX_P8S_PERM && (epi >= EPI_RES_TW || (CVX_P8S_PERM_PLAIN && (epi == EPI_QKV || epi == EPI_GELU_SPLIT))); }
+// 32 t + 8 g + 4 h + (0..3): the tile pair (2 t, 2 t + 1) is 8 CONSECUTIVE columns per lane, so the pairs move as 16-byte
+// accesses instead of 8-byte ones (the deferred-norm instances, and the plain to_qkv / ff1 instances of the large-problem kernel).
+__host__ __device__ constexpr bool epi_perm(int epi) { return epi >= EPI_RES_TW || epi == EPI_QKV || epi == EPI_GELU_SPLIT; }
 __device__ __forceinline__ int perm32(int r) { return (r & ~31) | ((r & 12) << 1) | ((r & 16) >> 2) | (r & 3); }
 // first of the 4 columns tile ni of lane group lc / 4 holds, relative to the wave tile's first column
 template <bool PERM> __device__ __forceinline__ int tile_col(int ni, int lc) { return PERM ? 32 * (ni >> 1) + 2 * lc + 4 * (ni & 1) : 16 * ni + lc; }
 
-#ifndef CVX_P8S_RES_AHEAD
-#define CVX_P8S_RES_AHEAD 2
-#endif
-#ifndef CVX_P8S_AMAX
-#define CVX_P8S_AMAX 0
-#endif
 #define CVX_P8_BARRIER() asm volatile("s_barrier" ::: "memory")
 #define CVX_P8_WAIT_DMA() asm volatile("s_waitcnt vmcnt(8)" ::: "memory")
 #define CVX_P8_WAIT_LDS() asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory")
@@ -70,13 +58,7 @@ __device__ __forceinline__ f32x2 mul2_rn(const f32x2 a, const f32x2 b) { return 
 // v_fma_mix_f32 straight from the packed halves, packed conversion of the residuals
 __device__ __forceinline__ void split2_pk(const f32x2 v, f16x2& hi, f16x2& lo, CvxSat& amax)
 {
-#if CVX_P8S_AMAX == 1                          // dev A/B of the saturation bookkeeping: plain C
-    amax.m = fmaxf(amax.m, fmaxf(fabsf(v[0]), fabsf(v[1])));
-#elif CVX_P8S_AMAX == 2                        // on the clamped values' bit patterns (integer max of the magnitudes)
-    amax.m = __builtin_bit_cast(float, max(__builtin_bit_cast(unsigned, amax.m), max(__builtin_bit_cast(unsigned, v[0]) & 0x7fffffffu, __builtin_bit_cast(unsigned, v[1]) & 0x7fffffffu)));
-#else
     cvx_amax3(amax, v[0], v[1]);
-#endif
     const float x0 = __builtin_amdgcn_fmed3f(v[0], -65504.f, 65504.f), x1 = __builtin_amdgcn_fmed3f(v[1], -65504.f, 65504.f);
     hi = __builtin_convertvector(f32x2{x0, x1}, f16x2);
     const unsigned int hb = __builtin_bit_cast(unsigned int, hi);
@@ -184,9 +166,9 @@ __device__ __forceinline__ void epilogue_rows(const cvx_gemm_args& p_in, f32x4 (
         else if (p.bias) b4 = *reinterpret_cast<const f32x4*>(p.bias + col0 + tile_col<PERM>(ni, lc));
         bias[ni][0] = f32x2{b4[0], b4[1]}; bias[ni][1] = f32x2{b4[2], b4[3]};
     }
-    // residual rows are requested CVX_P8S_RES_AHEAD row groups before they are added (explicitly: where hipcc puts these loads
-    // on its own moves with unrelated changes of the epilogue - the saturation bookkeeping cost 0.65 % of the step that way)
-    constexpr int RA = CVX_P8S_RES_AHEAD;
+    // residual rows are requested RA row groups before they are added (explicitly: where hipcc puts these loads on its own
+    // moves with unrelated changes of the epilogue - the saturation bookkeeping cost 0.65 % of the step that way)
+    constexpr int RA = 2;
     f32x4 rbuf[RA + 1][4];
     // (EPI_RES_TW: the residual may be a split pair - a lane's 4 hi halves travel in r[ni][0..1], its 4 lo halves in r[ni][2..3])
     const bool res_pair = (EPI == EPI_RES_TW) && so.res_hi != nullptr;

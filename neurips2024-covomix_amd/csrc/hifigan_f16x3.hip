@@ -34,9 +34,6 @@ constexpr int A_ROWS = 320;            // TMB + halo (<= 50) rounded up to the 1
 constexpr int A_TILE = A_ROWS * CK;    // halves of one (hi or lo) activation tile: 20 KiB
 constexpr int W_TILE = 256 * CK;       // halves of one (hi or lo) weight stage (TS taps x Np rows = 256 rows): 16 KiB
 constexpr int LDS_HALVES = 2 * 2 * A_TILE + 2 * 2 * W_TILE;      // 144 KiB
-#ifndef CVX_PAIR_PIPE
-#define CVX_PAIR_PIPE 1                 // dev A/B: 0 = the plain loop of the fused pair kernel (lgkmcnt(0) in front of every step)
-#endif
 
 struct Conv16Args {
     const f16* z_hi; const f16* z_lo;  // [B][Lp][Cp_in]
@@ -97,9 +94,6 @@ __global__ __launch_bounds__(512) void conv_f16x3_kernel(const ConvKArgs<GRP> P)
 
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int wm = wid / WN, wn = wid % WN;
-#ifdef CVX_CONV_TRACE
-    const unsigned long long tr0 = __builtin_amdgcn_s_memrealtime();
-#endif
     const float zs = p.z_scale ? *p.z_scale : 1.f;          // activation pre-scale of this stage's split pairs
     const float a_sc = p.acc_scale / zs;                    // (exact: both are powers of two)
     float amax = 0.f;
@@ -211,9 +205,6 @@ __global__ __launch_bounds__(512) void conv_f16x3_kernel(const ConvKArgs<GRP> P)
     }
 
 
-#ifdef CVX_CONV_TRACE
-    const unsigned long long tr1 = __builtin_amdgcn_s_memrealtime();
-#endif
     // ---- epilogue.  acc register 4*rg + e of lane (i31, g): position 8*rg + 4*g + e, channel i31.  After the quad
     // transpose lane q = lane & 3 holds position 8*rg + 4*g + q and the 4 channels 4*(i31 >> 2) .. +3.
     const int q = lane & 3;
@@ -297,19 +288,6 @@ __global__ __launch_bounds__(512) void conv_f16x3_kernel(const ConvKArgs<GRP> P)
         if (lane == 0 && omax > 0.f && omax < __builtin_inff() && __float_as_uint(omax) > __atomic_load_n(p.amax_out, __ATOMIC_RELAXED))
             atomicMax(p.amax_out, __float_as_uint(omax));        // (most waves cannot raise the maximum: no atomic)
     }
-#ifdef CVX_CONV_TRACE
-    // trace build (tools/archive/conv_trace.py): with out_scale = 0 the fp32 output is all zero; the block leaves its 100 MHz stamps
-    // (start, end of the main loop, end) and its CU in its own first output row
-    __syncthreads();
-    if (tid == 0 && p.out_x && p.out_scale == 0.f && l0 < p.L) {
-        unsigned long long* tb = reinterpret_cast<unsigned long long*>(p.out_x + ((int64_t)b * p.Lp + p.halo_l + l0) * NP);
-        unsigned hwid;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
-        unsigned xcc;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-        tb[0] = tr0; tb[1] = tr1; tb[2] = __builtin_amdgcn_s_memrealtime(); tb[3] = ((unsigned long long)xcc << 32) | hwid;
-    }
-#endif
 }
 
 // ---------------------------------------------------------------- the same convolution on v_mfma_f32_16x16x32_f16 (round 4)
@@ -787,23 +765,15 @@ __global__ __launch_bounds__(64 * NW, (TNI == 2 && NW == 8) ? 2 : NW / 2) void r
         __builtin_amdgcn_s_barrier();              // every wave is done reading the tile: it may be overwritten
     };
     auto run_pass = [&](const f16* wh, const f16* wl, const f16* nwh, const f16* nwl, int dil, bool prefetch_x, int next_tile) {
-        if constexpr (CVX_PAIR_PIPE && TNI == 2) run_pass_pipe(wh, wl, nwh, nwl, dil, prefetch_x, next_tile);
+        if constexpr (TNI == 2) run_pass_pipe(wh, wl, nwh, nwl, dil, prefetch_x, next_tile);
         else run_pass_plain(wh, wl, nwh, nwl, dil, prefetch_x, next_tile);
     };
 
     int tile = blockIdx.x;
     if (tile >= p.n_tiles) return;
-#ifdef CVX_PAIR_TRACE
-    unsigned long long tr[6] = {0, 0, 0, 0, 0, 0};
-    unsigned long long tlast_ = __builtin_readcyclecounter();
-#define PSTAMP(i) { const unsigned long long now_ = __builtin_readcyclecounter(); tr[i] += now_ - tlast_; tlast_ = now_; }
-#else
-#define PSTAMP(i)
-#endif
     load_x(tile);
     issue_w(p.w1h, p.w1l, 0, 0);
     store_z();
-    PSTAMP(0)
     for (; tile < p.n_tiles; tile += gridDim.x) {
         const int b = tile / p.tiles_per_seq, l0 = (tile - b * p.tiles_per_seq) * tm_out;
         const int Lb = cvx_item_len(p.items, b, p.L);
@@ -811,7 +781,6 @@ __global__ __launch_bounds__(64 * NW, (TNI == 2 && NW == 8) ? 2 : NW / 2) void r
         const bool has_next = next_tile < p.n_tiles;
 
         run_pass(p.w1h, p.w1l, p.w2h, p.w2l, p.dil, false, 0);            // pass 1: conv1 over the z tile
-        PSTAMP(1)
         // ---- epilogue 1: t = split(lrelu(acc*a1 + b1) * zs), zero outside the signal, over the z tile
 #pragma unroll
         for (int ni = 0; ni < TNI; ++ni) {
@@ -834,11 +803,8 @@ __global__ __launch_bounds__(64 * NW, (TNI == 2 && NW == 8) ? 2 : NW / 2) void r
                 *reinterpret_cast<cvx_f16x4*>(Zs + off + A_TILE) = zl;
             }
         }
-        PSTAMP(2)
         run_pass(p.w2h, p.w2l, has_next ? p.w1h : nullptr, p.w1l, 1, has_next, next_tile);      // pass 2: conv2 over the t tile
-        PSTAMP(3)
         if (has_next) store_z();                   // the next tile's z (its x rows arrived during pass 2)
-        PSTAMP(4)
         // ---- epilogue 2: x' = acc*a2 + b2 + x   (rows r < tm_out, positions < L).  The residual (and accumulate) vectors of the
         // wave's whole slice are requested first, unpredicated (rows clamped to the allocation): one exposed round trip to
         // the Infinity Cache per tile instead of one per store group (4 - 8 per tile).
@@ -883,15 +849,8 @@ __global__ __launch_bounds__(64 * NW, (TNI == 2 && NW == 8) ? 2 : NW / 2) void r
                 *reinterpret_cast<f32x4*>(p.out + o) = v;
             }
         }
-        PSTAMP(5)
     }
     cvx_sat_commit(p.sat, amax);
-#ifdef CVX_PAIR_TRACE
-    if (lane == 0 && p.accum == nullptr && p.out_scale == 0.f) {      // (trace build: out_scale 0 makes the output all zero; stamps go on top)
-        unsigned long long* tb = reinterpret_cast<unsigned long long*>(p.out) + ((size_t)blockIdx.x * 8 + wid) * 8;
-        for (int i = 0; i < 6; ++i) tb[i] = tr[i];
-    }
-#endif
 }
 
 // ---------------------------------------------------------------- layout converters (HBM-bound transposes)

@@ -36,10 +36,6 @@ constexpr int T2S_MAX_KEYS = 4096;
 constexpr int T2S_MAX_DIM = 4096;     // floats of the staged input vector (16 KiB of LDS)
 constexpr int SR = 8;                 // int32 per slot record / dialogue record (cvx_t2s_decoder.state / .dialogues)
 constexpr int T2S_MAX_BATCH = 64;
-#ifndef CVX_T2S_STAGE_HALF
-#define CVX_T2S_STAGE_HALF 0
-#endif
-constexpr bool STAGE_HALF = CVX_T2S_STAGE_HALF != 0;   // (dev A/B) eight slots staged as two passes of four
 
 enum { MODE_QKV = 0, MODE_PLAIN = 1, MODE_RES = 2, MODE_GEGLU = 3, MODE_LOGITS = 4 };
 
@@ -61,8 +57,8 @@ struct GemvArgs {
     float* v_cache;
     const int* state;        // slot records: state[SR * slot + 0] = pos
     int max_len;             // positions >= max_len are clamped (the host never asks for them; keeps a stray call in bounds)
-    // slot groups (batch > 8): the batch is ceil(batch / 8) groups of BQ = 8 slots; a block works on `gl` consecutive groups (the
-    // weight rows of its pairs stay in registers) and `gy` blocks share a row block (dispatched back to back on one XCD: L2 hits)
+    // slot groups (batch > 8): the batch is ceil(batch / 8) groups of BQ = 8 slots; `gy` blocks share a row block (dispatched back
+    // to back on one XCD: L2 hits) and block i of them starts at group i * gl (gl = 1: one group per block)
     int gy, gl, n_blocks;
     // MODE_GEGLU: rows j (value) and j + F (gate), F = N / 2; y[j] for j < F, zero fill up to y_pad
     int y_pad;
@@ -85,11 +81,8 @@ __device__ __forceinline__ float wave_sum(float v)
 }
 
 constexpr int PF = 4;                                      // 4 x 256 floats per row in flight (K <= 1024 entirely)
-#ifndef CVX_T2S_NT
-#define CVX_T2S_NT 1
-#endif
-// weight rows: streamed once per token step by one wave each -> non-temporal loads (A/B: -DCVX_T2S_NT=0)
-__device__ __forceinline__ f32x4 wload4(const float* p) { return CVX_T2S_NT ? gload4_nt(p) : gload4(p); }
+// weight rows: streamed once per token step by one wave each -> non-temporal loads
+__device__ __forceinline__ f32x4 wload4(const float* p) { return gload4_nt(p); }
 // ACTIVATION reads (x, q, att, h, logits, the state record, cache rows) are plain loads (round 4 measured L1-bypassing loads at
 // -36 % on this per-launch path: 147.8 -> 201.2 us per CoSingle step)
 __device__ __forceinline__ float aload(const float* p) { return *p; }
@@ -217,9 +210,9 @@ __device__ __forceinline__ void stage_chunk(const GemvArgs& a, int bofs, int c, 
     } else {
         // HB slots per pass: their 16-byte loads are independent (one L2 round trip per pass), then slot pair by slot pair with a
         // scheduling barrier in between - left alone the scheduler keeps the raw values, the products and the interleaved copies of all
-        // eight slots live at once (96 registers on top of the weight strips: two blocks per CU).  BQ = 8 stages in two passes of four
-        // slots under -DCVX_T2S_STAGE_HALF=1 (dev): 152 -> 144 registers only - still three blocks per CU - for a second round trip: off.
-        constexpr int HB = (BQ == 8 && STAGE_HALF) ? 4 : BQ;
+        // eight slots live at once (96 registers on top of the weight strips: two blocks per CU).  (BQ = 8 staged in two passes of
+        // four slots: 152 -> 144 registers only - still three blocks per CU - for a second round trip.)
+        constexpr int HB = BQ;
 #pragma unroll
         for (int h = 0; h < BQ / HB; ++h) {
             f32x4 v[HB];
@@ -328,7 +321,9 @@ __device__ __forceinline__ void gemv_epilogue(const GemvArgs& a, const PairInfo&
 // (Round 5 staged scalar-wise, four dependent L2 round trips per 1024 floats, ran the lane tree once per value - 96 exchanges per
 // pair at BQ = 8 against 20 now - and left the epilogue of all slots to lane 0.)  Per-(row, slot) arithmetic does not depend on BQ, PPW
 // or the grouping: same bits.
-template <int MODE, int BQ, int PPW, bool LOOP = false>
+// Only PPW = 1, LOOP = false is built (one row pair per wave, one slot group per block: see cvx_t2s_decode_steps).  The two parameters
+// stay because folding them into the body changes the compiler's schedule of that kernel.
+template <int MODE, int BQ, int PPW = 1, bool LOOP = false>
 __global__ __launch_bounds__(256) void gemv_kernel(const GemvArgs a)
 {
     __shared__ __attribute__((aligned(16))) float xs[BQ * 1024];
@@ -355,8 +350,7 @@ __global__ __launch_bounds__(256) void gemv_kernel(const GemvArgs a)
     constexpr int SH = SlotShift<BQ>::value;
     const int myb = BQ == 1 ? 0 : lane >> SH;                          // the slot (of a group) whose results the lane tree leaves here
     const bool writer = (lane & ((1 << SH) - 1)) == 0;
-    // LOOP (dev hint cvx_t2s_decoder.group_loop > 1): the block walks a.gl groups of slots with its weight strips in registers; the default
-    // is ONE group per block - no loop, so nothing (the second pair's strips in particular) has to stay live across a back edge
+    // LOOP: the block walks a.gl groups of slots with its weight strips in registers; the shipped form is ONE group per block - no loop, so nothing (the second pair's strips in particular) has to stay live across a back edge
     const int n_g = LOOP ? a.gl : 1;
 #pragma unroll 1
     for (int g = 0; g < n_g; ++g) {
@@ -658,41 +652,24 @@ __global__ __launch_bounds__(256) void geglu_kernel(const float* __restrict__ h,
 }
 
 
-constexpr int T2S_GROUP_LOOP = 1;   // default of cvx_t2s_decoder.group_loop: slot groups one block walks with its weight rows in registers
-template <int MODE, int BQ, int PPW>
-void launch_gemv_p(GemvArgs g, int pairs, int groups, hipStream_t st)
-{
-    g.n_blocks = (pairs + 4 * PPW - 1) / (4 * PPW);
-    const int want = g.gl > 0 ? g.gl : T2S_GROUP_LOOP;
-    g.gl = 1;
-    while (g.gl < want && groups % (2 * g.gl) == 0) g.gl *= 2;
-    g.gy = groups / g.gl;
-    const unsigned grid = g.gy > 1 ? (unsigned)((g.n_blocks + 7) / 8 * 8 * g.gy) : (unsigned)g.n_blocks;
-    if constexpr (PPW == 1 && BQ == 8) {
-        if (g.gl > 1) { hipLaunchKernelGGL((gemv_kernel<MODE, BQ, PPW, true>), dim3(grid), dim3(256), 0, st, g); return; }
-    }
-    if (g.gl > 1) { g.gy *= g.gl; g.gl = 1; }          // (the group loop exists at one row pair per wave, eight slots per group only)
-    const unsigned grid1 = g.gy > 1 ? (unsigned)((g.n_blocks + 7) / 8 * 8 * g.gy) : (unsigned)g.n_blocks;
-    hipLaunchKernelGGL((gemv_kernel<MODE, BQ, PPW, false>), dim3(grid1), dim3(256), 0, st, g);
-}
+// batch 1 / 2 / 4 / 8: one group of that many slots; above: ceil(batch / 8) groups of 8, one block per (row block, group) (the
+// per-slot buffers of the caller hold whole groups; the slots past `batch` compute on whatever they hold and nothing reads them)
 template <int MODE, int BQ>
-void launch_gemv_b(const GemvArgs& g, int pairs, int groups, bool two, hipStream_t st)
+void launch_gemv_b(GemvArgs g, int pairs, int groups, hipStream_t st)
 {
-    if constexpr (BQ >= 8) {
-        if (two) { launch_gemv_p<MODE, BQ, 2>(g, pairs, groups, st); return; }
-    }
-    launch_gemv_p<MODE, BQ, 1>(g, pairs, groups, st);
+    g.n_blocks = (pairs + 3) / 4;
+    g.gl = 1;
+    g.gy = groups;
+    const unsigned grid = g.gy > 1 ? (unsigned)((g.n_blocks + 7) / 8 * 8 * g.gy) : (unsigned)g.n_blocks;
+    hipLaunchKernelGGL((gemv_kernel<MODE, BQ>), dim3(grid), dim3(256), 0, st, g);
 }
-
-// batch 1 / 2 / 4 / 8: one group of that many slots; above: ceil(batch / 8) groups of 8 (the per-slot buffers of the caller hold
-// whole groups; the slots past `batch` compute on whatever they hold and nothing reads them)
 template <int MODE>
-void launch_gemv(const GemvArgs& g, int pairs, int batch, bool few_cus, hipStream_t st)
+void launch_gemv(const GemvArgs& g, int pairs, int batch, hipStream_t st)
 {
-    if (batch <= 1) launch_gemv_b<MODE, 1>(g, pairs, 1, few_cus, st);
-    else if (batch <= 2) launch_gemv_b<MODE, 2>(g, pairs, 1, few_cus, st);
-    else if (batch <= 4) launch_gemv_b<MODE, 4>(g, pairs, 1, few_cus, st);
-    else launch_gemv_b<MODE, 8>(g, pairs, (batch + 7) / 8, few_cus, st);
+    if (batch <= 1) launch_gemv_b<MODE, 1>(g, pairs, 1, st);
+    else if (batch <= 2) launch_gemv_b<MODE, 2>(g, pairs, 1, st);
+    else if (batch <= 4) launch_gemv_b<MODE, 4>(g, pairs, 1, st);
+    else launch_gemv_b<MODE, 8>(g, pairs, (batch + 7) / 8, st);
 }
 
 }  // namespace
@@ -746,56 +723,48 @@ extern "C" int cvx_t2s_decode_steps(const cvx_t2s_decoder* d, int32_t n_steps, c
     const int nb = d->batch;
     // ONE row pair per wave everywhere since the kernel holds 118 VGPRs (four blocks per CU): 64 slots 462 vs 480 us per CoMix step with two
     // pairs (170 VGPRs, two blocks), 32-CU side stream at 8 slots 434 vs 439 (round 5, at two blocks per CU either way, two pairs won there:
-    // 760 vs 813).  cvx_t2s_decoder.pairs_per_wave = 2 still selects the other form (same bits).
-    const bool few = d->pairs_per_wave >= 2;
+    // 760 vs 813).
     const int64_t cache_stride = (int64_t)d->max_len * d->inner;
     for (int step = 0; step < n_steps; ++step) {
         for (int l = 0; l < d->depth; ++l) {
             const cvx_t2s_layer& L = d->layers[l];
             GemvArgs g{};
-            g.gl = d->group_loop;
             // self-attention: q | k | v with RoPE; k, v appended to the cache at position pos
             g.W = L.wqkv_s; g.ldw = d->dim; g.x = d->x; g.x_stride = d->dim; g.gamma = L.gamma_s; g.y = d->q; g.y_stride = d->inner;
             g.N = 3 * d->inner; g.K = d->dim;
             g.inner = d->inner; g.rope_cos = d->rope_cos; g.rope_sin = d->rope_sin; g.k_cache = L.k_cache; g.v_cache = L.v_cache;
             g.cache_stride = cache_stride; g.state = d->state; g.max_len = d->max_len;
-            launch_gemv<MODE_QKV>(g, 3 * d->inner / 2, nb, few, st);
+            launch_gemv<MODE_QKV>(g, 3 * d->inner / 2, nb, st);
             AttnArgs at{d->q, L.k_cache, L.v_cache, d->inner, cache_stride, d->att, d->state, -1, 0, scale, d->max_len};
             hipLaunchKernelGGL(attn_kernel, dim3((unsigned)d->heads, (unsigned)nb), dim3(256), 0, st, at);
             g = GemvArgs{};
-            g.gl = d->group_loop;
             g.W = L.wo_s; g.ldw = d->inner; g.x = d->att; g.x_stride = d->inner; g.y = d->x; g.y_stride = d->dim; g.N = d->dim; g.K = d->inner;
-            launch_gemv<MODE_RES>(g, (d->dim + 1) / 2, nb, few, st);
+            launch_gemv<MODE_RES>(g, (d->dim + 1) / 2, nb, st);
             // cross-attention over [null kv | encoder context]
             g = GemvArgs{};
-            g.gl = d->group_loop;
             g.W = L.wq_c; g.ldw = d->dim; g.x = d->x; g.x_stride = d->dim; g.gamma = L.gamma_c; g.y = d->q; g.y_stride = d->inner;
             g.N = d->inner; g.K = d->dim;
-            launch_gemv<MODE_PLAIN>(g, d->inner / 2, nb, few, st);
+            launch_gemv<MODE_PLAIN>(g, d->inner / 2, nb, st);
             AttnArgs ac{d->q, L.kv_c, L.kv_c + d->inner, 2 * (int64_t)d->inner, (int64_t)d->ctx_rows * 2 * d->inner, d->att, d->state,
                         d->n_ctx > 0 ? d->n_ctx : -2, 1, scale, d->max_len};
             hipLaunchKernelGGL(attn_kernel, dim3((unsigned)d->heads, (unsigned)nb), dim3(256), 0, st, ac);
             g = GemvArgs{};
-            g.gl = d->group_loop;
             g.W = L.wo_c; g.ldw = d->inner; g.x = d->att; g.x_stride = d->inner; g.y = d->x; g.y_stride = d->dim; g.N = d->dim; g.K = d->inner;
-            launch_gemv<MODE_RES>(g, (d->dim + 1) / 2, nb, few, st);
+            launch_gemv<MODE_RES>(g, (d->dim + 1) / 2, nb, st);
             // GEGLU feed-forward
             g = GemvArgs{};
-            g.gl = d->group_loop;
             g.W = L.w1; g.ldw = d->dim; g.x = d->x; g.x_stride = d->dim; g.gamma = L.gamma_f; g.bias = L.b1; g.y = d->h;
             g.y_stride = d->ff_inner_pad; g.N = 2 * d->ff_inner; g.K = d->dim; g.y_pad = d->ff_inner_pad;
-            launch_gemv<MODE_GEGLU>(g, d->ff_inner_pad, nb, few, st);
+            launch_gemv<MODE_GEGLU>(g, d->ff_inner_pad, nb, st);
             g = GemvArgs{};
-            g.gl = d->group_loop;
             g.W = L.w2; g.ldw = d->ff_inner_pad; g.x = d->h; g.x_stride = d->ff_inner_pad; g.bias = L.b2; g.y = d->x; g.y_stride = d->dim;
             g.N = d->dim; g.K = d->ff_inner_pad;
-            launch_gemv<MODE_RES>(g, (d->dim + 1) / 2, nb, few, st);
+            launch_gemv<MODE_RES>(g, (d->dim + 1) / 2, nb, st);
         }
         GemvArgs g{};
-        g.gl = d->group_loop;
         g.W = d->emb; g.ldw = d->dim_emb; g.x = d->x; g.x_stride = d->dim; g.gamma = d->final_gamma; g.y = d->logits;
         g.y_stride = d->streams * d->vocab; g.N = d->vocab; g.K = d->dim_emb; g.streams = d->streams;
-        launch_gemv<MODE_LOGITS>(g, d->streams * ((d->vocab + 1) / 2), nb, few, st);
+        launch_gemv<MODE_LOGITS>(g, d->streams * ((d->vocab + 1) / 2), nb, st);
         SampleArgs sa{d->logits, d->uniforms, d->emb, d->x, d->tokens, d->state, d->queue, d->dialogues, d->start, nb, d->uniform_steps,
                       d->vocab, d->dim_emb, d->streams, d->max_len, d->top_k, d->vocab - 1, 1.0f / fmaxf(d->temperature, 1e-10f),
                       d->cfg_scale};

@@ -89,11 +89,9 @@ def _pair(x, rows=None, cols=None):
     return hi.data_ptr(), _p(lo), hi.stride(0) if hi.ndim == 2 else hi.shape[-1]
 
 
-# cvx_gemm_split_io.flags of every interleaved-operand GEMM (dev A/B, read here, never inside the library):
-# CVX_GEMM_MEDIUM_AUTO=0: 2048 rows and more always on the large-problem kernel (flag 16), =force: always on the medium one (8);
-# default: the library picks by how full the large kernel's last round of tiles would be.  Flag 4: one tile per block (large kernel).
-_GEMM_FLAGS = {"0": 16, "force": 8}.get(_os.environ.get("CVX_GEMM_MEDIUM_AUTO", "1"), 0)
-_GEMM_FLAGS |= int(_os.environ.get("CVX_GEMM_FLAGS_EXTRA", "0"), 0)      # dev builds (-DCVX_DEV_FLAGS): 0x10000 no K slices, 0x20000 at most two
+# cvx_gemm_split_io.flags of every interleaved-operand GEMM: 0, the library picks the kernel (for 2048 rows and more by how full the
+# large kernel's last round of tiles would be), unless the calling thread pins one with gemm_flags().
+_GEMM_FLAGS = 0                  # (the process-wide part, always 0: bench.py reads it to name the GEMM kernel it reports)
 _TL = threading.local()          # per-thread additions to the flags (gemm_flags): a schedule that pins a kernel must not leak into other threads
 
 
@@ -329,7 +327,7 @@ def gemm(a: torch.Tensor, w: torch.Tensor, out: torch.Tensor, *, bias=None, act=
                   f"out_split={out_split is not None} vt={vt_split is not None} ws={bool(io.workspace)}", file=sys.stderr, flush=True)
         w_hi_ptr, w_lo_ptr = hi.data_ptr(), _p(lo)
         if use_il:
-            io.flags = _GEMM_FLAGS | getattr(_TL, "flags", 0)
+            io.flags = getattr(_TL, "flags", 0)
             io.w_interleaved, g.ldw = 1, 2 * K
             w_hi_ptr, w_lo_ptr, inv_scale = il.data_ptr(), il.data_ptr() + 64, inv_il
         if norm is not None:

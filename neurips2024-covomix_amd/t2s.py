@@ -235,8 +235,6 @@ class TextToSemanticDecoder:
         for n in ("uniforms", "x", "q", "att", "h", "logits", "tokens", "state"):
             setattr(dec, n, b[n].data_ptr())
         dec.uniform_steps = self._steps
-        dec.group_loop = int(os.environ.get("CVX_T2S_GROUP_LOOP", "0"))          # dev A/B
-        dec.pairs_per_wave = int(os.environ.get("CVX_T2S_PPW", "0"))              # dev A/B
         if queue:
             dec.queue, dec.dialogues, dec.start = b["queue"].data_ptr(), b["dialogues"].data_ptr(), self.start.data_ptr()
         return dec

@@ -706,10 +706,8 @@ def test_gemm_large_problem_kernels_every_epilogue(ops, M):
         w = (torch.randn(N, Kw, generator=g) / math.sqrt(Kw)).to(dev_)
         ws = ops.split_f16(w)
         return w, ws, ops.split_f16_interleaved(ws)
-    saved = ops._GEMM_FLAGS
-    try:
-        for flags in (16, 0):                    # large-problem kernel pinned / the library's choice (medium kernel here)
-            ops._GEMM_FLAGS = flags
+    for flags in (16, 0):                    # large-problem kernel pinned / the library's choice (medium kernel here)
+        with ops.gemm_flags(flags):
             # plain + bias / residual / twin
             w, ws, wil = weights(1024)
             b, r = torch.randn(1024, generator=g).to(dev_), torch.randn(M, 1024, generator=g).to(dev_)
@@ -764,8 +762,6 @@ def test_gemm_large_problem_kernels_every_epilogue(ops, M):
                 assert rel_l2(got_v, v) < 1e-6, (flags, T)
                 free = torch.ones(Tp, dtype=torch.bool, device=dev_); free[slots] = False      # columns no frame maps to stay zero
                 assert float(vt[0][:, free].abs().max() if bool(free.any()) else 0) == 0
-    finally:
-        ops._GEMM_FLAGS = saved
 
 
 def test_gemm_large_problem_kernels_n_not_multiple_of_256(ops):
@@ -778,10 +774,8 @@ def test_gemm_large_problem_kernels_n_not_multiple_of_256(ops):
     x = torch.randn(M, K, generator=g).to(dev_)
     il = ops.SplitIL(M, K, dev_); ops.split_act_f16(x, il)
     xs = il.dense()[0].double() + il.dense()[1].double()
-    saved = ops._GEMM_FLAGS
-    try:
-        for flags in (16, 0):
-            ops._GEMM_FLAGS = flags
+    for flags in (16, 0):
+        with ops.gemm_flags(flags):
             for N in (576, 640):
                 w = (torch.randn(N, K, generator=g) / math.sqrt(K)).to(dev_)
                 ws = ops.split_f16(w); wil = ops.split_f16_interleaved(ws)
@@ -830,8 +824,6 @@ def test_gemm_large_problem_kernels_n_not_multiple_of_256(ops):
             slots = ops.vt_frame_slots(T, dev_)
             assert rel_l2((vh[:rows].double() + vl[:rows].double())[:, slots], v) < 1e-6, flags
             assert bool(torch.isnan(vh[rows:]).all()) and bool(torch.isnan(vl[rows:]).all()), flags
-    finally:
-        ops._GEMM_FLAGS = saved
 
 
 def test_gemm_persistent_blocks_walk_several_tiles(ops):
@@ -848,22 +840,20 @@ def test_gemm_persistent_blocks_walk_several_tiles(ops):
     w = (torch.randn(4096, K, generator=g) / math.sqrt(K)).to(dev_)
     ws = ops.split_f16(w); wil = ops.split_f16_interleaved(ws)
     b = torch.randn(4096, generator=g).to(dev_)
-    saved = ops._GEMM_FLAGS
-    try:
-        outs = []
-        for flags in (16, 16 | 4):               # (16 = CVX_GEMM_FLAG_NO_MEDIUM: 5000 rows would otherwise go to the medium-problem kernel)
-            ops._GEMM_FLAGS = flags
+    outs = []
+    for flags in (16, 16 | 4):               # (16 = CVX_GEMM_FLAG_NO_MEDIUM: 5000 rows would otherwise go to the medium-problem kernel)
+        with ops.gemm_flags(flags):
             o = ops.SplitIL(M, 4096, dev_)
             ops.gemm(x, w, torch.empty(M, 4096, device=dev_), w_split=ws, w_il=wil, a_split=il, bias=b, act=1, out_split=o, write_f32=False)
             outs.append(o.buf.clone())
-        want = F.gelu(xs @ w.double().T + b.double())
-        got = outs[0].view(M, 128, 2, 32)
-        assert rel_l2(got[:, :, 0].reshape(M, 4096).double() + got[:, :, 1].reshape(M, 4096).double(), want) < 1e-6
-        assert torch.equal(outs[0], outs[1])
-        # residual + fp32 on a narrower N (4 tile columns x 24 slots = 96 slots: one tile per block) and a wide one
-        r = torch.randn(M, 4096, generator=g).to(dev_)
-        c = torch.full((M, 4096), float("nan"), device=dev_)
-        ops._GEMM_FLAGS = 16
+    want = F.gelu(xs @ w.double().T + b.double())
+    got = outs[0].view(M, 128, 2, 32)
+    assert rel_l2(got[:, :, 0].reshape(M, 4096).double() + got[:, :, 1].reshape(M, 4096).double(), want) < 1e-6
+    assert torch.equal(outs[0], outs[1])
+    # residual + fp32 on a narrower N (4 tile columns x 24 slots = 96 slots: one tile per block) and a wide one
+    r = torch.randn(M, 4096, generator=g).to(dev_)
+    c = torch.full((M, 4096), float("nan"), device=dev_)
+    with ops.gemm_flags(16):
         ops.gemm(x, w, c, w_split=ws, w_il=wil, a_split=il, residual=r)
         assert rel_l2(c, xs @ w.double().T + r.double()) < 1e-6
         # QKV form with 16 heads: 12 tile columns x 24 slots = 288 slots, V blocks interleaved with q | k blocks in a block's walk
@@ -886,8 +876,6 @@ def test_gemm_persistent_blocks_walk_several_tiles(ops):
         assert rel_l2(qk[0].double() + qk[1].double(), (zq * c_[None, :, None, :] + rot * s_[None, :, None, :]).reshape(M, -1)) < 1e-6
         v = z[:, 2 * H * 64:].reshape(Bt, T, H, 64).permute(0, 2, 3, 1).reshape(Bt * H * 64, T)
         assert rel_l2((vt[0].double() + vt[1].double())[:, ops.vt_frame_slots(T, dev_)], v) < 1e-6
-    finally:
-        ops._GEMM_FLAGS = saved
 
 
 @pytest.mark.parametrize("M", [2100, 4096])

@@ -120,15 +120,11 @@ def test_nan_in_an_fp32_operand_raises_the_flag(ops):
         res = torch.randn(M, 512, generator=g).to(dev_)
         bbad = bias.clone(); bbad[300] = nan
         rbad = res.clone(); rbad[M - 1, 17] = nan
-        old = ops._GEMM_FLAGS
-        ops._GEMM_FLAGS = old | flags
-        try:
+        with ops.gemm_flags(flags):
             assert flagged(lambda: ops.gemm(a, w, c, bias=bias, residual=res, out_split=o, **kw)) == 0, (M, flags)
             assert flagged(lambda: ops.gemm(a, w, c, bias=bbad, residual=res, out_split=o, **kw)) != 0, (M, flags)
             assert flagged(lambda: ops.gemm(a, w, c, bias=bias, residual=rbad, out_split=o, **kw)) != 0, (M, flags)
             assert flagged(lambda: ops.gemm(a, w, c, bias=bbad, act=ops.ACT_GELU, out_split=o, write_f32=False, **kw)) != 0, (M, flags)
-        finally:
-            ops._GEMM_FLAGS = old
 
 
 def _full_width_state(kind="vomix"):

@@ -86,7 +86,7 @@ def f16x3_dma():
         a, w, c = r(M, k), r(n, k) / math.sqrt(k), torch.empty(M, n, device=dev)
         ws, asp = ops.split_f16(w), ops.split_act_f16(a)
         t = timeit(lambda: ops.gemm(a, w, c, w_split=ws, a_split=asp))
-        print(f"f16x3-dma[{os.environ.get('CVX_GEMM_STAGES','4')}st] {name:9s} N={n} K={k}: {t*1e3:8.3f} ms  {2*M*n*k/t/1e12:7.2f} TFLOP/s")
+        print(f"f16x3-dma {name:9s} N={n} K={k}: {t*1e3:8.3f} ms  {2*M*n*k/t/1e12:7.2f} TFLOP/s")
 
 
 if __name__ == "__main__" and os.environ.get("F16X3", "1") == "1":

@@ -67,8 +67,8 @@ for (N, K, K1, name, cnt) in [(3072, 1024, 0, "qkv", 8), (1024, 1024, 0, "out", 
     fn = lambda: ops.gemm(a_in, w, c, w_split=ws, w_il=wil, **kw)
     for rep in range(int(os.environ.get("ROUNDS", "3")) + 1):          # interleaved A/B/C rounds; the first one is a warm-up
         for flags in variants:
-            ops._GEMM_FLAGS = flags
-            t = timeit(fn, iters=10)
+            with ops.gemm_flags(flags):
+                t = timeit(fn, iters=10)
             if rep:
                 times[flags].append(t)
     times = {v: sorted(ts)[len(ts) // 2] for v, ts in times.items()}
