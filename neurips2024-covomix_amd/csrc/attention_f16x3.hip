@@ -357,6 +357,31 @@ __global__ __launch_bounds__(64 * NW * KS, (KS > 1 ? (NW * KS + 3) / 4 : ATT_WAV
 
 }  // namespace
 
+// Which attention_f16x3_kernel<NT, NW, KS> a launch takes (pure host arithmetic; launch_attention_f16x3 and the exported
+// cvx_attention_f16x3_form both call it).  T: frames per sequence, or the LONGEST sequence of a ragged batch; q_rows: query rows of
+// the launch.  Returns the form and writes queries per block, key groups and query waves per block.
+static int attention_f16x3_form(int32_t n_seq, int32_t T, int64_t q_rows, int32_t H, bool single, int* query_block, int* key_groups, int* query_waves)
+{
+    // 128-query blocks (4 waves, three blocks per CU).  256-query blocks (8 waves: half the L2 -> LDS tile traffic per score,
+    // one block per CU) measured 3 % SLOWER (218.6 vs 212.5 us, same joules; on zero operands 182 vs 159 us: the schedule
+    // loses what the traffic saves).
+    int qb = 128;
+    const int n_qt = (T + qb - 1) / qb;
+    const int64_t n_groups = (int64_t)n_seq * H;
+    const int64_t blocks = ((n_groups + 7) / 8) * 8 * n_qt;
+    // key-split groups for short launches (see the kernel): fewer than 2048 query rows = at most one 128-query block per CU (96 KiB of
+    // LDS with three groups).
+    int ksplit = 1, nwk = 4, form = CVX_ATT_FORM_A;
+    if (T >= 4 * KT && q_rows < 2048) {
+        ksplit = 3; form = CVX_ATT_FORM_B;
+        // half of the chip's SIMDs hold no wave at all when the 128-query blocks number fewer than 128: 64-query blocks (two query waves,
+        // four key groups: 8 waves per block) put a wave on every SIMD
+        if (blocks <= 128) { nwk = 2; ksplit = 4; qb = 64; form = CVX_ATT_FORM_C; }
+    }
+    *query_block = qb; *key_groups = ksplit; *query_waves = nwk;
+    return form + (single ? CVX_ATT_FORM_SINGLE_TERM : 0);
+}
+
 static int launch_attention_f16x3(const uint16_t* qk_hi, const uint16_t* qk_lo, const uint16_t* vt_hi, const uint16_t* vt_lo,
                                   float* out, uint16_t* out_hi, uint16_t* out_lo, const int32_t* cu_seqlens_dev,
                                   int32_t Bt, int32_t T, int64_t cols, int32_t Tp, int32_t H, float scale,
@@ -372,28 +397,14 @@ static int launch_attention_f16x3(const uint16_t* qk_hi, const uint16_t* qk_lo, 
     CVX_REQUIRE((((uintptr_t)qk_hi | (uintptr_t)qk_lo | (uintptr_t)vt_hi | (uintptr_t)vt_lo) & 15) == 0,
                 "attention_f16x3: inputs must be 16-byte aligned");
     if (Bt == 0) return CVX_OK;
-    // 128-query blocks (4 waves, three blocks per CU).  256-query blocks (8 waves: half the L2 -> LDS tile traffic per score,
-    // one block per CU) measured 3 % SLOWER (218.6 vs 212.5 us, same joules; on zero operands 182 vs 159 us: the schedule
-    // loses what the traffic saves).
-    int qb = 128;
-    int n_qt = (T + qb - 1) / qb;
+    int qb, ksplit, nwk;
+    const int64_t q_rows = cu_seqlens_dev ? cols : (int64_t)Bt * T;             // query rows of the launch
+    attention_f16x3_form(Bt, T, q_rows, H, single, &qb, &ksplit, &nwk);
+    const int n_qt = (T + qb - 1) / qb;
     const int n_groups = Bt * H;
-    dim3 grid((unsigned)(((n_groups + 7) / 8) * 8 * n_qt));
+    const dim3 grid((unsigned)(((n_groups + 7) / 8) * 8 * n_qt));
     if (out_hi) CVX_REQUIRE_SAT(s);
     uint32_t* sat = cvx_sat_flag_for(s);
-    // key-split groups for short launches (see the kernel): fewer than 2048 query rows = at most one 128-query block per CU (96 KiB of
-    // LDS with three groups).
-    int ksplit = 1, nwk = 4;
-    const int64_t q_rows = cu_seqlens_dev ? cols : (int64_t)Bt * T;             // query rows of the launch
-    if (T >= 4 * KT && q_rows < 2048) {
-        ksplit = 3;
-        // half of the chip's SIMDs hold no wave at all when the 128-query blocks number fewer than 128: 64-query blocks (two query waves,
-        // four key groups: 8 waves per block) put a wave on every SIMD
-        if (grid.x <= 128) {
-            nwk = 2; ksplit = 4; qb = 64; n_qt = (T + qb - 1) / qb;
-            grid = dim3((unsigned)(((n_groups + 7) / 8) * 8 * n_qt));
-        }
-    }
 #define CVX_ATT_LAUNCH_KS(NT_, KS_) CVX_ATT_LAUNCH_KW(NT_, 4, KS_)
 #define CVX_ATT_LAUNCH_KW(NT_, NW_, KS_)                                                                                                  \
     hipLaunchKernelGGL((attention_f16x3_kernel<NT_, NW_, KS_>), grid, dim3(64 * NW_ * KS_), 0, cvx_hip_stream(s),              \
@@ -435,4 +446,16 @@ extern "C" int cvx_attention_f16x3(const uint16_t* qk_hi, const uint16_t* qk_lo,
                                    int32_t Bt, int32_t T, int32_t Tp, int32_t H, float scale, cvx_stream_t s)
 {
     return cvx_attention_f16x3_scaled(qk_hi, qk_lo, vt_hi, vt_lo, out, out_hi, out_lo, Bt, T, Tp, H, scale, nullptr, nullptr, nullptr, s);
+}
+
+extern "C" int cvx_attention_f16x3_form(int32_t n_seq, int32_t max_T, int64_t q_rows, int32_t H, int32_t single_term,
+                                        int32_t* query_block, int32_t* key_groups, int32_t* query_waves)
+{
+    if (n_seq <= 0 || max_T <= 0 || H <= 0 || q_rows < max_T) return -1;
+    int qb, ks, nw;
+    const int form = attention_f16x3_form(n_seq, max_T, q_rows, H, single_term != 0, &qb, &ks, &nw);
+    if (query_block) *query_block = qb;
+    if (key_groups) *key_groups = ks;
+    if (query_waves) *query_waves = nw;
+    return form;
 }

@@ -759,6 +759,26 @@ def attention_f16x3(qk_split, vt_split, out: Optional[torch.Tensor], Bt: int, T:
     return out if out is not None else out_split
 
 
+ATTENTION_FORMS = ("A", "B", "C", "A1", "B1", "C1")
+
+
+def attention_form(Bt: int = 0, T: int = 0, H: int = 1, *, single_term: bool = False, ragged=None):
+    """Which attention_f16x3 kernel form the library launches for this problem: (name, queries per block, key groups,
+    query waves per block), name one of ATTENTION_FORMS (A: one key group; B: three; C: 64-query blocks, four; a trailing 1:
+    the single-term twin).  Host arithmetic of the library's own launch rule: no GPU needed.  ragged: a Ragged, or a plain
+    list of sequence lengths (Bt, T are then ignored)."""
+    if ragged is not None:
+        lengths = ragged.lengths if hasattr(ragged, "lengths") else [int(t) for t in ragged]
+        n, max_T, rows = len(lengths), max(lengths), sum(lengths)
+    else:
+        n, max_T, rows = Bt, T, Bt * T
+    qb, ks, nw = C.c_int32(), C.c_int32(), C.c_int32()
+    form = _lib.load().cvx_attention_f16x3_form(n, max_T, rows, H, int(single_term), C.byref(qb), C.byref(ks), C.byref(nw))
+    if form < 0:
+        raise ValueError(f"attention_form: no launch has n_seq={n} max_T={max_T} rows={rows} H={H}")
+    return ATTENTION_FORMS[form], qb.value, ks.value, nw.value
+
+
 def geglu(h: torch.Tensor, out: torch.Tensor, F: int) -> torch.Tensor:
     """out[r, c] = h[r, c] * gelu(h[r, F + c]) for c < F, zeros in the padding columns (text2semantic.py:154-157)."""
     _chk_f32(h, out)
