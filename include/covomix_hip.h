@@ -62,8 +62,9 @@ typedef const cvx_ctx* cvx_stream_t;
  * (device, stream) table and cvx_saturation_flag_bind / cvx_stream_set_cus / cvx_stream_cus.  108: cvx_t2s_decoder loses its
  * last two fields, the tuning hints group_loop and pairs_per_wave (the decode takes one row pair per wavefront and one group of
  * slots per thread block).  109: cvx_attention_f16x3_form (which kernel form a split-precision attention launch takes; host
- * arithmetic only, so that tests can place a problem on every form). */
-#define CVX_ABI_VERSION 109
+ * arithmetic only, so that tests can place a problem on every form).  110: CVX_ATT_FORM_D (256-query blocks, two query sets per
+ * wave, for launches of 512 such blocks and more); CVX_ATT_FORM_SINGLE_TERM is 4 (was 3). */
+#define CVX_ABI_VERSION 110
 int         cvx_version(void);
 const char* cvx_last_error_string(void);
 
@@ -314,15 +315,18 @@ int cvx_attention_f16x3_varlen(const uint16_t* qk_hi, const uint16_t* qk_lo, con
  * very function.  No GPU work, no stream, callable on a machine without a GPU.
  *   n_seq, H: sequences and heads; max_T: frames per sequence (equal-length batch) or the longest sequence (ragged batch);
  *   q_rows: query rows of the launch (n_seq * max_T, or the M packed rows of a ragged batch); single_term != 0: hi halves only.
- * Returns CVX_ATT_FORM_A / _B / _C, plus CVX_ATT_FORM_SINGLE_TERM for the single-term twins, or -1 for arguments no launch
+ * Returns CVX_ATT_FORM_A / _B / _C / _D, plus CVX_ATT_FORM_SINGLE_TERM for the single-term twins, or -1 for arguments no launch
  * can have; writes queries per block, key groups per block and query waves per block where the pointers are not NULL.
- *   A: 128-query blocks, one key group  (max_T < 128, or 2048 query rows and more)
+ *   D: 256-query blocks of four waves with two query sets each, one key group  (n_seq * H * ceil(max_T / 256) >= 512: the blocks
+ *      fill the two slots of every CU at least once; same bits per query as A; three-term launches only)
+ *   A: 128-query blocks, one key group  (otherwise: max_T < 128, or 2048 query rows and more)
  *   B: 128-query blocks, three key groups merged through LDS  (otherwise, more than 128 blocks of 128 queries)
  *   C: 64-query blocks of two query waves, four key groups    (otherwise, at most 128 such blocks) */
 #define CVX_ATT_FORM_A 0
 #define CVX_ATT_FORM_B 1
 #define CVX_ATT_FORM_C 2
-#define CVX_ATT_FORM_SINGLE_TERM 3
+#define CVX_ATT_FORM_D 3
+#define CVX_ATT_FORM_SINGLE_TERM 4
 int cvx_attention_f16x3_form(int32_t n_seq, int32_t max_T, int64_t q_rows, int32_t H, int32_t single_term,
                              int32_t* query_block, int32_t* key_groups, int32_t* query_waves);
 

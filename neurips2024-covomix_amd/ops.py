@@ -759,12 +759,13 @@ def attention_f16x3(qk_split, vt_split, out: Optional[torch.Tensor], Bt: int, T:
     return out if out is not None else out_split
 
 
-ATTENTION_FORMS = ("A", "B", "C", "A1", "B1", "C1")
+ATTENTION_FORMS = ("A", "B", "C", "D", "A1", "B1", "C1")       # (no D1: single-term launches stay on A1, which measured faster)
 
 
 def attention_form(Bt: int = 0, T: int = 0, H: int = 1, *, single_term: bool = False, ragged=None):
     """Which attention_f16x3 kernel form the library launches for this problem: (name, queries per block, key groups,
-    query waves per block), name one of ATTENTION_FORMS (A: one key group; B: three; C: 64-query blocks, four; a trailing 1:
+    query waves per block), name one of ATTENTION_FORMS (A: one key group; B: three; C: 64-query blocks, four; D: 256-query blocks whose
+    four waves own two query sets each, for launches of 512 such blocks and more, same bits per query as A; a trailing 1:
     the single-term twin).  Host arithmetic of the library's own launch rule: no GPU needed.  ragged: a Ragged, or a plain
     list of sequence lengths (Bt, T are then ignored)."""
     if ragged is not None:
