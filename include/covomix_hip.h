@@ -63,8 +63,10 @@ typedef const cvx_ctx* cvx_stream_t;
  * last two fields, the tuning hints group_loop and pairs_per_wave (the decode takes one row pair per wavefront and one group of
  * slots per thread block).  109: cvx_attention_f16x3_form (which kernel form a split-precision attention launch takes; host
  * arithmetic only, so that tests can place a problem on every form).  110: CVX_ATT_FORM_D (256-query blocks, two query sets per
- * wave, for launches of 512 such blocks and more); CVX_ATT_FORM_SINGLE_TERM is 4 (was 3). */
-#define CVX_ABI_VERSION 110
+ * wave, for launches of 512 such blocks and more); CVX_ATT_FORM_SINGLE_TERM is 4 (was 3).  111: text2semantic sampling controls -
+ * cvx_t2s_decoder grew filter_mode / top_p / n_dialogues at its end (top-p beside top-k), a dialogue queue may run under guidance
+ * (record pairs), cvx_t2s_sample_f32 (the filter + sampling of one decode step on caller-supplied logits). */
+#define CVX_ABI_VERSION 111
 int         cvx_version(void);
 const char* cvx_last_error_string(void);
 
@@ -587,7 +589,7 @@ int cvx_wav_to_int16(const float* wav, int16_t* pcm, int64_t n, cvx_stream_t s);
  * (covomix/covomix_model/text2semantic.py:748-820) at batch 1 with a KV cache: per decoder layer
  * Attention.forward for the causal self-attention (:225-270, rotary_embedding_torch.py:146-157) and the
  * cross-attention over [learned null k/v | encoder context] (:253-262), the GEGLU FeedForward (:154-167), then
- * final RMSNorm (:143-151), tied logits (:545), top_k (:126-132) + gumbel_sample (:105-113) from the caller's
+ * final RMSNorm (:143-151), tied logits (:545), top_k (:126-132) or top_p (:118-124) + gumbel_sample (:105-113) from the caller's
  * U(0,1) draws, eos bookkeeping (:803-818) and the embedding of the sampled ids as the next input.
  * No host synchronisation: positions live in the slot records on the device, so a captured graph replays.
  *
@@ -615,7 +617,23 @@ int cvx_wav_to_int16(const float* wav, int16_t* pcm, int64_t n, cvx_stream_t s);
  *       [1] step limit (<= uniform_steps, <= max_len), [2] flags; the device writes [3] status (0 pending, 1 running, 2 ended
  *       by its eos, 3 by its limit), [4] steps decoded, [5] the slot it ran in.  A slot whose dialogue ends takes the next
  *       pending one inside the sampling kernel of the same step (position 0, `start` as input) or idles when none is left;
- *       the caller fills the first `batch` slots itself (slot b <- dialogue b, queue[0] = batch).  Not with guidance.
+ *       the caller fills the first `batch` slots itself (slot b <- dialogue b, queue[0] = batch).
+ *   Continuous batching under guidance (queue != NULL and cfg_scale > 1): a guided utterance u occupies the dialogue records 2u
+ *       (text context; its uniforms and token row are the utterance's) and 2u + 1 (null context: [0] context rows = 1, kv_c row 0
+ *       of that record = the learned null key / value); the caller writes [1] and [2] of both alike.  The queue still counts
+ *       RECORDS: queue[1] = n_dialogues = twice the number of utterances (an odd n_dialogues is refused), and slot pair
+ *       (2s, 2s + 1) starts on records (2s, 2s + 1) with queue[0] = batch.  The even slot decides when the pair ends (eos unless
+ *       flag bit 0, or the step limit), writes [3] status, [4] steps and [5] slot into record 2u, MIRRORS them into record 2u + 1
+ *       ([3] and [4] equal, [5] = the odd slot), takes the next two records from the queue and re-arms both slots (position 0,
+ *       `start` as input of both); a pair is taken only if both of its records lie below queue[1]; with none left both slots
+ *       idle.  The token row of record 2u + 1 is a copy of that of 2u, as in the lock-step guided decode.
+ *   Filter (filter_mode): CVX_T2S_FILTER_TOP_K keeps the top_k largest logits (text2semantic.py:126-132: the reference's default is
+ *       top_k = ceil(0.1 * vocab); an entry is kept iff fewer than top_k logits are larger, so entries equal to the top_k-th
+ *       largest are all kept - torch.topk leaves open which of them it picks).  CVX_T2S_FILTER_TOP_P keeps entry i
+ *       iff the softmax mass of the entries sorted before it is <= top_p (:118-124), where "sorted before" means a larger logit, or
+ *       an equal logit at a lower index (the reference's torch.sort leaves the order of ties open).  Both act on the raw logits -
+ *       the guidance-combined ones under cfg_scale > 1 - before the temperature division and the Gumbel noise, and the kept set
+ *       is a function of the logits and the setting alone (not of the slot, the batch or the launch shape).
  * The caller must not ask for more than max_len steps per slot without a queue (extra steps are ignored on the device).
  */
 typedef struct {
@@ -643,9 +661,26 @@ typedef struct {
     int32_t* queue;                              /* NULL: slot b decodes dialogue b until the caller stops.  Else continuous batching (above) */
     int32_t* dialogues;
     const float* start;                          /* [dim] start token: the input of a slot that takes a new dialogue (queue != NULL) */
+    int32_t filter_mode;                         /* CVX_T2S_FILTER_TOP_K (0; top_k must lie in [1, vocab]) or CVX_T2S_FILTER_TOP_P (top_k unused) */
+    float top_p;                                 /* CVX_T2S_FILTER_TOP_P: the threshold, inside (0, 1) */
+    int32_t n_dialogues;                         /* host copy of queue[1] (0: not given).  Required - positive and even - for a queue under
+                                                  * guidance; the device still reads queue[1] */
 } cvx_t2s_decoder;
 
+#define CVX_T2S_FILTER_TOP_K 0
+#define CVX_T2S_FILTER_TOP_P 1
+
+/* CVX_EINVAL (nothing is launched) for an unknown filter_mode, top_k outside [1, vocab], top_p outside (0, 1) or an odd n_dialogues under
+ * guidance, as for every other inconsistent descriptor. */
 int cvx_t2s_decode_steps(const cvx_t2s_decoder* dec, int32_t n_steps, cvx_stream_t stream);
+
+/* The filter + sampling of one decode step alone (the device function cvx_t2s_decode_steps samples with; no slot state, no queue, no
+ * embedding write): tokens[r] = argmax_i (kept(r, i) ? logits[r, i] / max(temperature, 1e-10) + gumbel(uniforms[r, i]) : -inf), lowest
+ * index on ties, gumbel(u) = -log(-log(u)) with both logarithms clamped at 1e-20 (text2semantic.py:105-113).  logits, uniforms
+ * [rows, V] fp32 with V <= 1024; filter_mode / k / thres as cvx_t2s_decoder.filter_mode / top_k / top_p; tokens int64 [rows];
+ * kept NULL or uint8 [rows, V] (1 = entry passed the filter).  One thread block per row; rows do not influence each other. */
+int cvx_t2s_sample_f32(const float* logits, const float* uniforms, int64_t rows, int32_t V, int32_t filter_mode, int32_t k,
+                       float thres, float temperature, int64_t* tokens, uint8_t* kept, cvx_stream_t stream);
 
 /* out[r, c] = h[r, c] * gelu(h[r, F + c]) for c < F, 0 for F <= c < ld_out   (GEGLU, text2semantic.py:154-157;
  * the encoder's feed-forward; ld_out >= F pads the K dimension of the following GEMM). */

@@ -16,7 +16,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CVX_LIB_PATH") or os.path.join(_HERE, "libcovomix_hip.so")      # CVX_LIB_PATH: dev A/B builds
 
 _f32p = C.POINTER(C.c_float)
-ABI_VERSION = 110          # == cvx_version(): bumped whenever an argument struct or an entry point's meaning changes
+ABI_VERSION = 111          # == cvx_version(): bumped whenever an argument struct or an entry point's meaning changes
 
 
 class GemmArgs(C.Structure):
@@ -145,7 +145,11 @@ class T2SDecoder(C.Structure):
                [("temperature", C.c_float), ("layers", C.POINTER(T2SLayer))] + \
                [(n, C.c_void_p) for n in ("final_gamma", "emb", "rope_cos", "rope_sin", "uniforms",
                                           "x", "q", "att", "h", "logits", "tokens", "state")] + [("cfg_scale", C.c_float)] + \
-               [("uniform_steps", C.c_int32), ("queue", C.c_void_p), ("dialogues", C.c_void_p), ("start", C.c_void_p)]
+               [("uniform_steps", C.c_int32), ("queue", C.c_void_p), ("dialogues", C.c_void_p), ("start", C.c_void_p)] + \
+               [("filter_mode", C.c_int32), ("top_p", C.c_float), ("n_dialogues", C.c_int32)]
+
+
+T2S_FILTER_TOP_K, T2S_FILTER_TOP_P = 0, 1
 
 
 class ResblockArgs(C.Structure):
@@ -192,6 +196,8 @@ SIGNATURES = {
     "cvx_mel_magnitude_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p]),
     "cvx_mel_log_transpose_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]),
     "cvx_t2s_decode_steps": (C.c_int, [C.POINTER(T2SDecoder), C.c_int32, C.c_void_p]),
+    "cvx_t2s_sample_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float,
+                                     C.c_void_p, C.c_void_p, C.c_void_p]),
     "cvx_geglu_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_void_p]),
     "cvx_hubert_conv0_workspace_floats": (C.c_int64, [C.c_int64, C.c_int32]),
     "cvx_hubert_conv0_gn_gelu_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,

@@ -9,7 +9,8 @@
 // depend on the batch size, the slot or the position of the other slots: results are bit-identical to batch 1.
 // CONTINUOUS BATCHING (round 6): with a dialogue queue (cvx_t2s_decoder.queue) a slot whose dialogue has sampled its eos (or
 // reached its step limit) takes the next pending dialogue INSIDE sample_kernel - no host round trip, no idle slot-steps; the
-// per-dialogue buffers (context k/v, uniforms, tokens) are indexed by the dialogue number the slot record carries.
+// per-dialogue buffers (context k/v, uniforms, tokens) are indexed by the dialogue number the slot record carries.  Under guidance a
+// slot PAIR decodes a pair of dialogue records (text context, null context) and the even slot refills both.
 // Kernels (all fp32, fp32 accumulate):
 //   gemv_kernel<MODE>   block = 4 waves, every wave owns TWO output rows (the pairs are chosen so that the epilogue
 //                       has both members of a RoPE pair / a GEGLU (value, gate) pair in one wave); the input vector is
@@ -17,8 +18,8 @@
 //                       text2semantic.py:143-151) on the way; rows stream with 16-byte loads + a wave reduction.
 //   attn_kernel         one block per head over the cached keys (self: roped keys [0, pos]; cross: learned null k/v +
 //                       the encoder context, text2semantic.py:253-262); 16 lanes per key for coalesced 256-byte rows.
-//   sample_kernel       top-k (k = ceil(0.1 * V), :126-132) + Gumbel argmax (:105-113) from caller-supplied U(0,1)
-//                       draws, eos bookkeeping (:803-818), and the embedding of the sampled ids = next step's input.
+//   sample_kernel       the logit filter - top-k (:126-132; k from the descriptor) or top-p (:118-124) - + Gumbel argmax (:105-113) from
+//                       caller-supplied U(0,1) draws, eos bookkeeping (:803-818), and the embedding of the sampled ids = next step's input.
 // The reference rotates ALL cached keys again every step with rotary_embedding_torch's interleaved pairs
 // (rotary_embedding_torch.py:146-157); rotating a key once at its own position when it enters the cache is the same
 // arithmetic.  Interleaved pairs (2i, 2i+1) become half-split pairs (i, i+32) by permuting the rows of to_q / to_k
@@ -503,7 +504,7 @@ __global__ __launch_bounds__(256) void attn_kernel(const AttnArgs a)
     attn_body(a, blockIdx.x, blockIdx.y, gridDim.x, sc, red, part);
 }
 
-// ---------------------------------------------------------------- top-k + Gumbel argmax, eos bookkeeping, next input
+// ---------------------------------------------------------------- logit filter + Gumbel argmax, eos bookkeeping, next input
 struct SampleArgs {
     const float* logits;     // [batch][streams, V]
     const float* uniforms;   // [dialogue][uniform_steps][streams, V]
@@ -521,16 +522,110 @@ struct SampleArgs {
     float inv_temp;
     float cfg_scale;         // > 1: classifier-free guidance (text2semantic.py:780-792) - slots 2u (text context) and 2u + 1 (context
                              // masked out: the learned null key / value only) decode the SAME tokens: slot 2u samples from
-                             // null + (cond - null) * cfg_scale and feeds both; one-output models
+                             // null + (cond - null) * cfg_scale and feeds both; one-output models.  With a queue the pair decodes the
+                             // dialogue records (2u', 2u' + 1) and the even slot refills both
+    float top_p;             // FILT_TOP_P: the nucleus threshold
 };
 
-// NT threads (a multiple of 64, <= 1024); every thread owns the vocabulary entries tid, tid + NT, ...  The selection is an
-// exact function of the logits and the uniforms (rank counting, then argmax with the lowest index on ties), so it does not
-// depend on NT.  lg: 1024 floats, bv / bi: 16 entries, chosen: one int of LDS.
-template <int NT>
-__device__ __forceinline__ void sample_body(const SampleArgs& a, int b, float* lg, float* bv, int* bi, int* chosen)
+enum { FILT_TOP_K = CVX_T2S_FILTER_TOP_K, FILT_TOP_P = CVX_T2S_FILTER_TOP_P };
+
+// One row of logits -> one token: filter (text2semantic.py:118-132), then argmax of kept / temperature + Gumbel noise from the row's
+// uniform draws (:105-113).  lrow: the logits; nrow: NULL, or the null-context logits of a guided pair (the filter then acts on
+// null + (cond - null) * cfg_scale).  NT threads (a multiple of 64, <= 1024); every thread owns the vocabulary entries tid, tid + NT, ...
+// The kept set and the token are exact functions of the logits, the threshold and the uniforms, so they do not depend on NT, the slot,
+// the batch or the neighbouring slots:
+//   FILT_TOP_K  rank counting (entry i is kept iff fewer than top_k logits are larger: any order gives the same count);
+//   FILT_TOP_P  entry i is kept iff the softmax mass of the entries sorted before it is <= top_p (F.pad(cum_probs > thres, (1, -1)),
+//               :120-122).  "Sorted before" = a larger logit, or an equal logit at a LOWER INDEX (torch.sort leaves the order of ties
+//               open; this is the stable descending order).  The mass is summed per entry over ex[j] = exp(l_j - max) in ascending j
+//               (adding 0 for the entries that do not count), and compared with top_p times the sum of all ex[j] in ascending j - the
+//               same additions in the same order whoever computes them.  The largest entry has mass 0 before it and is always kept.
+// then argmax with the lowest index on ties.  KEEP: also write the kept mask (the stand-alone entry point).
+// lg: 1024 floats, ex: 1024 floats (FILT_TOP_P only), bv / bi: 16 entries, chosen: one int of LDS.  Returns the token (block-uniform);
+// the caller synchronises before it calls again.
+template <int NT, int FILT, bool KEEP>
+__device__ __forceinline__ int sample_select(const float* lrow, const float* nrow, float cfg_scale, const float* urow, int V, int top_k,
+                                             float top_p, float inv_temp, uint8_t* keep, float* lg, float* ex, float* bv, int* bi, int* chosen)
 {
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    for (int i = tid; i < V; i += NT) {
+        const float c = aload(lrow + i);
+        if (nrow) {             // null_logits + (logits - null_logits) * cond_scale, the reference's operation order (no contraction here)
+            const float n = aload(nrow + i);
+            lg[i] = n + (c - n) * cfg_scale;
+        } else lg[i] = c;
+    }
+    if (tid < 4 && V + tid < ((V + 3) & ~3)) lg[V + tid] = -INFINITY;      // (the loops below read whole 4-vectors)
+    __syncthreads();
+    if (FILT == FILT_TOP_P) {
+        float m = -INFINITY;
+        for (int i = tid; i < V; i += NT) m = fmaxf(m, lg[i]);
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+        if (lane == 0) bv[wid] = m;
+        __syncthreads();
+        m = bv[0];
+        for (int w = 1; w < NT / 64; ++w) m = fmaxf(m, bv[w]);             // (a maximum: exact in any order)
+        for (int i = tid; i < ((V + 3) & ~3); i += NT) ex[i] = i < V ? expf(lg[i] - m) : 0.f;
+        __syncthreads();                                                   // (bv is written again below)
+    }
+    float val = -INFINITY;
+    int idx = tid;
+    for (int i = tid; i < V; i += NT) {
+        const float me = lg[i];
+        bool kept;
+        if (FILT == FILT_TOP_P) {
+            float before = 0.f, tot = 0.f;
+            for (int j = 0; j < V; j += 4) {
+                const f32x4 l4 = *reinterpret_cast<const f32x4*>(lg + j);
+                const f32x4 e4 = *reinterpret_cast<const f32x4*>(ex + j);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const bool bf = l4[e] > me || (l4[e] == me && j + e < i);
+                    before += bf ? e4[e] : 0.f;
+                    tot += e4[e];
+                }
+            }
+            kept = before <= top_p * tot;
+        } else {
+            int cnt = 0;
+            for (int j = 0; j < V; j += 4) {         // rank of entry i = number of larger logits (exact: any order gives the same count)
+                const f32x4 l4 = *reinterpret_cast<const f32x4*>(lg + j);
+                cnt += (l4[0] > me ? 1 : 0) + (l4[1] > me ? 1 : 0) + (l4[2] > me ? 1 : 0) + (l4[3] > me ? 1 : 0);
+            }
+            kept = cnt < top_k;
+        }
+        if (KEEP) keep[i] = kept ? 1 : 0;
+        if (kept) {
+            const float u = urow[i];
+            const float g = -logf(fmaxf(-logf(fmaxf(u, 1e-20f)), 1e-20f));
+            const float v = me * inv_temp + g;
+            if (v > val) { val = v; idx = i; }       // (ascending i: the lowest index wins ties)
+        }
+    }
+    // argmax, lowest index on ties (torch.argmax)
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float ov = __shfl_xor(val, o, 64);
+        const int oi = __shfl_xor(idx, o, 64);
+        if (ov > val || (ov == val && oi < idx)) { val = ov; idx = oi; }
+    }
+    if (lane == 0) { bv[wid] = val; bi[wid] = idx; }
+    __syncthreads();
+    if (tid == 0) {
+        float best = bv[0]; int bt = bi[0];
+        for (int w = 1; w < NT / 64; ++w)
+            if (bv[w] > best || (bv[w] == best && bi[w] < bt)) { best = bv[w]; bt = bi[w]; }
+        *chosen = bt;
+    }
+    __syncthreads();
+    return *chosen;
+}
+
+template <int NT, int FILT>
+__device__ __forceinline__ void sample_body(const SampleArgs& a, int b, float* lg, float* ex, float* bv, int* bi, int* chosen)
+{
+    const int tid = threadIdx.x;
     const bool cfg = a.cfg_scale > 1.0f;
     if (cfg && (b & 1)) return;                     // the null-context slot follows its partner (block-uniform)
     int* const state = a.state + SR * b;
@@ -539,49 +634,11 @@ __device__ __forceinline__ void sample_body(const SampleArgs& a, int b, float* l
     const int64_t dlg = aloadi(state + 4);          // the dialogue this slot decodes (== b without a queue)
     bool eos = false;
     for (int s = 0; s < a.streams; ++s) {
-        for (int i = tid; i < a.V; i += NT) {
-            const float c = aload(a.logits + ((int64_t)b * a.streams + s) * a.V + i);
-            if (cfg) {          // null_logits + (logits - null_logits) * cond_scale, the reference's operation order (no contraction here)
-                const float n = aload(a.logits + ((int64_t)(b + 1) * a.streams + s) * a.V + i);
-                lg[i] = n + (c - n) * a.cfg_scale;
-            } else lg[i] = c;
-        }
-        if (tid < 4 && a.V + tid < ((a.V + 3) & ~3)) lg[a.V + tid] = -INFINITY;      // (the rank count below reads whole 4-vectors)
-        __syncthreads();
-        float val = -INFINITY;
-        int idx = tid;
-        for (int i = tid; i < a.V; i += NT) {
-            const float me = lg[i];
-            int cnt = 0;
-            for (int j = 0; j < a.V; j += 4) {       // rank of entry i = number of larger logits (exact: any order gives the same count)
-                const f32x4 l4 = *reinterpret_cast<const f32x4*>(lg + j);
-                cnt += (l4[0] > me ? 1 : 0) + (l4[1] > me ? 1 : 0) + (l4[2] > me ? 1 : 0) + (l4[3] > me ? 1 : 0);
-            }
-            if (cnt < a.top_k) {
-                const float u = a.uniforms[((dlg * a.uniform_steps + pos) * a.streams + s) * a.V + i];
-                const float g = -logf(fmaxf(-logf(fmaxf(u, 1e-20f)), 1e-20f));
-                const float v = me * a.inv_temp + g;
-                if (v > val) { val = v; idx = i; }   // (ascending i: the lowest index wins ties)
-            }
-        }
-        // argmax, lowest index on ties (torch.argmax)
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const float ov = __shfl_xor(val, o, 64);
-            const int oi = __shfl_xor(idx, o, 64);
-            if (ov > val || (ov == val && oi < idx)) { val = ov; idx = oi; }
-        }
-        if (lane == 0) { bv[wid] = val; bi[wid] = idx; }
-        __syncthreads();
-        if (tid == 0) {
-            float best = bv[0]; int bt = bi[0];
-            for (int w = 1; w < NT / 64; ++w)
-                if (bv[w] > best || (bv[w] == best && bi[w] < bt)) { best = bv[w]; bt = bi[w]; }
-            *chosen = bt;
-            a.tokens[(dlg * a.streams + s) * a.max_len + pos] = bt;
-        }
-        __syncthreads();
-        const int tok = *chosen;
+        const int tok = sample_select<NT, FILT, false>(a.logits + ((int64_t)b * a.streams + s) * a.V,
+                                                       cfg ? a.logits + ((int64_t)(b + 1) * a.streams + s) * a.V : nullptr, a.cfg_scale,
+                                                       a.uniforms + ((dlg * a.uniform_steps + pos) * a.streams + s) * a.V, a.V, a.top_k,
+                                                       a.top_p, a.inv_temp, nullptr, lg, ex, bv, bi, chosen);
+        if (tid == 0) a.tokens[(dlg * a.streams + s) * a.max_len + pos] = tok;
         eos = eos || (tok == a.eos_id);
         for (int d = tid; d < a.dim_emb; d += NT) {
             const float e = a.emb[(int64_t)tok * a.dim_emb + d];
@@ -601,44 +658,91 @@ __device__ __forceinline__ void sample_body(const SampleArgs& a, int b, float* l
         return;
     }
     // continuous batching: the dialogue ends with its first eos (text2semantic.py:803-818) or at its step limit; the slot then
-    // takes the next pending dialogue: position 0, the start token as input, that dialogue's context / uniforms / token rows
+    // takes the next pending dialogue: position 0, the start token as input, that dialogue's context / uniforms / token rows.
+    // Guidance: the even slot decides for the pair; the pair's dialogue records are (dlg, dlg + 1) and the queue hands out two records
+    // at a time.  A pair is taken only when BOTH of its records exist (nxt + 1 < n), so a refill never indexes past the n dialogues
+    // whatever the caller put into queue[1].
+    int* const sn = state + SR;                     // the null-context slot of a guided pair (touched under cfg only)
     const bool ends_eos = eos && !(aloadi(state + 6) & 1);
     const bool ends = ends_eos || pos + 1 >= aloadi(state + 5);        // (block-uniform: `eos` comes from LDS, the record is read by all)
     if (!ends) {
-        if (tid == 0) state[0] = pos + 1;
+        if (tid == 0) { state[0] = pos + 1; if (cfg) sn[0] = pos + 1; }
         return;
     }
     if (tid == 0) {
         int* const dr = a.dialogues + SR * dlg;
         dr[4] = pos + 1;
         dr[5] = b;
+        if (cfg) { dr[SR + 4] = pos + 1; dr[SR + 5] = b + 1; }
         __threadfence();
         dr[3] = ends_eos ? 2 : 3;
-        const int nxt = atomicAdd(a.queue, 1);
-        *chosen = nxt < aloadi(a.queue + 1) ? nxt : -1;
+        if (cfg) dr[SR + 3] = ends_eos ? 2 : 3;
+        const int take = cfg ? 2 : 1;
+        const int nxt = atomicAdd(a.queue, take);
+        *chosen = nxt + take - 1 < aloadi(a.queue + 1) ? nxt : -1;
     }
     __syncthreads();
     const int nxt = *chosen;
     if (nxt < 0) {                                  // nothing pending: the slot idles (every kernel clamps / skips at max_len)
-        if (tid == 0) { state[0] = a.max_len; state[1] = 1; }
+        if (tid == 0) {
+            state[0] = a.max_len; state[1] = 1;
+            if (cfg) { sn[0] = a.max_len; sn[1] = 1; }
+        }
         return;
     }
-    for (int d = tid; d < a.dim_emb * a.streams; d += NT) a.x[(int64_t)b * a.streams * a.dim_emb + d] = a.start[d];
+    for (int d = tid; d < a.dim_emb * a.streams; d += NT) {
+        const float e = a.start[d];
+        a.x[(int64_t)b * a.streams * a.dim_emb + d] = e;
+        if (cfg) a.x[(int64_t)(b + 1) * a.streams * a.dim_emb + d] = e;
+    }
     if (tid == 0) {
         int* const dn = a.dialogues + SR * nxt;
         state[0] = 0; state[1] = 0; state[2] = 0; state[3] = dn[0]; state[4] = nxt; state[5] = dn[1]; state[6] = dn[2];
         dn[5] = b;
         dn[3] = 1;
+        if (cfg) {
+            sn[0] = 0; sn[1] = 0; sn[2] = 0; sn[3] = dn[SR + 0]; sn[4] = nxt + 1; sn[5] = dn[1]; sn[6] = dn[2];
+            dn[SR + 5] = b + 1;
+            dn[SR + 3] = 1;
+        }
     }
 }
 
+// FILT_TOP_K is the instruction stream of every default launch; the nucleus filter's second LDS array (exp(l - max), 4 KiB on top of the
+// 4 KiB of logits) exists in its own instantiation only
+template <int FILT>
 __global__ __launch_bounds__(1024) void sample_kernel(const SampleArgs a)
 {
     __shared__ __attribute__((aligned(16))) float lg[1024];
+    __shared__ __attribute__((aligned(16))) float ex[FILT == FILT_TOP_P ? 1024 : 4];
     __shared__ float bv[16];
     __shared__ int bi[16];
     __shared__ int chosen;
-    sample_body<1024>(a, blockIdx.x, lg, bv, bi, &chosen);
+    sample_body<1024, FILT>(a, blockIdx.x, lg, ex, bv, bi, &chosen);
+}
+
+// the filter + sampling of sample_kernel alone: one block per row, no slot state, no queue, no embedding write
+struct SampleRowsArgs {
+    const float* logits;     // [rows, V]
+    const float* uniforms;   // [rows, V]
+    int64_t* tokens;         // [rows]
+    uint8_t* kept;           // [rows, V] or NULL
+    int V, top_k;
+    float top_p, inv_temp;
+};
+
+template <int FILT, bool KEEP>
+__global__ __launch_bounds__(1024) void sample_rows_kernel(const SampleRowsArgs a)
+{
+    __shared__ __attribute__((aligned(16))) float lg[1024];
+    __shared__ __attribute__((aligned(16))) float ex[FILT == FILT_TOP_P ? 1024 : 4];
+    __shared__ float bv[16];
+    __shared__ int bi[16];
+    __shared__ int chosen;
+    const int64_t r = blockIdx.x;
+    const int tok = sample_select<1024, FILT, KEEP>(a.logits + r * a.V, nullptr, 1.f, a.uniforms + r * a.V, a.V, a.top_k, a.top_p, a.inv_temp,
+                                                    KEEP ? a.kept + r * a.V : nullptr, lg, ex, bv, bi, &chosen);
+    if (threadIdx.x == 0) a.tokens[r] = tok;
 }
 
 __global__ __launch_bounds__(256) void geglu_kernel(const float* __restrict__ h, float* __restrict__ out, int64_t rows,
@@ -685,6 +789,37 @@ extern "C" int cvx_geglu_f32(const float* h, float* out, int64_t rows, int32_t F
     return CVX_OK;
 }
 
+// the filter settings of the decode and of cvx_t2s_sample_f32: top-k needs 1 <= k <= V, top-p a threshold inside (0, 1)
+static int t2s_filter_validate(int32_t mode, int32_t k, float thres, int32_t V)
+{
+    CVX_REQUIRE(mode == CVX_T2S_FILTER_TOP_K || mode == CVX_T2S_FILTER_TOP_P, "t2s: unknown filter mode %d", mode);
+    CVX_REQUIRE(mode != CVX_T2S_FILTER_TOP_K || (k >= 1 && k <= V), "t2s: top_k = %d outside [1, vocab = %d]", k, V);
+    CVX_REQUIRE(mode != CVX_T2S_FILTER_TOP_P || (thres > 0.f && thres < 1.f), "t2s: top_p = %g outside (0, 1)", (double)thres);
+    return CVX_OK;
+}
+
+extern "C" int cvx_t2s_sample_f32(const float* logits, const float* uniforms, int64_t rows, int32_t V, int32_t filter_mode, int32_t k,
+                                  float thres, float temperature, int64_t* tokens, uint8_t* kept, cvx_stream_t s)
+{
+    CVX_REQUIRE(logits && uniforms && tokens && rows >= 0 && rows <= 0x7fffffff && V > 0 && V <= 1024 && temperature >= 0.f,
+                "t2s_sample: bad arguments (rows=%lld V=%d)", (long long)rows, V);
+    const int frc = t2s_filter_validate(filter_mode, k, thres, V);
+    if (frc != CVX_OK) return frc;
+    if (rows == 0) return CVX_OK;
+    const SampleRowsArgs a{logits, uniforms, tokens, kept, V, k, thres, 1.0f / fmaxf(temperature, 1e-10f)};
+    const dim3 grid((unsigned)rows), block(1024);
+    hipStream_t st = cvx_hip_stream(s);
+    if (filter_mode == CVX_T2S_FILTER_TOP_P) {
+        if (kept) hipLaunchKernelGGL((sample_rows_kernel<FILT_TOP_P, true>), grid, block, 0, st, a);
+        else hipLaunchKernelGGL((sample_rows_kernel<FILT_TOP_P, false>), grid, block, 0, st, a);
+    } else {
+        if (kept) hipLaunchKernelGGL((sample_rows_kernel<FILT_TOP_K, true>), grid, block, 0, st, a);
+        else hipLaunchKernelGGL((sample_rows_kernel<FILT_TOP_K, false>), grid, block, 0, st, a);
+    }
+    CVX_CHECK_LAUNCH("cvx_t2s_sample_f32");
+    return CVX_OK;
+}
+
 static int t2s_validate(const cvx_t2s_decoder* d, int32_t n_steps)
 {
     CVX_REQUIRE(d && d->layers && n_steps >= 0, "t2s_decode: null decoder");
@@ -693,7 +828,7 @@ static int t2s_validate(const cvx_t2s_decoder* d, int32_t n_steps)
                 (d->streams == 1 || d->dim <= 1024) && d->vocab > 0 && d->vocab <= 1024 &&
                 d->ff_inner > 0 && d->ff_inner_pad >= d->ff_inner && d->ff_inner_pad % 4 == 0 && d->ff_inner_pad <= T2S_MAX_DIM &&
                 d->n_ctx >= 0 && d->n_ctx <= T2S_MAX_KEYS && d->max_len > 0 && d->max_len <= T2S_MAX_KEYS &&
-                d->top_k > 0 && d->top_k <= d->vocab && d->temperature >= 0.f && d->batch >= 1 && d->batch <= T2S_MAX_BATCH &&
+                d->temperature >= 0.f && d->batch >= 1 && d->batch <= T2S_MAX_BATCH &&
                 d->uniform_steps > 0 &&
                 d->ctx_rows > 0 && d->ctx_rows <= T2S_MAX_KEYS && d->n_ctx <= d->ctx_rows,
                 "t2s_decode: bad dimensions (dim=%d inner=%d heads=%d streams=%d dim_emb=%d vocab=%d ff=%d/%d n_ctx=%d/%d max_len=%d batch=%d)",
@@ -702,8 +837,14 @@ static int t2s_validate(const cvx_t2s_decoder* d, int32_t n_steps)
     CVX_REQUIRE(!(d->cfg_scale > 1.f) || (d->streams == 1 && d->batch % 2 == 0 && d->n_ctx == 0),
                 "t2s_decode: guidance (cfg_scale > 1) needs a one-output model, an even batch (context / null-context slot pairs) and "
                 "per-slot context rows (n_ctx == 0)");
-    CVX_REQUIRE(!d->queue || (d->dialogues && d->start && !(d->cfg_scale > 1.f) && d->n_ctx == 0),
-                "t2s_decode: a dialogue queue needs the dialogue records and the start token, per-dialogue context rows (n_ctx == 0) and no guidance");
+    CVX_REQUIRE(!d->queue || (d->dialogues && d->start && d->n_ctx == 0),
+                "t2s_decode: a dialogue queue needs the dialogue records, the start token and per-dialogue context rows (n_ctx == 0)");
+    CVX_REQUIRE(!(d->queue && d->cfg_scale > 1.f) || (d->n_dialogues > 0 && d->n_dialogues % 2 == 0),
+                "t2s_decode: a dialogue queue under guidance holds record PAIRS (text context, null context): n_dialogues = %d must be "
+                "the even, positive number of records", d->n_dialogues);
+    CVX_REQUIRE(d->n_dialogues >= 0, "t2s_decode: n_dialogues = %d", d->n_dialogues);
+    const int frc = t2s_filter_validate(d->filter_mode, d->top_k, d->top_p, d->vocab);
+    if (frc != CVX_OK) return frc;
     CVX_REQUIRE(d->final_gamma && d->emb && d->rope_cos && d->rope_sin && d->uniforms && d->x && d->q && d->att && d->h &&
                 d->logits && d->tokens && d->state, "t2s_decode: null buffer");
     for (int l = 0; l < d->depth; ++l) {
@@ -767,8 +908,9 @@ extern "C" int cvx_t2s_decode_steps(const cvx_t2s_decoder* d, int32_t n_steps, c
         launch_gemv<MODE_LOGITS>(g, d->streams * ((d->vocab + 1) / 2), nb, st);
         SampleArgs sa{d->logits, d->uniforms, d->emb, d->x, d->tokens, d->state, d->queue, d->dialogues, d->start, nb, d->uniform_steps,
                       d->vocab, d->dim_emb, d->streams, d->max_len, d->top_k, d->vocab - 1, 1.0f / fmaxf(d->temperature, 1e-10f),
-                      d->cfg_scale};
-        hipLaunchKernelGGL(sample_kernel, dim3((unsigned)nb), dim3(1024), 0, st, sa);
+                      d->cfg_scale, d->top_p};
+        if (d->filter_mode == CVX_T2S_FILTER_TOP_P) hipLaunchKernelGGL(sample_kernel<FILT_TOP_P>, dim3((unsigned)nb), dim3(1024), 0, st, sa);
+        else hipLaunchKernelGGL(sample_kernel<FILT_TOP_K>, dim3((unsigned)nb), dim3(1024), 0, st, sa);
     }
     CVX_CHECK_LAUNCH("cvx_t2s_decode_steps");
     return CVX_OK;

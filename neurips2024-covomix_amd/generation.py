@@ -71,6 +71,15 @@ def build_parser() -> ArgumentParser:
     p.add_argument("--km_path", type=str, default=None, help="k-means model (joblib) for --hubert_ckpt")
     p.add_argument("--nfe", type=int, default=32, help="extension: CFG-combined field evaluations of the midpoint solver (32 = the "
                    "reference's ode_step_size 0.0625, acoustic.py:586-591; 64 = BASELINE config 5's 64-step setting)")
+    p.add_argument("--t2s_temperature", type=float, default=None, help="extension: sampling temperature of the text2semantic decode "
+                   "(default: the reference's 1.0)")
+    p.add_argument("--t2s_cond_scale", type=float, default=None, help="extension: classifier-free guidance of the text2semantic decode "
+                   "(> 1 needs a checkpoint trained with cond_drop_prob > 0, one-output models; default: the reference's 1.0 = off)")
+    p.add_argument("--t2s_filter", type=str, choices=["top_k", "top_p"], default=None, help="extension: logit filter of the text2semantic "
+                   "decode (text2semantic.py:118-132; default: the reference's top_k)")
+    p.add_argument("--t2s_filter_thres", type=float, default=None, help="extension: the filter's thres (top_k: k = ceil(thres * vocab), "
+                   "reference default 0.1; top_p: the nucleus mass, reference default 0.9, inside (0, 1))")
+    p.add_argument("--t2s_top_k", type=int, default=None, help="extension: an explicit k for --t2s_filter top_k (overrides the thres)")
     p.add_argument("--gpus", type=int, default=1, help="extension: from a plain shell, start this many ranks (one per GPU, "
                    "utterances sharded; under torch.distributed.run the launcher's WORLD_SIZE is used instead)")
     return p
@@ -164,10 +173,33 @@ def _tokenize(txt: str) -> torch.Tensor:
     return _TOKENIZER([remove_punctuation(txt).lower()], padding=True, truncation=True, return_tensors="pt").input_ids
 
 
-def _predict_turns(work, t2s, device, seed: int, slots: int = 64) -> dict:
+def t2s_sampling_kwargs(args) -> dict:
+    """The --t2s_* flags as keywords of CoVoMixModel.synthesis_sample_text2semantic; a flag that was not given adds nothing (the
+    facade's defaults are the reference's behaviour)."""
+    kw = {}
+    if args.t2s_temperature is not None:
+        kw["temprature"] = float(args.t2s_temperature)
+    if args.t2s_cond_scale is not None:
+        kw["cond_scale"] = float(args.t2s_cond_scale)
+    if args.t2s_filter is not None:
+        kw["filter_logits_fn"] = args.t2s_filter
+    fkw = {}
+    if args.t2s_filter_thres is not None:
+        fkw["thres"] = float(args.t2s_filter_thres)
+    if args.t2s_top_k is not None:
+        if (args.t2s_filter or "top_k") != "top_k":
+            raise ValueError("--t2s_top_k goes with --t2s_filter top_k")
+        fkw["k"] = int(args.t2s_top_k)
+    if fkw:
+        kw["filter_fn_kwargs"] = fkw
+    return kw
+
+
+def _predict_turns(work, t2s, device, seed: int, slots: int = 64, sampling=None) -> dict:
     """(name, turn) -> predicted semantic tokens (int64 numpy).  work: list of (name, turn, source).  Sources that are
     already tokens are read; the others are decoded by text2semantic on the GPU through `slots` decode slots, every turn
-    with its OWN stream of uniforms (seeded from (--seed, name, turn)): the tokens do not depend on batching or ranks."""
+    with its OWN stream of uniforms (seeded from (--seed, name, turn)): the tokens do not depend on batching or ranks.
+    sampling: the --t2s_* flags as keywords (t2s_sampling_kwargs)."""
     out, todo = {}, []
     for name, k, (kind, v) in work:
         if kind == "sem":
@@ -190,7 +222,8 @@ def _predict_turns(work, t2s, device, seed: int, slots: int = 64) -> dict:
             for name, k, _ in part:
                 g = torch.Generator(device=device).manual_seed(_stable_seed(seed, name, k, 1))
                 uniforms.append(torch.rand(L, S, V, device=device, generator=g))
-            toks = t2s.synthesis_sample_text2semantic([ids.to(device) for _, _, ids in part], uniforms=uniforms, slots=slots)
+            toks = t2s.synthesis_sample_text2semantic([ids.to(device) for _, _, ids in part], uniforms=uniforms, slots=slots,
+                                                      **(sampling or {}))
             for (name, k, _), t in zip(part, toks):
                 out[(name, k)] = t.cpu().numpy().astype(np.int64)
     return out
@@ -287,6 +320,7 @@ def run(dialogue: bool, argv=None) -> int:
     model.eval()
     model = model.to(device)
     model.nfe = int(args.nfe)
+    t2s_kw = t2s_sampling_kwargs(args)
     if rank == 0:
         with open(os.path.join(args.saved_dir, "config.txt"), "w") as f:
             f.write("Vocoder: " + str(dict(h)) + "\n")
@@ -423,12 +457,12 @@ def run(dialogue: bool, argv=None) -> int:
     batch_log: list = []                     # (utterances, frames in the launch, generated frames, seconds) per batch -> last_stats
     load_s = 0.0
     if mode == "off":       # ---- text2semantic for this rank's utterances first (not timed, as in round 4), then ONE global packing
-        pred = _predict_turns(work, t2s, device, args.seed)
+        pred = _predict_turns(work, t2s, device, args.seed, sampling=t2s_kw)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     batch_log_t[0] = t0
     if mode == "batch":     # ---- every turn of this rank through the continuously batched decode (timed), then ONE global packing
-        pred = _predict_turns(work, t2s, device, args.seed)
+        pred = _predict_turns(work, t2s, device, args.seed, sampling=t2s_kw)
     head_start = not two_stage and len(mine) >= 2 * HEAD_START
     if head_start:
         # ---- a large directory: the model inputs of the first HEAD_START utterances are read, their fullest first-fit-decreasing bin
@@ -482,7 +516,7 @@ def run(dialogue: bool, argv=None) -> int:
                     else:
                         keep += b
                 pool = [pool[i] for i in sorted(keep)]
-        nfr = pl.run_two_stage(groups, lambda g: _predict_turns(g, t2s, device, args.seed), solve, device,
+        nfr = pl.run_two_stage(groups, lambda g: _predict_turns(g, t2s, device, args.seed, sampling=t2s_kw), solve, device,
                                overlap=(mode == "on"), collate=collate)
         frames = sum(nfr)
     drain()

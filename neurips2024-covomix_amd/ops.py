@@ -788,6 +788,20 @@ def geglu(h: torch.Tensor, out: torch.Tensor, F: int) -> torch.Tensor:
     return out
 
 
+def t2s_sample(logits: torch.Tensor, uniforms: torch.Tensor, filter_mode: int = 0, k: int = 1, thres: float = 0.0,
+               temperature: float = 1.0, return_kept: bool = False):
+    """The filter + Gumbel argmax of one text2semantic decode step on caller-supplied rows (cvx_t2s_sample_f32): logits, uniforms
+    [rows, V] fp32 -> int64 tokens [rows] (and the uint8 kept mask [rows, V]).  filter_mode / k / thres: t2s.filter_setting."""
+    _chk_f32(logits, uniforms)
+    assert logits.ndim == 2 and logits.shape == uniforms.shape and logits.is_contiguous() and uniforms.is_contiguous()
+    rows, V = logits.shape
+    tokens = torch.empty(rows, dtype=torch.int64, device=logits.device)
+    kept = torch.empty(rows, V, dtype=torch.uint8, device=logits.device) if return_kept else None
+    _lib.check(_lib.load().cvx_t2s_sample_f32(logits.data_ptr(), uniforms.data_ptr(), rows, V, int(filter_mode), int(k), float(thres),
+                                              float(temperature), tokens.data_ptr(), _p(kept), _stream()), "cvx_t2s_sample_f32")
+    return (tokens, kept) if return_kept else tokens
+
+
 def dwconv31_gelu_res(x: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, out: torch.Tensor,
                       Bt: int, T: int, ragged: Optional[Ragged] = None) -> torch.Tensor:
     _chk_f32(x, w, bias, out)

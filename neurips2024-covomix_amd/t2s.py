@@ -2,8 +2,10 @@
 
 Host mirror of the reference's `TextToSemantic.generate` sampling branch + `TextToSemanticWrapper.sample`
 (covomix/covomix_model/text2semantic.py:662-848, :1237-1251), the call `CoVoMixModel.synthesis_sample_text2semantic`
-forwards to (covomix/conditional_model.py:313-321).  Only what the generation scripts reach is built: cond_scale == 1
-(the reference asserts on anything else with its default cond_drop_prob = 0), no beam / speculative decoding, batch 1.
+forwards to (covomix/conditional_model.py:313-321).  Built: the sampling branch with its three controls - temperature,
+classifier-free guidance (cond_scale > 1, one-output models) and the logit filter (filter_logits_fn = top_k / top_p with
+filter_fn_kwargs, text2semantic.py:118-132, :796) - in every decode schedule below; no beam / speculative decoding, no padded
+text batches.
 
   encoder  (source transformer, once per utterance): the full-sequence kernels of the acoustic path - fp32 GEMM with
            the RoPE epilogue, flash attention, RMSNorm - plus a GEGLU kernel;
@@ -38,6 +40,33 @@ CHUNK = 16                     # token steps per graph replay / host check
 MAX_BATCH = 64                 # decode slots per step (kernel limit)
 WINDOW = 256                   # utterances queued on the device at a time (generate_many)
 SR = 8                         # int32 per slot / dialogue record (include/covomix_hip.h, cvx_t2s_decoder)
+
+
+def filter_setting(filter_logits_fn="top_k", filter_fn_kwargs=None, vocab: int = 0) -> tuple:
+    """(filter mode, k, thres) of the decode descriptor from the reference's `filter_logits_fn` / `filter_fn_kwargs`
+    (TextToSemantic.generate, text2semantic.py:668-669, :796).  filter_logits_fn: "top_k" or "top_p" (or a function of that name).
+      top_k: kwargs `thres` (default 0.1) and `k` (default None): k = ceil(thres * vocab) unless given (:126-128); 1 <= k <= vocab.
+      top_p: kwarg `thres` (default 0.9), 0 < thres < 1.  thres >= 1 is REFUSED rather than imitated: the reference compares a
+             rounded fp32 cumulative sum with it, which can exceed 1 and then drops the tail of the vocabulary by rounding luck.
+    ValueError outside these."""
+    name = filter_logits_fn if isinstance(filter_logits_fn, str) else getattr(filter_logits_fn, "__name__", None)
+    kw = dict(filter_fn_kwargs or {})
+    if name == "top_k":
+        thres, k = kw.pop("thres", TOP_K_THRES), kw.pop("k", None)
+        if kw:
+            raise ValueError(f"top_k takes thres and k, got {sorted(kw)}")
+        k = math.ceil(float(thres) * vocab) if k is None else int(k)
+        if not 1 <= k <= vocab:
+            raise ValueError(f"top_k: k = {k} outside [1, vocab = {vocab}]")
+        return (_lib.T2S_FILTER_TOP_K, k, 0.0)
+    if name == "top_p":
+        thres = float(kw.pop("thres", 0.9))
+        if kw:
+            raise ValueError(f"top_p takes thres, got {sorted(kw)}")
+        if not 0.0 < thres < 1.0:
+            raise ValueError(f"top_p: thres = {thres} outside (0, 1)")
+        return (_lib.T2S_FILTER_TOP_P, 0, thres)
+    raise ValueError(f"filter_logits_fn must be 'top_k' or 'top_p', got {filter_logits_fn!r}")
 
 
 def _dims(sd: Dict[str, torch.Tensor]) -> dict:
@@ -120,6 +149,7 @@ class TextToSemanticDecoder:
         ang = pos[:, None] * sd["target_transformer.layers.0.0.rotary_emb.freqs"][None, :]
         self.rope = (ang.cos().contiguous(), ang.sin().contiguous())
         self.top_k = math.ceil(TOP_K_THRES * d["vocab"])
+        self._default_filter = filter_setting(vocab=d["vocab"])         # (top_k, k = ceil(0.1 V)): the reference's default
         self.buf: Dict[str, torch.Tensor] = {}
         self._slots = self._dialogues = self._steps = 0   # capacities of the decode buffers (_ensure)
         self._gen = 0                                      # bumped when they are re-allocated (captured graphs hold their addresses)
@@ -220,15 +250,19 @@ class TextToSemanticDecoder:
         return self.encode_many([source_ids])[0]
 
     # ------------------------------------------------------------------ decoder
-    def _descriptor(self, temperature: float, batch: int = 1, cfg_scale: float = 1.0, queue: bool = False) -> "_lib.T2SDecoder":
+    def _descriptor(self, temperature: float, batch: int = 1, cfg_scale: float = 1.0, queue: bool = False, filt: Optional[tuple] = None,
+                    nd: int = 0) -> "_lib.T2SDecoder":
+        """filt: (mode, k, thres) of filter_setting (default: the reference's top_k); nd: dialogue records behind the queue"""
         d, b = self.d, self.buf
         dec = _lib.T2SDecoder()
+        dec.filter_mode, k, dec.top_p = filt or self._default_filter
+        dec.n_dialogues = int(nd)
         dec.batch, dec.ctx_rows = batch, self.max_source + 2
         dec.cfg_scale = float(cfg_scale)
         dec.dim, dec.inner, dec.heads = d["dim_target"], d["inner"], d["heads"]
         dec.ff_inner, dec.ff_inner_pad, dec.depth = d["ff_tgt"], self.Fp, d["target_depth"]
         dec.streams, dec.vocab, dec.dim_emb = d["streams"], d["vocab"], d["dim_emb"]
-        dec.n_ctx, dec.max_len, dec.top_k, dec.temperature = 0, self.max_length, self.top_k, float(temperature)
+        dec.n_ctx, dec.max_len, dec.top_k, dec.temperature = 0, self.max_length, k, float(temperature)
         dec.layers = C.cast(self._layers, C.POINTER(_lib.T2SLayer))
         dec.final_gamma, dec.emb = self.dec_final.data_ptr(), self.emb.data_ptr()
         dec.rope_cos, dec.rope_sin = self.rope[0].data_ptr(), self.rope[1].data_ptr()
@@ -239,9 +273,9 @@ class TextToSemanticDecoder:
             dec.queue, dec.dialogues, dec.start = b["queue"].data_ptr(), b["dialogues"].data_ptr(), self.start.data_ptr()
         return dec
 
-    def _run_steps(self, temperature: float, batch: int, n: int, cfg_scale: float = 1.0, queue: bool = False) -> None:
+    def _run_steps(self, temperature: float, batch: int, n: int, cfg_scale: float = 1.0, queue: bool = False, filt=None, nd: int = 0) -> None:
         """n token steps on the current stream without a graph."""
-        _lib.check(_lib.load().cvx_t2s_decode_steps(C.byref(self._descriptor(temperature, batch, cfg_scale, queue)), n,
+        _lib.check(_lib.load().cvx_t2s_decode_steps(C.byref(self._descriptor(temperature, batch, cfg_scale, queue, filt, nd)), n,
                                                     ops._stream()), "cvx_t2s_decode_steps")
 
     def _uniform_view(self, n: int) -> torch.Tensor:
@@ -291,7 +325,7 @@ class TextToSemanticDecoder:
         self._pin_ev[k].synchronize()
         return self._pin[k][:rows].tolist()
 
-    def _decode_chunks(self, temperature: float, nb: int, max_len: int, cfg_scale: float, watch, ignore_eos: bool = False) -> list:
+    def _decode_chunks(self, temperature: float, nb: int, max_len: int, cfg_scale: float, watch, ignore_eos: bool = False, filt=None) -> list:
         """Graph-replayed chunks of CHUNK token steps until every utterance slot in `watch` has sampled its eos (or max_len steps).
         The host looks at the eos flags ONE CHUNK BEHIND the device: the slot records of chunk i are copied between the replays of
         chunks i and i + 1 and read while chunk i + 1 runs - the decode chain never waits for a host round trip (nor for a host
@@ -301,7 +335,7 @@ class TextToSemanticDecoder:
         via_helper = ops.is_partition_stream()
         steps, i, pending = 0, 0, None
         while steps < max_len:
-            self._run_chunk(temperature, nb, cfg_scale)
+            self._run_chunk(temperature, nb, cfg_scale, False, filt)
             steps += CHUNK
             k = i & 1
             self._mirror_push(k, self.buf["state"][:nb], via_helper)
@@ -315,17 +349,19 @@ class TextToSemanticDecoder:
             self._pin_ev[pending].synchronize()      # (the helper stream's last copy: the buffers are reused by the next call)
         return self._read_state(nb)
 
-    def _graph(self, temperature: float, batch: int, cfg_scale: float = 1.0, queue: bool = False):
-        """The captured graph of CHUNK token steps for this (batch, stream CU count, mode); captured on first use.  Capturing runs the
+    def _graph(self, temperature: float, batch: int, cfg_scale: float = 1.0, queue: bool = False, filt=None, nd: int = 0):
+        """The captured graph of CHUNK token steps for this (batch, stream CU count, mode, filter); captured on first use.  (nd, the
+        number of dialogue records, is only validated by the C call: it is not part of the key.)  Capturing runs the
         steps once outside the capture (module load, kernel attributes): callers get their graph BEFORE they set up the decode state -
         the warm-up runs on idle slot records (position max_length: the sampling kernel returns at once, every other kernel clamps)."""
-        key = (temperature, batch, cfg_scale, ops.stream_cus(), queue, self._gen)   # (the kernels' shape follows the CUs the stream owns)
+        filt = filt or self._default_filter
+        key = (temperature, batch, cfg_scale, ops.stream_cus(), queue, self._gen, filt)   # (the kernels' shape follows the CUs the stream owns)
         g = self._graphs.get(key)
         if g is not None:
             return g
 
         def launch():
-            _lib.check(_lib.load().cvx_t2s_decode_steps(C.byref(self._descriptor(temperature, batch, cfg_scale, queue)), CHUNK,
+            _lib.check(_lib.load().cvx_t2s_decode_steps(C.byref(self._descriptor(temperature, batch, cfg_scale, queue, filt, nd)), CHUNK,
                                                         ops._stream()), "cvx_t2s_decode_steps")
         self.buf["state"].copy_(self._slot_records([]))
         launch()                                       # warm-up outside capture
@@ -343,13 +379,13 @@ class TextToSemanticDecoder:
         self._graphs[key] = g
         return g
 
-    def _run_chunk(self, temperature: float, batch: int = 1, cfg_scale: float = 1.0, queue: bool = False) -> None:
+    def _run_chunk(self, temperature: float, batch: int = 1, cfg_scale: float = 1.0, queue: bool = False, filt=None, nd: int = 0) -> None:
         """CHUNK token steps on the current stream: a graph replay of the per-launch path (the graph must exist - `_graph` - unless
         CVX_GRAPH=0 asks for plain launches)."""
         if os.environ.get("CVX_GRAPH", "1") != "1":
-            self._run_steps(temperature, batch, CHUNK, cfg_scale, queue)
+            self._run_steps(temperature, batch, CHUNK, cfg_scale, queue, filt, nd)
             return
-        self._graph(temperature, batch, cfg_scale, queue).replay()
+        self._graph(temperature, batch, cfg_scale, queue, filt, nd).replay()
 
     def _contexts(self, sources, rows=None) -> list:
         """encoder + the cross-attention k/v of the utterances into dialogue rows `rows` (default 0, 1, ...): [null | to_kv(enc)]
@@ -384,7 +420,7 @@ class TextToSemanticDecoder:
                               #  e.g. the generator's graph-safe state, would become inference tensors)
     def generate_batch(self, sources, uniforms=None, max_length: Optional[int] = None, temperature: float = 1.0,
                        generator: Optional[torch.Generator] = None, collect_logits: bool = False, cond_scale: float = 1.0,
-                       ignore_eos: bool = False):
+                       ignore_eos: bool = False, filter_logits_fn="top_k", filter_fn_kwargs=None):
         """Decode up to MAX_BATCH utterances together IN LOCK STEP (all start at position 0; the batch runs until the last one has
         sampled its eos).  sources: list of [n] / [1, n] id tensors; uniforms: optional list of [steps, streams, vocab] tensors (one
         per utterance).  Returns a list of (flat tokens, streams[, logits]) tuples, each exactly what `generate` returns for that
@@ -393,16 +429,19 @@ class TextToSemanticDecoder:
         cond_scale > 1: classifier-free guidance (text2semantic.py:780-792; one-output models, up to MAX_BATCH / 2 utterances):
         every utterance takes two decode slots - the text context and the context masked out (cross-attention then sees the
         learned null key / value only) - and each step samples from null + (cond - null) * cond_scale; logits returned under
-        collect_logits are the COMBINED ones, null + (cond - null) * cond_scale (what the reference filters and samples from)."""
+        collect_logits are the COMBINED ones, null + (cond - null) * cond_scale (what the reference filters and samples from).
+        filter_logits_fn / filter_fn_kwargs: the logit filter, as TextToSemantic.generate takes it (`filter_setting`); the default is
+        the reference's top_k with k = ceil(0.1 * vocab)."""
         d, b = self.d, self.buf
         S, V = d["streams"], d["vocab"]
+        filt = filter_setting(filter_logits_fn, filter_fn_kwargs, V)
         cfg = float(cond_scale) > 1.0
         if cfg:
             if S != 1:
                 raise NotImplementedError("guidance (cond_scale > 1) on a two-output model: the reference feeds the full-width hidden "
                                           "state to the half-width logit head there (text2semantic.py:783-785) and cannot run")
             return self._generate_guided(sources, uniforms, max_length, temperature, generator, collect_logits, float(cond_scale),
-                                         ignore_eos)
+                                         ignore_eos, filt)
         nb = len(sources)
         if not 1 <= nb <= MAX_BATCH:
             raise ValueError(f"1..{MAX_BATCH} utterances per decode batch, got {nb}")
@@ -414,7 +453,7 @@ class TextToSemanticDecoder:
         self._ensure(nb, nb, max_len)
         b = self.buf
         if not collect_logits and max_len > 0:
-            self._graph(float(temperature), nb)
+            self._graph(float(temperature), nb, 1.0, False, filt)
         ctx = self._contexts(sources)
         uview = self._uniform_view(nb)
         if us is None:            # (drawn step-major, as the [steps, batch, streams, vocab] buffer of earlier versions was: same seeds, same tokens)
@@ -428,20 +467,20 @@ class TextToSemanticDecoder:
         st = self._slot_records(ctx).tolist()[:nb]
         if collect_logits:                                              # (tests: one step at a time without a graph)
             for _ in range(max_len):
-                self._run_steps(float(temperature), nb, 1)
+                self._run_steps(float(temperature), nb, 1, 1.0, False, filt)
                 logits.append(b["logits"][:nb].clone())
                 st = self._read_state(nb)
                 if all(row[1] for row in st) and not ignore_eos:
                     break
         elif max_len > 0:
-            st = self._decode_chunks(float(temperature), nb, max_len, 1.0, range(nb), ignore_eos)
+            st = self._decode_chunks(float(temperature), nb, max_len, 1.0, range(nb), ignore_eos, filt)
         out = []
         for i in range(nb):
             length = min(st[i][2] if st[i][1] and st[i][2] <= max_len and not ignore_eos else max_len, max_len)
             out.append(self._cut(i, length, torch.stack([lg[i] for lg in logits]) if collect_logits and logits else None))
         return out
 
-    def _generate_guided(self, sources, uniforms, max_length, temperature, generator, collect_logits, cond_scale, ignore_eos=False):
+    def _generate_guided(self, sources, uniforms, max_length, temperature, generator, collect_logits, cond_scale, ignore_eos=False, filt=None):
         """generate_batch with cond_scale > 1: slots 2u (text context) / 2u + 1 (null context) per utterance u."""
         V, nu = self.d["vocab"], len(sources)
         nb = 2 * nu
@@ -455,7 +494,7 @@ class TextToSemanticDecoder:
         self._ensure(nb, nb, max_len)
         b = self.buf
         if not collect_logits and max_len > 0:
-            self._graph(float(temperature), nb, cond_scale)
+            self._graph(float(temperature), nb, cond_scale, False, filt)
         ctx = []
         for c in self._contexts(sources, range(0, nb, 2)):
             ctx += [c, 1]                                                # the null slot: row 0 (null k/v) only = every context key masked out
@@ -473,14 +512,14 @@ class TextToSemanticDecoder:
         st = self._slot_records(ctx).tolist()[:nb]
         if collect_logits:
             for _ in range(max_len):
-                self._run_steps(float(temperature), nb, 1, cond_scale)
+                self._run_steps(float(temperature), nb, 1, cond_scale, False, filt)
                 lg = b["logits"][:nb].clone()
                 logits.append(lg[1::2] + (lg[0::2] - lg[1::2]) * cond_scale)
                 st = self._read_state(nb)
                 if all(st[2 * u_][1] for u_ in range(nu)) and not ignore_eos:
                     break
         elif max_len > 0:
-            st = self._decode_chunks(float(temperature), nb, max_len, cond_scale, [2 * u_ for u_ in range(nu)], ignore_eos)
+            st = self._decode_chunks(float(temperature), nb, max_len, cond_scale, [2 * u_ for u_ in range(nu)], ignore_eos, filt)
         out = []
         for u_ in range(nu):
             i = 2 * u_
@@ -491,7 +530,8 @@ class TextToSemanticDecoder:
     @ops.gated
     @torch.no_grad()
     def generate_many(self, sources, uniforms=None, max_length: Optional[int] = None, temperature: float = 1.0,
-                      generator: Optional[torch.Generator] = None, slots: int = 32, ignore_eos: bool = False, limits=None, on_done=None):
+                      generator: Optional[torch.Generator] = None, slots: int = 32, ignore_eos: bool = False, limits=None, on_done=None,
+                      cond_scale: float = 1.0, filter_logits_fn="top_k", filter_fn_kwargs=None):
         """Decode ANY number of utterances through `slots` decode slots with continuous batching: every utterance runs the
         reference's loop (text2semantic.py:749-848) from position 0 to its first eos (:803-818) or its step limit, and the slot it
         ran in takes the next pending utterance in the sampling kernel of that very step (cvx_t2s_decoder.queue) - utterances end
@@ -500,21 +540,36 @@ class TextToSemanticDecoder:
         on_done(j, (flat, streams)): called for utterance j as soon as the host has seen it finish (the host reads the dialogue
         records one chunk of CHUNK steps behind the device) - the next pipeline stage can start on the first results while the
         rest decodes.  Returns the list of (flat tokens, streams) in input order - int64 tensors ON THE HOST (they travel through pinned
-        memory on a helper stream so that nothing makes the decode stream wait)."""
+        memory on a helper stream so that nothing makes the decode stream wait).
+        cond_scale > 1 (classifier-free guidance, one-output models): an utterance takes a PAIR of decode slots (text context / null
+        context) and a pair of dialogue records; the even slot of a pair ends the utterance and refills both (include/covomix_hip.h).
+        At most MAX_BATCH / 2 utterances are in flight (`slots` still counts slots: slots // 2 pairs), and WINDOW counts dialogue
+        records, so a window holds WINDOW / 2 guided utterances.  limits, ignore_eos, on_done and last_records keep their meaning
+        per utterance (last_records: the record of the text-context half; its slot is the even slot of the pair).
+        filter_logits_fn / filter_fn_kwargs: as generate_batch."""
         d = self.d
         S, V = d["streams"], d["vocab"]
         n = len(sources)
+        filt = filter_setting(filter_logits_fn, filter_fn_kwargs, V)
+        cond_scale = float(cond_scale)
+        cfg = cond_scale > 1.0
+        if cfg and S != 1:
+            raise NotImplementedError("guidance (cond_scale > 1) on a two-output model: the reference cannot run it (generate_batch)")
+        P = 2 if cfg else 1       # dialogue records (and decode slots) per utterance
         if n == 0:
             return []
-        if n > WINDOW:            # (the context k/v, uniforms and token rows of every queued utterance are resident: bounded windows)
+        win = WINDOW // P
+        if n > win:               # (the context k/v, uniforms and token rows of every queued utterance are resident: bounded windows)
             out = []
-            for w in range(0, n, WINDOW):
-                out += self.generate_many(sources[w:w + WINDOW], None if uniforms is None else uniforms[w:w + WINDOW], max_length, temperature,
-                                          generator, slots, ignore_eos, None if limits is None else limits[w:w + WINDOW],
-                                          None if on_done is None else (lambda j, r, w=w: on_done(w + j, r)))
+            for w in range(0, n, win):
+                out += self.generate_many(sources[w:w + win], None if uniforms is None else uniforms[w:w + win], max_length, temperature,
+                                          generator, slots, ignore_eos, None if limits is None else limits[w:w + win],
+                                          None if on_done is None else (lambda j, r, w=w: on_done(w + j, r)),
+                                          cond_scale, filter_logits_fn, filter_fn_kwargs)
             return out
-        nb = max(1, min(int(slots), MAX_BATCH, n))
+        nb = P * max(1, min(int(slots) // P, MAX_BATCH // P, n))
         nb = nb if nb in (1, 2, 4) else min((nb + 7) // 8 * 8, MAX_BATCH)      # whole kernel groups (idle slots cost nothing)
+        nrec = P * n
         max_len = min(int(max_length or self.max_length), self.max_length)
         us = None
         if uniforms is not None:
@@ -523,25 +578,33 @@ class TextToSemanticDecoder:
         lim = [max_len] * n if limits is None else [max(1, min(int(x), max_len)) for x in limits]
         if max_len <= 0:
             raise ValueError("generate_many needs at least one step")
-        self._ensure(nb, n, max_len)
+        self._ensure(nb, nrec, max_len)
         b = self.buf
         temperature = float(temperature)
-        self._graph(temperature, nb, 1.0, True)
-        ctx = self._contexts(sources)
-        uview = self._uniform_view(n)
+        self._graph(temperature, nb, cond_scale, True, filt, nrec)
+        if cfg:                   # record 2u: the text context; record 2u + 1: the null key / value row only (every context key masked out)
+            ctx = []
+            for c in self._contexts(sources, range(0, nrec, 2)):
+                ctx += [c, 1]
+            for L in self.dec:
+                L["kv_c"][1:nrec:2, 0].copy_(L["null"][None, :].expand(n, -1))
+        else:
+            ctx = self._contexts(sources)
+        uview = self._uniform_view(nrec)[0::P]            # the draws of utterance j live in its first record
         if us is None:
             uview[:, :max_len].copy_(torch.rand(n, max_len, S, V, device=self.device, generator=generator))
         else:
             for j, u in enumerate(us):
                 uview[j, :max_len].copy_(u[:max_len])
         flags = 1 if ignore_eos else 0
-        first = min(nb, n)
-        rec = torch.tensor([[ctx[j], lim[j], flags, 1 if j < first else 0, 0, j if j < first else 0, 0, 0] for j in range(n)], dtype=torch.int32)
-        b["dialogues"][:n].copy_(rec)
-        b["queue"].copy_(torch.tensor([first, n], dtype=torch.int32))
+        first = min(nb, nrec)     # records (= slots) that start at once; whole pairs under guidance (nb and nrec are even)
+        rec = torch.tensor([[ctx[r], lim[r // P], flags, 1 if r < first else 0, 0, r if r < first else 0, 0, 0] for r in range(nrec)],
+                           dtype=torch.int32)
+        b["dialogues"][:nrec].copy_(rec)
+        b["queue"].copy_(torch.tensor([first, nrec], dtype=torch.int32))
         slot = self._slot_records(ctx[:first]).clone()
-        for j in range(first):
-            slot[j, 5], slot[j, 6] = lim[j], flags
+        for r in range(first):
+            slot[r, 5], slot[r, 6] = lim[r // P], flags
         b["state"].copy_(slot)
         b["x"][:first].copy_(self.start[None, :].expand(first, -1))
         self._mirror_setup()
@@ -569,6 +632,7 @@ class TextToSemanticDecoder:
                     on_done(j, out[j])
 
         def collect(records):
+            records = records[0::P]
             self.last_records = records          # (tests / tools: status, steps and slot of every utterance)
             fresh = [j for j in range(n) if not seen[j] and records[j][3] >= 2]
             if fresh:
@@ -576,7 +640,7 @@ class TextToSemanticDecoder:
                     for j in fresh:
                         seen[j] = True
                         length = records[j][4]
-                        tok_pin[j, :, :length].copy_(b["tokens"][j, :, :length], non_blocking=True)
+                        tok_pin[j, :, :length].copy_(b["tokens"][P * j, :, :length], non_blocking=True)
                         ev = torch.cuda.Event()
                         ev.record()
                         copies.append((j, length, ev))
@@ -585,15 +649,15 @@ class TextToSemanticDecoder:
         i, pending = 0, None
         cap = (sum(lim) + CHUNK - 1) // CHUNK + 4          # (one slot decoding everything: cannot be reached)
         while not all(seen) and i < cap:
-            self._run_chunk(temperature, nb, 1.0, True)
+            self._run_chunk(temperature, nb, cond_scale, True, filt, nrec)
             k = i & 1
-            self._mirror_push(k, b["dialogues"][:n], via_helper)
+            self._mirror_push(k, b["dialogues"][:nrec], via_helper)
             if pending is not None:
-                collect(self._mirror_pull(pending, n))
+                collect(self._mirror_pull(pending, nrec))
             pending = k
             i += 1
         if not all(seen) and pending is not None:
-            collect(self._mirror_pull(pending, n))
+            collect(self._mirror_pull(pending, nrec))
         if pending is not None:
             self._pin_ev[pending].synchronize()
         finish(True)
@@ -604,16 +668,16 @@ class TextToSemanticDecoder:
     @ops.gated
     def generate(self, source_ids: torch.Tensor, uniforms: Optional[torch.Tensor] = None, max_length: Optional[int] = None,
                  temperature: float = 1.0, generator: Optional[torch.Generator] = None, return_streams: bool = False,
-                 collect_logits: bool = False, cond_scale: float = 1.0):
+                 collect_logits: bool = False, cond_scale: float = 1.0, filter_logits_fn="top_k", filter_fn_kwargs=None):
         """== TextToSemanticWrapper.sample(grapheme_token_ids): flat int64 tensor, stream 1 then stream 2 (two-output
         models), each cut after its eos.  uniforms [steps, streams, vocab] (or [steps, streams, 1, vocab]) replaces
         the random draws of gumbel_noise (text2semantic.py:108-110); default: torch.rand from `generator`.
         collect_logits (tests): step one token at a time without a graph and also return the pre-filter logits
-        [steps, streams, vocab]."""
+        [steps, streams, vocab].  cond_scale / filter_logits_fn / filter_fn_kwargs: see generate_batch."""
         if source_ids.ndim == 2 and source_ids.shape[0] != 1:
             raise NotImplementedError("one utterance per call (the generation scripts run batch 1); see generate_batch")
         res = self.generate_batch([source_ids], None if uniforms is None else [uniforms], max_length, temperature, generator,
-                                  collect_logits, cond_scale)[0]
+                                  collect_logits, cond_scale, False, filter_logits_fn, filter_fn_kwargs)[0]
         if collect_logits:
             return res
         return res if return_streams else res[0]

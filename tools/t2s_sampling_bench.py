@@ -1,0 +1,72 @@
+#!/usr/bin/env python3
+"""Step time of the text2semantic decode under the sampling controls, one JSON line per figure.
+
+  python tools/t2s_sampling_bench.py steps  [--top-p 0.9] [--root OTHER_CHECKOUT]
+      us per token step of the lock-step decode (generate_batch, ignore_eos, graph replay) for CoMix and CoSingle at 1 / 8 / 64
+      slots; --top-p adds the same figure under the nucleus filter.  --root runs the package of another checkout (the parent
+      commit, built there) so that parent and change can alternate in one session: run the command in turns, five rounds.
+  python tools/t2s_sampling_bench.py guided
+      64 guided CoSingle dialogues (cond_scale 1.5) that end at different steps (limits 100 ... 608, the eos ignored: the recipe of
+      config5.decode_ragged) through generate_many(cond_scale=) on 32 slot pairs against lock-step guided batches of 32.
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("what", choices=["steps", "guided"])
+    ap.add_argument("--root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    ap.add_argument("--top-p", type=float, default=None)
+    ap.add_argument("--steps", type=int, default=256)
+    ap.add_argument("--tag", default="")
+    args = ap.parse_args()
+    sys.path.insert(0, os.path.abspath(args.root))
+    import torch
+    import covomix_amd.synthetic as syn
+    from covomix_amd.t2s import TextToSemanticDecoder
+    dev = torch.device("cuda:0")
+    shapes = {"comix": dict(two_output=True, dim=512, dim_target=1024), "cosingle": dict(two_output=False, dim=512, dim_target=512)}
+
+    def model(name):
+        sd = {k: torch.from_numpy(v) for k, v in syn.t2s_state_dict(syn.t2s_param_shapes(**shapes[name]), seed=0).items()}
+        return TextToSemanticDecoder(sd, dev, max_length=max(args.steps, 608))
+
+    def timed(fn):
+        torch.cuda.synchronize(dev); t0 = time.perf_counter(); fn(); torch.cuda.synchronize(dev)
+        return time.perf_counter() - t0
+
+    g = torch.Generator().manual_seed(3)
+    if args.what == "steps":
+        for name in ("comix", "cosingle"):
+            m = model(name)
+            for slots in (1, 8, 64):
+                srcs = [torch.randint(1, 30000, (1, 64), generator=g) for _ in range(slots)]
+                for label, kw in (("default", {}),) + ((("top_p", dict(filter_logits_fn="top_p", filter_fn_kwargs={"thres": args.top_p})),) if args.top_p else ()):
+                    run = lambda: m.generate_batch(srcs, max_length=args.steps, ignore_eos=True, **kw)
+                    run()                                                 # graph + buffers of the timed shape
+                    t = min(timed(run) for _ in range(3))
+                    print(json.dumps({"tag": args.tag, "model": name, "slots": slots, "filter": label, "steps": args.steps,
+                                      "us_per_step": round(t / args.steps * 1e6, 1)}), flush=True)
+    else:
+        m = model("cosingle")
+        n, tokens, pairs = 64, 608, 32
+        lims = torch.randint(100, tokens + 1, (n,), generator=g).tolist()
+        srcs = [torch.randint(1, 30000, (1, 64), generator=g) for _ in range(n)]
+        many = lambda l: m.generate_many(srcs, max_length=tokens, slots=2 * pairs, ignore_eos=True, limits=l, cond_scale=1.5)
+        lock = lambda: [m.generate_batch(srcs[w:w + pairs], max_length=max(lims[w:w + pairs]), ignore_eos=True, cond_scale=1.5)
+                        for w in range(0, n, pairs)]
+        many([20] * n)
+        m.generate_batch(srcs[:pairs], max_length=20, ignore_eos=True, cond_scale=1.5)
+        for r in range(5):
+            t_many, t_lock = timed(lambda: many(lims)), timed(lock)
+            print(json.dumps({"tag": args.tag, "round": r, "dialogues": n, "slot_pairs": pairs, "useful_steps": sum(lims),
+                              "continuous_s": round(t_many, 4), "lock_step_s": round(t_lock, 4),
+                              "continuous_vs_lock_step": round(t_lock / t_many, 3)}), flush=True)
+
+
+if __name__ == "__main__":
+    main()
