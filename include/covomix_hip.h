@@ -65,8 +65,10 @@ typedef const cvx_ctx* cvx_stream_t;
  * arithmetic only, so that tests can place a problem on every form).  110: CVX_ATT_FORM_D (256-query blocks, two query sets per
  * wave, for launches of 512 such blocks and more); CVX_ATT_FORM_SINGLE_TERM is 4 (was 3).  111: text2semantic sampling controls -
  * cvx_t2s_decoder grew filter_mode / top_p / n_dialogues at its end (top-p beside top-k), a dialogue queue may run under guidance
- * (record pairs), cvx_t2s_sample_f32 (the filter + sampling of one decode step on caller-supplied logits). */
-#define CVX_ABI_VERSION 111
+ * (record pairs), cvx_t2s_sample_f32 (the filter + sampling of one decode step on caller-supplied logits).  112:
+ * cvx_hifigan_conv1d_f16x3_form (the tile height a split-precision convolution launch takes; host arithmetic only, so that tests can
+ * place a problem on every tile form). */
+#define CVX_ABI_VERSION 112
 int         cvx_version(void);
 const char* cvx_last_error_string(void);
 
@@ -381,7 +383,15 @@ int cvx_time_fourier_f32(const float* times, const float* w, float* out, int32_t
  * mel frames: item_len_dev holds the frames, the caller supplies the stage's mul / add).  A kernel given this table
  * writes ZEROS behind an item's last valid position (up to the common length), which is exactly the zero padding the
  * next convolution of a B = 1 run sees there; inputs must obey the same rule (zero-padded mel).  item_len_dev == NULL:
- * every item has the common length. */
+ * every item has the common length.
+ * `accum` (and `res`) are INPUTS under that rule: they must hold zeros behind an item's end, as every buffer one of these kernels
+ * wrote with the same table does.  With a non-zero accum there the kernels differ, and none of it is a promise:
+ *   cvx_hifigan_conv1d_f32, cvx_hifigan_resblock_pair_f16x3 (and the narrow stages of cvx_hifigan_resblock_*_f16x3): zero after the
+ *     accumulate - out is zero behind the end whatever accum holds there;
+ *   cvx_hifigan_conv1d_f16x3 / _group_ (and the wide stages of cvx_hifigan_resblock_*_f16x3): zero BEFORE the accumulate -
+ *     out_x = accum * out_scale behind the end (out_zhi / out_zlo are zero: they never see accum);
+ *   a non-zero res behind the end is dropped by all of them.
+ * The clamps: an item's length is min(common length, max(0, item_len_dev[b] * mul + add)). */
 typedef struct { const int32_t* item_len_dev; int32_t mul, add; } cvx_item_lengths;
 typedef struct {
     const float* x;  int32_t B, Cin, Lin;
@@ -459,6 +469,12 @@ int cvx_hifigan_conv1d_f16x3(const cvx_conv16_args* a, cvx_stream_t s);
  * own; outputs must not alias) as ONE launch: the same results as n calls above, bit for bit - the tiles of the short kernels fill the rounds
  * of the long one (round 6: the three ResBlocks of a generator stage, kernel sizes 3 / 7 / 11, models.py:104-110). */
 int cvx_hifigan_conv1d_group_f16x3(const cvx_conv16_args* a, int32_t n, cvx_stream_t s);
+/* Positions per thread block (the tile height: 256, 192 or 160 rows) of the launch the two calls above make for n_problems (1..3; the
+ * column tiles of a conv-transpose: up to 8) convolutions of Np output columns, L positions and B items on a context of `cus` compute
+ * units (> 0): 256 for Np <= 128; for Np = 256 the height whose rounds x height is smallest (192-row blocks where they need fewer
+ * rounds, 160-row blocks of the 16x16x32 kernel where they beat both at 1.13 x their cost).  The launcher calls the same function.
+ * Host arithmetic only - no device work; -1 for arguments no launch has. */
+int cvx_hifigan_conv1d_f16x3_form(int32_t Np, int32_t L, int32_t B, int32_t n_problems, int32_t cus);
 
 /* ResBlock1.forward (covomix/vocoder/models.py:35-42) on the split-precision convolution above - the operator-level
  * form of section 8(b)'s cvx_hifigan_resblock_* for the path the host actually runs: three times

@@ -16,7 +16,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CVX_LIB_PATH") or os.path.join(_HERE, "libcovomix_hip.so")      # CVX_LIB_PATH: dev A/B builds
 
 _f32p = C.POINTER(C.c_float)
-ABI_VERSION = 111          # == cvx_version(): bumped whenever an argument struct or an entry point's meaning changes
+ABI_VERSION = 112          # == cvx_version(): bumped whenever an argument struct or an entry point's meaning changes
 
 
 class GemmArgs(C.Structure):
@@ -219,6 +219,7 @@ SIGNATURES = {
     "cvx_hifigan_resblock_f16x3": (C.c_int, [C.POINTER(Resblock16Args), C.c_void_p]),
     "cvx_hifigan_resblock_stage_f16x3": (C.c_int, [C.POINTER(Resblock16Args), C.c_int32, C.c_void_p]),
     "cvx_hifigan_conv1d_group_f16x3": (C.c_int, [C.POINTER(Conv16Args), C.c_int32, C.c_void_p]),
+    "cvx_hifigan_conv1d_f16x3_form": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "cvx_hifigan_resblock_pair_f16x3": (C.c_int, [C.POINTER(Respair16Args), C.c_void_p]),
     "cvx_hifigan_conv_transpose1d_f32": (C.c_int, [C.POINTER(ConvArgs), C.c_void_p, C.c_void_p]),
     "cvx_hifigan_conv_transpose1d_packed_floats": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),

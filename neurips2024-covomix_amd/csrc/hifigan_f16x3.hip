@@ -951,19 +951,28 @@ void launch_conv16_m16(const Conv16Args* a, int n_grp, int B, int n_ztiles, hipS
     hipLaunchKernelGGL((conv_f16x3_m16_kernel<TM16, TN16, WN, false>), grid, dim3(512), lds, st, ConvKArgs<false>{a[0]});
 }
 
-// kernel instance by output tile width; Np = 256: one block per CU, and the block height is the one whose rounds x height comes
-// out smallest on this chip - 256 or 192 positions on the 32x32x16 kernel, or 160 on the 16x16x32 one (measured 13 % slower per
-// position, rocprofv3: 114 us for 256 blocks of 160 against 120.6 for 216 blocks of 192 on stage 0 of the bench shape, 8 x 5,000
-// positions - it wins where it fills the chip: 160 -> 216 -> 256 blocks there)
+// Positions per block (the tile height) of a convolution launch: 256 for Np <= 128; for Np = 256 (one block per CU) the height whose
+// rounds x height comes out smallest on this chip - 256 or 192 positions on the 32x32x16 kernel, or 160 on the 16x16x32 one (measured
+// 13 % slower per position, rocprofv3: 114 us for 256 blocks of 160 against 120.6 for 216 blocks of 192 on stage 0 of the bench shape,
+// 8 x 5,000 positions - it wins where it fills the chip: 160 -> 216 -> 256 blocks there).  nz: problems of a group, or output-column
+// tiles.  The ONE statement of the rule: dispatch_conv16 launches by it and cvx_hifigan_conv1d_f16x3_form reports it.
+int conv16_tile_rows(int Np, int L, int B, int nz, int cus)
+{
+    if (Np != 256) return 256;
+    auto cost = [&](int rows) { const int64_t n = (int64_t)((L + rows - 1) / rows) * B * nz; return (double)((n + cus - 1) / cus * rows); };
+    const double t256 = cost(256), t192 = cost(192), t160 = 1.13 * cost(160);
+    if (t160 < t256 && t160 < t192) return 160;
+    return t192 < t256 ? 192 : 256;
+}
+
+// kernel instance by output tile width and, for Np = 256, by the tile height of conv16_tile_rows
 // k: the problem (n_grp == 0, n_ztiles output-column tiles) or n_grp problems of one shape (one column tile each)
 void dispatch_conv16(const Conv16Args* k, int n_grp, int B, int n_ztiles, hipStream_t st, int cus)
 {
-    const int nz = n_grp > 0 ? n_grp : n_ztiles;
     if (k[0].Np == 256) {
-        auto cost = [&](int rows) { const int64_t n = (int64_t)((k[0].L + rows - 1) / rows) * B * nz; return (double)((n + cus - 1) / cus * rows); };
-        const double t256 = cost(256), t192 = cost(192), t160 = 1.13 * cost(160);
-        if (t160 < t256 && t160 < t192) launch_conv16_m16<5, 4, 4>(k, n_grp, B, n_ztiles, st);
-        else if (t192 < t256) launch_conv16<3, 2, 4>(k, n_grp, B, n_ztiles, st);
+        const int rows = conv16_tile_rows(256, k[0].L, B, n_grp > 0 ? n_grp : n_ztiles, cus);
+        if (rows == 160) launch_conv16_m16<5, 4, 4>(k, n_grp, B, n_ztiles, st);
+        else if (rows == 192) launch_conv16<3, 2, 4>(k, n_grp, B, n_ztiles, st);
         else launch_conv16<4, 2, 4>(k, n_grp, B, n_ztiles, st);
     }
     else if (k[0].Np == 128) launch_conv16<2, 2, 2>(k, n_grp, B, n_ztiles, st);
@@ -1059,6 +1068,12 @@ extern "C" int cvx_hifigan_conv1d_f16x3(const cvx_conv16_args* a, cvx_stream_t s
     dispatch_conv16(&k, 0, a->B, 1, cvx_hip_stream(s), cvx_ctx_cus(s));
     CVX_CHECK_LAUNCH("cvx_hifigan_conv1d_f16x3");
     return CVX_OK;
+}
+
+extern "C" int cvx_hifigan_conv1d_f16x3_form(int32_t Np, int32_t L, int32_t B, int32_t n_problems, int32_t cus)
+{
+    if ((Np != 32 && Np != 64 && Np != 128 && Np != 256) || L <= 0 || B <= 0 || n_problems < 1 || n_problems > 8 || cus <= 0) return -1;
+    return conv16_tile_rows(Np, L, B, n_problems, cus);
 }
 
 extern "C" int cvx_hifigan_conv1d_group_f16x3(const cvx_conv16_args* a, int32_t n, cvx_stream_t s)

@@ -1065,15 +1065,12 @@ def amax_pow2_scale(x: torch.Tensor, target: float, scale: torch.Tensor, scratch
     return scale
 
 
-def hifigan_conv1d_f16x3(z, wpk, bias, B: int, L: int, *, ksize: int, dil: int, res=None, accum=None, out_x=None,
-                         out_scale: float = 1.0, out_z=None, z_slope: float = 0.1, z_scale=None, items=None) -> None:
-    """z = (hi, lo) channels-last [B, Lp, Cp_in]; wpk from hifigan_pack_weight_f16x3; bias [Np] (zero padded)."""
-    ensure_saturation_bound()
+def _fill_conv16(a, z, wpk, bias, B: int, L: int, *, ksize: int, dil: int, res=None, accum=None, out_x=None,
+                 out_scale: float = 1.0, out_z=None, z_slope: float = 0.1, z_scale=None, items=None) -> None:
     zh, zl = z
     w_hi, w_lo, inv, np_, cp = wpk
     assert zh.dtype == torch.float16 and zh.is_contiguous() and zl.is_contiguous() and zh.shape == zl.shape
     assert zh.shape[0] == B and zh.shape[2] == cp and bias.numel() == np_
-    a = _lib.Conv16Args()
     a.z_hi, a.z_lo = zh.data_ptr(), zl.data_ptr()
     a.B, a.L, a.Lp, a.Cp_in, a.halo_l = B, L, zh.shape[1], cp, HIFI_HALO_L
     a.w_hi, a.w_lo, a.acc_scale, a.bias = w_hi.data_ptr(), w_lo.data_ptr(), inv, bias.data_ptr()
@@ -1090,7 +1087,37 @@ def hifigan_conv1d_f16x3(z, wpk, bias, B: int, L: int, *, ksize: int, dil: int, 
     a.z_slope = z_slope
     a.z_scale_dev = _sp(z_scale)
     _items(a.items, items)
+
+
+def hifigan_conv1d_f16x3(z, wpk, bias, B: int, L: int, **kw) -> None:
+    """z = (hi, lo) channels-last [B, Lp, Cp_in]; wpk from hifigan_pack_weight_f16x3; bias [Np] (zero padded).
+    Keywords: ksize, dil, res, accum, out_x, out_scale, out_z, z_slope, z_scale, items."""
+    ensure_saturation_bound()
+    a = _lib.Conv16Args()
+    _fill_conv16(a, z, wpk, bias, B, L, **kw)
     _lib.check(_lib.load().cvx_hifigan_conv1d_f16x3(C.byref(a), _stream()), "cvx_hifigan_conv1d_f16x3")
+
+
+def hifigan_conv1d_group_f16x3(problems, B: int, L: int) -> None:
+    """1..3 independent convolutions of one shape as ONE launch (cvx_hifigan_conv1d_group_f16x3): problems = dicts of the arguments
+    of hifigan_conv1d_f16x3 (z, wpk, bias and its keywords); bit-identical to calling it once per problem."""
+    ensure_saturation_bound()
+    n = len(problems)
+    arr = (_lib.Conv16Args * n)()
+    for j, pr in enumerate(problems):
+        pr = dict(pr)
+        _fill_conv16(arr[j], pr.pop("z"), pr.pop("wpk"), pr.pop("bias"), B, L, **pr)
+    _lib.check(_lib.load().cvx_hifigan_conv1d_group_f16x3(arr, n, _stream()), "cvx_hifigan_conv1d_group_f16x3")
+
+
+def hifigan_conv1d_form(np_: int, L: int, B: int, n_problems: int = 1, cus: Optional[int] = None) -> int:
+    """Positions per thread block (256, 192 or 160) of the launch hifigan_conv1d_f16x3 / _group_ / the conv-transpose (n_problems = its
+    column tiles) make for this shape on a stream of `cus` compute units (default: the current stream's).  The library's own
+    launch rule (cvx_hifigan_conv1d_f16x3_form): host arithmetic."""
+    rows = _lib.load().cvx_hifigan_conv1d_f16x3_form(np_, L, B, n_problems, stream_cus() if cus is None else int(cus))
+    if rows < 0:
+        raise ValueError(f"hifigan_conv1d_form: no launch has Np={np_} L={L} B={B} n_problems={n_problems} cus={cus}")
+    return rows
 
 
 def _fill_resblock16(a, x_cl, z, block, B: int, L: int, scratch: dict, accum, out, out_scale: float, z_scale, items) -> None:
