@@ -650,6 +650,21 @@ int cvx_wav_to_int16(const float* wav, int16_t* pcm, int64_t n, cvx_stream_t s);
  *       an equal logit at a lower index (the reference's torch.sort leaves the order of ties open).  Both act on the raw logits -
  *       the guidance-combined ones under cfg_scale > 1 - before the temperature division and the Gumbel noise, and the kept set
  *       is a function of the logits and the setting alone (not of the slot, the batch or the launch shape).
+ *   Log-probabilities (cvx_t2s_decode_steps_scored only): every step also stores the log-probability the model gave the step's token,
+ *       lp = (l[tok] - m) - logf(sum_j expf(l[j] - m)) with m = max_j l[j], into logprobs[(dialogue * streams + s) * max_len + pos] - a float
+ *       buffer laid out like tokens.  l is the row the filter sees: the raw logits, or the guidance-combined ones under cfg_scale > 1 (then
+ *       the value goes to record 2u; record 2u + 1 is unspecified) - before the filter, the temperature division and the Gumbel noise.  The
+ *       sum runs in one fixed order (lane t of a wave adds the entries t, t + 64, ..., t + 960 in ascending order, entries past vocab being
+ *       0, then the xor butterfly 32, 16, ..., 1 over the 64 lanes), so lp is a function of the row alone: not of the slot, the batch, the
+ *       refills or the launch shape.
+ *   Forced dialogues (cvx_t2s_decode_steps_scored only; cvx_t2s_decode_steps ignores the bit): flag bit 1 (value 2) of slot record [6] /
+ *       dialogue record [2] - honoured in the slot record with and without a queue.  The token row of a forced dialogue already holds its
+ *       tokens, each inside [0, vocab) (the caller checks; the device clamps a stray one): every step reads tokens[..., pos] instead of
+ *       sampling, reads no uniforms of that record, stores the token's log-probability and feeds the token's embedding (to both slots of a
+ *       guided pair).  An eos never ends a forced dialogue: only its step limit does (slot record [5] = the number of tokens to score), in
+ *       a queue as for every dialogue (status 3); without a queue the slot then sets [1] = 1, [2] = the limit and idles at position max_len.
+ *       Forced and sampled dialogues may share a queue; the log-probabilities of a sampled dialogue equal, bit for bit, those of the forced
+ *       dialogue over the tokens it sampled.
  * The caller must not ask for more than max_len steps per slot without a queue (extra steps are ignored on the device).
  */
 typedef struct {
@@ -689,6 +704,23 @@ typedef struct {
 /* CVX_EINVAL (nothing is launched) for an unknown filter_mode, top_k outside [1, vocab], top_p outside (0, 1) or an odd n_dialogues under
  * guidance, as for every other inconsistent descriptor. */
 int cvx_t2s_decode_steps(const cvx_t2s_decoder* dec, int32_t n_steps, cvx_stream_t stream);
+
+/* cvx_t2s_decode_steps with the log-probability epilogue and the forced mode (the comment block above): the same step chain, its sampling
+ * kernel in the scoring instantiation.  struct_size = sizeof(cvx_t2s_scoring) - any other size is CVX_EINVAL; logprobs [dialogues, streams,
+ * max_len] fp32 on the device (NULL is refused); logprob_len = floats per row of it, which must equal dec->max_len.  Every consistency check
+ * of cvx_t2s_decode_steps applies; a refused call launches nothing. */
+typedef struct {
+    uint32_t struct_size;
+    int32_t logprob_len;
+    float* logprobs;
+} cvx_t2s_scoring;
+
+int cvx_t2s_decode_steps_scored(const cvx_t2s_decoder* dec, const cvx_t2s_scoring* scoring, int32_t n_steps, cvx_stream_t stream);
+
+/* The log-probability epilogue alone (the device function cvx_t2s_decode_steps_scored uses): out[r] = log_softmax(logits[r, :])[tokens[r]]
+ * as defined above; logits [rows, V] fp32, tokens int64 [rows], out fp32 [rows].  One thread block per row.  A token outside [0, V) gives
+ * its row a NaN.  CVX_EINVAL (nothing is launched) for V < 1, V > 1024, rows < 0 or a NULL pointer. */
+int cvx_t2s_logprob_f32(const float* logits, const int64_t* tokens, int64_t rows, int32_t V, float* out, cvx_stream_t stream);
 
 /* The filter + sampling of one decode step alone (the device function cvx_t2s_decode_steps samples with; no slot state, no queue, no
  * embedding write): tokens[r] = argmax_i (kept(r, i) ? logits[r, i] / max(temperature, 1e-10) + gumbel(uniforms[r, i]) : -inf), lowest

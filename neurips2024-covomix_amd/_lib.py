@@ -150,6 +150,12 @@ class T2SDecoder(C.Structure):
 
 
 T2S_FILTER_TOP_K, T2S_FILTER_TOP_P = 0, 1
+T2S_FLAG_IGNORE_EOS, T2S_FLAG_FORCED = 1, 2      # slot record [6] / dialogue record [2] (FORCED: cvx_t2s_decode_steps_scored only)
+
+
+class T2SScoring(C.Structure):
+    """cvx_t2s_scoring: struct_size = sizeof(this); logprobs [dialogues, streams, max_len] fp32, logprob_len = max_len"""
+    _fields_ = [("struct_size", C.c_uint32), ("logprob_len", C.c_int32), ("logprobs", C.c_void_p)]
 
 
 class ResblockArgs(C.Structure):
@@ -196,6 +202,8 @@ SIGNATURES = {
     "cvx_mel_magnitude_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p]),
     "cvx_mel_log_transpose_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]),
     "cvx_t2s_decode_steps": (C.c_int, [C.POINTER(T2SDecoder), C.c_int32, C.c_void_p]),
+    "cvx_t2s_decode_steps_scored": (C.c_int, [C.POINTER(T2SDecoder), C.POINTER(T2SScoring), C.c_int32, C.c_void_p]),
+    "cvx_t2s_logprob_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]),
     "cvx_t2s_sample_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float,
                                      C.c_void_p, C.c_void_p, C.c_void_p]),
     "cvx_geglu_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_void_p]),

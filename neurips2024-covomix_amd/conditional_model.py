@@ -227,7 +227,7 @@ class CoVoMixModel:
     @torch.no_grad()
     def synthesis_sample_text2semantic(self, grapheme_token_ids, temprature=1.0, cond_scale=1.0, beam_search_decode=False,
                                        prompt_mel=None, uniforms=None, generator=None, max_length=None, slots=64,
-                                       filter_logits_fn="top_k", filter_fn_kwargs=None):
+                                       filter_logits_fn="top_k", filter_fn_kwargs=None, return_logprobs=False, best_of=1):
         """reference conditional_model.py:313-321 -> TextToSemanticWrapper.sample (text2semantic.py:1237-1251): the
         sampled semantic tokens as one flat int64 tensor (two-output models: stream 1 then stream 2) on the input's
         device.  (`temprature` is the reference's spelling.)  `uniforms` / `generator` (optional) fix the U(0,1) draws
@@ -235,7 +235,13 @@ class CoVoMixModel:
         continuously refilled decode slots (t2s.generate_many), guided calls (slot pairs) included, and returns a list (the
         reference decodes utterances one by one; the tokens are the same).  filter_logits_fn / filter_fn_kwargs (extension: the
         reference's wrapper does not pass them on): the logit filter of TextToSemantic.generate, "top_k" (thres, k) or "top_p"
-        (thres) - t2s.filter_setting; the default is the reference's."""
+        (thres) - t2s.filter_setting; the default is the reference's.
+        return_logprobs (extension): returns (tokens, streams [S, L], logprobs float32 [S, L]) per utterance instead of the tokens alone -
+        the log-probability the model gave every sampled token (t2s.generate_batch); `t2s.sequence_logprob(logprobs, streams, eos)` is the
+        utterance's mean log-probability per token.
+        best_of = N > 1 (extension): N candidates per utterance are decoded through the continuously refilled slots (N * n dialogues, or
+        record pairs under guidance) and the one with the largest sequence_logprob is returned; the lowest candidate index wins ties.
+        Caller-supplied `uniforms` of an utterance are then [N, steps, S, V].  best_of = 1 is the call without it, bit for bit."""
         if not self.is_text2semantic:
             raise TypeError("this checkpoint is an acoustic model: use synthesis_sample")
         assert cond_scale >= 1., "cond_scale >= 1 (text2semantic.py:683)"
@@ -246,14 +252,63 @@ class CoVoMixModel:
              "(text2semantic.py:684): this checkpoint's hyper_parameters['cond_drop_prob'] is 0 or absent")
         if beam_search_decode:
             raise NotImplementedError("beam search decoding is not built (the generation scripts sample)")
-        self._get_t2s()
+        from .t2s import best_candidate, check_best_of, sequence_logprob
         ids = grapheme_token_ids
-        if isinstance(ids, (list, tuple)):          # extension: several utterances decoded together (bit-identical tokens)
+        many = isinstance(ids, (list, tuple))
+        best_of = check_best_of(best_of, len(ids) if many else None, uniforms)
+        self._get_t2s()
+        if best_of > 1:
+            # candidate c of utterance j is dialogue j * N + c of one generate_many call: its own draws, the slots shared by all of them
+            N, ids_l = best_of, list(ids) if many else [ids]
+            us = None
+            if uniforms is not None:
+                us = [u[c] for u in (list(uniforms) if many else [uniforms]) for c in range(N)]
+            res = self._t2s.generate_many([i for i in ids_l for _ in range(N)], us, max_length, float(temprature), generator, slots=slots,
+                                          cond_scale=float(cond_scale), filter_logits_fn=filter_logits_fn, filter_fn_kwargs=filter_fn_kwargs,
+                                          return_logprobs=True)
+            eos = self._t2s.d["vocab"] - 1
+            out = []
+            for j, i in enumerate(ids_l):
+                cand = res[j * N:(j + 1) * N]
+                r = cand[best_candidate([sequence_logprob(c[2], c[1], eos) for c in cand])]
+                out.append(tuple(t.to(i.device) for t in r) if return_logprobs else r[0].to(i.device))
+            return out if many else out[0]
+        if many:                                    # extension: several utterances decoded together (bit-identical tokens)
             ids = list(ids)
             # any number of utterances through 64 continuously refilled decode slots (guidance: 32 slot pairs)
+            if return_logprobs:
+                res = self._t2s.generate_many(ids, uniforms, max_length, float(temprature), generator, slots=slots, cond_scale=float(cond_scale),
+                                              filter_logits_fn=filter_logits_fn, filter_fn_kwargs=filter_fn_kwargs, return_logprobs=True)
+                return [tuple(t.to(i.device) for t in r) for r, i in zip(res, ids)]
             res = self._t2s.generate_many(ids, uniforms, max_length, float(temprature), generator, slots=slots, cond_scale=float(cond_scale),
                                           filter_logits_fn=filter_logits_fn, filter_fn_kwargs=filter_fn_kwargs)
             return [r[0].to(i.device) for r, i in zip(res, ids)]
+        if return_logprobs:
+            res = self._t2s.generate(ids, uniforms=uniforms, max_length=max_length, temperature=float(temprature), generator=generator,
+                                     cond_scale=float(cond_scale), filter_logits_fn=filter_logits_fn, filter_fn_kwargs=filter_fn_kwargs,
+                                     return_logprobs=True)
+            return tuple(t.to(ids.device) for t in res)
         out = self._t2s.generate(ids, uniforms=uniforms, max_length=max_length, temperature=float(temprature), generator=generator,
                                  cond_scale=float(cond_scale), filter_logits_fn=filter_logits_fn, filter_fn_kwargs=filter_fn_kwargs)
         return out.to(ids.device) if ids.device != out.device else out
+
+    @ops.gated
+    @torch.no_grad()
+    def score_text2semantic(self, grapheme_token_ids, streams, cond_scale=1.0):
+        """Teacher-forced scoring (extension; what the reference's evaluate_text2semantic measures through
+        TextToSemantic.forward(..., return_loss=True)): the log-probability of every token of `streams` - int64 [S, L], the streams a
+        sampling call returned - under the text: float32 [S, L] (t2s.score_many).  One utterance, or LISTS of texts and streams (-> a
+        list).  cond_scale > 1 scores under the guidance-combined logits and needs what sampling with it needs."""
+        if not self.is_text2semantic:
+            raise TypeError("this checkpoint is an acoustic model")
+        assert cond_scale >= 1., "cond_scale >= 1 (text2semantic.py:683)"
+        assert not (cond_scale > 1 and float(self.hparams.get("cond_drop_prob", 0.0)) == 0.0), \
+            ("you need to train with conditional drop probability greater than 0 to use classifier free guidance at inference "
+             "(text2semantic.py:684): this checkpoint's hyper_parameters['cond_drop_prob'] is 0 or absent")
+        many = isinstance(grapheme_token_ids, (list, tuple))
+        if many != isinstance(streams, (list, tuple)):
+            raise ValueError("score_text2semantic: one utterance and its streams, or a list of each")
+        dec = self._get_t2s()
+        res = dec.score_many(list(grapheme_token_ids) if many else [grapheme_token_ids], list(streams) if many else [streams],
+                             cond_scale=float(cond_scale))
+        return res if many else res[0]

@@ -20,6 +20,8 @@
 //                       the encoder context, text2semantic.py:253-262); 16 lanes per key for coalesced 256-byte rows.
 //   sample_kernel       the logit filter - top-k (:126-132; k from the descriptor) or top-p (:118-124) - + Gumbel argmax (:105-113) from
 //                       caller-supplied U(0,1) draws, eos bookkeeping (:803-818), and the embedding of the sampled ids = next step's input.
+//                       Its LOGP instantiations (cvx_t2s_decode_steps_scored) also store the log-probability of the step's token and honour
+//                       FORCED dialogues, which read given tokens instead of sampling (teacher-forced scoring).
 // The reference rotates ALL cached keys again every step with rotary_embedding_torch's interleaved pairs
 // (rotary_embedding_torch.py:146-157); rotating a key once at its own position when it enters the cache is the same
 // arithmetic.  Interleaved pairs (2i, 2i+1) become half-split pairs (i, i+32) by permuting the rows of to_q / to_k
@@ -512,7 +514,8 @@ struct SampleArgs {
     float* x;                // [batch][streams * dim_emb]  next step's input (residual stream)
     int64_t* tokens;         // [dialogue][streams, max_len]
     int* state;              // [batch][SR]: [0] pos  [1] done  [2] length at the first eos  [3] context rows  [4] dialogue  [5] step limit
-                             //              [6] flags (bit 0: the eos does not end the dialogue)
+                             //              [6] flags (bit 0: the eos does not end the dialogue; bit 1, LOGP instantiations only: FORCED - the
+                             //              token row already holds the tokens, nothing is sampled, only the step limit ends the dialogue)
     int* queue;              // NULL, or {next pending dialogue, number of dialogues}: continuous batching
     int* dialogues;          // [n][SR] (queue != NULL): in [0] context rows [1] step limit [2] flags; out [3] status (0 pending, 1 running,
                              //   2 ended by its eos, 3 by its limit) [4] steps decoded [5] the slot it ran in
@@ -525,6 +528,7 @@ struct SampleArgs {
                              // null + (cond - null) * cfg_scale and feeds both; one-output models.  With a queue the pair decodes the
                              // dialogue records (2u', 2u' + 1) and the even slot refills both
     float top_p;             // FILT_TOP_P: the nucleus threshold
+    float* logprobs;         // LOGP instantiations: [dialogue][streams, max_len], laid out like tokens
 };
 
 enum { FILT_TOP_K = CVX_T2S_FILTER_TOP_K, FILT_TOP_P = CVX_T2S_FILTER_TOP_P };
@@ -622,7 +626,54 @@ __device__ __forceinline__ int sample_select(const float* lrow, const float* nro
     return *chosen;
 }
 
-template <int NT, int FILT>
+// The row the filter sees, alone (a forced step, the stand-alone log-prob entry): the loads and the guidance combination of sample_select,
+// the same operations in the same order, so lg holds the same bits.  lg: 1024 floats of LDS; synchronises before it returns.
+template <int NT>
+__device__ __forceinline__ void stage_row(const float* lrow, const float* nrow, float cfg_scale, int V, float* lg)
+{
+    const int tid = threadIdx.x;
+    for (int i = tid; i < V; i += NT) {
+        const float c = aload(lrow + i);
+        if (nrow) {
+            const float n = aload(nrow + i);
+            lg[i] = n + (c - n) * cfg_scale;
+        } else lg[i] = c;
+    }
+    __syncthreads();
+}
+
+// log-softmax of the staged row lg[0, V) at entry tok: lp = (lg[tok] - m) - logf(sum_j expf(lg[j] - m)), m = the row maximum (exact in any
+// order).  The sum is a function of the row alone - whatever NT, the slot, the batch or the launch: ex[j] = expf(lg[j] - m) for j < V and 0
+// up to 1024; lane t of the first wave adds ex[t], ex[t + 64], ..., ex[t + 960] in that order, then the xor butterfly 32, 16, 8, 4, 2, 1
+// over the 64 lanes.  lg: the row (as sample_select / stage_row left it, already synchronised), ex: 1024 floats, bv: 16 floats of LDS.
+// The result is valid in thread 0; the caller synchronises before lg, ex or bv are written again.
+template <int NT>
+__device__ __forceinline__ float row_logprob(const float* lg, int V, int tok, float* ex, float* bv)
+{
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    float m = -INFINITY;
+    for (int i = tid; i < V; i += NT) m = fmaxf(m, lg[i]);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+    if (lane == 0) bv[wid] = m;
+    __syncthreads();
+    m = bv[0];
+    for (int w = 1; w < NT / 64; ++w) m = fmaxf(m, bv[w]);
+    for (int i = tid; i < 1024; i += NT) ex[i] = i < V ? expf(lg[i] - m) : 0.f;
+    __syncthreads();
+    float lp = 0.f;
+    if (tid < 64) {
+        float sum = 0.f;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) sum += ex[tid + 64 * i];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
+        lp = (lg[tok] - m) - logf(sum);
+    }
+    return lp;
+}
+
+template <int NT, int FILT, bool LOGP>
 __device__ __forceinline__ void sample_body(const SampleArgs& a, int b, float* lg, float* ex, float* bv, int* bi, int* chosen)
 {
     const int tid = threadIdx.x;
@@ -632,13 +683,27 @@ __device__ __forceinline__ void sample_body(const SampleArgs& a, int b, float* l
     const int pos = aloadi(state);
     if (pos >= a.max_len) return;                   // (block-uniform; also: an idle slot of a drained queue)
     const int64_t dlg = aloadi(state + 4);          // the dialogue this slot decodes (== b without a queue)
+    // FORCED (flag bit 1, the LOGP instantiations only): the token row already holds the dialogue's tokens - nothing is sampled, the row's
+    // uniforms are not read, and only the step limit ends the dialogue (block-uniform: every thread reads the record)
+    const bool forced = LOGP ? (aloadi(state + 6) & 2) != 0 : false;
     bool eos = false;
     for (int s = 0; s < a.streams; ++s) {
-        const int tok = sample_select<NT, FILT, false>(a.logits + ((int64_t)b * a.streams + s) * a.V,
-                                                       cfg ? a.logits + ((int64_t)(b + 1) * a.streams + s) * a.V : nullptr, a.cfg_scale,
-                                                       a.uniforms + ((dlg * a.uniform_steps + pos) * a.streams + s) * a.V, a.V, a.top_k,
-                                                       a.top_p, a.inv_temp, nullptr, lg, ex, bv, bi, chosen);
-        if (tid == 0) a.tokens[(dlg * a.streams + s) * a.max_len + pos] = tok;
+        const float* const lrow = a.logits + ((int64_t)b * a.streams + s) * a.V;
+        const float* const nrow = cfg ? a.logits + ((int64_t)(b + 1) * a.streams + s) * a.V : nullptr;
+        int tok;
+        if (LOGP && forced) {
+            stage_row<NT>(lrow, nrow, a.cfg_scale, a.V, lg);
+            // (the host refuses tokens outside [0, V); the clamp keeps a stray one from indexing emb)
+            tok = (int)min((int64_t)(a.V - 1), max((int64_t)0, a.tokens[(dlg * a.streams + s) * a.max_len + pos]));
+        } else {
+            tok = sample_select<NT, FILT, false>(lrow, nrow, a.cfg_scale, a.uniforms + ((dlg * a.uniform_steps + pos) * a.streams + s) * a.V,
+                                                 a.V, a.top_k, a.top_p, a.inv_temp, nullptr, lg, ex, bv, bi, chosen);
+            if (tid == 0) a.tokens[(dlg * a.streams + s) * a.max_len + pos] = tok;
+        }
+        if (LOGP) {          // of the row the filter saw: before the filter, the temperature and the noise
+            const float lp = row_logprob<NT>(lg, a.V, tok, ex, bv);
+            if (tid == 0) a.logprobs[(dlg * a.streams + s) * a.max_len + pos] = lp;
+        }
         eos = eos || (tok == a.eos_id);
         for (int d = tid; d < a.dim_emb; d += NT) {
             const float e = a.emb[(int64_t)tok * a.dim_emb + d];
@@ -649,6 +714,16 @@ __device__ __forceinline__ void sample_body(const SampleArgs& a, int b, float* l
         __syncthreads();
     }
     if (a.queue == nullptr) {
+        if (LOGP && forced) {       // the slot record's step limit ends a forced dialogue: done, its length, and the slot idles
+            if (tid == 0) {
+                const bool last = pos + 1 >= aloadi(state + 5);
+                const int np = last ? a.max_len : pos + 1;
+                if (last) { state[1] = 1; state[2] = pos + 1; }
+                state[0] = np;
+                if (cfg) { int* const sn = state + SR; if (last) { sn[1] = 1; sn[2] = pos + 1; } sn[0] = np; }
+            }
+            return;
+        }
         if (tid == 0) {
             int done = aloadi(state + 1), len = aloadi(state + 2);
             if (eos && done == 0) { done = 1; len = pos + 1; state[1] = 1; state[2] = len; }
@@ -663,7 +738,7 @@ __device__ __forceinline__ void sample_body(const SampleArgs& a, int b, float* l
     // at a time.  A pair is taken only when BOTH of its records exist (nxt + 1 < n), so a refill never indexes past the n dialogues
     // whatever the caller put into queue[1].
     int* const sn = state + SR;                     // the null-context slot of a guided pair (touched under cfg only)
-    const bool ends_eos = eos && !(aloadi(state + 6) & 1);
+    const bool ends_eos = eos && !(aloadi(state + 6) & 1) && !forced;
     const bool ends = ends_eos || pos + 1 >= aloadi(state + 5);        // (block-uniform: `eos` comes from LDS, the record is read by all)
     if (!ends) {
         if (tid == 0) { state[0] = pos + 1; if (cfg) sn[0] = pos + 1; }
@@ -710,15 +785,30 @@ __device__ __forceinline__ void sample_body(const SampleArgs& a, int b, float* l
 
 // FILT_TOP_K is the instruction stream of every default launch; the nucleus filter's second LDS array (exp(l - max), 4 KiB on top of the
 // 4 KiB of logits) exists in its own instantiation only
-template <int FILT>
+// LOGP (cvx_t2s_decode_steps_scored): the log-prob epilogue and the forced mode, in instantiations of their own
+template <int FILT, bool LOGP = false>
 __global__ __launch_bounds__(1024) void sample_kernel(const SampleArgs a)
 {
     __shared__ __attribute__((aligned(16))) float lg[1024];
-    __shared__ __attribute__((aligned(16))) float ex[FILT == FILT_TOP_P ? 1024 : 4];
+    __shared__ __attribute__((aligned(16))) float ex[(FILT == FILT_TOP_P || LOGP) ? 1024 : 4];
     __shared__ float bv[16];
     __shared__ int bi[16];
     __shared__ int chosen;
-    sample_body<1024, FILT>(a, blockIdx.x, lg, ex, bv, bi, &chosen);
+    sample_body<1024, FILT, LOGP>(a, blockIdx.x, lg, ex, bv, bi, &chosen);
+}
+
+// the log-prob epilogue alone: one block per row, no slot state (cvx_t2s_logprob_f32)
+__global__ __launch_bounds__(1024) void logprob_rows_kernel(const float* logits, const int64_t* tokens, int V, float* out)
+{
+    __shared__ __attribute__((aligned(16))) float lg[1024];
+    __shared__ __attribute__((aligned(16))) float ex[1024];
+    __shared__ float bv[16];
+    const int64_t r = blockIdx.x;
+    stage_row<1024>(logits + r * V, nullptr, 1.f, V, lg);
+    const int64_t t = tokens[r];
+    const bool in = t >= 0 && t < V;                      // (a token outside [0, V) indexes nothing: its row gets a NaN)
+    const float lp = row_logprob<1024>(lg, V, in ? (int)t : 0, ex, bv);
+    if (threadIdx.x == 0) out[r] = in ? lp : __int_as_float(0x7fc00000);
 }
 
 // the filter + sampling of sample_kernel alone: one block per row, no slot state, no queue, no embedding write
@@ -855,10 +945,19 @@ static int t2s_validate(const cvx_t2s_decoder* d, int32_t n_steps)
     return CVX_OK;
 }
 
-extern "C" int cvx_t2s_decode_steps(const cvx_t2s_decoder* d, int32_t n_steps, cvx_stream_t s)
+extern "C" int cvx_t2s_logprob_f32(const float* logits, const int64_t* tokens, int64_t rows, int32_t V, float* out, cvx_stream_t s)
 {
-    const int rc = t2s_validate(d, n_steps);
-    if (rc != CVX_OK) return rc;
+    CVX_REQUIRE(logits && tokens && out && rows >= 0 && rows <= 0x7fffffff && V >= 1 && V <= 1024,
+                "t2s_logprob: bad arguments (rows=%lld V=%d)", (long long)rows, V);
+    if (rows == 0) return CVX_OK;
+    hipLaunchKernelGGL(logprob_rows_kernel, dim3((unsigned)rows), dim3(1024), 0, cvx_hip_stream(s), logits, tokens, V, out);
+    CVX_CHECK_LAUNCH("cvx_t2s_logprob_f32");
+    return CVX_OK;
+}
+
+// the step chain of cvx_t2s_decode_steps (logprobs == NULL) and cvx_t2s_decode_steps_scored: they differ in the sampling kernel only
+static int t2s_decode_run(const cvx_t2s_decoder* d, int32_t n_steps, float* logprobs, cvx_stream_t s)
+{
     hipStream_t st = cvx_hip_stream(s);
     const float scale = 0.125f;        // dim_head ** -0.5
     const int nb = d->batch;
@@ -908,10 +1007,32 @@ extern "C" int cvx_t2s_decode_steps(const cvx_t2s_decoder* d, int32_t n_steps, c
         launch_gemv<MODE_LOGITS>(g, d->streams * ((d->vocab + 1) / 2), nb, st);
         SampleArgs sa{d->logits, d->uniforms, d->emb, d->x, d->tokens, d->state, d->queue, d->dialogues, d->start, nb, d->uniform_steps,
                       d->vocab, d->dim_emb, d->streams, d->max_len, d->top_k, d->vocab - 1, 1.0f / fmaxf(d->temperature, 1e-10f),
-                      d->cfg_scale, d->top_p};
-        if (d->filter_mode == CVX_T2S_FILTER_TOP_P) hipLaunchKernelGGL(sample_kernel<FILT_TOP_P>, dim3((unsigned)nb), dim3(1024), 0, st, sa);
+                      d->cfg_scale, d->top_p, logprobs};
+        if (logprobs) {
+            if (d->filter_mode == CVX_T2S_FILTER_TOP_P) hipLaunchKernelGGL((sample_kernel<FILT_TOP_P, true>), dim3((unsigned)nb), dim3(1024), 0, st, sa);
+            else hipLaunchKernelGGL((sample_kernel<FILT_TOP_K, true>), dim3((unsigned)nb), dim3(1024), 0, st, sa);
+        } else if (d->filter_mode == CVX_T2S_FILTER_TOP_P) hipLaunchKernelGGL(sample_kernel<FILT_TOP_P>, dim3((unsigned)nb), dim3(1024), 0, st, sa);
         else hipLaunchKernelGGL(sample_kernel<FILT_TOP_K>, dim3((unsigned)nb), dim3(1024), 0, st, sa);
     }
     CVX_CHECK_LAUNCH("cvx_t2s_decode_steps");
     return CVX_OK;
+}
+
+extern "C" int cvx_t2s_decode_steps(const cvx_t2s_decoder* d, int32_t n_steps, cvx_stream_t s)
+{
+    const int rc = t2s_validate(d, n_steps);
+    if (rc != CVX_OK) return rc;
+    return t2s_decode_run(d, n_steps, nullptr, s);
+}
+
+extern "C" int cvx_t2s_decode_steps_scored(const cvx_t2s_decoder* d, const cvx_t2s_scoring* sc, int32_t n_steps, cvx_stream_t s)
+{
+    CVX_REQUIRE(sc && sc->struct_size == sizeof(cvx_t2s_scoring), "t2s_decode_scored: cvx_t2s_scoring.struct_size = %u, this library knows %u",
+                sc ? sc->struct_size : 0u, (unsigned)sizeof(cvx_t2s_scoring));
+    CVX_REQUIRE(sc->logprobs, "t2s_decode_scored: null logprobs");
+    const int rc = t2s_validate(d, n_steps);
+    if (rc != CVX_OK) return rc;
+    CVX_REQUIRE(sc->logprob_len == d->max_len, "t2s_decode_scored: logprob_len = %d, the rows of logprobs are laid out like those of tokens "
+                "(max_len = %d floats)", sc->logprob_len, d->max_len);
+    return t2s_decode_run(d, n_steps, sc->logprobs, s);
 }

@@ -80,6 +80,8 @@ def build_parser() -> ArgumentParser:
     p.add_argument("--t2s_filter_thres", type=float, default=None, help="extension: the filter's thres (top_k: k = ceil(thres * vocab), "
                    "reference default 0.1; top_p: the nucleus mass, reference default 0.9, inside (0, 1))")
     p.add_argument("--t2s_top_k", type=int, default=None, help="extension: an explicit k for --t2s_filter top_k (overrides the thres)")
+    p.add_argument("--t2s_best_of", type=int, default=1, help="extension: decode this many candidates per turn through the continuously "
+                   "refilled slots and keep the one the model finds most likely (largest mean token log-probability; 1 = off: today's files)")
     p.add_argument("--gpus", type=int, default=1, help="extension: from a plain shell, start this many ranks (one per GPU, "
                    "utterances sharded; under torch.distributed.run the launcher's WORLD_SIZE is used instead)")
     return p
@@ -192,7 +194,18 @@ def t2s_sampling_kwargs(args) -> dict:
         fkw["k"] = int(args.t2s_top_k)
     if fkw:
         kw["filter_fn_kwargs"] = fkw
+    best_of = int(getattr(args, "t2s_best_of", 1))
+    if best_of < 1:
+        raise ValueError(f"--t2s_best_of {best_of}: at least 1")
+    if best_of > 1:
+        kw["best_of"] = best_of
     return kw
+
+
+def _candidate_salt(c: int) -> int:
+    """The salt of candidate c of a turn's text2semantic draws (--t2s_best_of): candidate 0 keeps the salt the single decode always had
+    (1: the same files with --t2s_best_of 1); candidate c > 0 takes one that depends on c only (2 is the acoustic noise's)."""
+    return 1 if c == 0 else 0x100 + int(c)
 
 
 def _predict_turns(work, t2s, device, seed: int, slots: int = 64, sampling=None) -> dict:
@@ -213,15 +226,22 @@ def _predict_turns(work, t2s, device, seed: int, slots: int = 64, sampling=None)
         # ALL turns through t2s.generate_many: 64 continuously refilled decode slots - a turn that has sampled its eos frees its slot for
         # the next one on the device (the reference decodes turn by turn, dialogue_generation.py:297-304).  In windows of 256 turns: the
         # uniform draws of a window (8 MB per turn at 2048 steps) and its context k/v are resident while it decodes.
+        # --t2s_best_of N: N candidates per turn, each with its own draws ([N, L, S, V] per turn), in windows of WINDOW / N turns - the
+        # draws are made window by window, so the resident memory stays that of WINDOW records.
         from .t2s import WINDOW
         dec = t2s._get_t2s()
         S, V, L = dec.d["streams"], dec.d["vocab"], dec.max_length
-        for w in range(0, len(todo), WINDOW):
-            part = todo[w:w + WINDOW]
+        best_of = int((sampling or {}).get("best_of", 1))
+        win = max(1, WINDOW // best_of)
+        for w in range(0, len(todo), win):
+            part = todo[w:w + win]
             uniforms = []
             for name, k, _ in part:
-                g = torch.Generator(device=device).manual_seed(_stable_seed(seed, name, k, 1))
-                uniforms.append(torch.rand(L, S, V, device=device, generator=g))
+                draws = []
+                for c in range(best_of):
+                    g = torch.Generator(device=device).manual_seed(_stable_seed(seed, name, k, _candidate_salt(c)))
+                    draws.append(torch.rand(L, S, V, device=device, generator=g))
+                uniforms.append(draws[0] if best_of == 1 else torch.stack(draws))
             toks = t2s.synthesis_sample_text2semantic([ids.to(device) for _, _, ids in part], uniforms=uniforms, slots=slots,
                                                       **(sampling or {}))
             for (name, k, _), t in zip(part, toks):

@@ -802,6 +802,18 @@ def t2s_sample(logits: torch.Tensor, uniforms: torch.Tensor, filter_mode: int = 
     return (tokens, kept) if return_kept else tokens
 
 
+def t2s_logprob(logits: torch.Tensor, tokens: torch.Tensor) -> torch.Tensor:
+    """log_softmax(logits[r])[tokens[r]] with the decode's log-prob epilogue (cvx_t2s_logprob_f32): logits [rows, V] fp32, tokens int64
+    [rows] -> fp32 [rows].  The summation order is fixed: a function of the row alone."""
+    _chk_f32(logits)
+    assert logits.ndim == 2 and logits.is_contiguous() and tokens.is_cuda and tokens.dtype == torch.int64 and tokens.is_contiguous()
+    rows, V = logits.shape
+    assert tokens.shape == (rows,)
+    out = torch.empty(rows, dtype=torch.float32, device=logits.device)
+    _lib.check(_lib.load().cvx_t2s_logprob_f32(logits.data_ptr(), tokens.data_ptr(), rows, V, out.data_ptr(), _stream()), "cvx_t2s_logprob_f32")
+    return out
+
+
 def dwconv31_gelu_res(x: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, out: torch.Tensor,
                       Bt: int, T: int, ragged: Optional[Ragged] = None) -> torch.Tensor:
     _chk_f32(x, w, bias, out)

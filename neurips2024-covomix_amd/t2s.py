@@ -5,7 +5,8 @@ Host mirror of the reference's `TextToSemantic.generate` sampling branch + `Text
 forwards to (covomix/conditional_model.py:313-321).  Built: the sampling branch with its three controls - temperature,
 classifier-free guidance (cond_scale > 1, one-output models) and the logit filter (filter_logits_fn = top_k / top_p with
 filter_fn_kwargs, text2semantic.py:118-132, :796) - in every decode schedule below; no beam / speculative decoding, no padded
-text batches.
+text batches.  Beside the tokens: the log-probability of every sampled token (return_logprobs), teacher-forced scoring of given tokens
+through the same decode slots (score_many) and the mean token log-probability best-of-N selects by (sequence_logprob).
 
   encoder  (source transformer, once per utterance): the full-sequence kernels of the acoustic path - fp32 GEMM with
            the RoPE epilogue, flash attention, RMSNorm - plus a GEGLU kernel;
@@ -67,6 +68,69 @@ def filter_setting(filter_logits_fn="top_k", filter_fn_kwargs=None, vocab: int =
             raise ValueError(f"top_p: thres = {thres} outside (0, 1)")
         return (_lib.T2S_FILTER_TOP_P, 0, thres)
     raise ValueError(f"filter_logits_fn must be 'top_k' or 'top_p', got {filter_logits_fn!r}")
+
+
+def sequence_logprob(logprobs: torch.Tensor, streams: torch.Tensor, eos: int) -> float:
+    """The mean log-probability per counted token of one decoded utterance: per stream the positions up to AND INCLUDING its first eos
+    count (all of them when it has none - what is behind an eos is padding, mask_after_eos, text2semantic.py:73-76); the result is the sum
+    of logprobs over the counted positions of all streams divided by their number.  logprobs float [S, L], streams int64 [S, L] (what
+    `generate(return_logprobs=True)` returns); summed in fp64 on the host."""
+    lp, st = torch.as_tensor(logprobs).detach().cpu().double(), torch.as_tensor(streams).detach().cpu()
+    if lp.shape != st.shape or lp.numel() == 0 or lp.ndim not in (1, 2):
+        raise ValueError(f"sequence_logprob: logprobs {tuple(lp.shape)} and streams {tuple(st.shape)} must be the same non-empty [S, L]")
+    lp, st = lp.reshape(-1, lp.shape[-1]), st.reshape(-1, st.shape[-1])
+    after = (st == eos).cumsum(dim=-1) > 0
+    counted = ~torch.nn.functional.pad(after, (1, -1), value=False)
+    return float(lp[counted].sum() / int(counted.sum()))
+
+
+def best_candidate(scores) -> int:
+    """best-of-N: the index of the largest score; the LOWEST index wins ties.  A NaN score never wins against a number."""
+    scores = [float(x) for x in scores]
+    if not scores:
+        raise ValueError("best_candidate: no candidates")
+    best = 0
+    for c in range(1, len(scores)):
+        if scores[c] > scores[best] or (math.isnan(scores[best]) and not math.isnan(scores[c])):
+            best = c
+    return best
+
+
+def check_best_of(best_of, n_utterances: Optional[int] = None, uniforms=None) -> int:
+    """best_of of synthesis_sample_text2semantic: an integer >= 1; caller-supplied uniforms then hold the draws of every candidate,
+    [best_of, steps, S, V] per utterance.  ValueError otherwise."""
+    if isinstance(best_of, bool) or not isinstance(best_of, int) or best_of < 1:
+        raise ValueError(f"best_of must be an integer >= 1, got {best_of!r}")
+    if best_of > 1 and uniforms is not None:
+        us = [uniforms] if n_utterances is None else list(uniforms)
+        if n_utterances is not None and len(us) != n_utterances:
+            raise ValueError(f"best_of: {len(us)} uniform tensors for {n_utterances} utterances")
+        for u in us:
+            if u.ndim < 4 or u.shape[0] != best_of:
+                raise ValueError(f"best_of = {best_of}: the uniforms of an utterance are [best_of, steps, S, V], got {tuple(u.shape)}")
+    return best_of
+
+
+def check_targets(targets, streams: int, vocab: int, max_length: int) -> list:
+    """The targets of score_many as int64 [S, L] host tensors.  ValueError for a shape other than [S, L] ([L] is taken as [1, L]),
+    L < 1, L > max_length or a token outside [0, vocab): such a token must never reach the device, where it would index the embedding."""
+    out = []
+    for j, t in enumerate(targets):
+        t = torch.as_tensor(t).detach().cpu()
+        if t.dtype not in (torch.int64, torch.int32):
+            raise ValueError(f"target {j}: integer tokens expected, got {t.dtype}")
+        t = t.to(torch.int64)
+        if t.ndim == 1:
+            t = t[None, :]
+        if t.ndim != 2 or t.shape[0] != streams:
+            raise ValueError(f"target {j}: [S = {streams}, L] expected, got {tuple(t.shape)}")
+        L = t.shape[1]
+        if L < 1 or L > max_length:
+            raise ValueError(f"target {j}: length {L} outside [1, max_length = {max_length}]")
+        if int(t.min()) < 0 or int(t.max()) >= vocab:
+            raise ValueError(f"target {j}: tokens outside [0, vocab = {vocab})")
+        out.append(t.contiguous())
+    return out
 
 
 def _dims(sd: Dict[str, torch.Tensor]) -> dict:
@@ -167,12 +231,14 @@ class TextToSemanticDecoder:
         """per-slot buffers hold whole kernel groups: 1 / 2 / 4 slots, or a multiple of 8 (include/covomix_hip.h)"""
         return n if n in (1, 2, 4) else (n + 7) // 8 * 8
 
-    def _ensure(self, slots: int, dialogues: int, steps: int) -> None:
+    def _ensure(self, slots: int, dialogues: int, steps: int, logprobs: bool = False) -> None:
         """Decode buffers for `slots` decode slots (x, q, att, h, logits, slot records, the self-attention caches), `dialogues`
         utterances in flight or queued (context k/v, token rows, dialogue records) and `steps` uniform draws per dialogue.  They only
         grow; growing re-allocates (and drops the captured graphs, which hold the old addresses).  The uniform draws per dialogue
         are rounded up to whole chunks of CHUNK steps: a lock-step decode (_decode_chunks) runs whole chunks, and its sampling kernel
-        reads the draws of every position it reaches (up to the model's max_length, whatever the call's max_length)."""
+        reads the draws of every position it reaches (up to the model's max_length, whatever the call's max_length).
+        logprobs: the log-prob buffer [dialogues, streams, max_length] of the scored decode as well - allocated on first use only (only
+        scored graphs hold its address, so allocating it leaves the captured graphs alone), and re-allocated with the token rows."""
         d, dev = self.d, self.device
         S, V, I = d["streams"], d["vocab"], d["inner"]
         f32 = lambda *s: torch.zeros(*s, dtype=torch.float32, device=dev)
@@ -193,7 +259,10 @@ class TextToSemanticDecoder:
             self.buf.update(tokens=torch.zeros(dialogues, S, self.max_length, dtype=torch.int64, device=dev),
                             dialogues=torch.zeros(dialogues, SR, dtype=torch.int32, device=dev),
                             queue=torch.zeros(2, dtype=torch.int32, device=dev))
+            self.buf.pop("logprobs", None)
             self._dialogues, grown = dialogues, True
+        if logprobs and "logprobs" not in self.buf:
+            self.buf["logprobs"] = f32(self._dialogues, S, self.max_length)
         steps = (max(steps, 1) + CHUNK - 1) // CHUNK * CHUNK
         if steps > self._steps or "uniforms" not in self.buf or self.buf["uniforms"].numel() < self._dialogues * self._steps * S * V:
             self._steps = max(self._steps, steps)
@@ -273,10 +342,20 @@ class TextToSemanticDecoder:
             dec.queue, dec.dialogues, dec.start = b["queue"].data_ptr(), b["dialogues"].data_ptr(), self.start.data_ptr()
         return dec
 
-    def _run_steps(self, temperature: float, batch: int, n: int, cfg_scale: float = 1.0, queue: bool = False, filt=None, nd: int = 0) -> None:
+    def _launch_steps(self, temperature: float, batch: int, n: int, cfg_scale: float, queue: bool, filt, nd: int, scored: bool) -> None:
+        """n token steps on the current stream.  scored: cvx_t2s_decode_steps_scored (log-probs of every step's token into
+        buf["logprobs"], forced dialogues honoured); else cvx_t2s_decode_steps, exactly as before that entry existed."""
+        dec = self._descriptor(temperature, batch, cfg_scale, queue, filt, nd)
+        if not scored:
+            _lib.check(_lib.load().cvx_t2s_decode_steps(C.byref(dec), n, ops._stream()), "cvx_t2s_decode_steps")
+            return
+        sc = _lib.T2SScoring(C.sizeof(_lib.T2SScoring), self.max_length, self.buf["logprobs"].data_ptr())
+        _lib.check(_lib.load().cvx_t2s_decode_steps_scored(C.byref(dec), C.byref(sc), n, ops._stream()), "cvx_t2s_decode_steps_scored")
+
+    def _run_steps(self, temperature: float, batch: int, n: int, cfg_scale: float = 1.0, queue: bool = False, filt=None, nd: int = 0,
+                   scored: bool = False) -> None:
         """n token steps on the current stream without a graph."""
-        _lib.check(_lib.load().cvx_t2s_decode_steps(C.byref(self._descriptor(temperature, batch, cfg_scale, queue, filt, nd)), n,
-                                                    ops._stream()), "cvx_t2s_decode_steps")
+        self._launch_steps(temperature, batch, n, cfg_scale, queue, filt, nd, scored)
 
     def _uniform_view(self, n: int) -> torch.Tensor:
         """[n, steps, streams, vocab] view of the uniform draws of the first n dialogues"""
@@ -325,7 +404,8 @@ class TextToSemanticDecoder:
         self._pin_ev[k].synchronize()
         return self._pin[k][:rows].tolist()
 
-    def _decode_chunks(self, temperature: float, nb: int, max_len: int, cfg_scale: float, watch, ignore_eos: bool = False, filt=None) -> list:
+    def _decode_chunks(self, temperature: float, nb: int, max_len: int, cfg_scale: float, watch, ignore_eos: bool = False, filt=None,
+                       scored: bool = False) -> list:
         """Graph-replayed chunks of CHUNK token steps until every utterance slot in `watch` has sampled its eos (or max_len steps).
         The host looks at the eos flags ONE CHUNK BEHIND the device: the slot records of chunk i are copied between the replays of
         chunks i and i + 1 and read while chunk i + 1 runs - the decode chain never waits for a host round trip (nor for a host
@@ -335,7 +415,7 @@ class TextToSemanticDecoder:
         via_helper = ops.is_partition_stream()
         steps, i, pending = 0, 0, None
         while steps < max_len:
-            self._run_chunk(temperature, nb, cfg_scale, False, filt)
+            self._run_chunk(temperature, nb, cfg_scale, False, filt, 0, scored)
             steps += CHUNK
             k = i & 1
             self._mirror_push(k, self.buf["state"][:nb], via_helper)
@@ -349,20 +429,19 @@ class TextToSemanticDecoder:
             self._pin_ev[pending].synchronize()      # (the helper stream's last copy: the buffers are reused by the next call)
         return self._read_state(nb)
 
-    def _graph(self, temperature: float, batch: int, cfg_scale: float = 1.0, queue: bool = False, filt=None, nd: int = 0):
-        """The captured graph of CHUNK token steps for this (batch, stream CU count, mode, filter); captured on first use.  (nd, the
+    def _graph(self, temperature: float, batch: int, cfg_scale: float = 1.0, queue: bool = False, filt=None, nd: int = 0, scored: bool = False):
+        """The captured graph of CHUNK token steps for this (batch, stream CU count, mode, filter, scoring); captured on first use.  (nd, the
         number of dialogue records, is only validated by the C call: it is not part of the key.)  Capturing runs the
         steps once outside the capture (module load, kernel attributes): callers get their graph BEFORE they set up the decode state -
         the warm-up runs on idle slot records (position max_length: the sampling kernel returns at once, every other kernel clamps)."""
         filt = filt or self._default_filter
-        key = (temperature, batch, cfg_scale, ops.stream_cus(), queue, self._gen, filt)   # (the kernels' shape follows the CUs the stream owns)
+        key = (temperature, batch, cfg_scale, ops.stream_cus(), queue, self._gen, filt, bool(scored))   # (the kernels' shape follows the CUs the stream owns)
         g = self._graphs.get(key)
         if g is not None:
             return g
 
         def launch():
-            _lib.check(_lib.load().cvx_t2s_decode_steps(C.byref(self._descriptor(temperature, batch, cfg_scale, queue, filt, nd)), CHUNK,
-                                                        ops._stream()), "cvx_t2s_decode_steps")
+            self._launch_steps(temperature, batch, CHUNK, cfg_scale, queue, filt, nd, scored)
         self.buf["state"].copy_(self._slot_records([]))
         launch()                                       # warm-up outside capture
         cur = torch.cuda.current_stream()
@@ -379,13 +458,14 @@ class TextToSemanticDecoder:
         self._graphs[key] = g
         return g
 
-    def _run_chunk(self, temperature: float, batch: int = 1, cfg_scale: float = 1.0, queue: bool = False, filt=None, nd: int = 0) -> None:
+    def _run_chunk(self, temperature: float, batch: int = 1, cfg_scale: float = 1.0, queue: bool = False, filt=None, nd: int = 0,
+                   scored: bool = False) -> None:
         """CHUNK token steps on the current stream: a graph replay of the per-launch path (the graph must exist - `_graph` - unless
         CVX_GRAPH=0 asks for plain launches)."""
         if os.environ.get("CVX_GRAPH", "1") != "1":
-            self._run_steps(temperature, batch, CHUNK, cfg_scale, queue, filt, nd)
+            self._run_steps(temperature, batch, CHUNK, cfg_scale, queue, filt, nd, scored)
             return
-        self._graph(temperature, batch, cfg_scale, queue, filt, nd).replay()
+        self._graph(temperature, batch, cfg_scale, queue, filt, nd, scored).replay()
 
     def _contexts(self, sources, rows=None) -> list:
         """encoder + the cross-attention k/v of the utterances into dialogue rows `rows` (default 0, 1, ...): [null | to_kv(enc)]
@@ -405,22 +485,26 @@ class TextToSemanticDecoder:
             flat.index_copy_(0, first, L["null"][None, :].expand(n, -1))
         return [t + 1 for t in rg.lengths]
 
-    def _cut(self, j: int, length: int, logits=None):
-        """(flat tokens, streams[, logits]) of dialogue row j after `length` steps: mask_after_eos (text2semantic.py:73-76)"""
+    def _cut(self, j: int, length: int, logits=None, logprobs: bool = False):
+        """(flat tokens, streams[, logits][, logprobs]) of dialogue row j after `length` steps: mask_after_eos (text2semantic.py:73-76)"""
         eos = self.d["vocab"] - 1
         streams = self.buf["tokens"][j, :, :length].clone()
         after = (streams == eos).cumsum(dim=-1) > 0
         after = torch.nn.functional.pad(after, (1, -1), value=False)
         flat = streams.masked_fill(after, PAD_ID).reshape(-1)
         item = (flat[flat != PAD_ID], streams)
-        return item if logits is None else item + (logits[:length],)
+        if logits is not None:
+            item += (logits[:length],)
+        if logprobs:
+            item += (self.buf["logprobs"][j, :, :length].clone(),)
+        return item
 
     @ops.gated
     @torch.no_grad()          # (not inference_mode: tensors torch creates lazily during the first graph capture,
                               #  e.g. the generator's graph-safe state, would become inference tensors)
     def generate_batch(self, sources, uniforms=None, max_length: Optional[int] = None, temperature: float = 1.0,
                        generator: Optional[torch.Generator] = None, collect_logits: bool = False, cond_scale: float = 1.0,
-                       ignore_eos: bool = False, filter_logits_fn="top_k", filter_fn_kwargs=None):
+                       ignore_eos: bool = False, filter_logits_fn="top_k", filter_fn_kwargs=None, return_logprobs: bool = False):
         """Decode up to MAX_BATCH utterances together IN LOCK STEP (all start at position 0; the batch runs until the last one has
         sampled its eos).  sources: list of [n] / [1, n] id tensors; uniforms: optional list of [steps, streams, vocab] tensors (one
         per utterance).  Returns a list of (flat tokens, streams[, logits]) tuples, each exactly what `generate` returns for that
@@ -431,7 +515,10 @@ class TextToSemanticDecoder:
         learned null key / value only) - and each step samples from null + (cond - null) * cond_scale; logits returned under
         collect_logits are the COMBINED ones, null + (cond - null) * cond_scale (what the reference filters and samples from).
         filter_logits_fn / filter_fn_kwargs: the logit filter, as TextToSemantic.generate takes it (`filter_setting`); the default is
-        the reference's top_k with k = ceil(0.1 * vocab)."""
+        the reference's top_k with k = ceil(0.1 * vocab).
+        return_logprobs: every result gains, as its LAST entry, a float32 [S, length] tensor aligned with `streams`: the log-probability
+        the model gave each sampled token - log_softmax of the row the filter sees (the guidance-combined logits under cond_scale > 1),
+        before the filter, the temperature and the noise (include/covomix_hip.h).  Off (the default) nothing changes."""
         d, b = self.d, self.buf
         S, V = d["streams"], d["vocab"]
         filt = filter_setting(filter_logits_fn, filter_fn_kwargs, V)
@@ -441,7 +528,7 @@ class TextToSemanticDecoder:
                 raise NotImplementedError("guidance (cond_scale > 1) on a two-output model: the reference feeds the full-width hidden "
                                           "state to the half-width logit head there (text2semantic.py:783-785) and cannot run")
             return self._generate_guided(sources, uniforms, max_length, temperature, generator, collect_logits, float(cond_scale),
-                                         ignore_eos, filt)
+                                         ignore_eos, filt, return_logprobs)
         nb = len(sources)
         if not 1 <= nb <= MAX_BATCH:
             raise ValueError(f"1..{MAX_BATCH} utterances per decode batch, got {nb}")
@@ -450,10 +537,11 @@ class TextToSemanticDecoder:
         if uniforms is not None:
             us = [u.to(self.device, torch.float32).reshape(u.shape[0], S, V) for u in uniforms]
             max_len = min([max_len] + [u.shape[0] for u in us])
-        self._ensure(nb, nb, max_len)
+        scored = bool(return_logprobs)
+        self._ensure(nb, nb, max_len, scored)
         b = self.buf
         if not collect_logits and max_len > 0:
-            self._graph(float(temperature), nb, 1.0, False, filt)
+            self._graph(float(temperature), nb, 1.0, False, filt, 0, scored)
         ctx = self._contexts(sources)
         uview = self._uniform_view(nb)
         if us is None:            # (drawn step-major, as the [steps, batch, streams, vocab] buffer of earlier versions was: same seeds, same tokens)
@@ -467,20 +555,21 @@ class TextToSemanticDecoder:
         st = self._slot_records(ctx).tolist()[:nb]
         if collect_logits:                                              # (tests: one step at a time without a graph)
             for _ in range(max_len):
-                self._run_steps(float(temperature), nb, 1, 1.0, False, filt)
+                self._run_steps(float(temperature), nb, 1, 1.0, False, filt, 0, scored)
                 logits.append(b["logits"][:nb].clone())
                 st = self._read_state(nb)
                 if all(row[1] for row in st) and not ignore_eos:
                     break
         elif max_len > 0:
-            st = self._decode_chunks(float(temperature), nb, max_len, 1.0, range(nb), ignore_eos, filt)
+            st = self._decode_chunks(float(temperature), nb, max_len, 1.0, range(nb), ignore_eos, filt, scored)
         out = []
         for i in range(nb):
             length = min(st[i][2] if st[i][1] and st[i][2] <= max_len and not ignore_eos else max_len, max_len)
-            out.append(self._cut(i, length, torch.stack([lg[i] for lg in logits]) if collect_logits and logits else None))
+            out.append(self._cut(i, length, torch.stack([lg[i] for lg in logits]) if collect_logits and logits else None, scored))
         return out
 
-    def _generate_guided(self, sources, uniforms, max_length, temperature, generator, collect_logits, cond_scale, ignore_eos=False, filt=None):
+    def _generate_guided(self, sources, uniforms, max_length, temperature, generator, collect_logits, cond_scale, ignore_eos=False, filt=None,
+                         scored=False):
         """generate_batch with cond_scale > 1: slots 2u (text context) / 2u + 1 (null context) per utterance u."""
         V, nu = self.d["vocab"], len(sources)
         nb = 2 * nu
@@ -491,10 +580,11 @@ class TextToSemanticDecoder:
         if uniforms is not None:
             us = [u.to(self.device, torch.float32).reshape(u.shape[0], 1, V) for u in uniforms]
             max_len = min([max_len] + [u.shape[0] for u in us])
-        self._ensure(nb, nb, max_len)
+        scored = bool(scored)
+        self._ensure(nb, nb, max_len, scored)
         b = self.buf
         if not collect_logits and max_len > 0:
-            self._graph(float(temperature), nb, cond_scale, False, filt)
+            self._graph(float(temperature), nb, cond_scale, False, filt, 0, scored)
         ctx = []
         for c in self._contexts(sources, range(0, nb, 2)):
             ctx += [c, 1]                                                # the null slot: row 0 (null k/v) only = every context key masked out
@@ -512,26 +602,26 @@ class TextToSemanticDecoder:
         st = self._slot_records(ctx).tolist()[:nb]
         if collect_logits:
             for _ in range(max_len):
-                self._run_steps(float(temperature), nb, 1, cond_scale, False, filt)
+                self._run_steps(float(temperature), nb, 1, cond_scale, False, filt, 0, scored)
                 lg = b["logits"][:nb].clone()
                 logits.append(lg[1::2] + (lg[0::2] - lg[1::2]) * cond_scale)
                 st = self._read_state(nb)
                 if all(st[2 * u_][1] for u_ in range(nu)) and not ignore_eos:
                     break
         elif max_len > 0:
-            st = self._decode_chunks(float(temperature), nb, max_len, cond_scale, [2 * u_ for u_ in range(nu)], ignore_eos, filt)
+            st = self._decode_chunks(float(temperature), nb, max_len, cond_scale, [2 * u_ for u_ in range(nu)], ignore_eos, filt, scored)
         out = []
         for u_ in range(nu):
             i = 2 * u_
             length = min(st[i][2] if st[i][1] and st[i][2] <= max_len and not ignore_eos else max_len, max_len)
-            out.append(self._cut(i, length, torch.stack([lg[u_] for lg in logits]) if collect_logits and logits else None))
+            out.append(self._cut(i, length, torch.stack([lg[u_] for lg in logits]) if collect_logits and logits else None, scored))
         return out
 
     @ops.gated
     @torch.no_grad()
     def generate_many(self, sources, uniforms=None, max_length: Optional[int] = None, temperature: float = 1.0,
                       generator: Optional[torch.Generator] = None, slots: int = 32, ignore_eos: bool = False, limits=None, on_done=None,
-                      cond_scale: float = 1.0, filter_logits_fn="top_k", filter_fn_kwargs=None):
+                      cond_scale: float = 1.0, filter_logits_fn="top_k", filter_fn_kwargs=None, return_logprobs: bool = False, forced=None):
         """Decode ANY number of utterances through `slots` decode slots with continuous batching: every utterance runs the
         reference's loop (text2semantic.py:749-848) from position 0 to its first eos (:803-818) or its step limit, and the slot it
         ran in takes the next pending utterance in the sampling kernel of that very step (cvx_t2s_decoder.queue) - utterances end
@@ -546,10 +636,27 @@ class TextToSemanticDecoder:
         At most MAX_BATCH / 2 utterances are in flight (`slots` still counts slots: slots // 2 pairs), and WINDOW counts dialogue
         records, so a window holds WINDOW / 2 guided utterances.  limits, ignore_eos, on_done and last_records keep their meaning
         per utterance (last_records: the record of the text-context half; its slot is the even slot of the pair).
-        filter_logits_fn / filter_fn_kwargs: as generate_batch."""
+        filter_logits_fn / filter_fn_kwargs: as generate_batch.
+        return_logprobs: every result gains a float32 [S, length] host tensor aligned with `streams` (generate_batch), through the same
+        pinned-memory path as the tokens.  Off, nothing changes.
+        forced (with return_logprobs; `score_many` is the public form): a list with, per utterance, None (sampled as usual) or int64
+        [S, L] tokens to SCORE instead of sampling - a forced dialogue (include/covomix_hip.h): the steps read these tokens, draw no
+        uniforms (that utterance's entry of `uniforms` may be None), ignore every eos and stop after L steps whatever `limits` says;
+        its `streams` are the tokens given.  Forced and sampled utterances share the queue and the slots."""
         d = self.d
         S, V = d["streams"], d["vocab"]
         n = len(sources)
+        scored = bool(return_logprobs)
+        if forced is not None:
+            if not scored or len(forced) != n:
+                raise ValueError("forced: one entry per utterance, with return_logprobs=True")
+            if all(f is None for f in forced):
+                forced = None
+        if forced is not None:
+            forced = list(forced)
+            fi = [j for j in range(n) if forced[j] is not None]
+            for j, t in zip(fi, check_targets([forced[j] for j in fi], S, V, self.max_length)):
+                forced[j] = t
         filt = filter_setting(filter_logits_fn, filter_fn_kwargs, V)
         cond_scale = float(cond_scale)
         cfg = cond_scale > 1.0
@@ -565,23 +672,29 @@ class TextToSemanticDecoder:
                 out += self.generate_many(sources[w:w + win], None if uniforms is None else uniforms[w:w + win], max_length, temperature,
                                           generator, slots, ignore_eos, None if limits is None else limits[w:w + win],
                                           None if on_done is None else (lambda j, r, w=w: on_done(w + j, r)),
-                                          cond_scale, filter_logits_fn, filter_fn_kwargs)
+                                          cond_scale, filter_logits_fn, filter_fn_kwargs, return_logprobs,
+                                          None if forced is None else forced[w:w + win])
             return out
         nb = P * max(1, min(int(slots) // P, MAX_BATCH // P, n))
         nb = nb if nb in (1, 2, 4) else min((nb + 7) // 8 * 8, MAX_BATCH)      # whole kernel groups (idle slots cost nothing)
         nrec = P * n
         max_len = min(int(max_length or self.max_length), self.max_length)
         us = None
+        is_forced = [forced is not None and forced[j] is not None for j in range(n)]
         if uniforms is not None:
-            us = [u.to(self.device, torch.float32).reshape(u.shape[0], S, V) for u in uniforms]
-            max_len = min([max_len] + [u.shape[0] for u in us])
+            us = [None if (u is None and is_forced[j]) else u.to(self.device, torch.float32).reshape(u.shape[0], S, V) for j, u in enumerate(uniforms)]
+            max_len = min([max_len] + [u.shape[0] for u in us if u is not None])
         lim = [max_len] * n if limits is None else [max(1, min(int(x), max_len)) for x in limits]
         if max_len <= 0:
             raise ValueError("generate_many needs at least one step")
-        self._ensure(nb, nrec, max_len)
+        span = max_len                # steps an utterance can take: the rows of the pinned result buffers
+        if forced is not None:
+            lim = [forced[j].shape[1] if is_forced[j] else lim[j] for j in range(n)]
+            span = max(span, max(lim))
+        self._ensure(nb, nrec, max_len, scored)
         b = self.buf
         temperature = float(temperature)
-        self._graph(temperature, nb, cond_scale, True, filt, nrec)
+        self._graph(temperature, nb, cond_scale, True, filt, nrec, scored)
         if cfg:                   # record 2u: the text context; record 2u + 1: the null key / value row only (every context key masked out)
             ctx = []
             for c in self._contexts(sources, range(0, nrec, 2)):
@@ -592,19 +705,25 @@ class TextToSemanticDecoder:
             ctx = self._contexts(sources)
         uview = self._uniform_view(nrec)[0::P]            # the draws of utterance j live in its first record
         if us is None:
-            uview[:, :max_len].copy_(torch.rand(n, max_len, S, V, device=self.device, generator=generator))
+            if not all(is_forced):                         # (a forced dialogue reads no draws: a pure scoring call draws none)
+                uview[:, :max_len].copy_(torch.rand(n, max_len, S, V, device=self.device, generator=generator))
         else:
             for j, u in enumerate(us):
-                uview[j, :max_len].copy_(u[:max_len])
-        flags = 1 if ignore_eos else 0
+                if u is not None:
+                    uview[j, :max_len].copy_(u[:max_len])
+        flags = [_lib.T2S_FLAG_FORCED if is_forced[j] else (_lib.T2S_FLAG_IGNORE_EOS if ignore_eos else 0) for j in range(n)]
+        if forced is not None:                             # the token row of a forced dialogue holds its tokens before its first step
+            for j in range(n):
+                if is_forced[j]:
+                    b["tokens"][P * j, :, :lim[j]].copy_(ops.h2d(forced[j], self.device))
         first = min(nb, nrec)     # records (= slots) that start at once; whole pairs under guidance (nb and nrec are even)
-        rec = torch.tensor([[ctx[r], lim[r // P], flags, 1 if r < first else 0, 0, r if r < first else 0, 0, 0] for r in range(nrec)],
+        rec = torch.tensor([[ctx[r], lim[r // P], flags[r // P], 1 if r < first else 0, 0, r if r < first else 0, 0, 0] for r in range(nrec)],
                            dtype=torch.int32)
         b["dialogues"][:nrec].copy_(rec)
         b["queue"].copy_(torch.tensor([first, nrec], dtype=torch.int32))
         slot = self._slot_records(ctx[:first]).clone()
         for r in range(first):
-            slot[r, 5], slot[r, 6] = lim[r // P], flags
+            slot[r, 5], slot[r, 6] = lim[r // P], flags[r // P]
         b["state"].copy_(slot)
         b["x"][:first].copy_(self.start[None, :].expand(first, -1))
         self._mirror_setup()
@@ -615,7 +734,8 @@ class TextToSemanticDecoder:
         # once the host has SEEN it finished: any stream may read them) and are cut on the host - nothing here makes the decode
         # stream wait, so the chunks stay back to back (a device-side boolean index per utterance cost a stream sync each: 64
         # utterances on 64 slots ran 996 ms against 746 ms in lock step)
-        tok_pin = torch.empty(n, S, max_len, dtype=torch.int64).pin_memory()
+        tok_pin = torch.empty(n, S, span, dtype=torch.int64).pin_memory()
+        lp_pin = torch.empty(n, S, span, dtype=torch.float32).pin_memory() if scored else None
         copies: list = []                                  # (j, steps, event) in flight on the helper stream
         eos = V - 1
 
@@ -628,6 +748,8 @@ class TextToSemanticDecoder:
                 after = torch.nn.functional.pad(after, (1, -1), value=False)
                 flat = streams.masked_fill(after, PAD_ID).reshape(-1)
                 out[j] = (flat[flat != PAD_ID], streams)
+                if scored:
+                    out[j] += (lp_pin[j, :, :length].clone(),)
                 if on_done is not None:
                     on_done(j, out[j])
 
@@ -641,6 +763,8 @@ class TextToSemanticDecoder:
                         seen[j] = True
                         length = records[j][4]
                         tok_pin[j, :, :length].copy_(b["tokens"][P * j, :, :length], non_blocking=True)
+                        if scored:
+                            lp_pin[j, :, :length].copy_(b["logprobs"][P * j, :, :length], non_blocking=True)
                         ev = torch.cuda.Event()
                         ev.record()
                         copies.append((j, length, ev))
@@ -649,7 +773,7 @@ class TextToSemanticDecoder:
         i, pending = 0, None
         cap = (sum(lim) + CHUNK - 1) // CHUNK + 4          # (one slot decoding everything: cannot be reached)
         while not all(seen) and i < cap:
-            self._run_chunk(temperature, nb, cond_scale, True, filt, nrec)
+            self._run_chunk(temperature, nb, cond_scale, True, filt, nrec, scored)
             k = i & 1
             self._mirror_push(k, b["dialogues"][:nrec], via_helper)
             if pending is not None:
@@ -665,19 +789,42 @@ class TextToSemanticDecoder:
             raise RuntimeError(f"text2semantic continuous decode: {seen.count(False)} of {n} utterances did not finish in {i} chunks")
         return out
 
+    def score_many(self, sources, targets, cond_scale: float = 1.0, slots: int = 64):
+        """Teacher-forced scoring: the log-probability the model gives every token of targets[j] under the text sources[j] - what the
+        reference's TextToSemantic.forward(..., return_loss=True) averages (text2semantic.py), position by position.  targets[j]: int64
+        [S, L_j], the `streams` that `generate` returns; -> list of float32 [S, L_j] host tensors: entry [s, t] is the log-softmax, at
+        token targets[j][s, t], of the step-t logits given the tokens before t (the guidance-combined logits under cond_scale > 1, one-output
+        models).  The targets run as forced dialogues through `slots` continuously refilled decode slots, in windows of WINDOW records as
+        generate_many; the values are bit-identical whatever the slots, the batch or the neighbours - and equal, bit for bit, the log-probs
+        `generate(return_logprobs=True)` returned when it sampled those tokens.  ValueError for L_j < 1, L_j > max_length or a token
+        outside [0, vocab); NotImplementedError for guidance on a two-output model."""
+        sources, targets = list(sources), list(targets)
+        if len(sources) != len(targets):
+            raise ValueError(f"score_many: {len(sources)} sources, {len(targets)} targets")
+        if float(cond_scale) > 1.0 and self.d["streams"] != 1:
+            raise NotImplementedError("guidance (cond_scale > 1) on a two-output model: the reference cannot run it (generate_batch)")
+        tg = check_targets(targets, self.d["streams"], self.d["vocab"], self.max_length)
+        if not tg:
+            return []
+        res = self.generate_many(sources, None, max(t.shape[1] for t in tg), 1.0, None, slots, cond_scale=cond_scale,
+                                 return_logprobs=True, forced=tg)
+        return [r[2] for r in res]
+
     @ops.gated
     def generate(self, source_ids: torch.Tensor, uniforms: Optional[torch.Tensor] = None, max_length: Optional[int] = None,
                  temperature: float = 1.0, generator: Optional[torch.Generator] = None, return_streams: bool = False,
-                 collect_logits: bool = False, cond_scale: float = 1.0, filter_logits_fn="top_k", filter_fn_kwargs=None):
+                 collect_logits: bool = False, cond_scale: float = 1.0, filter_logits_fn="top_k", filter_fn_kwargs=None,
+                 return_logprobs: bool = False):
         """== TextToSemanticWrapper.sample(grapheme_token_ids): flat int64 tensor, stream 1 then stream 2 (two-output
         models), each cut after its eos.  uniforms [steps, streams, vocab] (or [steps, streams, 1, vocab]) replaces
         the random draws of gumbel_noise (text2semantic.py:108-110); default: torch.rand from `generator`.
         collect_logits (tests): step one token at a time without a graph and also return the pre-filter logits
-        [steps, streams, vocab].  cond_scale / filter_logits_fn / filter_fn_kwargs: see generate_batch."""
+        [steps, streams, vocab].  cond_scale / filter_logits_fn / filter_fn_kwargs: see generate_batch.  return_logprobs: returns
+        (flat tokens, streams[, logits], logprobs) - logprobs float32 [S, length] aligned with streams (generate_batch)."""
         if source_ids.ndim == 2 and source_ids.shape[0] != 1:
             raise NotImplementedError("one utterance per call (the generation scripts run batch 1); see generate_batch")
         res = self.generate_batch([source_ids], None if uniforms is None else [uniforms], max_length, temperature, generator,
-                                  collect_logits, cond_scale, False, filter_logits_fn, filter_fn_kwargs)[0]
-        if collect_logits:
+                                  collect_logits, cond_scale, False, filter_logits_fn, filter_fn_kwargs, return_logprobs)[0]
+        if collect_logits or return_logprobs:
             return res
         return res if return_streams else res[0]

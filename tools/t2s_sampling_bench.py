@@ -8,6 +8,13 @@
   python tools/t2s_sampling_bench.py guided
       64 guided CoSingle dialogues (cond_scale 1.5) that end at different steps (limits 100 ... 608, the eos ignored: the recipe of
       config5.decode_ragged) through generate_many(cond_scale=) on 32 slot pairs against lock-step guided batches of 32.
+  python tools/t2s_sampling_bench.py steps --logprobs
+      adds the step time with the log-prob epilogue on (return_logprobs=True: the scoring instantiation of the sampling kernel).
+  python tools/t2s_sampling_bench.py score
+      score_many of 64 x 608-token targets (forced dialogues) against generate_many of the same 64 x 608 steps, both on 64 slots.
+  python tools/t2s_sampling_bench.py bestof
+      dialogues per second of best-of 1 / 2 / 4 on 56 CoMix dialogues (608 steps each, the eos ignored: N * 56 decodes through 64 slots,
+      log-probs on for N > 1, selection included).
 """
 import argparse
 import json
@@ -18,7 +25,8 @@ import time
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("what", choices=["steps", "guided"])
+    ap.add_argument("what", choices=["steps", "guided", "score", "bestof"])
+    ap.add_argument("--logprobs", action="store_true")
     ap.add_argument("--root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     ap.add_argument("--top-p", type=float, default=None)
     ap.add_argument("--steps", type=int, default=256)
@@ -45,12 +53,43 @@ def main():
             m = model(name)
             for slots in (1, 8, 64):
                 srcs = [torch.randint(1, 30000, (1, 64), generator=g) for _ in range(slots)]
-                for label, kw in (("default", {}),) + ((("top_p", dict(filter_logits_fn="top_p", filter_fn_kwargs={"thres": args.top_p})),) if args.top_p else ()):
+                forms = (("default", {}),) + ((("top_p", dict(filter_logits_fn="top_p", filter_fn_kwargs={"thres": args.top_p})),) if args.top_p else ())
+                forms += ((("logprobs", dict(return_logprobs=True)),) if args.logprobs else ())
+                for label, kw in forms:
                     run = lambda: m.generate_batch(srcs, max_length=args.steps, ignore_eos=True, **kw)
                     run()                                                 # graph + buffers of the timed shape
                     t = min(timed(run) for _ in range(3))
                     print(json.dumps({"tag": args.tag, "model": name, "slots": slots, "filter": label, "steps": args.steps,
                                       "us_per_step": round(t / args.steps * 1e6, 1)}), flush=True)
+    elif args.what == "score":
+        for name in ("comix", "cosingle"):
+            m = model(name)
+            n, tokens, S, V = 64, 608, m.d["streams"], m.d["vocab"]
+            srcs = [torch.randint(1, 30000, (1, 64), generator=g) for _ in range(n)]
+            tg = [torch.randint(0, V, (S, tokens), generator=g) for _ in range(n)]
+            score = lambda: m.score_many(srcs, tg, slots=64)
+            sample = lambda: m.generate_many(srcs, max_length=tokens, slots=64, ignore_eos=True)
+            score(); sample()
+            for r in range(5):
+                t_score, t_sample = timed(score), timed(sample)
+                print(json.dumps({"tag": args.tag, "model": name, "round": r, "dialogues": n, "tokens": tokens, "score_many_s": round(t_score, 4),
+                                  "generate_many_s": round(t_sample, 4), "score_vs_generate": round(t_score / t_sample, 3)}), flush=True)
+    elif args.what == "bestof":
+        from covomix_amd.t2s import best_candidate, sequence_logprob
+        m = model("comix")
+        n, tokens, eos = 56, 608, m.d["vocab"] - 1
+        srcs = [torch.randint(1, 30000, (1, 64), generator=g) for _ in range(n)]
+
+        def run(N):
+            if N == 1:
+                return m.generate_many(srcs, max_length=tokens, slots=64, ignore_eos=True)
+            res = m.generate_many([s_ for s_ in srcs for _ in range(N)], max_length=tokens, slots=64, ignore_eos=True, return_logprobs=True)
+            return [res[j * N + best_candidate([sequence_logprob(c[2], c[1], eos) for c in res[j * N:(j + 1) * N]])] for j in range(n)]
+        for N in (1, 2, 4):
+            run(N)
+            t = min(timed(lambda: run(N)) for _ in range(3))
+            print(json.dumps({"tag": args.tag, "best_of": N, "dialogues": n, "tokens": tokens, "seconds": round(t, 4),
+                              "dialogues_per_s": round(n / t, 1)}), flush=True)
     else:
         m = model("cosingle")
         n, tokens, pairs = 64, 608, 32
