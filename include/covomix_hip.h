@@ -67,8 +67,9 @@ typedef const cvx_ctx* cvx_stream_t;
  * cvx_t2s_decoder grew filter_mode / top_p / n_dialogues at its end (top-p beside top-k), a dialogue queue may run under guidance
  * (record pairs), cvx_t2s_sample_f32 (the filter + sampling of one decode step on caller-supplied logits).  112:
  * cvx_hifigan_conv1d_f16x3_form (the tile height a split-precision convolution launch takes; host arithmetic only, so that tests can
- * place a problem on every tile form). */
-#define CVX_ABI_VERSION 112
+ * place a problem on every tile form).  113: cvx_gemm_f32_form (which of its four kernels an fp32 GEMM launch takes; host arithmetic
+ * only, so that tests can place a problem on every kernel). */
+#define CVX_ABI_VERSION 113
 int         cvx_version(void);
 const char* cvx_last_error_string(void);
 
@@ -139,6 +140,19 @@ typedef struct {
     const float* rope_cos; const float* rope_sin; int32_t rope_T; int32_t rope_cols;
 } cvx_gemm_args;
 int cvx_gemm_bias_act_f32(const cvx_gemm_args* a, cvx_stream_t s);
+
+/* Which kernel cvx_gemm_bias_act_f32 launches for a shape: the launcher takes its decision from this very function.  No GPU work,
+ * no stream, callable on a machine without a GPU.  -1 for a shape no launch can have (M < 1, N < 1, K < 4 or K % 4 != 0).
+ *   T64:          64-row tiles, operands staged through registers  (K % 32 == 0; M <= 64, or fewer than 256 tiles of 128 x 128)
+ *   T64_GENERIC:  64-row tiles, predicated loads                   (the same shapes with K % 32 != 0)
+ *   T128_DMA:     128-row tiles, operands by LDS-DMA               (K % 32 == 0, M > 64, 256 tiles of 128 x 128 and more)
+ *   T128_GENERIC: 128-row tiles, predicated loads                  (the same shapes with K % 32 != 0)
+ * The four agree to fp32 rounding, not bit for bit. */
+#define CVX_GEMM_F32_FORM_T64          0
+#define CVX_GEMM_F32_FORM_T64_GENERIC  1
+#define CVX_GEMM_F32_FORM_T128_DMA     2
+#define CVX_GEMM_F32_FORM_T128_GENERIC 3
+int cvx_gemm_f32_form(int32_t M, int32_t N, int32_t K);
 
 /* Split-precision variant of the same contract (same nn.Linear call sites): every fp32 operand is an
  * (fp16 hi, fp16 lo) pair, hi = fp16(x), lo = fp16(x - hi), and  a*w ~= a_hi*w_hi + a_hi*w_lo + a_lo*w_hi

@@ -16,7 +16,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CVX_LIB_PATH") or os.path.join(_HERE, "libcovomix_hip.so")      # CVX_LIB_PATH: dev A/B builds
 
 _f32p = C.POINTER(C.c_float)
-ABI_VERSION = 112          # == cvx_version(): bumped whenever an argument struct or an entry point's meaning changes
+ABI_VERSION = 113          # == cvx_version(): bumped whenever an argument struct or an entry point's meaning changes
 
 
 class GemmArgs(C.Structure):
@@ -237,6 +237,7 @@ SIGNATURES = {
                                            C.c_int32, C.c_int32, C.c_float, C.c_void_p]),
     "cvx_last_error_string": (C.c_char_p, []),
     "cvx_gemm_bias_act_f32": (C.c_int, [C.POINTER(GemmArgs), C.c_void_p]),
+    "cvx_gemm_f32_form": (C.c_int, [C.c_int32, C.c_int32, C.c_int32]),
     "cvx_split_f16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_void_p]),
     "cvx_gemm_f16x3_workspace_floats": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "cvx_rope_attention_workspace_floats": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),

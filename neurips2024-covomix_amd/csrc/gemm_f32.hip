@@ -3,24 +3,26 @@
 // Every nn.Linear of the CoVoMix vector field (reference acoustic.py:225-246, :306-310,
 // :361-365, :200, :503-516) goes through this kernel; 86 % of the path's FLOPs.
 //
-// Design (MI355X): 256 threads = 4 waves (2x2), block tile (TM*64) x 128, K-step 32.
-//   * both operands are K-contiguous ("NT"), staged global -> VGPR -> LDS with 16-byte
-//     loads, LDS rows padded to 36 floats so the ds_read_b128 fragment reads are
-//     bank-conflict free;
+// Design (MI355X): 256 threads = 4 waves (2x2), block tile 64 x 128 or 128 x 128, K-step 32.  Four kernels, chosen from
+// the shape alone by gemm_f32_form (the one statement of the rule; cvx_gemm_f32_form reports it):
+//   T64           gemm_f32_kernel<1>          64-row tiles, K % 32 == 0: small M, or fewer than 256 tiles of 128 x 128
+//   T64_GENERIC   gemm_f32_generic_kernel<1>  the same shapes with K % 32 != 0 (predicated loads)
+//   T128_DMA      gemm_f32_glds_kernel        128-row tiles, K % 32 == 0, operands by LDS-DMA (its own comment below)
+//   T128_GENERIC  gemm_f32_generic_kernel<2>  128-row tiles, K % 32 != 0 (only to_embed's 80 x-columns at full size)
+//   * both operands are K-contiguous ("NT"); the 64-row kernel stages global -> VGPR -> LDS with 16-byte
+//     loads, LDS rows padded to 36 floats so the ds_read_b128 fragment reads are bank-conflict free;
 //   * one ds_read_b128 feeds FOUR MFMAs: lanes 0-31 hold k = 8q..8q+3, lanes 32-63 hold
 //     k = 8q+4..8q+7 of their row, and MFMA t contracts the (8q+t, 8q+4+t) pair - the
 //     k order inside a tile is free as long as A and B use the same one;
 //   * two LDS buffers; the K loop is ONE branch-free basic block per step (out-of-range
 //     rows are clamped, not predicated: their products land in accumulator rows/columns the
 //     epilogue never stores), with the next tile's global loads issued first, its LDS
-//     writes placed between the 3rd and 4th MFMA group, and one barrier per step - so the
-//     matrix pipe always has queued work while loads, address math and LDS writes retire;
+//     writes placed between the 3rd and 4th MFMA group, and one barrier per step;
 //   * XCD-aware block->tile map: an XCD owns whole M row-panels, so each A panel is
 //     fetched into exactly one L2.
 // Epilogue fuses bias, GELU/SiLU, half-split RoPE (a wave owns one whole 64-wide head, so
 // the (j, j+32) partner is the same accumulator register of the neighbouring MFMA tile)
-// and the residual add.  K % 32 != 0 (only to_embed's 80 x-columns) takes the predicated
-// generic kernel.
+// and the residual add.
 #include "gemm_common.h"
 #include <stdlib.h>
 
@@ -47,7 +49,7 @@ __device__ __forceinline__ void mfma_group(const float* a, const float* b, int q
 }
 
 // ------------------------------------------------------------------ fast path: K % 32 == 0
-template <int TM>   // TM = MFMA tiles per wave along M (block M = TM*64)
+template <int TM>   // TM = MFMA tiles per wave along M (block M = TM*64); instantiated for TM = 1 only (128-row tiles: the LDS-DMA kernel)
 __global__ __launch_bounds__(256, 2) void gemm_f32_kernel(const cvx_gemm_args p, int tiles_m, int tiles_n, int map_mode)
 {
     constexpr int BM = TM * 64;
@@ -141,29 +143,6 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_kernel(const cvx_gemm_args p,
 #pragma unroll
         for (int i = 0; i < 4; ++i) *reinterpret_cast<f32x4*>(bn + 32 * i * LDS_LD) = rb[i];
         mfma_group<TM>(a, b, 3, acc);
-        if constexpr (TM == 2) {
-            // Issue order of this step (one scheduling region): memory instructions are spread ONE per MFMA
-            // instead of in bursts.  Measured on the probe (tools/archive/mfma_probe.hip): a burst of 8 global loads
-            // costs 107 vs 135 TFLOP/s when the operands stream from HBM.
-            //   q0: 4 frag reads | 8 x (MFMA, global load) | 4 x (2 MFMA, q1 frag read)
-            //   q1: 4 x (4 MFMA, q2 frag read)
-            //   q2: 8 x (MFMA, LDS write of the next tile) | 4 x (2 MFMA, q3 frag read)
-            //   q3: 16 MFMA
-#define CVX_SGB(mask, n) __builtin_amdgcn_sched_group_barrier(mask, n, 0)
-            CVX_SGB(0x100, 4);
-#pragma unroll
-            for (int i = 0; i < 8; ++i) { CVX_SGB(0x008, 1); CVX_SGB(0x020, 1); }
-#pragma unroll
-            for (int i = 0; i < 4; ++i) { CVX_SGB(0x008, 2); CVX_SGB(0x100, 1); }
-#pragma unroll
-            for (int i = 0; i < 4; ++i) { CVX_SGB(0x008, 4); CVX_SGB(0x100, 1); }
-#pragma unroll
-            for (int i = 0; i < 8; ++i) { CVX_SGB(0x008, 1); CVX_SGB(0x200, 1); }
-#pragma unroll
-            for (int i = 0; i < 4; ++i) { CVX_SGB(0x008, 2); CVX_SGB(0x100, 1); }
-            CVX_SGB(0x008, 16);
-#undef CVX_SGB
-        }
         __syncthreads();
     }
     gemm_epilogue<TM>(p, acc, m0, n0, wm, wn, lane);
@@ -347,29 +326,37 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_generic_kernel(const cvx_gemm
     gemm_epilogue<TM>(p, acc, m0, n0, wm, wn, lane);
 }
 
-template <int TM>
-int launch_gemm(const cvx_gemm_args& a, hipStream_t st)
+// The ONE statement of the launch rule: cvx_gemm_bias_act_f32 launches by it and cvx_gemm_f32_form reports it.
+// Small-M problems (time tables, short utterances) use the 64-row tile to fill more CUs; K % 32 != 0 takes the predicated kernels.
+int gemm_f32_form(int M, int N, int K)
 {
-    constexpr int BM = TM * 64;
-    const size_t lds = (size_t)2 * (BM + BN) * LDS_LD * sizeof(float);
-    const bool fast = (a.K % BK == 0);
-    cvx_allow_dynamic_lds(fast ? reinterpret_cast<const void*>(gemm_f32_kernel<TM>)
-                               : reinterpret_cast<const void*>(gemm_f32_generic_kernel<TM>), (int)lds);
+    if (M < 1 || N < 1 || K < 4 || K % 4 != 0) return -1;
+    const long blocks128 = (((long)M + 127) / 128) * (((long)N + BN - 1) / BN);   // tiles of 128 x 128
+    const bool fast = (K % BK == 0);
+    if (M <= 64 || blocks128 < 256) return fast ? CVX_GEMM_F32_FORM_T64 : CVX_GEMM_F32_FORM_T64_GENERIC;
+    return fast ? CVX_GEMM_F32_FORM_T128_DMA : CVX_GEMM_F32_FORM_T128_GENERIC;
+}
+
+int launch_gemm(const cvx_gemm_args& a, int form, hipStream_t st)
+{
+    void (*kernel)(const cvx_gemm_args, int, int, int) = nullptr;
+    int BM = 64;
+    bool dma = false;
+    switch (form) {
+    case CVX_GEMM_F32_FORM_T64:          kernel = gemm_f32_kernel<1>; break;
+    case CVX_GEMM_F32_FORM_T64_GENERIC:  kernel = gemm_f32_generic_kernel<1>; break;
+    case CVX_GEMM_F32_FORM_T128_DMA:     kernel = gemm_f32_glds_kernel; BM = 128; dma = true; break;
+    case CVX_GEMM_F32_FORM_T128_GENERIC: kernel = gemm_f32_generic_kernel<2>; BM = 128; break;
+    default: CVX_REQUIRE(false, "gemm: no launch form for M=%d N=%d K=%d", a.M, a.N, a.K);
+    }
+    // two buffers of an A and a W tile: rows padded to LDS_LD floats, or unpadded (swizzled) where they arrive by LDS-DMA
+    const size_t lds = (size_t)2 * (BM + BN) * (dma ? BK : LDS_LD) * sizeof(float);
+    cvx_allow_dynamic_lds(reinterpret_cast<const void*>(kernel), (int)lds);
     const int tiles_n = (a.N + BN - 1) / BN, tiles_m = (a.M + BM - 1) / BM;
     const int map_mode = 1;             // XCD-aware block -> tile map (gemm_common.h)
     const int grid_m = map_mode == 1 ? ((tiles_m + 7) / 8) * 8 : tiles_m;
     dim3 grid((unsigned)(grid_m * tiles_n));
-    if constexpr (TM == 2) {
-        if (fast) {
-            const size_t lds_dma = (size_t)4 * 128 * BK * sizeof(float);
-            cvx_allow_dynamic_lds(reinterpret_cast<const void*>(gemm_f32_glds_kernel), (int)lds_dma);
-            hipLaunchKernelGGL(gemm_f32_glds_kernel, grid, dim3(256), lds_dma, st, a, tiles_m, tiles_n, map_mode);
-            CVX_CHECK_LAUNCH("cvx_gemm_bias_act_f32");
-            return CVX_OK;
-        }
-    }
-    if (fast) hipLaunchKernelGGL(gemm_f32_kernel<TM>, grid, dim3(256), lds, st, a, tiles_m, tiles_n, map_mode);
-    else      hipLaunchKernelGGL(gemm_f32_generic_kernel<TM>, grid, dim3(256), lds, st, a, tiles_m, tiles_n, map_mode);
+    hipLaunchKernelGGL(kernel, grid, dim3(256), lds, st, a, tiles_m, tiles_n, map_mode);
     CVX_CHECK_LAUNCH("cvx_gemm_bias_act_f32");
     return CVX_OK;
 }
@@ -400,9 +387,7 @@ extern "C" int cvx_gemm_bias_act_f32(const cvx_gemm_args* a, cvx_stream_t s)
     const int rc = cvxg::validate_gemm_args(a);
     if (rc != CVX_OK) return rc;
     if (a->M == 0) return CVX_OK;
-    hipStream_t st = cvx_hip_stream(s);
-    // Small-M problems (time tables, short utterances) use the 64-row tile to fill more CUs.
-    const long blocks128 = (long)((a->M + 127) / 128) * ((a->N + BN - 1) / BN);
-    if (a->M <= 64 || blocks128 < 256) return launch_gemm<1>(*a, st);
-    return launch_gemm<2>(*a, st);
+    return launch_gemm(*a, gemm_f32_form(a->M, a->N, a->K), cvx_hip_stream(s));
 }
+
+extern "C" int cvx_gemm_f32_form(int32_t M, int32_t N, int32_t K) { return gemm_f32_form(M, N, K); }

@@ -352,6 +352,19 @@ def gemm(a: torch.Tensor, w: torch.Tensor, out: torch.Tensor, *, bias=None, act=
     return out
 
 
+GEMM_F32_FORMS = ("T64", "T64_GENERIC", "T128_DMA", "T128_GENERIC")
+
+
+def gemm_f32_form(M: int, N: int, K: int) -> str:
+    """Which kernel the fp32 GEMM (gemm without w_split) launches for this shape, one of GEMM_F32_FORMS: 64- or 128-row tiles,
+    register-staged / LDS-DMA operands for K % 32 == 0, predicated loads otherwise.  Host arithmetic of the library's own launch
+    rule (cvx_gemm_f32_form): no GPU needed."""
+    form = _lib.load().cvx_gemm_f32_form(M, N, K)
+    if form < 0:
+        raise ValueError(f"gemm_f32_form: no launch has M={M} N={N} K={K}")
+    return GEMM_F32_FORMS[form]
+
+
 def split_act_f16(x: torch.Tensor, hi=None, lo: Optional[torch.Tensor] = None, scale=None):
     """(hi, lo) fp16 halves of an fp32 activation tensor - for GEMMs that take A pre-split.
     With `hi` given and lo=None only the (saturating) fp16 cast is written; hi may be a SplitIL (interleaved pair).

@@ -227,7 +227,7 @@ def test_abi_refuses_bad_sampling_descriptors(decoders):
         assert lib.cvx_t2s_sample_f32(lg.data_ptr(), lg.data_ptr(), 2, V, mode, k, thres, 1.0, tok.data_ptr(), None, ops._stream()) == EINVAL
     torch.cuda.synchronize()
     assert tok.tolist() == [-7, -7]
-    assert lib.cvx_version() == 112 == _lib.ABI_VERSION
+    assert lib.cvx_version() == 113 == _lib.ABI_VERSION
 
 
 # ---------------------------------------------------------------- facade and CLI

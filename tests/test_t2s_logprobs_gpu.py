@@ -262,7 +262,7 @@ def test_nothing_moves_when_the_feature_is_off(name):
     keys = set(model._graphs)
     lp = model.generate(src, uniforms=uni, return_logprobs=True)              # on: one more graph, the old ones stay
     assert torch.equal(lp[0], flat) and keys < set(model._graphs) and "logprobs" in model.buf
-    assert _lib.load().cvx_version() == 112 == _lib.ABI_VERSION
+    assert _lib.load().cvx_version() == 113 == _lib.ABI_VERSION
 
 
 # ---------------------------------------------------------------- 6. facade and CLI
@@ -388,4 +388,4 @@ def test_scored_entry_refuses_bad_descriptors(decoders):
     assert call(batch=65) == EINVAL and call(vocab=1025) == EINVAL and call(state=None) == EINVAL
     torch.cuda.synchronize()
     assert torch.equal(model.buf["state"], sentinel) and bool((lp == 3.0).all())
-    assert lib.cvx_version() == 112 == _lib.ABI_VERSION
+    assert lib.cvx_version() == 113 == _lib.ABI_VERSION
