@@ -68,7 +68,8 @@ typedef const cvx_ctx* cvx_stream_t;
  * (record pairs), cvx_t2s_sample_f32 (the filter + sampling of one decode step on caller-supplied logits).  112:
  * cvx_hifigan_conv1d_f16x3_form (the tile height a split-precision convolution launch takes; host arithmetic only, so that tests can
  * place a problem on every tile form).  113: cvx_gemm_f32_form (which of its four kernels an fp32 GEMM launch takes; host arithmetic
- * only, so that tests can place a problem on every kernel). */
+ * only, so that tests can place a problem on every kernel).  Still 113 (symbols added, no struct or entry point changed): cvx_t2s_beam_steps
+ * with its own size-carrying struct, cvx_t2s_beam_select_f32 - beam search on the decode slots. */
 #define CVX_ABI_VERSION 113
 int         cvx_version(void);
 const char* cvx_last_error_string(void);
@@ -730,6 +731,66 @@ typedef struct {
 } cvx_t2s_scoring;
 
 int cvx_t2s_decode_steps_scored(const cvx_t2s_decoder* dec, const cvx_t2s_scoring* scoring, int32_t n_steps, cvx_stream_t stream);
+
+/* Beam search on the decode slots - the deterministic decode behind the reference's beam_search_decode flag, which its generate accepts
+ * and never implements (text2semantic.py:673-677): the algorithm below is this library's definition.
+ * Per utterance: B = beam_size hypotheses (1 <= B <= 16) in B neighbouring slots; utterance u owns slots [u B, (u + 1) B), and
+ * dec->batch = utterances * B <= 64.  S = streams, V = vocab, eos = V - 1.  One step:
+ *   lp[s][j] = log_softmax of stream s's raw logits row exactly as defined under "Log-probabilities" above (same m, expf and summation tree);
+ *       temperature, filter and uniforms play no part.
+ *   Shortlist: per live hypothesis and stream the min(B, V) entries with the largest lp, ordered by (lp descending, index ascending): the
+ *       rank of entry i is the number of entries j with lp[j] > lp[i], or lp[j] == lp[i] and j < i.
+ *   Candidates of a live hypothesis p with cumulative score c[p]: S = 1: (p, a) scored c[p] + lp[0][tok_a]; S = 2: (p, a, b) scored
+ *       c[p] + (lp[0][tok_a] + lp[1][tok_b]) - fp32 in this association; order key q = (p B + a) B + b (b = 0 for S = 1).  A FINISHED
+ *       hypothesis (one that took an eos in any stream) has one candidate: itself, score unchanged, q = p B B.  A hypothesis with score
+ *       -inf has none (before step 0 the caller gives hypothesis 0 score 0 and the others -inf).
+ *   Selection: the B candidates with the largest score, ties to the lowest q; new slot i receives the i-th best.  A slot for which no
+ *       candidate is left becomes a dead hypothesis: parent i, tokens -1, score -inf, finished.
+ *   The utterance ends when all B hypotheses are finished, or at its step limit; its slots then idle at position max_len.
+ * KV caches are never copied: a cache row (slot, position) is written once per utterance, by the hypothesis that sits in that slot at that
+ * step, and owner int32 [2][batch][max_len] (ping-ponged by step parity; row ((pos & 1) * batch + slot)) names, for every past position of
+ * the hypothesis in a slot, the slot whose cache holds it.  The self-attention of the beam chain reads key / value j from slot owner[..][j]
+ * with the arithmetic, loop shape and accumulation order of the direct kernel (an identity table gives the same bits); the selection writes
+ * the next row: the parent's row for positions 0..pos, then the slot itself.  The caller fills the table with the identity
+ * (owner[*][slot][*] = slot) before step 0.  History is kept as back-pointers: parents [max_len][batch] (index INSIDE the group),
+ * hist_tokens int32 / hist_logprobs fp32 [max_len][batch][streams] (a carried finished hypothesis records tokens -1, log-probs 0).
+ * groups int32 [batch / B][4]: [0] steps done (the caller writes 0), [1] ended (the caller writes 0; 1 for a group that must stay idle),
+ * [2] step limit (<= max_len), [3] reserved.  Slot records: the caller writes [0] = 0, [1] = 0, [2] = 0, [3] context rows and [4] the
+ * dialogue (the B slots of an utterance name the same one) as for cvx_t2s_decode_steps (idle groups: [0] = max_len); the selection writes
+ * [0] position (max_len once the hypothesis is finished or the utterance has ended), [1] finished-or-ended, [2] the steps the hypothesis
+ * took up to and including its eos step (all steps when it never finished).  scores fp32 [batch] / finished uint8 [batch]: in and out.
+ * short_lp fp32 / short_tokens int32 [batch][streams][16]: workspace.  backtrack != 0: after the n_steps steps (n_steps may be 0) a
+ * back-track kernel writes dec->tokens int64 [batch][streams][max_len] and logprobs fp32 [batch][streams][max_len] (hist_len = max_len)
+ * of the hypothesis in every slot from the back-pointers.  Per step: the launches of cvx_t2s_decode_steps plus one.  No host
+ * synchronisation, graph-capturable.  CVX_EINVAL (nothing is launched): struct_size != sizeof, dec->queue != NULL, dec->cfg_scale > 1,
+ * beam_size outside [1, 16], batch % beam_size != 0, hist_len != max_len, a NULL pointer, and everything cvx_t2s_decode_steps refuses. */
+typedef struct cvx_t2s_beam {
+    uint32_t struct_size;
+    int32_t beam_size;
+    int32_t hist_len;
+    int32_t backtrack;
+    float* scores;
+    uint8_t* finished;
+    int32_t* owner;
+    int32_t* groups;
+    int32_t* parents;
+    int32_t* hist_tokens;
+    float* hist_logprobs;
+    float* short_lp;
+    int32_t* short_tokens;
+    float* logprobs;
+} cvx_t2s_beam;
+
+int cvx_t2s_beam_steps(const cvx_t2s_decoder* dec, const cvx_t2s_beam* beam, int32_t n_steps, cvx_stream_t stream);
+
+/* The selection step alone (the device functions cvx_t2s_beam_steps selects with; no slot state): groups G of beam_size B hypotheses,
+ * logits [G * B, streams, V] fp32, scores_in [G * B], finished_in uint8 [G * B] -> per new slot: parents (index inside the group), tokens
+ * int64 [G * B, streams] and token_lp fp32 [G * B, streams] (-1 and 0 for a carried or dead hypothesis), scores_out, finished_out.  Groups
+ * do not influence each other.  CVX_EINVAL (nothing is launched) for beam_size outside [1, 16], streams outside {1, 2}, V outside
+ * [1, 1024], groups < 0 or a NULL pointer. */
+int cvx_t2s_beam_select_f32(const float* logits, const float* scores_in, const uint8_t* finished_in, int32_t groups, int32_t beam_size,
+                            int32_t streams, int32_t V, int32_t* parents, int64_t* tokens, float* token_lp, float* scores_out,
+                            uint8_t* finished_out, cvx_stream_t stream);
 
 /* The log-probability epilogue alone (the device function cvx_t2s_decode_steps_scored uses): out[r] = log_softmax(logits[r, :])[tokens[r]]
  * as defined above; logits [rows, V] fp32, tokens int64 [rows], out fp32 [rows].  One thread block per row.  A token outside [0, V) gives

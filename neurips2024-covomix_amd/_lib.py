@@ -158,6 +158,13 @@ class T2SScoring(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("logprob_len", C.c_int32), ("logprobs", C.c_void_p)]
 
 
+class T2SBeam(C.Structure):
+    """cvx_t2s_beam: struct_size = sizeof(this); device state of the beam chain (include/covomix_hip.h)"""
+    _fields_ = [("struct_size", C.c_uint32), ("beam_size", C.c_int32), ("hist_len", C.c_int32), ("backtrack", C.c_int32)] + \
+               [(n, C.c_void_p) for n in ("scores", "finished", "owner", "groups", "parents", "hist_tokens", "hist_logprobs", "short_lp",
+                                          "short_tokens", "logprobs")]
+
+
 class ResblockArgs(C.Structure):
     _fields_ = [("x", C.c_void_p), ("B", C.c_int32), ("C", C.c_int32), ("L", C.c_int32),
                 ("Wp1", C.c_void_p * 3), ("b1", C.c_void_p * 3), ("Wp2", C.c_void_p * 3), ("b2", C.c_void_p * 3),
@@ -203,6 +210,9 @@ SIGNATURES = {
     "cvx_mel_log_transpose_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]),
     "cvx_t2s_decode_steps": (C.c_int, [C.POINTER(T2SDecoder), C.c_int32, C.c_void_p]),
     "cvx_t2s_decode_steps_scored": (C.c_int, [C.POINTER(T2SDecoder), C.POINTER(T2SScoring), C.c_int32, C.c_void_p]),
+    "cvx_t2s_beam_steps": (C.c_int, [C.POINTER(T2SDecoder), C.POINTER(T2SBeam), C.c_int32, C.c_void_p]),
+    "cvx_t2s_beam_select_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "cvx_t2s_logprob_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]),
     "cvx_t2s_sample_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float,
                                      C.c_void_p, C.c_void_p, C.c_void_p]),

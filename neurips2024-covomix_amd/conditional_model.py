@@ -227,7 +227,8 @@ class CoVoMixModel:
     @torch.no_grad()
     def synthesis_sample_text2semantic(self, grapheme_token_ids, temprature=1.0, cond_scale=1.0, beam_search_decode=False,
                                        prompt_mel=None, uniforms=None, generator=None, max_length=None, slots=64,
-                                       filter_logits_fn="top_k", filter_fn_kwargs=None, return_logprobs=False, best_of=1):
+                                       filter_logits_fn="top_k", filter_fn_kwargs=None, return_logprobs=False, best_of=1,
+                                       beam_size=10, length_penalty=1.0):
         """reference conditional_model.py:313-321 -> TextToSemanticWrapper.sample (text2semantic.py:1237-1251): the
         sampled semantic tokens as one flat int64 tensor (two-output models: stream 1 then stream 2) on the input's
         device.  (`temprature` is the reference's spelling.)  `uniforms` / `generator` (optional) fix the U(0,1) draws
@@ -241,7 +242,12 @@ class CoVoMixModel:
         utterance's mean log-probability per token.
         best_of = N > 1 (extension): N candidates per utterance are decoded through the continuously refilled slots (N * n dialogues, or
         record pairs under guidance) and the one with the largest sequence_logprob is returned; the lowest candidate index wins ties.
-        Caller-supplied `uniforms` of an utterance are then [N, steps, S, V].  best_of = 1 is the call without it, bit for bit."""
+        Caller-supplied `uniforms` of an utterance are then [N, steps, S, V].  best_of = 1 is the call without it, bit for bit.
+        beam_search_decode=True (the flag the reference's generate accepts and never implements, text2semantic.py:673-677): beam search
+        with `beam_size` hypotheses (default 10, the reference's; 1..16) - t2s.generate_beam: deterministic, so `temprature` and
+        `filter_*` are unused, and `uniforms`, `generator` or best_of > 1 with it are a ValueError; returns the tokens of the hypothesis with
+        the largest cumulative log-probability / (tokens scored) ** length_penalty (or the tuple under return_logprobs; lists run in
+        lock-step waves of 64 // beam_size utterances).  Guided beams (cond_scale > 1) are not built: NotImplementedError."""
         if not self.is_text2semantic:
             raise TypeError("this checkpoint is an acoustic model: use synthesis_sample")
         assert cond_scale >= 1., "cond_scale >= 1 (text2semantic.py:683)"
@@ -250,11 +256,21 @@ class CoVoMixModel:
         assert not (cond_scale > 1 and float(self.hparams.get("cond_drop_prob", 0.0)) == 0.0), \
             ("you need to train with conditional drop probability greater than 0 to use classifier free guidance at inference "
              "(text2semantic.py:684): this checkpoint's hyper_parameters['cond_drop_prob'] is 0 or absent")
-        if beam_search_decode:
-            raise NotImplementedError("beam search decoding is not built (the generation scripts sample)")
-        from .t2s import best_candidate, check_best_of, sequence_logprob
+        from .t2s import best_candidate, check_beam_size, check_best_of, sequence_logprob
         ids = grapheme_token_ids
         many = isinstance(ids, (list, tuple))
+        if beam_search_decode:
+            if uniforms is not None or generator is not None:
+                raise ValueError("beam search is deterministic: it takes no uniforms and no generator")
+            if not (isinstance(best_of, int) and not isinstance(best_of, bool) and best_of == 1):
+                raise ValueError("beam search already keeps beam_size hypotheses: best_of > 1 does not combine with it")
+            check_beam_size(beam_size)
+            if cond_scale > 1:
+                raise NotImplementedError("beam search under guidance (cond_scale > 1) is not built: a guided hypothesis would need a slot "
+                                          "pair (text context / null context) sharing one ancestry")
+            res = self._get_t2s().generate_beam(list(ids) if many else ids, beam_size, max_length, float(length_penalty))
+            pick = (lambda r, i: tuple(t.to(i.device) for t in r[:3])) if return_logprobs else (lambda r, i: r[0].to(i.device))
+            return [pick(r, i) for r, i in zip(res, ids)] if many else pick(res, ids)
         best_of = check_best_of(best_of, len(ids) if many else None, uniforms)
         self._get_t2s()
         if best_of > 1:

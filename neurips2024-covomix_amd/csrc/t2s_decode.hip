@@ -22,6 +22,12 @@
 //                       caller-supplied U(0,1) draws, eos bookkeeping (:803-818), and the embedding of the sampled ids = next step's input.
 //                       Its LOGP instantiations (cvx_t2s_decode_steps_scored) also store the log-probability of the step's token and honour
 //                       FORCED dialogues, which read given tokens instead of sampling (teacher-forced scoring).
+// BEAM SEARCH (cvx_t2s_beam_steps; the algorithm: include/covomix_hip.h): the B hypotheses of an utterance sit in B neighbouring slots and
+// continue from each other's KV caches through an ancestry table - no cache row is ever copied:
+//   attn_owner_kernel      attn_kernel's body with key / value j read from the cache of slot owner[j] (the row staged in LDS);
+//   beam_shortlist_kernel  per live row the min(B, V) largest log-softmax entries (row_logprob's maximum and sum), in place of sample_kernel;
+//   beam_merge_kernel      per utterance the B best of the <= B^3 candidates; writes back-pointers, scores, slot records, the next inputs and
+//                          the next ancestry rows;  beam_backtrack_kernel: the back-pointers into token / log-prob rows, once at the end.
 // The reference rotates ALL cached keys again every step with rotary_embedding_torch's interleaved pairs
 // (rotary_embedding_torch.py:146-157); rotating a key once at its own position when it enters the cache is the same
 // arithmetic.  Interleaved pairs (2i, 2i+1) become half-split pairs (i, i+32) by permuting the rows of to_q / to_k
@@ -424,7 +430,13 @@ struct AttnArgs {
 };
 
 // sc: T2S_MAX_KEYS floats, red: 4 floats, part: 16 x 64 floats (16-byte aligned) of LDS; all 256 threads of the block
-__device__ __forceinline__ void attn_body(const AttnArgs& a, int h, int b, int heads, float* sc, float* red, float (*part)[64])
+// IND (self-attention of the beam chain): key / value j come from the cache of slot own[j], own = the slot's row of the ancestry table
+// owner[2][batch][max_len] (row ((pos & 1) * batch + b)), staged in LDS (own: T2S_MAX_KEYS ints) with one load per thread and 256 keys - a
+// key is still ONE global round trip and four stay in flight; loop shape, arithmetic and accumulation order are those of the direct form:
+// an identity table gives the same bits.
+template <bool IND = false>
+__device__ __forceinline__ void attn_body(const AttnArgs& a, int h, int b, int heads, float* sc, float* red, float (*part)[64],
+                                          const int* owner = nullptr, int* own = nullptr)
 {
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int HD64 = heads * 64;
@@ -436,6 +448,12 @@ __device__ __forceinline__ void attn_body(const AttnArgs& a, int h, int b, int h
     const int64_t kvb = a.by_dialogue ? aloadi(a.state + SR * b + 4) : b;
     const float* const kb = a.k + kvb * a.batch_stride;
     const float* const vb = a.v + kvb * a.batch_stride;
+    if constexpr (IND) {
+        const int nbat = (int)gridDim.y;                   // (an entry outside [0, batch) is clamped: a stray table stays inside the caches)
+        const int* const orow = owner + ((int64_t)(aloadi(a.state + SR * b) & 1) * nbat + b) * a.max_len;
+        for (int j = tid; j < n; j += 256) own[j] = min(max(aloadi(orow + j), 0), nbat - 1);
+        __syncthreads();
+    }
     const int sub = tid & 15, grp = tid >> 4;              // 16 lanes per key, 16 keys per pass
     const f32x4 q4 = aload4(a.q + (int64_t)b * HD64 + h * 64 + 4 * sub);
     float mx = -3.0e38f;
@@ -446,7 +464,8 @@ __device__ __forceinline__ void attn_body(const AttnArgs& a, int h, int b, int h
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
             const int j = j0 + 16 * u + grp;
-            if (j < n) k4[u] = aload4(kb + (int64_t)j * a.stride + h * 64 + 4 * sub);
+            if constexpr (IND) { if (j < n) k4[u] = aload4(a.k + own[j] * a.batch_stride + (int64_t)j * a.stride + h * 64 + 4 * sub); }
+            else if (j < n) k4[u] = aload4(kb + (int64_t)j * a.stride + h * 64 + 4 * sub);
         }
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
@@ -478,7 +497,10 @@ __device__ __forceinline__ void attn_body(const AttnArgs& a, int h, int b, int h
     for (int j0 = grp; j0 < n; j0 += 64) {              // (value rows four at a time; accumulated in ascending key order as before)
         f32x4 v4[4];
 #pragma unroll
-        for (int u = 0; u < 4; ++u) if (j0 + 16 * u < n) v4[u] = aload4(vb + (int64_t)(j0 + 16 * u) * a.stride + h * 64 + 4 * sub);
+        for (int u = 0; u < 4; ++u) {
+            if constexpr (IND) { if (j0 + 16 * u < n) v4[u] = aload4(a.v + own[j0 + 16 * u] * a.batch_stride + (int64_t)(j0 + 16 * u) * a.stride + h * 64 + 4 * sub); }
+            else if (j0 + 16 * u < n) v4[u] = aload4(vb + (int64_t)(j0 + 16 * u) * a.stride + h * 64 + 4 * sub);
+        }
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
             if (j0 + 16 * u < n) {
@@ -504,6 +526,16 @@ __global__ __launch_bounds__(256) void attn_kernel(const AttnArgs a)
     __shared__ float red[4];
     __shared__ __attribute__((aligned(16))) float part[16][64];
     attn_body(a, blockIdx.x, blockIdx.y, gridDim.x, sc, red, part);
+}
+
+// self-attention of the beam chain: keys and values through the ancestry table
+__global__ __launch_bounds__(256) void attn_owner_kernel(const AttnArgs a, const int* owner)
+{
+    __shared__ float sc[T2S_MAX_KEYS];
+    __shared__ int own[T2S_MAX_KEYS];
+    __shared__ float red[4];
+    __shared__ __attribute__((aligned(16))) float part[16][64];
+    attn_body<true>(a, blockIdx.x, blockIdx.y, gridDim.x, sc, red, part, owner, own);
 }
 
 // ---------------------------------------------------------------- logit filter + Gumbel argmax, eos bookkeeping, next input
@@ -673,6 +705,33 @@ __device__ __forceinline__ float row_logprob(const float* lg, int V, int tok, fl
     return lp;
 }
 
+// row_logprob's m (every thread) and sum (the threads of the first wave) alone: the same operations in the same order, so the beam shortlist
+// takes every entry's log-prob from the same bits.  (A copy, not a call from row_logprob: splitting that function changes the schedule of the
+// scoring kernels, which stay as they were.)
+template <int NT>
+__device__ __forceinline__ float row_expsum(const float* lg, int V, float* ex, float* bv, float& m)
+{
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    m = -INFINITY;
+    for (int i = tid; i < V; i += NT) m = fmaxf(m, lg[i]);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+    if (lane == 0) bv[wid] = m;
+    __syncthreads();
+    m = bv[0];
+    for (int w = 1; w < NT / 64; ++w) m = fmaxf(m, bv[w]);
+    for (int i = tid; i < 1024; i += NT) ex[i] = i < V ? expf(lg[i] - m) : 0.f;
+    __syncthreads();
+    float sum = 0.f;
+    if (tid < 64) {
+#pragma unroll
+        for (int i = 0; i < 16; ++i) sum += ex[tid + 64 * i];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
+    }
+    return sum;
+}
+
 template <int NT, int FILT, bool LOGP>
 __device__ __forceinline__ void sample_body(const SampleArgs& a, int b, float* lg, float* ex, float* bv, int* bi, int* chosen)
 {
@@ -835,6 +894,276 @@ __global__ __launch_bounds__(1024) void sample_rows_kernel(const SampleRowsArgs 
     if (threadIdx.x == 0) a.tokens[r] = tok;
 }
 
+// ---------------------------------------------------------------- beam search: per-row shortlist, per-utterance selection, back-track
+// (the algorithm: include/covomix_hip.h, cvx_t2s_beam_steps)
+constexpr int BEAM_MAX = 16;
+
+// The K = min(B, V) entries of one row with the largest log-softmax, ordered by (value descending, index ascending): entry i has rank
+// #{j: lp[j] > lp[i] or (lp[j] == lp[i] and j < i)} - a total order, so exactly K entries have a rank below K whatever the ties.
+// lp[j] = (lg[j] - m) - logf(sum) with row_logprob's m and sum: the same function of the row.  lg: the staged row (stage_row), ex: 1024
+// floats, bv: 16 floats, ls: one float of LDS; out_lp / out_tok [K]: LDS or global.  The caller synchronises before lg / ex are written again.
+template <int NT>
+__device__ __forceinline__ void beam_shortlist(const float* lg, int V, int K, float* ex, float* bv, float* ls, float* out_lp, int* out_tok)
+{
+    const int tid = threadIdx.x;
+    float m;
+    const float sum = row_expsum<NT>(lg, V, ex, bv, m);
+    if (tid == 0) *ls = logf(sum);
+    __syncthreads();                                   // (the first wave has read ex)
+    const float l = *ls;
+    for (int i = tid; i < 1024; i += NT) ex[i] = i < V ? (lg[i] - m) - l : -INFINITY;
+    __syncthreads();
+    for (int i = tid; i < V; i += NT) {
+        const float me = ex[i];
+        int cnt = 0;
+        for (int j = 0; j < V; j += 4) {
+            const f32x4 l4 = *reinterpret_cast<const f32x4*>(ex + j);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) cnt += (l4[e] > me || (l4[e] == me && j + e < i)) ? 1 : 0;
+        }
+        if (cnt < K) { out_lp[cnt] = me; out_tok[cnt] = i; }
+    }
+}
+
+// The B best candidates of one utterance.  Candidate q = (p B + a) B + b: hypothesis p continued with entry a of its stream-0 shortlist and
+// entry b of its stream-1 shortlist (b = 0 for one stream), score sc[p] + lp0 or sc[p] + (lp0 + lp1) in fp32; a finished p has the single
+// candidate q = p B B with its score unchanged; a p with score -inf has none.  Order: score descending, q ascending.  sel[r] = the r-th best
+// q, or -1 when fewer than r + 1 candidates exist.  sc / fin [B], sl_lp [B][S][BEAM_MAX]: LDS or global; bv / bi: 16 entries of LDS.
+// NT = 1024 threads hold the B^3 <= 4096 candidates four each; B rounds of a block-wide argmax.
+template <int NT>
+__device__ __forceinline__ void beam_merge(const float* sc, const int* fin, const float* sl_lp, int B, int S, int K, float* bv, int* bi, int* sel)
+{
+    static_assert(BEAM_MAX * BEAM_MAX * BEAM_MAX <= 4 * NT, "four candidates per thread");
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    constexpr int NONE = 0x7fffffff;
+    f32x4 cs = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};       // the thread's candidates q = tid + NT k, and the mask of those still in play
+    unsigned ok = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int q = tid + NT * k;
+        const int p = q / (B * B), a = (q / B) % B, b = q % B;
+        if (p < B) {
+            const float c = sc[p];
+            if (c > -INFINITY) {
+                if (fin[p]) { if (a == 0 && b == 0) { ok |= 1u << k; cs[k] = c; } }
+                else if (a < K && (S == 2 ? b < K : b == 0)) {
+                    const float l0 = sl_lp[(p * S) * BEAM_MAX + a];
+                    ok |= 1u << k;
+                    cs[k] = S == 2 ? c + (l0 + sl_lp[(p * S + 1) * BEAM_MAX + b]) : c + l0;
+                }
+            }
+        }
+    }
+    for (int r = 0; r < B; ++r) {
+        float v = -INFINITY;
+        int q = NONE;
+#pragma unroll
+        for (int k = 0; k < 4; ++k)                    // (ascending q: the lowest wins ties)
+            if (((ok >> k) & 1u) && (q == NONE || cs[k] > v)) { v = cs[k]; q = tid + NT * k; }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const float ov = __shfl_xor(v, o, 64);
+            const int oq = __shfl_xor(q, o, 64);
+            if (oq != NONE && (q == NONE || ov > v || (ov == v && oq < q))) { v = ov; q = oq; }
+        }
+        if (lane == 0) { bv[wid] = v; bi[wid] = q; }
+        __syncthreads();
+        v = bv[0]; q = bi[0];
+        for (int w = 1; w < NT / 64; ++w) {
+            const float ov = bv[w];
+            const int oq = bi[w];
+            if (oq != NONE && (q == NONE || ov > v || (ov == v && oq < q))) { v = ov; q = oq; }
+        }
+        if (q != NONE && (q % NT) == tid) ok &= ~(1u << (q / NT));
+        if (tid == 0) sel[r] = q == NONE ? -1 : q;
+        __syncthreads();
+    }
+}
+
+// what new hypothesis i is, from its candidate q (thread-local; sl_*: the shortlists beam_merge saw)
+struct BeamPick { int parent, tok0, tok1; float lp0, lp1, score; int fin; };      // (scalars: an array indexed by the stream leaves the registers)
+__device__ __forceinline__ BeamPick beam_pick(int q, int i, const float* sc, const int* fin, const float* sl_lp, const int* sl_tok, int B, int S,
+                                              int eos_id)
+{
+    BeamPick r;
+    r.parent = i; r.tok0 = r.tok1 = -1; r.lp0 = r.lp1 = 0.f; r.score = -INFINITY; r.fin = 1;               // no candidate left: a dead slot
+    if (q < 0) return r;
+    const int p = q / (B * B), a = (q / B) % B, b = q % B;
+    r.parent = p;
+    r.score = sc[p];
+    if (fin[p]) return r;                                                                                  // carried: nothing new
+    r.tok0 = sl_tok[(p * S) * BEAM_MAX + a];
+    r.lp0 = sl_lp[(p * S) * BEAM_MAX + a];
+    if (S == 2) {
+        r.tok1 = sl_tok[(p * S + 1) * BEAM_MAX + b];
+        r.lp1 = sl_lp[(p * S + 1) * BEAM_MAX + b];
+        r.score = r.score + (r.lp0 + r.lp1);
+    } else r.score = r.score + r.lp0;
+    r.fin = (r.tok0 == eos_id || (S == 2 && r.tok1 == eos_id)) ? 1 : 0;
+    return r;
+}
+
+// the selection step alone (cvx_t2s_beam_select_f32): one block per group of B hypotheses, its B * S rows one after the other
+struct BeamSelectArgs {
+    const float* logits;     // [G * B, S, V]
+    const float* scores_in;  // [G * B]
+    const uint8_t* finished_in;
+    int B, S, V;
+    int32_t* parents;        // [G * B] (index inside the group)
+    int64_t* tokens;         // [G * B, S]
+    float* token_lp;         // [G * B, S]
+    float* scores_out;
+    uint8_t* finished_out;
+};
+
+__global__ __launch_bounds__(1024) void beam_select_kernel(const BeamSelectArgs a)
+{
+    __shared__ __attribute__((aligned(16))) float lg[1024];
+    __shared__ __attribute__((aligned(16))) float ex[1024];
+    __shared__ float bv[16];
+    __shared__ int bi[16];
+    __shared__ float ls;
+    __shared__ float sl_lp[BEAM_MAX * 2 * BEAM_MAX];
+    __shared__ int sl_tok[BEAM_MAX * 2 * BEAM_MAX];
+    __shared__ float sc[BEAM_MAX];
+    __shared__ int fin[BEAM_MAX];
+    __shared__ int sel[BEAM_MAX];
+    const int tid = threadIdx.x, B = a.B, S = a.S;
+    const int64_t base = (int64_t)blockIdx.x * B;
+    const int K = min(B, a.V);
+    if (tid < B) { sc[tid] = a.scores_in[base + tid]; fin[tid] = a.finished_in[base + tid] ? 1 : 0; }
+    __syncthreads();
+    for (int row = 0; row < B * S; ++row) {
+        const int p = row / S;
+        if (fin[p] || !(sc[p] > -INFINITY)) continue;                  // (block-uniform) no candidates from this row
+        stage_row<1024>(a.logits + (base * S + row) * a.V, nullptr, 1.f, a.V, lg);
+        beam_shortlist<1024>(lg, a.V, K, ex, bv, &ls, sl_lp + row * BEAM_MAX, sl_tok + row * BEAM_MAX);
+        __syncthreads();
+    }
+    beam_merge<1024>(sc, fin, sl_lp, B, S, K, bv, bi, sel);
+    if (tid < B) {
+        const BeamPick r = beam_pick(sel[tid], tid, sc, fin, sl_lp, sl_tok, B, S, a.V - 1);
+        a.parents[base + tid] = r.parent;
+        a.tokens[(base + tid) * S] = r.tok0; a.token_lp[(base + tid) * S] = r.lp0;
+        if (S == 2) { a.tokens[(base + tid) * S + 1] = r.tok1; a.token_lp[(base + tid) * S + 1] = r.lp1; }
+        a.scores_out[base + tid] = r.score;
+        a.finished_out[base + tid] = (uint8_t)r.fin;
+    }
+}
+
+// the beam chain's selection: beam_shortlist_kernel (one block per live row) then beam_merge_kernel (one block per utterance)
+struct BeamArgs {
+    const float* logits;     // [batch][streams, V]
+    const float* emb;
+    float* x;
+    int* state;              // slot records: [0] position (max_len: a finished hypothesis or an ended utterance), [1] finished, [2] its steps
+    float* scores;           // [batch]
+    uint8_t* finished;       // [batch]
+    int* owner;              // [2][batch][max_len]
+    int* groups;             // [batch / B][4]: [0] steps done [1] ended [2] step limit
+    int* parents;            // [max_len][batch] (index inside the group)
+    int* hist_tok;           // [max_len][batch][streams]
+    float* hist_lp;
+    float* short_lp;         // [batch][streams][BEAM_MAX]
+    int* short_tok;
+    int64_t* tokens;         // [batch][streams][max_len] (back-track)
+    float* logprobs;
+    int batch, B, V, dim_emb, streams, max_len;
+};
+
+__global__ __launch_bounds__(1024) void beam_shortlist_kernel(const BeamArgs a)
+{
+    __shared__ __attribute__((aligned(16))) float lg[1024];
+    __shared__ __attribute__((aligned(16))) float ex[1024];
+    __shared__ float bv[16];
+    __shared__ float ls;
+    const int row = blockIdx.x, slot = row / a.streams;
+    if (aloadi(a.state + SR * slot) >= a.max_len) return;             // (block-uniform) finished, ended or idle: no candidates from this row
+    stage_row<1024>(a.logits + (int64_t)row * a.V, nullptr, 1.f, a.V, lg);
+    beam_shortlist<1024>(lg, a.V, min(a.B, a.V), ex, bv, &ls, a.short_lp + row * BEAM_MAX, a.short_tok + row * BEAM_MAX);
+}
+
+__global__ __launch_bounds__(1024) void beam_merge_kernel(const BeamArgs a)
+{
+    __shared__ float bv[16];
+    __shared__ int bi[16];
+    __shared__ float sc[BEAM_MAX];
+    __shared__ int fin[BEAM_MAX], len[BEAM_MAX], sel[BEAM_MAX];
+    __shared__ int n_par[BEAM_MAX], n_fin[BEAM_MAX], n_tok[BEAM_MAX][2];
+    const int tid = threadIdx.x, B = a.B, S = a.streams;
+    const int u = blockIdx.x, base = u * B;
+    int* const gs = a.groups + 4 * u;
+    const int t = aloadi(gs);
+    if (aloadi(gs + 1) != 0 || t < 0 || t >= min(aloadi(gs + 2), a.max_len)) return;       // (block-uniform) ended, or nothing to decode
+    if (tid < B) {
+        sc[tid] = a.scores[base + tid];
+        fin[tid] = a.finished[base + tid] ? 1 : 0;
+        len[tid] = aloadi(a.state + SR * (base + tid) + 2);
+    }
+    __syncthreads();
+    const float* const sl_lp = a.short_lp + (int64_t)base * S * BEAM_MAX;
+    const int* const sl_tok = a.short_tok + (int64_t)base * S * BEAM_MAX;
+    beam_merge<1024>(sc, fin, sl_lp, B, S, min(B, a.V), bv, bi, sel);
+    BeamPick r;
+    if (tid < B) {
+        r = beam_pick(sel[tid], tid, sc, fin, sl_lp, sl_tok, B, S, a.V - 1);
+        const int64_t h = (int64_t)t * a.batch + base + tid;
+        a.parents[h] = r.parent;
+        a.hist_tok[h * S] = r.tok0; a.hist_lp[h * S] = r.lp0;
+        if (S == 2) { a.hist_tok[h * S + 1] = r.tok1; a.hist_lp[h * S + 1] = r.lp1; }
+        n_par[tid] = r.parent; n_fin[tid] = r.fin; n_tok[tid][0] = r.tok0; n_tok[tid][1] = r.tok1;
+    }
+    __syncthreads();                                    // (every old score / flag / length has been read)
+    bool all_fin = true;
+    for (int i = 0; i < B; ++i) all_fin = all_fin && n_fin[i] != 0;
+    const bool ends = all_fin || t + 1 >= min(aloadi(gs + 2), a.max_len);
+    if (tid < B) {
+        const int slot = base + tid;
+        int* const st = a.state + SR * slot;
+        a.scores[slot] = r.score;
+        a.finished[slot] = (uint8_t)r.fin;
+        // a finished hypothesis keeps the steps it took; the slots of an ended utterance idle at max_len (the attention kernel's idle exit)
+        const int steps = r.fin ? (sel[tid] >= 0 && fin[r.parent] ? len[r.parent] : (sel[tid] >= 0 ? t + 1 : 0)) : (ends ? t + 1 : 0);
+        st[0] = (r.fin || ends) ? a.max_len : t + 1;
+        st[1] = (r.fin || ends) ? 1 : 0;
+        st[2] = steps;
+    }
+    if (tid == 0) { gs[0] = t + 1; if (ends) gs[1] = 1; }
+    if (ends) return;
+    // the next input of every live hypothesis, and its row of the ancestry table: the parent's row for positions 0..t, then itself
+    for (int idx = tid; idx < B * S * a.dim_emb; idx += 1024) {
+        const int i = idx / (S * a.dim_emb), rem = idx - i * (S * a.dim_emb), s = rem / a.dim_emb, d = rem - s * a.dim_emb;
+        if (!n_fin[i]) a.x[((int64_t)(base + i) * S + s) * a.dim_emb + d] = a.emb[(int64_t)n_tok[i][s] * a.dim_emb + d];
+    }
+    const int* const src = a.owner + (int64_t)(t & 1) * a.batch * a.max_len;
+    int* const dst = a.owner + (int64_t)((t + 1) & 1) * a.batch * a.max_len;
+    for (int i = 0; i < B; ++i) {
+        if (n_fin[i]) continue;
+        const int* const sr = src + (int64_t)(base + n_par[i]) * a.max_len;
+        int* const dr = dst + (int64_t)(base + i) * a.max_len;
+        for (int j = tid; j <= t; j += 1024) dr[j] = aloadi(sr + j);
+        if (tid == 0) dr[t + 1] = base + i;             // (t + 1 < max_len: the utterance has not ended)
+    }
+}
+
+// tokens / logprobs [slot][streams][max_len] of every hypothesis from the back-pointers: one thread per slot walks its ancestry
+__global__ __launch_bounds__(64) void beam_backtrack_kernel(const BeamArgs a)
+{
+    const int slot = blockIdx.x * 64 + threadIdx.x;
+    if (slot >= a.batch) return;
+    const int base = slot / a.B * a.B, S = a.streams;
+    const int T = min(max(aloadi(a.groups + 4 * (slot / a.B)), 0), a.max_len);
+    int cur = slot - base;
+    for (int t = T - 1; t >= 0; --t) {
+        const int64_t h = (int64_t)t * a.batch + base + cur;
+        for (int s = 0; s < S; ++s) {
+            a.tokens[((int64_t)slot * S + s) * a.max_len + t] = a.hist_tok[h * S + s];
+            a.logprobs[((int64_t)slot * S + s) * a.max_len + t] = a.hist_lp[h * S + s];
+        }
+        cur = min(max(aloadi(a.parents + h), 0), a.B - 1);
+    }
+}
+
 __global__ __launch_bounds__(256) void geglu_kernel(const float* __restrict__ h, float* __restrict__ out, int64_t rows,
                                                    int F, int64_t ld_out)
 {
@@ -955,8 +1284,17 @@ extern "C" int cvx_t2s_logprob_f32(const float* logits, const int64_t* tokens, i
     return CVX_OK;
 }
 
-// the step chain of cvx_t2s_decode_steps (logprobs == NULL) and cvx_t2s_decode_steps_scored: they differ in the sampling kernel only
-static int t2s_decode_run(const cvx_t2s_decoder* d, int32_t n_steps, float* logprobs, cvx_stream_t s)
+static BeamArgs beam_args(const cvx_t2s_decoder* d, const cvx_t2s_beam* bm)
+{
+    return BeamArgs{d->logits, d->emb, d->x, d->state, bm->scores, bm->finished, bm->owner, bm->groups, bm->parents, bm->hist_tokens,
+                    bm->hist_logprobs, bm->short_lp, bm->short_tokens, d->tokens, bm->logprobs, d->batch, bm->beam_size, d->vocab, d->dim_emb,
+                    d->streams, d->max_len};
+}
+
+// the step chain of cvx_t2s_decode_steps (logprobs == NULL) and cvx_t2s_decode_steps_scored: they differ in the sampling kernel only.
+// bm (cvx_t2s_beam_steps): the self-attention reads through the ancestry table, and the shortlist + merge kernels stand in for the sampling
+// kernel - one launch more per step; every other launch is the same.
+static int t2s_decode_run(const cvx_t2s_decoder* d, int32_t n_steps, float* logprobs, cvx_stream_t s, const cvx_t2s_beam* bm = nullptr)
 {
     hipStream_t st = cvx_hip_stream(s);
     const float scale = 0.125f;        // dim_head ** -0.5
@@ -976,7 +1314,8 @@ static int t2s_decode_run(const cvx_t2s_decoder* d, int32_t n_steps, float* logp
             g.cache_stride = cache_stride; g.state = d->state; g.max_len = d->max_len;
             launch_gemv<MODE_QKV>(g, 3 * d->inner / 2, nb, st);
             AttnArgs at{d->q, L.k_cache, L.v_cache, d->inner, cache_stride, d->att, d->state, -1, 0, scale, d->max_len};
-            hipLaunchKernelGGL(attn_kernel, dim3((unsigned)d->heads, (unsigned)nb), dim3(256), 0, st, at);
+            if (bm) hipLaunchKernelGGL(attn_owner_kernel, dim3((unsigned)d->heads, (unsigned)nb), dim3(256), 0, st, at, (const int*)bm->owner);
+            else hipLaunchKernelGGL(attn_kernel, dim3((unsigned)d->heads, (unsigned)nb), dim3(256), 0, st, at);
             g = GemvArgs{};
             g.W = L.wo_s; g.ldw = d->inner; g.x = d->att; g.x_stride = d->inner; g.y = d->x; g.y_stride = d->dim; g.N = d->dim; g.K = d->inner;
             launch_gemv<MODE_RES>(g, (d->dim + 1) / 2, nb, st);
@@ -1005,6 +1344,12 @@ static int t2s_decode_run(const cvx_t2s_decoder* d, int32_t n_steps, float* logp
         g.W = d->emb; g.ldw = d->dim_emb; g.x = d->x; g.x_stride = d->dim; g.gamma = d->final_gamma; g.y = d->logits;
         g.y_stride = d->streams * d->vocab; g.N = d->vocab; g.K = d->dim_emb; g.streams = d->streams;
         launch_gemv<MODE_LOGITS>(g, d->streams * ((d->vocab + 1) / 2), nb, st);
+        if (bm) {
+            const BeamArgs ba = beam_args(d, bm);
+            hipLaunchKernelGGL(beam_shortlist_kernel, dim3((unsigned)(nb * d->streams)), dim3(1024), 0, st, ba);
+            hipLaunchKernelGGL(beam_merge_kernel, dim3((unsigned)(nb / bm->beam_size)), dim3(1024), 0, st, ba);
+            continue;
+        }
         SampleArgs sa{d->logits, d->uniforms, d->emb, d->x, d->tokens, d->state, d->queue, d->dialogues, d->start, nb, d->uniform_steps,
                       d->vocab, d->dim_emb, d->streams, d->max_len, d->top_k, d->vocab - 1, 1.0f / fmaxf(d->temperature, 1e-10f),
                       d->cfg_scale, d->top_p, logprobs};
@@ -1035,4 +1380,44 @@ extern "C" int cvx_t2s_decode_steps_scored(const cvx_t2s_decoder* d, const cvx_t
     CVX_REQUIRE(sc->logprob_len == d->max_len, "t2s_decode_scored: logprob_len = %d, the rows of logprobs are laid out like those of tokens "
                 "(max_len = %d floats)", sc->logprob_len, d->max_len);
     return t2s_decode_run(d, n_steps, sc->logprobs, s);
+}
+
+extern "C" int cvx_t2s_beam_steps(const cvx_t2s_decoder* d, const cvx_t2s_beam* bm, int32_t n_steps, cvx_stream_t s)
+{
+    CVX_REQUIRE(bm && bm->struct_size == sizeof(cvx_t2s_beam), "t2s_beam_steps: cvx_t2s_beam.struct_size = %u, this library knows %u",
+                bm ? bm->struct_size : 0u, (unsigned)sizeof(cvx_t2s_beam));
+    const int rc = t2s_validate(d, n_steps);
+    if (rc != CVX_OK) return rc;
+    CVX_REQUIRE(!d->queue, "t2s_beam_steps: a dialogue queue cannot feed beam groups (queue must be NULL)");
+    CVX_REQUIRE(!(d->cfg_scale > 1.f), "t2s_beam_steps: guidance (cfg_scale > 1) is not built for beam search");
+    CVX_REQUIRE(bm->beam_size >= 1 && bm->beam_size <= BEAM_MAX && d->batch % bm->beam_size == 0,
+                "t2s_beam_steps: beam_size = %d outside [1, %d] or no divisor of batch = %d", bm->beam_size, BEAM_MAX, d->batch);
+    CVX_REQUIRE(bm->hist_len == d->max_len, "t2s_beam_steps: hist_len = %d, the back-pointer arrays and logprobs hold max_len = %d steps",
+                bm->hist_len, d->max_len);
+    CVX_REQUIRE(bm->scores && bm->finished && bm->owner && bm->groups && bm->parents && bm->hist_tokens && bm->hist_logprobs && bm->short_lp &&
+                bm->short_tokens && bm->logprobs, "t2s_beam_steps: null pointer in cvx_t2s_beam");
+    if (n_steps > 0) {
+        const int rr = t2s_decode_run(d, n_steps, nullptr, s, bm);
+        if (rr != CVX_OK) return rr;
+    }
+    if (bm->backtrack) {
+        hipLaunchKernelGGL(beam_backtrack_kernel, dim3((unsigned)((d->batch + 63) / 64)), dim3(64), 0, cvx_hip_stream(s), beam_args(d, bm));
+        CVX_CHECK_LAUNCH("cvx_t2s_beam_steps");
+    }
+    return CVX_OK;
+}
+
+extern "C" int cvx_t2s_beam_select_f32(const float* logits, const float* scores_in, const uint8_t* finished_in, int32_t groups,
+                                       int32_t beam_size, int32_t streams, int32_t V, int32_t* parents, int64_t* tokens, float* token_lp,
+                                       float* scores_out, uint8_t* finished_out, cvx_stream_t s)
+{
+    CVX_REQUIRE(logits && scores_in && finished_in && parents && tokens && token_lp && scores_out && finished_out,
+                "t2s_beam_select: null pointer");
+    CVX_REQUIRE(groups >= 0 && beam_size >= 1 && beam_size <= BEAM_MAX && (streams == 1 || streams == 2) && V >= 1 && V <= 1024,
+                "t2s_beam_select: bad arguments (groups=%d beam_size=%d streams=%d V=%d)", groups, beam_size, streams, V);
+    if (groups == 0) return CVX_OK;
+    const BeamSelectArgs a{logits, scores_in, finished_in, beam_size, streams, V, parents, tokens, token_lp, scores_out, finished_out};
+    hipLaunchKernelGGL(beam_select_kernel, dim3((unsigned)groups), dim3(1024), 0, cvx_hip_stream(s), a);
+    CVX_CHECK_LAUNCH("cvx_t2s_beam_select_f32");
+    return CVX_OK;
 }

@@ -82,6 +82,9 @@ def build_parser() -> ArgumentParser:
     p.add_argument("--t2s_top_k", type=int, default=None, help="extension: an explicit k for --t2s_filter top_k (overrides the thres)")
     p.add_argument("--t2s_best_of", type=int, default=1, help="extension: decode this many candidates per turn through the continuously "
                    "refilled slots and keep the one the model finds most likely (largest mean token log-probability; 1 = off: today's files)")
+    p.add_argument("--t2s_beam_size", type=int, default=0, help="extension: beam search with this many hypotheses per turn (1..16) instead of "
+                   "sampling - deterministic: no draws, temperature and filter unused; not together with --t2s_best_of > 1 or guidance "
+                   "(0 = off: sampling, today's files)")
     p.add_argument("--gpus", type=int, default=1, help="extension: from a plain shell, start this many ranks (one per GPU, "
                    "utterances sharded; under torch.distributed.run the launcher's WORLD_SIZE is used instead)")
     return p
@@ -199,6 +202,13 @@ def t2s_sampling_kwargs(args) -> dict:
         raise ValueError(f"--t2s_best_of {best_of}: at least 1")
     if best_of > 1:
         kw["best_of"] = best_of
+    beam = int(getattr(args, "t2s_beam_size", 0))
+    if beam:
+        if not 1 <= beam <= 16:
+            raise ValueError(f"--t2s_beam_size {beam}: 0 (sampling) or 1..16")
+        if best_of > 1 or kw.get("cond_scale", 1.0) > 1.0:
+            raise ValueError("--t2s_beam_size does not combine with --t2s_best_of > 1 or guidance (--t2s_cond_scale > 1)")
+        kw["beam_search_decode"], kw["beam_size"] = True, beam
     return kw
 
 
@@ -235,6 +245,11 @@ def _predict_turns(work, t2s, device, seed: int, slots: int = 64, sampling=None)
         win = max(1, WINDOW // best_of)
         for w in range(0, len(todo), win):
             part = todo[w:w + win]
+            if (sampling or {}).get("beam_search_decode"):          # --t2s_beam_size: no draws, lock-step waves of 64 // beam_size turns
+                toks = t2s.synthesis_sample_text2semantic([ids.to(device) for _, _, ids in part], **sampling)
+                for (name, k, _), t in zip(part, toks):
+                    out[(name, k)] = t.cpu().numpy().astype(np.int64)
+                continue
             uniforms = []
             for name, k, _ in part:
                 draws = []

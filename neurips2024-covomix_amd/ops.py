@@ -827,6 +827,28 @@ def t2s_logprob(logits: torch.Tensor, tokens: torch.Tensor) -> torch.Tensor:
     return out
 
 
+def t2s_beam_select(logits: torch.Tensor, scores: torch.Tensor, finished: torch.Tensor, beam_size: int):
+    """One selection step of the beam search (cvx_t2s_beam_select_f32; the algorithm: include/covomix_hip.h): logits [G * B, S, V] fp32, scores
+    fp32 [G * B], finished uint8 / bool [G * B] -> (parents int32 [G * B] - the index inside the group -, tokens int64 [G * B, S], token
+    log-probs fp32 [G * B, S], scores fp32 [G * B], finished uint8 [G * B]) of the new hypotheses."""
+    _chk_f32(logits, scores)
+    assert logits.ndim == 3 and logits.is_contiguous() and scores.is_contiguous()
+    rows, S, V = logits.shape
+    B = int(beam_size)
+    assert B >= 1 and rows % B == 0 and scores.shape == (rows,) and finished.shape == (rows,) and finished.is_cuda
+    fin = finished.to(torch.uint8).contiguous()
+    dev = logits.device
+    parents = torch.empty(rows, dtype=torch.int32, device=dev)
+    tokens = torch.empty(rows, S, dtype=torch.int64, device=dev)
+    lp = torch.empty(rows, S, dtype=torch.float32, device=dev)
+    out_sc = torch.empty(rows, dtype=torch.float32, device=dev)
+    out_fin = torch.empty(rows, dtype=torch.uint8, device=dev)
+    _lib.check(_lib.load().cvx_t2s_beam_select_f32(logits.data_ptr(), scores.data_ptr(), fin.data_ptr(), rows // B, B, S, V, parents.data_ptr(),
+                                                   tokens.data_ptr(), lp.data_ptr(), out_sc.data_ptr(), out_fin.data_ptr(), _stream()),
+               "cvx_t2s_beam_select_f32")
+    return parents, tokens, lp, out_sc, out_fin
+
+
 def dwconv31_gelu_res(x: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, out: torch.Tensor,
                       Bt: int, T: int, ragged: Optional[Ragged] = None) -> torch.Tensor:
     _chk_f32(x, w, bias, out)

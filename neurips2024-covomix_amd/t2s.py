@@ -4,8 +4,9 @@ Host mirror of the reference's `TextToSemantic.generate` sampling branch + `Text
 (covomix/covomix_model/text2semantic.py:662-848, :1237-1251), the call `CoVoMixModel.synthesis_sample_text2semantic`
 forwards to (covomix/conditional_model.py:313-321).  Built: the sampling branch with its three controls - temperature,
 classifier-free guidance (cond_scale > 1, one-output models) and the logit filter (filter_logits_fn = top_k / top_p with
-filter_fn_kwargs, text2semantic.py:118-132, :796) - in every decode schedule below; no beam / speculative decoding, no padded
-text batches.  Beside the tokens: the log-probability of every sampled token (return_logprobs), teacher-forced scoring of given tokens
+filter_fn_kwargs, text2semantic.py:118-132, :796) - in every decode schedule below; beam search (`generate_beam`: the flag the
+reference's generate accepts without a body, text2semantic.py:673-677 - the algorithm is defined in include/covomix_hip.h); no speculative
+decoding, no padded text batches.  Beside the tokens: the log-probability of every sampled token (return_logprobs), teacher-forced scoring of given tokens
 through the same decode slots (score_many) and the mean token log-probability best-of-N selects by (sequence_logprob).
 
   encoder  (source transformer, once per utterance): the full-sequence kernels of the acoustic path - fp32 GEMM with
@@ -41,6 +42,7 @@ CHUNK = 16                     # token steps per graph replay / host check
 MAX_BATCH = 64                 # decode slots per step (kernel limit)
 WINDOW = 256                   # utterances queued on the device at a time (generate_many)
 SR = 8                         # int32 per slot / dialogue record (include/covomix_hip.h, cvx_t2s_decoder)
+BEAM_MAX = 16                  # hypotheses per utterance (kernel limit)
 
 
 def filter_setting(filter_logits_fn="top_k", filter_fn_kwargs=None, vocab: int = 0) -> tuple:
@@ -109,6 +111,40 @@ def check_best_of(best_of, n_utterances: Optional[int] = None, uniforms=None) ->
             if u.ndim < 4 or u.shape[0] != best_of:
                 raise ValueError(f"best_of = {best_of}: the uniforms of an utterance are [best_of, steps, S, V], got {tuple(u.shape)}")
     return best_of
+
+
+def check_beam_size(beam_size) -> int:
+    """beam_size of generate_beam: an integer in [1, BEAM_MAX].  ValueError otherwise."""
+    if isinstance(beam_size, bool) or not isinstance(beam_size, int) or not 1 <= beam_size <= BEAM_MAX:
+        raise ValueError(f"beam_size must be an integer in [1, {BEAM_MAX}], got {beam_size!r}")
+    return beam_size
+
+
+def beam_backtrack(parents, tokens, logprobs, slot: int, steps: int):
+    """The sequence of the hypothesis that sits in `slot` after `steps` steps, from the back-pointer records of the selection step:
+    parents [T, B] (the slot the hypothesis came from), tokens [T, B, S], logprobs [T, B, S] -> (tokens [S, steps], logprobs [S, steps],
+    path [steps]: the slot at every step).  What the device's back-track kernel computes."""
+    S = tokens.shape[2]
+    tk = torch.zeros(S, steps, dtype=tokens.dtype)
+    lp = torch.zeros(S, steps, dtype=logprobs.dtype)
+    path = [0] * steps
+    cur = int(slot)
+    for t in range(steps - 1, -1, -1):
+        path[t] = cur
+        tk[:, t], lp[:, t] = tokens[t, cur], logprobs[t, cur]
+        cur = int(parents[t, cur])
+    return tk, lp, path
+
+
+def beam_rank(scores, lengths, streams: int, length_penalty: float = 1.0) -> list:
+    """Slots of one utterance, best first: by c / n ** length_penalty with c the cumulative log-probability and n = steps * streams the
+    tokens scored (up to and including the eos step); ties - and dead hypotheses, c = -inf, last - go to the lowest slot."""
+    def value(i):
+        n = int(lengths[i]) * streams
+        c = float(scores[i])
+        return c / float(n) ** float(length_penalty) if n > 0 and c > -math.inf else -math.inf
+    vals = [value(i) for i in range(len(scores))]
+    return sorted(range(len(vals)), key=lambda i: (-vals[i], i))
 
 
 def check_targets(targets, streams: int, vocab: int, max_length: int) -> list:
@@ -788,6 +824,153 @@ class TextToSemanticDecoder:
         if not all(seen):
             raise RuntimeError(f"text2semantic continuous decode: {seen.count(False)} of {n} utterances did not finish in {i} chunks")
         return out
+
+    # ------------------------------------------------------------------ beam search
+    def _ensure_beam(self) -> dict:
+        """Device state of the beam chain (cvx_t2s_beam), for the decode buffers' current slot capacity: allocated on first use, and again
+        when those buffers were re-allocated.  Nothing else holds its addresses but the beam graphs."""
+        if getattr(self, "_beam", None) is not None and self._beam["gen"] == self._gen:
+            return self._beam
+        n, L, S, dev = self._slots, self.max_length, self.d["streams"], self.device
+        i32 = lambda *s: torch.zeros(*s, dtype=torch.int32, device=dev)
+        f32 = lambda *s: torch.zeros(*s, dtype=torch.float32, device=dev)
+        self._beam = dict(gen=self._gen, scores=f32(n), finished=torch.zeros(n, dtype=torch.uint8, device=dev), owner=i32(2 * n * L),
+                          groups=i32(n, 4), parents=i32(L * n), hist_tokens=i32(L * n * S), hist_logprobs=f32(L * n * S),
+                          short_lp=f32(n * S * BEAM_MAX), short_tokens=i32(n * S * BEAM_MAX), logprobs=f32(n, S, L))
+        return self._beam
+
+    def _launch_beam(self, batch: int, beam_size: int, n: int, backtrack: bool = False) -> None:
+        """n steps of the beam chain (cvx_t2s_beam_steps) on the current stream; backtrack: then tokens / log-probs from the back-pointers"""
+        bm = self._ensure_beam()
+        dec = self._descriptor(1.0, batch)
+        bs = _lib.T2SBeam(C.sizeof(_lib.T2SBeam), beam_size, self.max_length, 1 if backtrack else 0,
+                          *[bm[k].data_ptr() for k in ("scores", "finished", "owner", "groups", "parents", "hist_tokens", "hist_logprobs",
+                                                      "short_lp", "short_tokens", "logprobs")])
+        _lib.check(_lib.load().cvx_t2s_beam_steps(C.byref(dec), C.byref(bs), n, ops._stream()), "cvx_t2s_beam_steps")
+
+    def _beam_idle(self) -> None:
+        """every slot idle, every group ended: the state a warm-up or a capture may run on"""
+        self.buf["state"].copy_(self._slot_records([]))
+        g = torch.zeros(self._slots, 4, dtype=torch.int32)
+        g[:, 1] = 1
+        self._ensure_beam()["groups"].copy_(g)
+
+    def _beam_graph(self, batch: int, beam_size: int):
+        """The captured graph of CHUNK beam steps for this (batch, beam size, stream CU count); `_graph`'s procedure, a key of its own shape."""
+        self._ensure_beam()
+        key = ("beam", beam_size, batch, ops.stream_cus(), self._gen)
+        g = self._graphs.get(key)
+        if g is not None:
+            return g
+        self._beam_idle()
+        self._launch_beam(batch, beam_size, CHUNK)       # warm-up outside capture
+        cur = torch.cuda.current_stream()
+        if self._cap is None:
+            self._cap = torch.cuda.Stream(device=self.device)
+        ops.saturation_share(cur, self._cap)
+        with ops.CAPTURE_GATE.exclusive():
+            cur.synchronize()
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g, stream=self._cap, capture_error_mode="thread_local"):
+                self._launch_beam(batch, beam_size, CHUNK)
+        if len(self._graphs) >= 8:
+            self._graphs.clear()
+        self._graphs[key] = g
+        return g
+
+    def _beam_wave(self, sources, B: int, max_len: int, length_penalty: float) -> list:
+        """One lock-step wave: utterance u in slots [u B, (u + 1) B).  -> per utterance the list of its B hypotheses, best first."""
+        d = self.d
+        S, n = d["streams"], len(sources)
+        nb = n * B
+        self._ensure(nb, nb, 0)
+        bm = self._ensure_beam()
+        use_graph = os.environ.get("CVX_GRAPH", "1") == "1"
+        if use_graph:
+            self._beam_graph(nb, B)
+        ctx = self._contexts(sources)
+        rows = [[0, 0, 0, ctx[i // B], i // B, 0, 0, 0] if i < nb else [self.max_length, 1, 0, 1, 0, 0, 0, 0] for i in range(self._slots)]
+        self.buf["state"].copy_(torch.tensor(rows, dtype=torch.int32))
+        self.buf["x"][:nb].copy_(self.start[None, :].expand(nb, -1))
+        sc = torch.full((self._slots,), -math.inf)
+        sc[0:nb:B] = 0.0                                   # before step 0 only hypothesis 0 of an utterance is live
+        bm["scores"].copy_(sc)
+        bm["finished"].zero_()
+        bm["owner"].copy_(torch.arange(self._slots, dtype=torch.int32)[None, :, None].expand(2, -1, self.max_length).reshape(-1))
+        g = torch.zeros(self._slots, 4, dtype=torch.int32)
+        g[:, 1] = 1
+        g[:n, 1], g[:n, 2] = 0, max_len
+        bm["groups"].copy_(g)
+        # chunks of CHUNK steps; the host reads the slot records one chunk behind the device (_decode_chunks)
+        self._mirror_setup()
+        via_helper = ops.is_partition_stream()
+        steps, i, pending = 0, 0, None
+        while steps < max_len:
+            if use_graph:
+                self._beam_graph(nb, B).replay()
+            else:
+                self._launch_beam(nb, B, CHUNK)
+            steps += CHUNK
+            k = i & 1
+            self._mirror_push(k, self.buf["state"][:nb], via_helper)
+            if pending is not None and all(r[1] for r in self._mirror_pull(pending, nb)):
+                break
+            pending = k
+            i += 1
+        if pending is not None:
+            self._pin_ev[pending].synchronize()
+        self._launch_beam(nb, B, 0, backtrack=True)
+        st = self._read_state(nb)
+        scores, groups = bm["scores"][:nb].cpu(), bm["groups"][:n].tolist()
+        tokens, logprobs = self.buf["tokens"][:nb].cpu(), bm["logprobs"][:nb].cpu()
+        eos = d["vocab"] - 1
+        out = []
+        for u in range(n):
+            T = groups[u][0]
+            lengths = [st[u * B + i][2] for i in range(B)]
+            order = beam_rank(scores[u * B:(u + 1) * B], lengths, S, length_penalty)
+            hyps = []
+            for i in order:
+                streams = tokens[u * B + i, :, :lengths[i]].clone()
+                after = (streams == eos).cumsum(dim=-1) > 0          # mask_after_eos (text2semantic.py:73-76)
+                after = torch.nn.functional.pad(after, (1, -1), value=False)
+                flat = streams.masked_fill(after, PAD_ID).reshape(-1)
+                hyps.append((flat[flat != PAD_ID], streams, logprobs[u * B + i, :, :lengths[i]].clone(), float(scores[u * B + i])))
+            out.append(hyps)
+            rec = lambda name, *tail: bm[name][:T * nb * math.prod(tail)].view(T, nb, *tail)[:, u * B:(u + 1) * B].cpu()
+            self.last_beam.append(dict(steps=T, order=order, lengths=lengths, scores=scores[u * B:(u + 1) * B].clone(),
+                                       parents=rec("parents"), tokens=rec("hist_tokens", S), logprobs=rec("hist_logprobs", S)))
+        return out
+
+    @ops.gated
+    @torch.no_grad()
+    def generate_beam(self, sources, beam_size: int = 10, max_length: Optional[int] = None, length_penalty: float = 1.0,
+                      return_beams: bool = False):
+        """Beam search (the algorithm: include/covomix_hip.h, cvx_t2s_beam_steps): deterministic, no draws - temperature, logit filter and
+        uniforms play no part.  Every step keeps the beam_size hypotheses with the largest cumulative log-probability (fp32); a hypothesis
+        that takes an eos in any stream is finished and competes with its score unchanged; the utterance ends when all are finished or after
+        max_length steps.  The hypotheses of an utterance sit in beam_size neighbouring decode slots and continue from each other's KV
+        caches through a device-side ancestry table - no cache row is copied.
+        sources: one text ([n] / [1, n] ids) or a list; a list runs in lock-step waves of MAX_BATCH // beam_size utterances (each ends on
+        its own, its slots then idle).  beam_size: 1..16 (the reference's default is 10).
+        Returns, per utterance, (flat tokens, streams int64 [S, L], logprobs float32 [S, L], score) of the hypothesis with the largest
+        score / (L * S) ** length_penalty (ties: the lowest slot) - host tensors; score is the cumulative log-probability, the fp32 sum
+        the selection kept, and logprobs equal, bit for bit, what score_many gives for `streams`.  return_beams: the list of all beam_size
+        hypotheses instead, best first (dead ones, score -inf, last).  `last_beam` keeps, per utterance of the call, the records of the search
+        (tests, tools): steps, the slots best first (`order`), their lengths and scores, and the back-pointers parents [steps, B], tokens /
+        logprobs [steps, B, S] (beam_backtrack turns them into sequences)."""
+        B = check_beam_size(beam_size)
+        one = torch.is_tensor(sources)
+        srcs = [sources] if one else list(sources)
+        max_len = min(int(max_length or self.max_length), self.max_length)
+        if max_len < 1:
+            raise ValueError("generate_beam needs at least one step")
+        self.last_beam = []
+        per, out = MAX_BATCH // B, []
+        for w in range(0, len(srcs), per):
+            out += self._beam_wave(srcs[w:w + per], B, max_len, float(length_penalty))
+        res = out if return_beams else [h[0] for h in out]
+        return res[0] if one else res
 
     def score_many(self, sources, targets, cond_scale: float = 1.0, slots: int = 64):
         """Teacher-forced scoring: the log-probability the model gives every token of targets[j] under the text sources[j] - what the

@@ -15,6 +15,9 @@
   python tools/t2s_sampling_bench.py bestof
       dialogues per second of best-of 1 / 2 / 4 on 56 CoMix dialogues (608 steps each, the eos ignored: N * 56 decodes through 64 slots,
       log-probs on for N > 1, selection included).
+  python tools/t2s_sampling_bench.py beam [--beam-size 10]
+      us per beam step (generate_beam, graph replay) for CoMix and CoSingle with 1 and 6 utterances (10 and 60 slots at beam size 10).
+      The sampled step at the same slot counts: `steps --slots 10,60` (with --root for the parent commit), in turns, five rounds.
 """
 import argparse
 import json
@@ -25,12 +28,14 @@ import time
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("what", choices=["steps", "guided", "score", "bestof"])
+    ap.add_argument("what", choices=["steps", "guided", "score", "bestof", "beam"])
     ap.add_argument("--logprobs", action="store_true")
     ap.add_argument("--root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     ap.add_argument("--top-p", type=float, default=None)
     ap.add_argument("--steps", type=int, default=256)
     ap.add_argument("--tag", default="")
+    ap.add_argument("--slots", default="1,8,64", help="steps: the slot counts")
+    ap.add_argument("--beam-size", type=int, default=10)
     args = ap.parse_args()
     sys.path.insert(0, os.path.abspath(args.root))
     import torch
@@ -51,7 +56,7 @@ def main():
     if args.what == "steps":
         for name in ("comix", "cosingle"):
             m = model(name)
-            for slots in (1, 8, 64):
+            for slots in [int(x) for x in args.slots.split(",")]:
                 srcs = [torch.randint(1, 30000, (1, 64), generator=g) for _ in range(slots)]
                 forms = (("default", {}),) + ((("top_p", dict(filter_logits_fn="top_p", filter_fn_kwargs={"thres": args.top_p})),) if args.top_p else ())
                 forms += ((("logprobs", dict(return_logprobs=True)),) if args.logprobs else ())
@@ -61,6 +66,18 @@ def main():
                     t = min(timed(run) for _ in range(3))
                     print(json.dumps({"tag": args.tag, "model": name, "slots": slots, "filter": label, "steps": args.steps,
                                       "us_per_step": round(t / args.steps * 1e6, 1)}), flush=True)
+    elif args.what == "beam":
+        B = args.beam_size
+        for name in ("comix", "cosingle"):
+            m = model(name)
+            for n in (1, 6):
+                srcs = [torch.randint(1, 30000, (1, 64), generator=g) for _ in range(n)]
+                run = lambda: m.generate_beam(srcs, beam_size=B, max_length=args.steps)
+                run()                                                     # graph + buffers of the timed shape
+                t = min(timed(run) for _ in range(3))
+                done = min(r["steps"] for r in m.last_beam)               # (an utterance whose hypotheses all finish ends early)
+                print(json.dumps({"tag": args.tag, "model": name, "beam_size": B, "utterances": n, "slots": n * B, "steps": args.steps,
+                                  "steps_of_the_shortest": done, "us_per_step": round(t / args.steps * 1e6, 1)}), flush=True)
     elif args.what == "score":
         for name in ("comix", "cosingle"):
             m = model(name)
