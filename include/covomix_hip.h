@@ -69,7 +69,8 @@ typedef const cvx_ctx* cvx_stream_t;
  * cvx_hifigan_conv1d_f16x3_form (the tile height a split-precision convolution launch takes; host arithmetic only, so that tests can
  * place a problem on every tile form).  113: cvx_gemm_f32_form (which of its four kernels an fp32 GEMM launch takes; host arithmetic
  * only, so that tests can place a problem on every kernel).  Still 113 (symbols added, no struct or entry point changed): cvx_t2s_beam_steps
- * with its own size-carrying struct, cvx_t2s_beam_select_f32 - beam search on the decode slots. */
+ * with its own size-carrying struct, cvx_t2s_beam_select_f32 - beam search on the decode slots; cvx_t2s_beam_queue_steps with
+ * cvx_t2s_beam_queue - beam search through continuously refilled slot groups. */
 #define CVX_ABI_VERSION 113
 int         cvx_version(void);
 const char* cvx_last_error_string(void);
@@ -782,6 +783,50 @@ typedef struct cvx_t2s_beam {
 } cvx_t2s_beam;
 
 int cvx_t2s_beam_steps(const cvx_t2s_decoder* dec, const cvx_t2s_beam* beam, int32_t n_steps, cvx_stream_t stream);
+
+/* Beam search through CONTINUOUSLY REFILLED slot groups: a list of n utterances runs through the dec->batch / B groups of B neighbouring
+ * slots; a group whose utterance ends takes the next pending one inside the selection launch of that very step (no host round trip), as a
+ * slot of the sampled decode takes the next dialogue.  The step chain, the selection and every hypothesis are those of cvx_t2s_beam_steps:
+ * an utterance gets, bit for bit, what it gets alone.  dec->queue stays NULL (the dialogue queue of the sampled decode plays no part).
+ *   beam: a complete cvx_t2s_beam as for cvx_t2s_beam_steps, with groups record [3] = the utterance the group decodes; its parents,
+ *       hist_tokens, hist_logprobs and logprobs are not written (history is kept per utterance, below).
+ *   queue int32[2] = {next pending utterance, number of utterances}; utterances int32[n][8]: the caller writes [0] context rows, [1] step
+ *       limit; the device writes [3] status (0 pending, 1 running, 2 all hypotheses finished, 3 step limit), [4] steps decoded, [5] the group
+ *       it ran in.  Slot record [4] of the B slots of a group names the utterance: it indexes kv_c as a dialogue does.  The caller starts group
+ *       g on utterance g (g < min(groups, n)): slot and group records as for cvx_t2s_beam_steps, utterance records [3] = 1, [5] = g, and
+ *       queue[0] = min(groups, n); groups beyond stay ended ([1] = 1, slots at max_len).  owner[0][slot][0] = slot for the slots that
+ *       start; nothing else of the ancestry table needs a value.
+ *   When a group's utterance ends - all B hypotheses finished, or t + 1 has reached its limit (clamped into [1, max_len]) - the selection
+ *       launch writes final_scores fp32 / final_steps int32 / final_finished uint8 [n][B] (what scores, slot record [2] and finished hold
+ *       at the end of cvx_t2s_beam_steps), status and steps, takes the next utterance with one atomicAdd on queue[0] (taken only below
+ *       queue[1]) and re-arms the group: group record {0, 0, limit, utterance}, scores {0, -inf, ...}, finished 0, slot records position 0,
+ *       [1] = [2] = 0, [3] = context rows (clamped into [1, ctx_rows]), [4] = utterance, x of all B slots = `start` ([dim] start token) and
+ *       owner[0][slot][0] = slot.  With no utterance left the group ends, its slots idle at max_len.  Cache and ancestry rows of the ended
+ *       utterance stay in place and are never read: the new utterance's ancestry rows name only positions it has written.
+ *   History by UTTERANCE: parents int32 [n][hist_len][B], hist_tokens int32 / hist_logprobs fp32 [n][hist_len][B][streams].  backtrack != 0
+ *       (in `beam`): after the n_steps steps (n_steps may be 0) one thread per (utterance, hypothesis) writes tokens int64 / logprobs fp32
+ *       [n * B][streams][max_len] from the back-pointers over the steps utterance record [4] holds (the caller zeroes it).
+ * No host synchronisation, graph-capturable (n_utterances sizes the back-track launch only; the steps read queue[1]).  CVX_EINVAL (nothing is
+ * launched): struct_size != sizeof of either struct, a NULL pointer, n_utterances < 1, dec->queue != NULL, dec->cfg_scale > 1, beam_size
+ * outside [1, 16], batch % beam_size != 0, hist_len != max_len, and everything cvx_t2s_decode_steps refuses. */
+typedef struct cvx_t2s_beam_queue {
+    uint32_t struct_size;
+    int32_t n_utterances;
+    int32_t* queue;
+    int32_t* utterances;
+    const float* start;
+    int32_t* parents;
+    int32_t* hist_tokens;
+    float* hist_logprobs;
+    float* final_scores;
+    int32_t* final_steps;
+    uint8_t* final_finished;
+    int64_t* tokens;
+    float* logprobs;
+} cvx_t2s_beam_queue;
+
+int cvx_t2s_beam_queue_steps(const cvx_t2s_decoder* dec, const cvx_t2s_beam* beam, const cvx_t2s_beam_queue* bq, int32_t n_steps,
+                             cvx_stream_t stream);
 
 /* The selection step alone (the device functions cvx_t2s_beam_steps selects with; no slot state): groups G of beam_size B hypotheses,
  * logits [G * B, streams, V] fp32, scores_in [G * B], finished_in uint8 [G * B] -> per new slot: parents (index inside the group), tokens

@@ -165,6 +165,13 @@ class T2SBeam(C.Structure):
                                           "short_tokens", "logprobs")]
 
 
+class T2SBeamQueue(C.Structure):
+    """cvx_t2s_beam_queue: struct_size = sizeof(this); the utterance queue, per-utterance history and results of cvx_t2s_beam_queue_steps"""
+    _fields_ = [("struct_size", C.c_uint32), ("n_utterances", C.c_int32)] + \
+               [(n, C.c_void_p) for n in ("queue", "utterances", "start", "parents", "hist_tokens", "hist_logprobs", "final_scores",
+                                          "final_steps", "final_finished", "tokens", "logprobs")]
+
+
 class ResblockArgs(C.Structure):
     _fields_ = [("x", C.c_void_p), ("B", C.c_int32), ("C", C.c_int32), ("L", C.c_int32),
                 ("Wp1", C.c_void_p * 3), ("b1", C.c_void_p * 3), ("Wp2", C.c_void_p * 3), ("b2", C.c_void_p * 3),
@@ -211,6 +218,7 @@ SIGNATURES = {
     "cvx_t2s_decode_steps": (C.c_int, [C.POINTER(T2SDecoder), C.c_int32, C.c_void_p]),
     "cvx_t2s_decode_steps_scored": (C.c_int, [C.POINTER(T2SDecoder), C.POINTER(T2SScoring), C.c_int32, C.c_void_p]),
     "cvx_t2s_beam_steps": (C.c_int, [C.POINTER(T2SDecoder), C.POINTER(T2SBeam), C.c_int32, C.c_void_p]),
+    "cvx_t2s_beam_queue_steps": (C.c_int, [C.POINTER(T2SDecoder), C.POINTER(T2SBeam), C.POINTER(T2SBeamQueue), C.c_int32, C.c_void_p]),
     "cvx_t2s_beam_select_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "cvx_t2s_logprob_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]),

@@ -28,6 +28,9 @@
 //   beam_shortlist_kernel  per live row the min(B, V) largest log-softmax entries (row_logprob's maximum and sum), in place of sample_kernel;
 //   beam_merge_kernel      per utterance the B best of the <= B^3 candidates; writes back-pointers, scores, slot records, the next inputs and
 //                          the next ancestry rows;  beam_backtrack_kernel: the back-pointers into token / log-prob rows, once at the end.
+// cvx_t2s_beam_queue_steps runs a LIST of utterances through the groups: beam_merge_queue_kernel ends an utterance, takes the next pending
+// one from a device-side queue and re-arms the whole group inside the same launch; the history is then kept per utterance
+// (beam_backtrack_queue_kernel).
 // The reference rotates ALL cached keys again every step with rotary_embedding_torch's interleaved pairs
 // (rotary_embedding_torch.py:146-157); rotating a key once at its own position when it enters the cache is the same
 // arithmetic.  Interleaved pairs (2i, 2i+1) become half-split pairs (i, i+32) by permuting the rows of to_q / to_k
@@ -1164,6 +1167,156 @@ __global__ __launch_bounds__(64) void beam_backtrack_kernel(const BeamArgs a)
     }
 }
 
+// ---------------------------------------------------------------- beam search through continuously refilled groups (cvx_t2s_beam_queue_steps)
+// what beam_merge_queue_kernel and beam_backtrack_queue_kernel need beyond BeamArgs (a second kernel argument, as attn_owner_kernel's table)
+struct BeamQueueArgs {
+    int* queue;              // {next pending utterance, number of utterances}
+    int* utterances;         // [n][SR]: in [0] context rows [1] step limit; out [3] status [4] steps decoded [5] the group it ran in
+    const float* start;      // [streams * dim_emb] start token: the input of every slot of a re-armed group
+    int* parents;            // [n][max_len][B] - history by UTTERANCE (a group decodes several, one after the other)
+    int* hist_tok;           // [n][max_len][B][streams]
+    float* hist_lp;
+    float* final_scores;     // [n][B]: scores / steps / finished flags of the B hypotheses when the utterance ended
+    int* final_steps;
+    uint8_t* final_fin;
+    int64_t* tokens;         // [n * B][streams][max_len] (back-track)
+    float* logprobs;
+    int n, ctx_rows;         // (n: the back-track's thread count; the merge reads queue[1])
+};
+
+// beam_merge_kernel (a copy: sharing the body through a template moved the parent's schedule) with the history indexed by the group's
+// utterance (group record [3]) and, when the utterance ends, the refill of the whole group inside the same launch: finals, status and steps
+// of the ended utterance, the next pending one from the queue (one atomicAdd), and the group re-armed at position 0 - or idle when none is left
+__global__ __launch_bounds__(1024) void beam_merge_queue_kernel(const BeamArgs a, const BeamQueueArgs qa)
+{
+    __shared__ float bv[16];
+    __shared__ int bi[16];
+    __shared__ float sc[BEAM_MAX];
+    __shared__ int fin[BEAM_MAX], len[BEAM_MAX], sel[BEAM_MAX];
+    __shared__ int n_par[BEAM_MAX], n_fin[BEAM_MAX], n_tok[BEAM_MAX][2];
+    __shared__ int chosen;
+    const int tid = threadIdx.x, B = a.B, S = a.streams;
+    const int u = blockIdx.x, base = u * B;
+    int* const gs = a.groups + 4 * u;
+    const int t = aloadi(gs);
+    const int lim = min(max(aloadi(gs + 2), 1), a.max_len);
+    if (aloadi(gs + 1) != 0 || t < 0 || t >= lim) return;                  // (block-uniform) idle, or nothing to decode
+    const int utt = min(max(aloadi(gs + 3), 0), max(aloadi(qa.queue + 1) - 1, 0));   // (a stray record stays inside the n utterances)
+    if (tid < B) {
+        sc[tid] = a.scores[base + tid];
+        fin[tid] = a.finished[base + tid] ? 1 : 0;
+        len[tid] = aloadi(a.state + SR * (base + tid) + 2);
+    }
+    __syncthreads();
+    const float* const sl_lp = a.short_lp + (int64_t)base * S * BEAM_MAX;
+    const int* const sl_tok = a.short_tok + (int64_t)base * S * BEAM_MAX;
+    beam_merge<1024>(sc, fin, sl_lp, B, S, min(B, a.V), bv, bi, sel);
+    BeamPick r;
+    if (tid < B) {
+        r = beam_pick(sel[tid], tid, sc, fin, sl_lp, sl_tok, B, S, a.V - 1);
+        const int64_t h = ((int64_t)utt * a.max_len + t) * B + tid;
+        qa.parents[h] = r.parent;
+        qa.hist_tok[h * S] = r.tok0; qa.hist_lp[h * S] = r.lp0;
+        if (S == 2) { qa.hist_tok[h * S + 1] = r.tok1; qa.hist_lp[h * S + 1] = r.lp1; }
+        n_par[tid] = r.parent; n_fin[tid] = r.fin; n_tok[tid][0] = r.tok0; n_tok[tid][1] = r.tok1;
+    }
+    __syncthreads();                                    // (every old score / flag / length has been read)
+    bool all_fin = true;
+    for (int i = 0; i < B; ++i) all_fin = all_fin && n_fin[i] != 0;
+    const bool ends = all_fin || t + 1 >= lim;
+    if (!ends) {
+        if (tid < B) {
+            const int slot = base + tid;
+            int* const st = a.state + SR * slot;
+            a.scores[slot] = r.score;
+            a.finished[slot] = (uint8_t)r.fin;
+            st[0] = r.fin ? a.max_len : t + 1;
+            st[1] = r.fin ? 1 : 0;
+            st[2] = r.fin ? (sel[tid] >= 0 && fin[r.parent] ? len[r.parent] : (sel[tid] >= 0 ? t + 1 : 0)) : 0;
+        }
+        if (tid == 0) gs[0] = t + 1;
+        // the next input of every live hypothesis, and its row of the ancestry table: the parent's row for positions 0..t, then itself
+        for (int idx = tid; idx < B * S * a.dim_emb; idx += 1024) {
+            const int i = idx / (S * a.dim_emb), rem = idx - i * (S * a.dim_emb), s = rem / a.dim_emb, d = rem - s * a.dim_emb;
+            if (!n_fin[i]) a.x[((int64_t)(base + i) * S + s) * a.dim_emb + d] = a.emb[(int64_t)n_tok[i][s] * a.dim_emb + d];
+        }
+        const int* const src = a.owner + (int64_t)(t & 1) * a.batch * a.max_len;
+        int* const dst = a.owner + (int64_t)((t + 1) & 1) * a.batch * a.max_len;
+        for (int i = 0; i < B; ++i) {
+            if (n_fin[i]) continue;
+            const int* const sr = src + (int64_t)(base + n_par[i]) * a.max_len;
+            int* const dr = dst + (int64_t)(base + i) * a.max_len;
+            for (int j = tid; j <= t; j += 1024) dr[j] = aloadi(sr + j);
+            if (tid == 0) dr[t + 1] = base + i;         // (t + 1 < max_len: the utterance has not ended)
+        }
+        return;
+    }
+    // the utterance ends: its finals (a finished hypothesis keeps the steps it took, the others took all t + 1), status and steps
+    if (tid < B) {
+        const int64_t f = (int64_t)utt * B + tid;
+        qa.final_scores[f] = r.score;
+        qa.final_steps[f] = r.fin ? (sel[tid] >= 0 && fin[r.parent] ? len[r.parent] : (sel[tid] >= 0 ? t + 1 : 0)) : t + 1;
+        qa.final_fin[f] = (uint8_t)r.fin;
+    }
+    if (tid == 0) {
+        int* const ur = qa.utterances + SR * utt;
+        ur[4] = t + 1;
+        ur[5] = u;
+        __threadfence();
+        ur[3] = all_fin ? 2 : 3;
+        const int nxt = atomicAdd(qa.queue, 1);
+        chosen = nxt >= 0 && nxt < aloadi(qa.queue + 1) ? nxt : -1;
+    }
+    __syncthreads();
+    const int nxt = chosen;
+    if (nxt < 0) {                                      // nothing pending: the group ends as in the lock-step chain, its slots idle at max_len
+        if (tid < B) {
+            const int slot = base + tid;
+            int* const st = a.state + SR * slot;
+            a.scores[slot] = r.score;
+            a.finished[slot] = (uint8_t)r.fin;
+            st[0] = a.max_len; st[1] = 1; st[2] = qa.final_steps[(int64_t)utt * B + tid];
+        }
+        if (tid == 0) { gs[0] = t + 1; gs[1] = 1; }
+        return;
+    }
+    // re-arm the group on utterance nxt: position 0, the start token, hypothesis 0 alone live.  The cache and owner rows of the ended utterance
+    // stay where they are: the new one's owner rows name only positions it has written itself
+    int* const un = qa.utterances + SR * nxt;
+    for (int idx = tid; idx < B * S * a.dim_emb; idx += 1024) a.x[(int64_t)base * S * a.dim_emb + idx] = qa.start[idx % (S * a.dim_emb)];
+    if (tid < B) {
+        const int slot = base + tid;
+        int* const st = a.state + SR * slot;
+        a.scores[slot] = tid == 0 ? 0.f : -__builtin_inff();
+        a.finished[slot] = 0;
+        st[0] = 0; st[1] = 0; st[2] = 0; st[3] = min(max(aloadi(un), 1), qa.ctx_rows); st[4] = nxt;
+        a.owner[(int64_t)slot * a.max_len] = slot;      // (parity 0, position 0)
+    }
+    if (tid == 0) {
+        gs[0] = 0; gs[1] = 0; gs[2] = min(max(aloadi(un + 1), 1), a.max_len); gs[3] = nxt;
+        un[5] = u;
+        un[3] = 1;
+    }
+}
+
+// tokens / logprobs [utterance * B + hypothesis][streams][max_len] from the per-utterance back-pointers: one thread per (utterance, hypothesis)
+__global__ __launch_bounds__(64) void beam_backtrack_queue_kernel(const BeamArgs a, const BeamQueueArgs qa)
+{
+    const int row = blockIdx.x * 64 + threadIdx.x;
+    if (row >= qa.n * a.B) return;
+    const int utt = row / a.B, S = a.streams;
+    const int T = min(max(aloadi(qa.utterances + SR * utt + 4), 0), a.max_len);
+    int cur = row - utt * a.B;
+    for (int t = T - 1; t >= 0; --t) {
+        const int64_t h = ((int64_t)utt * a.max_len + t) * a.B + cur;
+        for (int s = 0; s < S; ++s) {
+            qa.tokens[((int64_t)row * S + s) * a.max_len + t] = qa.hist_tok[h * S + s];
+            qa.logprobs[((int64_t)row * S + s) * a.max_len + t] = qa.hist_lp[h * S + s];
+        }
+        cur = min(max(aloadi(qa.parents + h), 0), a.B - 1);
+    }
+}
+
 __global__ __launch_bounds__(256) void geglu_kernel(const float* __restrict__ h, float* __restrict__ out, int64_t rows,
                                                    int F, int64_t ld_out)
 {
@@ -1293,8 +1446,9 @@ static BeamArgs beam_args(const cvx_t2s_decoder* d, const cvx_t2s_beam* bm)
 
 // the step chain of cvx_t2s_decode_steps (logprobs == NULL) and cvx_t2s_decode_steps_scored: they differ in the sampling kernel only.
 // bm (cvx_t2s_beam_steps): the self-attention reads through the ancestry table, and the shortlist + merge kernels stand in for the sampling
-// kernel - one launch more per step; every other launch is the same.
-static int t2s_decode_run(const cvx_t2s_decoder* d, int32_t n_steps, float* logprobs, cvx_stream_t s, const cvx_t2s_beam* bm = nullptr)
+// kernel - one launch more per step; every other launch is the same.  bq (cvx_t2s_beam_queue_steps): the merge that refills its group.
+static int t2s_decode_run(const cvx_t2s_decoder* d, int32_t n_steps, float* logprobs, cvx_stream_t s, const cvx_t2s_beam* bm = nullptr,
+                          const BeamQueueArgs* bq = nullptr)
 {
     hipStream_t st = cvx_hip_stream(s);
     const float scale = 0.125f;        // dim_head ** -0.5
@@ -1347,7 +1501,8 @@ static int t2s_decode_run(const cvx_t2s_decoder* d, int32_t n_steps, float* logp
         if (bm) {
             const BeamArgs ba = beam_args(d, bm);
             hipLaunchKernelGGL(beam_shortlist_kernel, dim3((unsigned)(nb * d->streams)), dim3(1024), 0, st, ba);
-            hipLaunchKernelGGL(beam_merge_kernel, dim3((unsigned)(nb / bm->beam_size)), dim3(1024), 0, st, ba);
+            if (bq) hipLaunchKernelGGL(beam_merge_queue_kernel, dim3((unsigned)(nb / bm->beam_size)), dim3(1024), 0, st, ba, *bq);
+            else hipLaunchKernelGGL(beam_merge_kernel, dim3((unsigned)(nb / bm->beam_size)), dim3(1024), 0, st, ba);
             continue;
         }
         SampleArgs sa{d->logits, d->uniforms, d->emb, d->x, d->tokens, d->state, d->queue, d->dialogues, d->start, nb, d->uniform_steps,
@@ -1403,6 +1558,41 @@ extern "C" int cvx_t2s_beam_steps(const cvx_t2s_decoder* d, const cvx_t2s_beam* 
     if (bm->backtrack) {
         hipLaunchKernelGGL(beam_backtrack_kernel, dim3((unsigned)((d->batch + 63) / 64)), dim3(64), 0, cvx_hip_stream(s), beam_args(d, bm));
         CVX_CHECK_LAUNCH("cvx_t2s_beam_steps");
+    }
+    return CVX_OK;
+}
+
+extern "C" int cvx_t2s_beam_queue_steps(const cvx_t2s_decoder* d, const cvx_t2s_beam* bm, const cvx_t2s_beam_queue* bq, int32_t n_steps,
+                                        cvx_stream_t s)
+{
+    CVX_REQUIRE(bm && bm->struct_size == sizeof(cvx_t2s_beam), "t2s_beam_queue_steps: cvx_t2s_beam.struct_size = %u, this library knows %u",
+                bm ? bm->struct_size : 0u, (unsigned)sizeof(cvx_t2s_beam));
+    CVX_REQUIRE(bq && bq->struct_size == sizeof(cvx_t2s_beam_queue),
+                "t2s_beam_queue_steps: cvx_t2s_beam_queue.struct_size = %u, this library knows %u", bq ? bq->struct_size : 0u,
+                (unsigned)sizeof(cvx_t2s_beam_queue));
+    const int rc = t2s_validate(d, n_steps);
+    if (rc != CVX_OK) return rc;
+    CVX_REQUIRE(!d->queue, "t2s_beam_queue_steps: the dialogue queue of the sampled decode plays no part (dec->queue must be NULL)");
+    CVX_REQUIRE(!(d->cfg_scale > 1.f), "t2s_beam_queue_steps: guidance (cfg_scale > 1) is not built for beam search");
+    CVX_REQUIRE(bm->beam_size >= 1 && bm->beam_size <= BEAM_MAX && d->batch % bm->beam_size == 0,
+                "t2s_beam_queue_steps: beam_size = %d outside [1, %d] or no divisor of batch = %d", bm->beam_size, BEAM_MAX, d->batch);
+    CVX_REQUIRE(bm->hist_len == d->max_len, "t2s_beam_queue_steps: hist_len = %d, the history arrays hold max_len = %d steps per utterance",
+                bm->hist_len, d->max_len);
+    CVX_REQUIRE(bq->n_utterances >= 1, "t2s_beam_queue_steps: n_utterances = %d", bq->n_utterances);
+    CVX_REQUIRE(bm->scores && bm->finished && bm->owner && bm->groups && bm->parents && bm->hist_tokens && bm->hist_logprobs && bm->short_lp &&
+                bm->short_tokens && bm->logprobs, "t2s_beam_queue_steps: null pointer in cvx_t2s_beam");
+    CVX_REQUIRE(bq->queue && bq->utterances && bq->start && bq->parents && bq->hist_tokens && bq->hist_logprobs && bq->final_scores &&
+                bq->final_steps && bq->final_finished && bq->tokens && bq->logprobs, "t2s_beam_queue_steps: null pointer in cvx_t2s_beam_queue");
+    const BeamQueueArgs qa{bq->queue, bq->utterances, bq->start, bq->parents, bq->hist_tokens, bq->hist_logprobs, bq->final_scores,
+                           bq->final_steps, bq->final_finished, bq->tokens, bq->logprobs, bq->n_utterances, d->ctx_rows};
+    if (n_steps > 0) {
+        const int rr = t2s_decode_run(d, n_steps, nullptr, s, bm, &qa);
+        if (rr != CVX_OK) return rr;
+    }
+    if (bm->backtrack) {
+        hipLaunchKernelGGL(beam_backtrack_queue_kernel, dim3((unsigned)(((int64_t)bq->n_utterances * bm->beam_size + 63) / 64)), dim3(64), 0,
+                           cvx_hip_stream(s), beam_args(d, bm), qa);
+        CVX_CHECK_LAUNCH("cvx_t2s_beam_queue_steps");
     }
     return CVX_OK;
 }

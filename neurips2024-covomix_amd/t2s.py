@@ -5,7 +5,8 @@ Host mirror of the reference's `TextToSemantic.generate` sampling branch + `Text
 forwards to (covomix/conditional_model.py:313-321).  Built: the sampling branch with its three controls - temperature,
 classifier-free guidance (cond_scale > 1, one-output models) and the logit filter (filter_logits_fn = top_k / top_p with
 filter_fn_kwargs, text2semantic.py:118-132, :796) - in every decode schedule below; beam search (`generate_beam`: the flag the
-reference's generate accepts without a body, text2semantic.py:673-677 - the algorithm is defined in include/covomix_hip.h); no speculative
+reference's generate accepts without a body, text2semantic.py:673-677 - the algorithm is defined in include/covomix_hip.h; `generate_beam_many`:
+any number of utterances through continuously refilled groups of beam_size slots); no speculative
 decoding, no padded text batches.  Beside the tokens: the log-probability of every sampled token (return_logprobs), teacher-forced scoring of given tokens
 through the same decode slots (score_many) and the mean token log-probability best-of-N selects by (sequence_logprob).
 
@@ -971,6 +972,168 @@ class TextToSemanticDecoder:
             out += self._beam_wave(srcs[w:w + per], B, max_len, float(length_penalty))
         res = out if return_beams else [h[0] for h in out]
         return res[0] if one else res
+
+    # ------------------------------------------------------------------ beam search through continuously refilled groups
+    def _ensure_beam_queue(self, records: int) -> dict:
+        """Device state of cvx_t2s_beam_queue for `records` hypotheses (utterances * beam_size) queued at a time: allocated on first use, and
+        again when it must grow or the decode buffers were re-allocated.  The ancestry table of this chain is its own and gets its values
+        here, on the device, once.  Only the "beamq" graphs hold these addresses: they are dropped with the buffers."""
+        bq = getattr(self, "_beamq", None)
+        if bq is not None and bq["gen"] == self._gen and bq["records"] >= records:
+            return bq
+        for key in [k for k in self._graphs if k[0] == "beamq"]:
+            del self._graphs[key]
+        R, n, L, S, dev = max(records, 8), self._slots, self.max_length, self.d["streams"], self.device
+        i32 = lambda *s: torch.zeros(*s, dtype=torch.int32, device=dev)
+        f32 = lambda *s: torch.zeros(*s, dtype=torch.float32, device=dev)
+        self._beamq = dict(gen=self._gen, records=R, queue=i32(2), utterances=i32(R, SR), parents=i32(R * L), hist_tokens=i32(R * L * S),
+                           hist_logprobs=f32(R * L * S), final_scores=f32(R), final_steps=i32(R),
+                           final_finished=torch.zeros(R, dtype=torch.uint8, device=dev),
+                           tokens=torch.zeros(R, S, L, dtype=torch.int64, device=dev), logprobs=f32(R, S, L),
+                           owner=torch.arange(n, dtype=torch.int32, device=dev)[None, :, None].expand(2, -1, L).contiguous(),
+                           slot_ids=torch.arange(n, dtype=torch.int32, device=dev))
+        return self._beamq
+
+    def _launch_beam_queue(self, batch: int, beam_size: int, n_utt: int, n: int, backtrack: bool = False) -> None:
+        """n steps of the refilled beam chain (cvx_t2s_beam_queue_steps) on the current stream; backtrack: then tokens / log-probs of every
+        (utterance, hypothesis) from the per-utterance back-pointers"""
+        bm, bq = self._ensure_beam(), self._beamq
+        dec = self._descriptor(1.0, batch)
+        bs = _lib.T2SBeam(C.sizeof(_lib.T2SBeam), beam_size, self.max_length, 1 if backtrack else 0, bm["scores"].data_ptr(),
+                          bm["finished"].data_ptr(), bq["owner"].data_ptr(),
+                          *[bm[k].data_ptr() for k in ("groups", "parents", "hist_tokens", "hist_logprobs", "short_lp", "short_tokens", "logprobs")])
+        qs = _lib.T2SBeamQueue(C.sizeof(_lib.T2SBeamQueue), n_utt, bq["queue"].data_ptr(), bq["utterances"].data_ptr(), self.start.data_ptr(),
+                               *[bq[k].data_ptr() for k in ("parents", "hist_tokens", "hist_logprobs", "final_scores", "final_steps",
+                                                           "final_finished", "tokens", "logprobs")])
+        _lib.check(_lib.load().cvx_t2s_beam_queue_steps(C.byref(dec), C.byref(bs), C.byref(qs), n, ops._stream()), "cvx_t2s_beam_queue_steps")
+
+    def _beam_queue_graph(self, batch: int, beam_size: int):
+        """The captured graph of CHUNK steps of the refilled beam chain; `_beam_graph`'s procedure.  (The number of utterances sizes the
+        back-track launch only, which is not part of the graph: the steps read the device-side queue.)"""
+        key = ("beamq", beam_size, batch, ops.stream_cus(), self._gen)
+        g = self._graphs.get(key)
+        if g is not None:
+            return g
+        self._beam_idle()
+        self._launch_beam_queue(batch, beam_size, 1, CHUNK)       # warm-up outside capture
+        cur = torch.cuda.current_stream()
+        if self._cap is None:
+            self._cap = torch.cuda.Stream(device=self.device)
+        ops.saturation_share(cur, self._cap)
+        with ops.CAPTURE_GATE.exclusive():
+            cur.synchronize()
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g, stream=self._cap, capture_error_mode="thread_local"):
+                self._launch_beam_queue(batch, beam_size, 1, CHUNK)
+        if len(self._graphs) >= 8:
+            self._graphs.clear()
+        self._graphs[key] = g
+        return g
+
+    def _beam_queue_window(self, sources, B: int, lim: list, length_penalty: float, slots: int) -> list:
+        """One window of generate_beam_many: its utterances' contexts resident, the groups refilled on the device until all have ended."""
+        d = self.d
+        S, n, L = d["streams"], len(sources), self.max_length
+        G = max(1, min(slots // B, MAX_BATCH // B, n))
+        nb = G * B                                         # (the buffers hold whole 8-slot kernel groups: _ensure)
+        self._ensure(nb, n, 0)
+        bm, bq = self._ensure_beam(), self._ensure_beam_queue(max(n * B, WINDOW))
+        use_graph = os.environ.get("CVX_GRAPH", "1") == "1"
+        if use_graph:
+            self._beam_queue_graph(nb, B)
+        ctx = self._contexts(sources)
+        rows = [[0, 0, 0, ctx[i // B], i // B, 0, 0, 0] if i < nb else [L, 1, 0, 1, 0, 0, 0, 0] for i in range(self._slots)]
+        self.buf["state"].copy_(torch.tensor(rows, dtype=torch.int32))
+        self.buf["x"][:nb].copy_(self.start[None, :].expand(nb, -1))
+        sc = torch.full((self._slots,), -math.inf)
+        sc[0:nb:B] = 0.0                                   # before step 0 only hypothesis 0 of an utterance is live
+        bm["scores"].copy_(sc)
+        bm["finished"].zero_()
+        g = torch.zeros(self._slots, 4, dtype=torch.int32)
+        g[:, 1] = 1
+        for u in range(G):                                 # group u starts on utterance u
+            g[u] = torch.tensor([0, 0, lim[u], u], dtype=torch.int32)
+        bm["groups"].copy_(g)
+        bq["owner"].view(2, self._slots, L)[0, :nb, 0].copy_(bq["slot_ids"][:nb])     # (position 0 of a starting slot: the slot itself)
+        bq["utterances"][:n].copy_(torch.tensor([[ctx[j], lim[j], 0, 1 if j < G else 0, 0, j if j < G else 0, 0, 0] for j in range(n)],
+                                                dtype=torch.int32))
+        bq["queue"].copy_(torch.tensor([G, n], dtype=torch.int32))
+        # chunks of CHUNK steps; the host reads the utterance records one chunk behind the device (generate_many)
+        self._mirror_setup()
+        via_helper = ops.is_partition_stream()
+        i, pending, rec = 0, None, None
+        done = lambda r: r is not None and all(row[3] >= 2 for row in r)
+        cap = (sum(lim) + CHUNK - 1) // CHUNK + 4          # (one group decoding everything: cannot be reached)
+        while not done(rec) and i < cap:
+            if use_graph:
+                self._beam_queue_graph(nb, B).replay()
+            else:
+                self._launch_beam_queue(nb, B, n, CHUNK)
+            k = i & 1
+            self._mirror_push(k, bq["utterances"][:n], via_helper)
+            if pending is not None:
+                rec = self._mirror_pull(pending, n)
+            pending = k
+            i += 1
+        if not done(rec) and pending is not None:
+            rec = self._mirror_pull(pending, n)
+        if pending is not None:
+            self._pin_ev[pending].synchronize()
+        if not done(rec):
+            left = n if rec is None else sum(1 for row in rec if row[3] < 2)
+            raise RuntimeError(f"text2semantic refilled beam decode: {left} of {n} utterances did not finish in {i} chunks")
+        self._launch_beam_queue(nb, B, n, 0, backtrack=True)
+        scores, lengths_all = bq["final_scores"][:n * B].cpu(), bq["final_steps"][:n * B].tolist()
+        tokens, logprobs = bq["tokens"][:n * B].cpu(), bq["logprobs"][:n * B].cpu()
+        hist = lambda name, *tail: bq[name][:n * L * B * math.prod(tail)].view(n, L, B, *tail)
+        parents, h_tok, h_lp = hist("parents"), hist("hist_tokens", S), hist("hist_logprobs", S)
+        eos = d["vocab"] - 1
+        out = []
+        for u in range(n):
+            T = rec[u][4]
+            lengths = lengths_all[u * B:(u + 1) * B]
+            order = beam_rank(scores[u * B:(u + 1) * B], lengths, S, length_penalty)
+            hyps = []
+            for i in order:
+                streams = tokens[u * B + i, :, :lengths[i]].clone()
+                after = (streams == eos).cumsum(dim=-1) > 0          # mask_after_eos (text2semantic.py:73-76)
+                after = torch.nn.functional.pad(after, (1, -1), value=False)
+                flat = streams.masked_fill(after, PAD_ID).reshape(-1)
+                hyps.append((flat[flat != PAD_ID], streams, logprobs[u * B + i, :, :lengths[i]].clone(), float(scores[u * B + i])))
+            out.append(hyps)
+            self.last_beam.append(dict(steps=T, order=order, lengths=lengths, scores=scores[u * B:(u + 1) * B].clone(),
+                                       parents=parents[u, :T].cpu(), tokens=h_tok[u, :T].cpu(), logprobs=h_lp[u, :T].cpu(),
+                                       status=rec[u][3], group=rec[u][5]))
+        return out
+
+    @ops.gated
+    @torch.no_grad()
+    def generate_beam_many(self, sources, beam_size: int = 10, max_length: Optional[int] = None, length_penalty: float = 1.0,
+                           return_beams: bool = False, slots: int = 64, limits=None):
+        """generate_beam for ANY number of utterances through continuously refilled slot GROUPS (cvx_t2s_beam_queue_steps): slots // beam_size
+        groups (at most MAX_BATCH // beam_size) of beam_size neighbouring slots; a group whose utterance has ended - all hypotheses finished,
+        or its step limit - takes the next pending utterance inside the selection kernel of that very step, as generate_many's slots do.
+        Every utterance gets, bit for bit, what generate_beam gives it alone.  limits: optional per-utterance step limits (default
+        max_length for all).  Windows of WINDOW // beam_size utterances (a record is a hypothesis), one packed encoder pass each.
+        Returns what generate_beam returns for a list, in input order, host tensors; `last_beam` keeps generate_beam's record per utterance
+        plus `status` (2: all hypotheses finished, 3: step limit) and `group` (the group it ran in).
+        ValueError (before any device work): beam_size outside 1..16, slots < beam_size, limits of another length than sources."""
+        B = check_beam_size(beam_size)
+        srcs = list(sources)
+        n = len(srcs)
+        if int(slots) < B:
+            raise ValueError(f"generate_beam_many: slots = {slots} hold no group of beam_size = {B}")
+        if limits is not None and len(limits) != n:
+            raise ValueError(f"generate_beam_many: {len(limits)} limits for {n} utterances")
+        max_len = min(int(max_length or self.max_length), self.max_length)
+        if max_len < 1:
+            raise ValueError("generate_beam_many needs at least one step")
+        lim = [max_len] * n if limits is None else [max(1, min(int(x), max_len)) for x in limits]
+        self.last_beam = []
+        out, win = [], max(1, WINDOW // B)
+        for w in range(0, n, win):
+            out += self._beam_queue_window(srcs[w:w + win], B, lim[w:w + win], float(length_penalty), int(slots))
+        return out if return_beams else [h[0] for h in out]
 
     def score_many(self, sources, targets, cond_scale: float = 1.0, slots: int = 64):
         """Teacher-forced scoring: the log-probability the model gives every token of targets[j] under the text sources[j] - what the

@@ -18,6 +18,10 @@
   python tools/t2s_sampling_bench.py beam [--beam-size 10]
       us per beam step (generate_beam, graph replay) for CoMix and CoSingle with 1 and 6 utterances (10 and 60 slots at beam size 10).
       The sampled step at the same slot counts: `steps --slots 10,60` (with --root for the parent commit), in turns, five rounds.
+  python tools/t2s_sampling_bench.py beamq [--beam-size 10]
+      128 utterances that end at different steps (limits 100 ... 608: the set of config5.decode_ragged) for CoMix and CoSingle:
+      generate_beam_many (continuously refilled groups) against generate_beam in lock-step waves of 64 // beam_size utterances, each wave
+      as long as its longest utterance; in turns, five rounds, utterances per second.
 """
 import argparse
 import json
@@ -28,7 +32,7 @@ import time
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("what", choices=["steps", "guided", "score", "bestof", "beam"])
+    ap.add_argument("what", choices=["steps", "guided", "score", "bestof", "beam", "beamq"])
     ap.add_argument("--logprobs", action="store_true")
     ap.add_argument("--root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     ap.add_argument("--top-p", type=float, default=None)
@@ -36,6 +40,7 @@ def main():
     ap.add_argument("--tag", default="")
     ap.add_argument("--slots", default="1,8,64", help="steps: the slot counts")
     ap.add_argument("--beam-size", type=int, default=10)
+    ap.add_argument("--utterances", default="1,6", help="beam: the utterance counts (a kernel trace wants one shape: --utterances 6)")
     args = ap.parse_args()
     sys.path.insert(0, os.path.abspath(args.root))
     import torch
@@ -70,7 +75,7 @@ def main():
         B = args.beam_size
         for name in ("comix", "cosingle"):
             m = model(name)
-            for n in (1, 6):
+            for n in [int(x) for x in args.utterances.split(",")]:
                 srcs = [torch.randint(1, 30000, (1, 64), generator=g) for _ in range(n)]
                 run = lambda: m.generate_beam(srcs, beam_size=B, max_length=args.steps)
                 run()                                                     # graph + buffers of the timed shape
@@ -78,6 +83,26 @@ def main():
                 done = min(r["steps"] for r in m.last_beam)               # (an utterance whose hypotheses all finish ends early)
                 print(json.dumps({"tag": args.tag, "model": name, "beam_size": B, "utterances": n, "slots": n * B, "steps": args.steps,
                                   "steps_of_the_shortest": done, "us_per_step": round(t / args.steps * 1e6, 1)}), flush=True)
+    elif args.what == "beamq":
+        B, n, tokens = args.beam_size, 128, 608
+        per = 64 // B
+        lims = torch.randint(100, tokens + 1, (n,), generator=g).tolist()
+        srcs = [torch.randint(1, 30000, (1, 64), generator=g) for _ in range(n)]
+        for name in ("comix", "cosingle"):
+            m = model(name)
+            many = lambda l: m.generate_beam_many(srcs, beam_size=B, max_length=tokens, limits=l)
+            waves = lambda: [m.generate_beam(srcs[w:w + per], beam_size=B, max_length=max(lims[w:w + per])) for w in range(0, n, per)]
+            many([20] * n)                                                # graphs + buffers of the timed shapes
+            m.generate_beam(srcs[:per], beam_size=B, max_length=20)
+            m.generate_beam(srcs[:n % per or per], beam_size=B, max_length=20)
+            for r in range(5):
+                t_many = timed(lambda: many(lims))
+                early = sum(1 for rec in m.last_beam if rec["status"] == 2)   # (ended before its limit: all hypotheses finished)
+                t_waves = timed(waves)
+                print(json.dumps({"tag": args.tag, "model": name, "round": r, "utterances": n, "beam_size": B, "groups": per,
+                                  "useful_steps": sum(lims), "ended_by_eos": early, "refilled_s": round(t_many, 4),
+                                  "waves_s": round(t_waves, 4), "refilled_utt_per_s": round(n / t_many, 2),
+                                  "waves_utt_per_s": round(n / t_waves, 2), "refilled_vs_waves": round(t_waves / t_many, 3)}), flush=True)
     elif args.what == "score":
         for name in ("comix", "cosingle"):
             m = model(name)
