@@ -70,7 +70,9 @@ typedef const cvx_ctx* cvx_stream_t;
  * place a problem on every tile form).  113: cvx_gemm_f32_form (which of its four kernels an fp32 GEMM launch takes; host arithmetic
  * only, so that tests can place a problem on every kernel).  Still 113 (symbols added, no struct or entry point changed): cvx_t2s_beam_steps
  * with its own size-carrying struct, cvx_t2s_beam_select_f32 - beam search on the decode slots; cvx_t2s_beam_queue_steps with
- * cvx_t2s_beam_queue - beam search through continuously refilled slot groups. */
+ * cvx_t2s_beam_queue - beam search through continuously refilled slot groups.  Still 113 (additive, one formerly ignored
+ * flag bit; no struct or entry point changes): the V^T stores of a to_qkv launch of the eight-phase kernels go line-major, 16 bytes
+ * per lane (same values, same addresses); CVX_GEMM_FLAG_VT_PIECES keeps the earlier store code selectable. */
 #define CVX_ABI_VERSION 113
 int         cvx_version(void);
 const char* cvx_last_error_string(void);
@@ -236,6 +238,8 @@ typedef struct {
 #define CVX_GEMM_FLAG_TILE256 128   /* ... 256-row tiles always (bit-identical results either way: A/B measurements) */
 #define CVX_GEMM_FLAG_TILE_MIXED 32 /* ... whole rounds of 256-row tiles + one launch of 192-row tiles over the rest, wherever such a split exists
                                      * (default: where it is the cheapest of the three; bit-identical results) */
+#define CVX_GEMM_FLAG_VT_PIECES 512 /* to_qkv on the eight-phase kernels: the earlier V^T stores (8 bytes per lane, row group by row group) instead of
+                                     * line-major 16-byte stores (bit-identical results: the bit-identity test, A/B measurements) */
 int cvx_split_f16(const float* w, uint16_t* hi, uint16_t* lo, int64_t n, float scale, cvx_stream_t s);
 /* n_sets interleaved split copies of ONE weight matrix with its COLUMNS scaled: out[s][n][il(k)] = split( W[n,k] * colscale[s*cs_ld + k] *
  * set_scale_dev[s*ss_ld] * scale ), each [N][K/32][hi 32 | lo 32] (the w_interleaved layout, row length 2K halves), K % 32 == 0.

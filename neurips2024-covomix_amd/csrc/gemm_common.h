@@ -55,7 +55,7 @@ struct SplitOut { _Float16* hi; _Float16* lo; int64_t ldc_h; int write_f32;
                   // switches operands, and divided by *a2_scale at the end
                   const float* a2_scale; };
 // sat: sticky saturation flag of the device (cvx_common.h), NULL = no bookkeeping.  dbg: kernel-choice bits from the public
-// cvx_gemm_split_io.flags (8 one tile per block, 16 / 32 / 64 192-row / 256-row / mixed tiles: bit-identical results).  The host
+// cvx_gemm_split_io.flags (8 one tile per block, 16 / 32 / 64 192-row / 256-row / mixed tiles, 128 the earlier V^T stores: bit-identical results).  The host
 // sets no other dbg bit and no trace (what bit 0 / trace still guard in the 16x16x32 kernels is a former timing experiment).
 
 // accumulator factor: 1 / (weight pre-scale) / (activation pre-scale); both powers of two, so the division is exact

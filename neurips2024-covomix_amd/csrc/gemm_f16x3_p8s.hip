@@ -49,7 +49,7 @@ constexpr int LDS_B = DUMP_B + 8 * 1024;
 // waves whose A slots fall past row 192 issue dummy pieces so that the counted vmcnt holds) - a tile costs 0.8 of a 256-row one (0.75 of the MFMAs, the same W stream), and
 // the launcher takes it where fewer, shorter rounds of tiles come out (9,298 rows x N = 1024: 196 tiles of 192 rows = one round at 0.75
 // against 148 tiles of 256 rows = one round at 1.0).  Every output element is the same sum in the same order: same bits.
-template <bool HAS_A2, bool SWAP, bool PERM = false, int MI = 8>
+template <bool HAS_A2, bool SWAP, bool PERM = false, int MI = 8, bool LEAN = false>
 __device__ __forceinline__ void tile_mainloop(const cvx_gemm_args& p, const PreSplitA& A, const f16* __restrict__ W, char* smem,
                                               int m0, int n0, int m0n, int n0n, bool first, int lane, int wid, int wr, int wc,
                                               f32x4 (&acc)[MI][4], const float a2_ratio = 1.f)
@@ -64,14 +64,16 @@ __device__ __forceinline__ void tile_mainloop(const cvx_gemm_args& p, const PreS
     const int64_t ldaB = A.ld * 2, lda2B = A.ld2 * 2, ldwB = p.ldw * 2;
     const bool has_next = m0n >= 0;
     auto set_offsets = [&](int h, int mm, int nn) {               // quarters A_h / W_h of the tile at (mm, nn)
+        int ln = lane;                                            // LEAN: see the kernel (the lane's parts are worked out HERE, not held through the K loop)
+        if constexpr (LEAN) asm volatile("" : "+v"(ln));
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
             const int slot = 2 * wid + j, pr0 = 8 * slot;
             const int ra0 = a_slot ? (slot / (RH / 8)) * RG + h * RH + (slot % (RH / 8)) * 8 : 0;
             const int rb0 = (pr0 >> 5) * 64 + h * 32 + (pr0 & 31);
-            const int ra = ra0 + (lane >> 3), rb = rb0 + (lane >> 3);
-            const uint32_t ca = (uint32_t)(((lane & 7) ^ ((ra >> 1) & 7)) * 16);
-            const uint32_t cb = (uint32_t)(((lane & 7) ^ ((rb >> 1) & 7)) * 16);
+            const int ra = ra0 + (ln >> 3), rb = rb0 + (ln >> 3);
+            const uint32_t ca = (uint32_t)(((ln & 7) ^ ((ra >> 1) & 7)) * 16);
+            const uint32_t cb = (uint32_t)(((ln & 7) ^ ((rb >> 1) & 7)) * 16);
             const uint32_t ga = (uint32_t)min(mm + ra, p.M - 1), gb = (uint32_t)min(nn + (PERM ? perm32(rb) : rb), p.N - 1);
             offA[h][j] = ga * (uint32_t)ldaB + ca;                 // (every operand spans < 4 GiB: checked by the launcher)
             offA2[h][j] = HAS_A2 ? ga * (uint32_t)lda2B + ca : 0u;
@@ -248,12 +250,21 @@ __global__ __launch_bounds__(512, 2) void gemm_f16x3_p8s_kernel(
         bool v_block = false;
         if constexpr (EPI == EPI_QKV || EPI == EPI_QKV_RS) v_block = n0 >= p.rope_cols;          // block-uniform: this tile holds V columns
         constexpr bool PERM = epi_perm(EPI);
+        // to_qkv (LEAN): the main loop and the epilogues each see the lane id through an opaque copy made per tile, and set_offsets through
+        // one made where it runs.  Otherwise what they derive from it (the V^T lines, the permuted columns, the exchange's lane halves, the
+        // lane's parts of the NEXT tile's DMA offsets) is hoisted out of the tile loop or the K loop, lives beside 128 accumulators and
+        // the fragments, and goes to scratch: 164 bytes per lane in the 256-row instance before, none now (tests/test_qkv_vt_stores.py).
+        constexpr bool LEAN = EPI == EPI_QKV || EPI == EPI_QKV_RS;
+        int lane_e = lane, lane_m = lane;
+        if constexpr (LEAN) asm volatile("" : "+v"(lane_m));
         if (v_block) {
-            tile_mainloop<HAS_A2, false, PERM, MI>(p, A, W, smem_p8s, m0, n0, m0n, n0n, first, lane, wid, wr, wc, acc, a2_ratio);
-            if (!(so.dbg & 1)) epilogue_vt<MI, false, EPI == EPI_QKV_RS, PERM>(p, acc, row0, col0, lane, so, acc_scale);
+            tile_mainloop<HAS_A2, false, PERM, MI, LEAN>(p, A, W, smem_p8s, m0, n0, m0n, n0n, first, lane_m, wid, wr, wc, acc, a2_ratio);
+            if constexpr (LEAN) asm volatile("" : "+v"(lane_e));
+            if (!(so.dbg & 1)) epilogue_vt<MI, false, EPI == EPI_QKV_RS, PERM>(p, acc, row0, col0, lane_e, so, acc_scale);
         } else {
-            tile_mainloop<HAS_A2, true, PERM, MI>(p, A, W, smem_p8s, m0, n0, m0n, n0n, first, lane, wid, wr, wc, acc, a2_ratio);
-            if (!(so.dbg & 1)) epilogue_rows<EPI, MI>(p, acc, row0, col0, lane, so, acc_scale);  // (dbg bit 0: main loop only, timing)
+            tile_mainloop<HAS_A2, true, PERM, MI, LEAN>(p, A, W, smem_p8s, m0, n0, m0n, n0n, first, lane_m, wid, wr, wc, acc, a2_ratio);
+            if constexpr (LEAN) asm volatile("" : "+v"(lane_e));
+            if (!(so.dbg & 1)) epilogue_rows<EPI, MI>(p, acc, row0, col0, lane_e, so, acc_scale);  // (dbg bit 0: main loop only, timing)
         }
         if (nslot < 0) break;
         // the epilogue's own loads / stores share the vmcnt counter with the DMA: start the next tile from a clean count

@@ -324,11 +324,12 @@ __device__ __forceinline__ void epilogue_rows(const cvx_gemm_args& p_in, f32x4 (
 // ---- epilogue of a V block of a to_qkv projection, UN-swapped layout:
 // acc[mi][ni][r] = C[row0 + 16 mi + 4 (lane >> 4) + r][col0 + 16 ni + (lane & 15)]: 4 consecutive frames per lane ->
 // vt[((b*H + head)*64 + d) * vt_ld + slot(t)], 8 bytes per store when the four frames are one aligned slot group
+// This is the earlier store order, row group by row group (so.dbg bit 7 = CVX_GEMM_FLAG_VT_PIECES keeps it selectable:
+// the bit-identity test and A/B measurements): the 32-byte pieces of one V^T line are issued a whole row group apart.
 template <int MI = 8, bool PRE = false, bool RS = false, bool PERM = false>
-__device__ __forceinline__ void epilogue_vt(const cvx_gemm_args& p, f32x4 (&acc)[MI][4], int row0, int col0, int lane,
-                                            const SplitOut& so, float acc_scale, const EpiPre<MI>* pre = nullptr)
+__device__ __forceinline__ void epilogue_vt_pieces(const cvx_gemm_args& p, f32x4 (&acc)[MI][4], int row0, int col0, int lane,
+                                                   const SplitOut& so, float acc_scale, const EpiPre<MI>* pre = nullptr)
 {
-    if (col0 >= p.N) return;                    // wave tile entirely past the last column (H % 4 != 0; wave-uniform)
     const int H = p.rope_cols / 128, T = p.rope_T;
     const int head = (col0 - p.rope_cols) / 64;
     float vs0;
@@ -367,6 +368,137 @@ __device__ __forceinline__ void epilogue_vt(const cvx_gemm_args& p, f32x4 (&acc)
                     if (so.vt_lo) so.vt_lo[o] = l[e];
                 }
             }
+        }
+    }
+    cvx_sat_commit(so.sat, amax);
+}
+
+// The same values at the same addresses, stored LINE-MAJOR and 16 bytes at a time.
+//  * Order: column group ni outside, row groups mi inside, hi then lo - the pieces of one V^T line leave back to back instead of a
+//    whole row group apart (a 128-byte line = the 64 slots of four row groups).
+//  * Width: lane group g = lane >> 4 holds frames 16 mi + 4 g ... + 3, and vt_slot puts the groups 0, 2, 1, 3 of an aligned 16-frame
+//    block at halves 0-3, 4-7, 8-11, 12-15 of its slot block - the two groups that are neighbours in slot space sit 32 lanes apart.
+//    One v_permlane32_swap per packed register brings them together: 16 bytes (8 adjacent slots) per lane, 64 contiguous bytes per
+//    V^T row and store instruction.  With x = (x_dn, x_up) the two 32-lane halves of a register, swap(x, y) = ((x_dn, y_dn), (x_up, y_up)).
+//      offset 0 (the block starts a slot block): swap(A[j], A[j+1]) - the lower half-wave stores block j, the upper block j + 1;
+//      offset 8 (T = 1000: every odd sequence): the slot block is the upper half of block m and the lower half of block m + 1;
+//        swap(A[j], A[j]) for even j shows A[j]'s lower half to the upper lanes, which own A[j-1]'s upper half (pair j-1, j), and
+//        A[j]'s upper half to the lower lanes, which own A[j+1]'s lower half (pair j, j+1).
+//    The choice is wave-uniform per row group (row0 is).  Whatever is not covered - offsets 4 and 12, a block that straddles two
+//    sequences or the end of M, an unpaired block, the outer halves of an offset-8 run, unaligned buffers - takes the 8-byte / scalar
+//    stores of epilogue_vt_pieces, per lane.
+constexpr bool VT_EXCHANGE = true;              // (false: line-major order only - the timing build that tells the two mechanisms apart)
+typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+
+template <int MI = 8, bool PRE = false, bool RS = false, bool PERM = false>
+__device__ __forceinline__ void epilogue_vt(const cvx_gemm_args& p, f32x4 (&acc)[MI][4], int row0_in, int col0, int lane,
+                                            const SplitOut& so, float acc_scale, const EpiPre<MI>* pre = nullptr)
+{
+    static_assert(MI % 2 == 0, "row groups are exchanged in pairs");
+    if (col0 >= p.N) return;                    // wave tile entirely past the last column (H % 4 != 0; wave-uniform)
+    if (so.dbg & 128) { epilogue_vt_pieces<MI, PRE, RS, PERM>(p, acc, row0_in, col0, lane, so, acc_scale, pre); return; }
+    const int row0 = __builtin_amdgcn_readfirstlane(row0_in);
+    const int H = p.rope_cols / 128, T = p.rope_T;
+    const int head = (col0 - p.rope_cols) / 64;
+    float vs0;
+    if constexpr (PRE) vs0 = pre->vs; else vs0 = so.vt_scale ? *so.vt_scale : 1.f;
+    const float vs = vs0 * acc_scale;
+    const int g = lane >> 4;
+    const bool upper = lane >= 32;
+    CvxSat amax;
+    // 16-byte stores need 16-byte aligned lines (vt_ld % 8 == 0 is the entry point's rule; the buffers are the caller's)
+    const bool wide = VT_EXCHANGE && ((((uintptr_t)so.vt_hi | (uintptr_t)so.vt_lo) & 15) == 0) && (so.vt_ld & 7) == 0;
+    int bq[MI], tb[MI];                         // wave-uniform: sequence and frame of the row group's first row
+    unsigned k0 = 0, k8 = 0;                    // bit mi: the row group lies whole inside one sequence and M, at offset 0 / 8 of a slot block
+#pragma unroll
+    for (int mi = 0; mi < MI; ++mi) {
+        bq[mi] = (row0 + 16 * mi) / T; tb[mi] = row0 + 16 * mi - bq[mi] * T;
+        const bool whole = wide && row0 + 16 * mi + 15 < p.M && tb[mi] + 15 < T;
+        if (whole && (tb[mi] & 15) == 0) k0 |= 1u << mi;
+        if (whole && (tb[mi] & 15) == 8) k8 |= 1u << mi;
+    }
+    // deferred norm: the four frames' sqrt(D) / ||x|| ride on the accumulator scale.  Every column group needs them again: re-read (one
+    // 16-byte load per row group, L1 hits after the first) rather than 8 x 4 registers held through the epilogue, which spilled.
+    const bool rs_vec = RS && (((uintptr_t)so.row_scale) & 15) == 0;
+    const unsigned pair0 = k0 & (k0 >> 1) & 0x55555555u;       // bit j (even): blocks j, j + 1 exchange at offset 0
+    const unsigned pair8 = k8 & (k8 >> 1);                     // bit m: blocks m, m + 1 share a slot block at offset 8
+    const unsigned cov_dn = pair0 | (pair0 << 1) | (pair8 << 1), cov_up = pair0 | (pair0 << 1) | pair8;
+    const unsigned cov = upper ? cov_up : cov_dn;              // bit mi: this lane's frames of row group mi leave in a 16-byte store
+#pragma unroll
+    for (int ni = 0; ni < 4; ++ni) {
+        const int d = PERM ? perm32(16 * ni + (lane & 15)) : 16 * ni + (lane & 15);      // (the W tile's rows may be permuted inside 32)
+        const float bv = p.bias ? p.bias[col0 + d] * vs0 : 0.f;
+        auto split = [&](int mi, f16x4& h, f16x4& l) {
+            h = f16x4{0, 0, 0, 0}; l = f16x4{0, 0, 0, 0};
+            const int r0 = row0 + 16 * mi + 4 * g;
+            if (r0 >= p.M) return;
+            f32x4 rs4 = f32x4{vs, vs, vs, vs};
+            if constexpr (RS) {
+                if (rs_vec && r0 + 3 < p.M) rs4 = *reinterpret_cast<const f32x4*>(so.row_scale + r0) * vs;
+                else {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) rs4[e] = vs * so.row_scale[min(r0 + e, p.M - 1)];
+                }
+            }
+            split4_pk(f32x4{fmaf(acc[mi][ni][0], rs4[0], bv), fmaf(acc[mi][ni][1], rs4[1], bv), fmaf(acc[mi][ni][2], rs4[2], bv), fmaf(acc[mi][ni][3], rs4[3], bv)}, h, l, amax);
+        };
+        auto line = [&](int b) { return ((int64_t)(b * H + head) * 64 + d) * so.vt_ld; };
+        auto pieces = [&](int mi, const f16x4 h, const f16x4 l) {            // the 8-byte / scalar stores of epilogue_vt_pieces
+            const int r0 = row0 + 16 * mi + 4 * g;
+            if (r0 >= p.M) return;
+            int b = bq[mi], t0 = tb[mi] + 4 * g;
+            if (t0 >= T) { b = r0 / T; t0 = r0 - b * T; }          // (the row group straddles sequences)
+            if ((t0 & 3) == 0 && t0 + 3 < T && r0 + 3 < p.M) {
+                const int64_t o = line(b) + vt_slot(t0);
+                *reinterpret_cast<f16x4*>(so.vt_hi + o) = h;
+                if (so.vt_lo) *reinterpret_cast<f16x4*>(so.vt_lo + o) = l;
+            } else {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const int row = r0 + e;
+                    if (row >= p.M) break;
+                    const int bb = row / T, tt = row - bb * T;
+                    const int64_t o = line(bb) + vt_slot(tt);
+                    so.vt_hi[o] = h[e];
+                    if (so.vt_lo) so.vt_lo[o] = l[e];
+                }
+            }
+        };
+        // first | second = the lane's 8 adjacent slots, hi halves then lo halves
+        auto store16 = [&](int64_t o, const u32x2 h1, const u32x2 h2, const u32x2 l1, const u32x2 l2) {
+            *reinterpret_cast<u32x4*>(so.vt_hi + o) = u32x4{h1[0], h1[1], h2[0], h2[1]};
+            if (so.vt_lo) *reinterpret_cast<u32x4*>(so.vt_lo + o) = u32x4{l1[0], l1[1], l2[0], l2[1]};
+        };
+        u32x2 ph = u32x2{0, 0}, pl = u32x2{0, 0};           // this lane's halves of row group j - 1
+#pragma unroll
+        for (int j = 0; j < MI; j += 2) {
+            f16x4 h0, l0, h1, l1;
+            split(j, h0, l0);
+            split(j + 1, h1, l1);
+            const u32x2 a0h = __builtin_bit_cast(u32x2, h0), a0l = __builtin_bit_cast(u32x2, l0);
+            const u32x2 a1h = __builtin_bit_cast(u32x2, h1), a1l = __builtin_bit_cast(u32x2, l1);
+            if ((pair0 >> j) & 1) {
+                const auto hx = __builtin_amdgcn_permlane32_swap(a0h[0], a1h[0], false, false), hy = __builtin_amdgcn_permlane32_swap(a0h[1], a1h[1], false, false);
+                const auto lx = __builtin_amdgcn_permlane32_swap(a0l[0], a1l[0], false, false), ly = __builtin_amdgcn_permlane32_swap(a0l[1], a1l[1], false, false);
+                const int64_t o = line(upper ? bq[j + 1] : bq[j]) + (upper ? tb[j + 1] : tb[j]) + 8 * (g & 1);
+                store16(o, u32x2{hx[0], hy[0]}, u32x2{hx[1], hy[1]}, u32x2{lx[0], ly[0]}, u32x2{lx[1], ly[1]});
+            } else {
+                const bool up = j > 0 && ((pair8 >> (j > 0 ? j - 1 : 0)) & 1), dn = (pair8 >> j) & 1;
+                if (up || dn) {
+                    const auto hx = __builtin_amdgcn_permlane32_swap(a0h[0], a0h[0], false, false), hy = __builtin_amdgcn_permlane32_swap(a0h[1], a0h[1], false, false);
+                    const auto lx = __builtin_amdgcn_permlane32_swap(a0l[0], a0l[0], false, false), ly = __builtin_amdgcn_permlane32_swap(a0l[1], a0l[1], false, false);
+                    if (upper ? up : dn) {
+                        // upper lanes: own frames of j - 1 | the lower half of j; lower lanes: the upper half of j | own frames of j + 1
+                        const int64_t o = line(upper ? bq[j] : bq[j + 1]) + (upper ? tb[j] : tb[j + 1]) - 8 + 8 * (g & 1);
+                        store16(o, upper ? ph : u32x2{hx[1], hy[1]}, upper ? u32x2{hx[0], hy[0]} : a1h,
+                                upper ? pl : u32x2{lx[1], ly[1]}, upper ? u32x2{lx[0], ly[0]} : a1l);
+                    }
+                }
+            }
+            if (!((cov >> j) & 1)) pieces(j, h0, l0);
+            if (!((cov >> (j + 1)) & 1)) pieces(j + 1, h1, l1);
+            ph = a1h; pl = a1l;
         }
     }
     cvx_sat_commit(so.sat, amax);

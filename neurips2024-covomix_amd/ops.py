@@ -99,7 +99,7 @@ _TL = threading.local()          # per-thread additions to the flags (gemm_flags
 def gemm_flags(extra: int):
     """with ops.gemm_flags(16): every GEMM THIS THREAD launches inside the block carries the extra cvx_gemm_split_io.flags bits
     (16 = CVX_GEMM_FLAG_NO_MEDIUM pins the large-problem kernel, 64 / 128 its tile height: A/B measurements and the bit-identity
-    tests).  Thread-local: another host thread's solve is not affected (round-4 advice)."""
+    tests; 512 = CVX_GEMM_FLAG_VT_PIECES keeps to_qkv's earlier 8-byte V^T stores, same bits).  Thread-local: another host thread's solve is not affected (round-4 advice)."""
     old = getattr(_TL, "flags", 0)
     _TL.flags = old | int(extra)
     try:

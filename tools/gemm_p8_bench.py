@@ -3,7 +3,8 @@
 split q|k + transposed split v; out: residual; ff1: bias + GELU + split, no fp32 store; ff2: bias + residual + split twin;
 skip: K-split A|A2 + bias), interleaved A and W.  Columns = cvx_gemm_split_io.flags values (VARIANTS=, default "144,80,16,8"):
 16 + 128 large-problem kernel with 256-row tiles, 16 + 64 with 192-row tiles, 16 its own choice of height, 8 medium-problem kernel,
-0 the library's choice of kernel (+ 4 one tile per block; dev builds: + 256 main loop only).
+0 the library's choice of kernel (+ 4 one tile per block; + 512 to_qkv's earlier 8-byte V^T stores; dev builds: + 256 main loop only).
+Per column: median and min of the interleaved rounds (ROUNDS=3).
 Env: M=16000, SHAPES=qkv,ff2, ZERO=1 (power probe), REPS=20."""
 import math, os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -71,9 +72,10 @@ for (N, K, K1, name, cnt) in [(3072, 1024, 0, "qkv", 8), (1024, 1024, 0, "out", 
                 t = timeit(fn, iters=10)
             if rep:
                 times[flags].append(t)
+    mins = {v: min(ts) for v, ts in times.items()}
     times = {v: sorted(ts)[len(ts) // 2] for v, ts in times.items()}
     for flags in variants:
         tot[flags] += times[flags] * cnt
     fl = 2.0 * M * N * K
-    print(f"{name:5s} N={N:5d} K={K:5d}: " + "   ".join(f"[{v}] {times[v]:7.1f} us ({3*fl/times[v]/1e6:5.0f} TF)" for v in variants), flush=True)
+    print(f"{name:5s} N={N:5d} K={K:5d}: " + "   ".join(f"[{v}] {times[v]:7.1f} us ({3*fl/times[v]/1e6:5.0f} TF, min {mins[v]:7.1f})" for v in variants), flush=True)
 print("per-eval GEMM total (ms): " + "  ".join(f"[{v}] {tot[v]/1e3:.2f}" for v in variants))
