@@ -737,6 +737,42 @@ typedef struct {
 
 int cvx_t2s_decode_steps_scored(const cvx_t2s_decoder* dec, const cvx_t2s_scoring* scoring, int32_t n_steps, cvx_stream_t stream);
 
+/* Per-dialogue sampling settings and forced prefixes: the step chain of cvx_t2s_decode_steps (scoring == NULL) or of
+ * cvx_t2s_decode_steps_scored (scoring != NULL, checked as there), ending in a sampling kernel that takes its settings, per slot and per
+ * step, from row `d` of a device-resident table - d being the DIALOGUE the slot decodes (slot record [4]), not the slot, so a slot that
+ * the queue refills samples with the new dialogue's settings from its first step.
+ *   table [n_records][8] 32-bit words, one row per dialogue record:
+ *     [0] float inv_temp     1.0f / fmaxf(temperature, 1e-10f) computed in fp32 (the bits cvx_t2s_decode_steps computes from dec->temperature)
+ *     [1] int32 filter_mode  CVX_T2S_FILTER_TOP_K or CVX_T2S_FILTER_TOP_P, chosen per step (block-uniform)
+ *     [2] int32 top_k        [3] float top_p      the setting of that mode, as in cvx_t2s_decoder
+ *     [4] float cfg_scale    read only in the guided pair layout: the even slot combines null + (cond - null) * cfg_scale with ITS dialogue's scale
+ *     [5] int32 prefix_len   P >= 0, below        [6], [7] reserved, 0
+ *   dec->temperature, filter_mode, top_k and top_p are ignored and need not be valid.  dec->cfg_scale keeps only its role as the layout
+ *   switch: > 1 means slot pairs and record pairs (above), and row 2u + 1 of a pair mirrors row 2u (only row 2u is read).  With dec->queue
+ *   and without (slot b then decodes dialogue b and reads row b).
+ *   Prefix: while a slot's position is below P the step is a forced step (Forced dialogues, above) - it reads tokens[..., pos] of the
+ *   dialogue's token row (clamped into [0, vocab)), reads no uniforms, feeds the token's embedding (to both slots of a guided pair), stores
+ *   the token's log-probability when scoring != NULL, and an eos among these tokens does not end the dialogue.  From position P on the step
+ *   samples as cvx_t2s_decode_steps does; uniforms stay indexed by position, so the rows below P are never read.  The forced read exists
+ *   with and without scoring; flag bit 1 (a wholly forced dialogue) is honoured with scoring only, as in cvx_t2s_decode_steps_scored.
+ *   Clamps: stray table values index nothing - the device clamps top_k into [1, vocab], takes an unknown mode as top-k, clamps P into
+ *   [0, step limit] (slot record [5]; [0, max_len] without a queue) and a record number outside the table onto its first / last row.  The
+ *   caller validates what it writes; the device does not report.
+ *   Bit identity: every dialogue gets the tokens and log-probabilities it gets from cvx_t2s_decode_steps(_scored) alone with its row's
+ *   settings in the descriptor - whatever the other rows hold, whichever slot it runs in; a dialogue with prefix P gets from position P on
+ *   what the un-prefixed decode gets when it sampled the same P tokens.
+ * No host synchronisation; graph-capturable.  CVX_EINVAL, nothing launched: struct_size != sizeof(cvx_t2s_per_dialogue), per or table NULL,
+ * n_records < 1, n_records < dec->n_dialogues (when given) or, without a queue, < dec->batch, and everything cvx_t2s_decode_steps(_scored)
+ * refuses apart from the ignored scalars. */
+typedef struct cvx_t2s_per_dialogue {
+    uint32_t struct_size;
+    int32_t n_records;
+    const void* table;
+} cvx_t2s_per_dialogue;
+
+int cvx_t2s_decode_steps_per_dialogue(const cvx_t2s_decoder* dec, const cvx_t2s_scoring* scoring, const cvx_t2s_per_dialogue* per,
+                                      int32_t n_steps, cvx_stream_t stream);
+
 /* Beam search on the decode slots - the deterministic decode behind the reference's beam_search_decode flag, which its generate accepts
  * and never implements (text2semantic.py:673-677): the algorithm below is this library's definition.
  * Per utterance: B = beam_size hypotheses (1 <= B <= 16) in B neighbouring slots; utterance u owns slots [u B, (u + 1) B), and

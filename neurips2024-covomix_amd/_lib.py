@@ -158,6 +158,15 @@ class T2SScoring(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("logprob_len", C.c_int32), ("logprobs", C.c_void_p)]
 
 
+class T2SPerDialogue(C.Structure):
+    """cvx_t2s_per_dialogue: struct_size = sizeof(this); table [n_records, 8] 32-bit words on the device, one row per dialogue record:
+    [0] float inv_temp [1] int32 filter mode [2] int32 top_k [3] float top_p [4] float cfg_scale [5] int32 prefix_len [6], [7] 0"""
+    _fields_ = [("struct_size", C.c_uint32), ("n_records", C.c_int32), ("table", C.c_void_p)]
+
+
+T2S_PER_WORDS = 8                                # 32-bit words per row of that table
+
+
 class T2SBeam(C.Structure):
     """cvx_t2s_beam: struct_size = sizeof(this); device state of the beam chain (include/covomix_hip.h)"""
     _fields_ = [("struct_size", C.c_uint32), ("beam_size", C.c_int32), ("hist_len", C.c_int32), ("backtrack", C.c_int32)] + \
@@ -217,6 +226,8 @@ SIGNATURES = {
     "cvx_mel_log_transpose_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]),
     "cvx_t2s_decode_steps": (C.c_int, [C.POINTER(T2SDecoder), C.c_int32, C.c_void_p]),
     "cvx_t2s_decode_steps_scored": (C.c_int, [C.POINTER(T2SDecoder), C.POINTER(T2SScoring), C.c_int32, C.c_void_p]),
+    "cvx_t2s_decode_steps_per_dialogue": (C.c_int, [C.POINTER(T2SDecoder), C.POINTER(T2SScoring), C.POINTER(T2SPerDialogue), C.c_int32,
+                                                    C.c_void_p]),
     "cvx_t2s_beam_steps": (C.c_int, [C.POINTER(T2SDecoder), C.POINTER(T2SBeam), C.c_int32, C.c_void_p]),
     "cvx_t2s_beam_queue_steps": (C.c_int, [C.POINTER(T2SDecoder), C.POINTER(T2SBeam), C.POINTER(T2SBeamQueue), C.c_int32, C.c_void_p]),
     "cvx_t2s_beam_select_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,

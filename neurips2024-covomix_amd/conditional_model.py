@@ -228,7 +228,7 @@ class CoVoMixModel:
     def synthesis_sample_text2semantic(self, grapheme_token_ids, temprature=1.0, cond_scale=1.0, beam_search_decode=False,
                                        prompt_mel=None, uniforms=None, generator=None, max_length=None, slots=64,
                                        filter_logits_fn="top_k", filter_fn_kwargs=None, return_logprobs=False, best_of=1,
-                                       beam_size=10, length_penalty=1.0):
+                                       beam_size=10, length_penalty=1.0, prefix=None, best_of_temperatures=None):
         """reference conditional_model.py:313-321 -> TextToSemanticWrapper.sample (text2semantic.py:1237-1251): the
         sampled semantic tokens as one flat int64 tensor (two-output models: stream 1 then stream 2) on the input's
         device.  (`temprature` is the reference's spelling.)  `uniforms` / `generator` (optional) fix the U(0,1) draws
@@ -247,19 +247,46 @@ class CoVoMixModel:
         with `beam_size` hypotheses (default 10, the reference's; 1..16) - t2s.generate_beam: deterministic, so `temprature` and
         `filter_*` are unused, and `uniforms`, `generator` or best_of > 1 with it are a ValueError; returns the tokens of the hypothesis with
         the largest cumulative log-probability / (tokens scored) ** length_penalty (or the tuple under return_logprobs; lists run in
-        lock-step waves of 64 // beam_size utterances).  Guided beams (cond_scale > 1) are not built: NotImplementedError."""
+        lock-step waves of 64 // beam_size utterances).  Guided beams (cond_scale > 1) are not built: NotImplementedError.
+        Per-utterance settings (extension; t2s.generate_many(settings=...)): with a LIST of texts, `temprature`, `cond_scale`,
+        `filter_logits_fn` and `filter_fn_kwargs` may each be a list of the same length - utterance j then decodes with entry j, in the same
+        slots and the same captured graph as the others, and gets what it gets alone with those values (lists whose entries are all equal
+        take the scalar path).  Guided and unguided utterances do not share a call (ValueError).
+        prefix (extension): int64 [S, P] tokens the decode continues from (a list, None where an utterance has none, for a list of texts):
+        the result starts with them (t2s.generate_many(prefixes=...)).
+        best_of_temperatures (extension): a sequence of N temperatures - best_of = N with candidate c of every utterance decoded at
+        temperature c, all in the one generate_many call of best_of; a best_of other than 1 or N is a ValueError.
+        None of these combines with beam search (ValueError)."""
         if not self.is_text2semantic:
             raise TypeError("this checkpoint is an acoustic model: use synthesis_sample")
-        assert cond_scale >= 1., "cond_scale >= 1 (text2semantic.py:683)"
-        # text2semantic.py:684: guidance needs a model trained with condition dropping - the checkpoint's `cond_drop_prob`
-        # hyper-parameter (conditional_model.py:52, :78, :114); checkpoints without the key were built with the default 0
-        assert not (cond_scale > 1 and float(self.hparams.get("cond_drop_prob", 0.0)) == 0.0), \
-            ("you need to train with conditional drop probability greater than 0 to use classifier free guidance at inference "
-             "(text2semantic.py:684): this checkpoint's hyper_parameters['cond_drop_prob'] is 0 or absent")
-        from .t2s import best_candidate, check_beam_size, check_best_of, sequence_logprob
         ids = grapheme_token_ids
         many = isinstance(ids, (list, tuple))
+        lists = {k: list(v) for k, v in (("temperature", temprature), ("cond_scale", cond_scale), ("filter_logits_fn", filter_logits_fn),
+                                         ("filter_fn_kwargs", filter_fn_kwargs)) if isinstance(v, (list, tuple))}
+        for k, v in lists.items():
+            if not many or len(v) != len(ids):
+                raise ValueError(f"a list of {k} values goes with a list of texts of the same length ({len(v)} values, "
+                                 f"{len(ids) if many else 'one'} text{'s' if many else ''})")
+        scales = [float(c) for c in lists.get("cond_scale", [cond_scale])]
+        assert all(c >= 1. for c in scales), "cond_scale >= 1 (text2semantic.py:683)"
+        # text2semantic.py:684: guidance needs a model trained with condition dropping - the checkpoint's `cond_drop_prob`
+        # hyper-parameter (conditional_model.py:52, :78, :114); checkpoints without the key were built with the default 0
+        assert not (any(c > 1 for c in scales) and float(self.hparams.get("cond_drop_prob", 0.0)) == 0.0), \
+            ("you need to train with conditional drop probability greater than 0 to use classifier free guidance at inference "
+             "(text2semantic.py:684): this checkpoint's hyper_parameters['cond_drop_prob'] is 0 or absent")
+        if lists.get("temperature") and all(x == lists["temperature"][0] for x in lists["temperature"]):
+            temprature = lists.pop("temperature")[0]
+        if lists.get("cond_scale") and all(x == lists["cond_scale"][0] for x in lists["cond_scale"]):
+            cond_scale = lists.pop("cond_scale")[0]
+        if lists.get("filter_logits_fn") and all(x == lists["filter_logits_fn"][0] for x in lists["filter_logits_fn"]):
+            filter_logits_fn = lists.pop("filter_logits_fn")[0]
+        if lists.get("filter_fn_kwargs") and all(x == lists["filter_fn_kwargs"][0] for x in lists["filter_fn_kwargs"]):
+            filter_fn_kwargs = lists.pop("filter_fn_kwargs")[0]
+        per = bool(lists) or prefix is not None or best_of_temperatures is not None
+        from .t2s import best_candidate, check_beam_size, check_best_of, sequence_logprob
         if beam_search_decode:
+            if per:
+                raise ValueError("beam search takes no per-utterance settings, no prefix and no best_of_temperatures")
             if uniforms is not None or generator is not None:
                 raise ValueError("beam search is deterministic: it takes no uniforms and no generator")
             if not (isinstance(best_of, int) and not isinstance(best_of, bool) and best_of == 1):
@@ -271,8 +298,47 @@ class CoVoMixModel:
             res = self._get_t2s().generate_beam(list(ids) if many else ids, beam_size, max_length, float(length_penalty))
             pick = (lambda r, i: tuple(t.to(i.device) for t in r[:3])) if return_logprobs else (lambda r, i: r[0].to(i.device))
             return [pick(r, i) for r, i in zip(res, ids)] if many else pick(res, ids)
+        if best_of_temperatures is not None:
+            temps = [float(t) for t in best_of_temperatures]
+            if not temps or (best_of != 1 and best_of != len(temps)):
+                raise ValueError(f"best_of_temperatures holds {len(temps)} temperatures: best_of = {best_of!r} disagrees (leave it out)")
+            best_of = len(temps)
         best_of = check_best_of(best_of, len(ids) if many else None, uniforms)
         self._get_t2s()
+        if per:
+            # one generate_many call: dialogue j * N + c is candidate c of utterance j, every dialogue with its own row of settings
+            N, ids_l = best_of, list(ids) if many else [ids]
+            n = len(ids_l)
+            if prefix is None:
+                pres = None
+            elif many != isinstance(prefix, (list, tuple)) or (many and len(prefix) != n):
+                raise ValueError("prefix: one [S, P] tensor for one text, or a list (None: no prefix) as long as the list of texts")
+            else:
+                pres = [p for p in (list(prefix) if many else [prefix]) for _ in range(N)]
+            sets = [{k: v[j] for k, v in lists.items()} for j in range(n)]
+            if "filter_logits_fn" in lists and "filter_fn_kwargs" not in lists and filter_fn_kwargs is not None:
+                sets = [dict(s_, filter_fn_kwargs=filter_fn_kwargs) for s_ in sets]      # (one kwargs dict for every utterance's filter)
+            if best_of_temperatures is not None:
+                sets = [dict(s_, temperature=t) for s_ in sets for t in temps]
+            else:
+                sets = [s_ for s_ in sets for _ in range(N)]
+            us = None
+            if uniforms is not None:
+                us = list(uniforms) if many else [uniforms]
+                us = [u[c] for u in us for c in range(N)] if N > 1 else us
+            res = self._t2s.generate_many([i for i in ids_l for _ in range(N)], us, max_length,
+                                          1.0 if "temperature" in lists else float(temprature), generator, slots=slots,
+                                          cond_scale=max(scales) if "cond_scale" in lists else float(cond_scale),
+                                          filter_logits_fn="top_k" if "filter_logits_fn" in lists else filter_logits_fn,
+                                          filter_fn_kwargs=None if "filter_logits_fn" in lists or "filter_fn_kwargs" in lists else filter_fn_kwargs,
+                                          return_logprobs=bool(return_logprobs) or N > 1, settings=sets, prefixes=pres)
+            eos = self._t2s.d["vocab"] - 1
+            out = []
+            for j, i in enumerate(ids_l):
+                cand = res[j * N:(j + 1) * N]
+                r = cand[best_candidate([sequence_logprob(c[2], c[1], eos) for c in cand])] if N > 1 else cand[0]
+                out.append(tuple(t.to(i.device) for t in r) if return_logprobs else r[0].to(i.device))
+            return out if many else out[0]
         if best_of > 1:
             # candidate c of utterance j is dialogue j * N + c of one generate_many call: its own draws, the slots shared by all of them
             N, ids_l = best_of, list(ids) if many else [ids]

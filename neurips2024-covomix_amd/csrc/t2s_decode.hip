@@ -22,6 +22,8 @@
 //                       caller-supplied U(0,1) draws, eos bookkeeping (:803-818), and the embedding of the sampled ids = next step's input.
 //                       Its LOGP instantiations (cvx_t2s_decode_steps_scored) also store the log-probability of the step's token and honour
 //                       FORCED dialogues, which read given tokens instead of sampling (teacher-forced scoring).
+//   sample_per_kernel   sample_kernel with temperature, filter, guidance scale and a forced prefix length read per step from a table row of
+//                       the DIALOGUE the slot decodes (cvx_t2s_decode_steps_per_dialogue): utterances with different settings share the slots.
 // BEAM SEARCH (cvx_t2s_beam_steps; the algorithm: include/covomix_hip.h): the B hypotheses of an utterance sit in B neighbouring slots and
 // continue from each other's KV caches through an ancestry table - no cache row is ever copied:
 //   attn_owner_kernel      attn_kernel's body with key / value j read from the cache of slot owner[j] (the row staged in LDS);
@@ -859,6 +861,147 @@ __global__ __launch_bounds__(1024) void sample_kernel(const SampleArgs a)
     sample_body<1024, FILT, LOGP>(a, blockIdx.x, lg, ex, bv, bi, &chosen);
 }
 
+// ---------------------------------------------------------------- per-dialogue settings and forced prefixes
+// (cvx_t2s_decode_steps_per_dialogue).  A SIBLING of sample_body, not a flag on it: sharing a body can move the schedule of the existing
+// instantiations (row_expsum above), and those stay as they are.  What differs from sample_body:
+//   - inverse temperature, filter mode, top_k, top_p and the guidance scale come from the settings row of the DIALOGUE the slot decodes
+//     (slot record [4]), so a refilled slot picks up the new dialogue's settings because it now names that dialogue;
+//   - the filter is chosen at run time (block-uniform): a branch around the two sample_select forms, the second LDS array always present;
+//   - prefix_len P: while pos < P the step is a forced step - the token comes from the dialogue's token row (clamped into [0, V)), no
+//     uniforms are read, its eos does not end the dialogue - in BOTH instantiations; from P on the step samples, uniforms indexed by pos.
+// Everything else - eos bookkeeping, the refill from the queue, the guided pair's mirroring - is sample_body's, statement for statement.
+struct PerArgs {
+    const int* table;        // [n_records][PER_WORDS] 32-bit words: [0] float inv_temp [1] int filter mode [2] int top_k [3] float top_p
+                             //                                     [4] float cfg_scale [5] int prefix_len [6], [7] reserved
+    int n_records;
+};
+constexpr int PER_WORDS = 8;
+
+template <int NT, bool LOGP>
+__device__ __forceinline__ void sample_body_per(const SampleArgs& a, const PerArgs& p, int b, float* lg, float* ex, float* bv, int* bi, int* chosen)
+{
+    const int tid = threadIdx.x;
+    const bool cfg = a.cfg_scale > 1.0f;            // the launch's LAYOUT (slot pairs); the scale itself is the dialogue's
+    if (cfg && (b & 1)) return;
+    int* const state = a.state + SR * b;
+    const int pos = aloadi(state);
+    if (pos >= a.max_len) return;
+    const int64_t dlg = aloadi(state + 4);
+    // the dialogue's settings (block-uniform: every thread reads the same row).  A stray record number reads row 0 / the last row, and
+    // stray values cannot index anything: top_k is clamped into [1, V], an unknown mode is top-k, P is clamped into [0, step limit]
+    const int* const row = p.table + (int64_t)PER_WORDS * min((int64_t)(p.n_records - 1), max((int64_t)0, dlg));
+    const float inv_temp = __int_as_float(row[0]);
+    const bool nucleus = row[1] == FILT_TOP_P;
+    const int top_k = min(a.V, max(1, row[2]));
+    const float top_p = __int_as_float(row[3]);
+    const float scale = __int_as_float(row[4]);
+    const int plim = a.queue ? aloadi(state + 5) : a.max_len;           // (without a queue the slot record's limit is the caller's business)
+    const int P = min(max(plim, 0), max(0, row[5]));
+    const bool forced = LOGP ? (aloadi(state + 6) & 2) != 0 : false;
+    const bool given = forced || pos < P;           // this step reads its token (block-uniform)
+    bool eos = false;
+    for (int s = 0; s < a.streams; ++s) {
+        const float* const lrow = a.logits + ((int64_t)b * a.streams + s) * a.V;
+        const float* const nrow = cfg ? a.logits + ((int64_t)(b + 1) * a.streams + s) * a.V : nullptr;
+        int tok;
+        if (given) {
+            if (LOGP) stage_row<NT>(lrow, nrow, scale, a.V, lg);
+            tok = (int)min((int64_t)(a.V - 1), max((int64_t)0, a.tokens[(dlg * a.streams + s) * a.max_len + pos]));
+        } else {
+            const float* const urow = a.uniforms + ((dlg * a.uniform_steps + pos) * a.streams + s) * a.V;
+            if (nucleus) tok = sample_select<NT, FILT_TOP_P, false>(lrow, nrow, scale, urow, a.V, top_k, top_p, inv_temp, nullptr, lg, ex, bv, bi, chosen);
+            else tok = sample_select<NT, FILT_TOP_K, false>(lrow, nrow, scale, urow, a.V, top_k, top_p, inv_temp, nullptr, lg, ex, bv, bi, chosen);
+            if (tid == 0) a.tokens[(dlg * a.streams + s) * a.max_len + pos] = tok;
+        }
+        if (LOGP) {
+            const float lp = row_logprob<NT>(lg, a.V, tok, ex, bv);
+            if (tid == 0) a.logprobs[(dlg * a.streams + s) * a.max_len + pos] = lp;
+        }
+        eos = eos || (tok == a.eos_id && !given);   // (an eos that was given - forced or inside the prefix - ends nothing)
+        for (int d = tid; d < a.dim_emb; d += NT) {
+            const float e = a.emb[(int64_t)tok * a.dim_emb + d];
+            a.x[((int64_t)b * a.streams + s) * a.dim_emb + d] = e;
+            if (cfg) a.x[((int64_t)(b + 1) * a.streams + s) * a.dim_emb + d] = e;
+        }
+        if (cfg && tid == 0) a.tokens[((dlg + 1) * a.streams + s) * a.max_len + pos] = tok;
+        __syncthreads();
+    }
+    if (a.queue == nullptr) {
+        if (LOGP && forced) {
+            if (tid == 0) {
+                const bool last = pos + 1 >= aloadi(state + 5);
+                const int np = last ? a.max_len : pos + 1;
+                if (last) { state[1] = 1; state[2] = pos + 1; }
+                state[0] = np;
+                if (cfg) { int* const sn = state + SR; if (last) { sn[1] = 1; sn[2] = pos + 1; } sn[0] = np; }
+            }
+            return;
+        }
+        if (tid == 0) {
+            int done = aloadi(state + 1), len = aloadi(state + 2);
+            if (eos && done == 0) { done = 1; len = pos + 1; state[1] = 1; state[2] = len; }
+            state[0] = pos + 1;
+            if (cfg) { int* const sn = state + SR; sn[1] = done; sn[2] = len; sn[0] = pos + 1; }
+        }
+        return;
+    }
+    int* const sn = state + SR;
+    const bool ends_eos = eos && !(aloadi(state + 6) & 1);             // (`eos` already leaves out the given tokens)
+    const bool ends = ends_eos || pos + 1 >= aloadi(state + 5);
+    if (!ends) {
+        if (tid == 0) { state[0] = pos + 1; if (cfg) sn[0] = pos + 1; }
+        return;
+    }
+    if (tid == 0) {
+        int* const dr = a.dialogues + SR * dlg;
+        dr[4] = pos + 1;
+        dr[5] = b;
+        if (cfg) { dr[SR + 4] = pos + 1; dr[SR + 5] = b + 1; }
+        __threadfence();
+        dr[3] = ends_eos ? 2 : 3;
+        if (cfg) dr[SR + 3] = ends_eos ? 2 : 3;
+        const int take = cfg ? 2 : 1;
+        const int nxt = atomicAdd(a.queue, take);
+        *chosen = nxt + take - 1 < aloadi(a.queue + 1) ? nxt : -1;
+    }
+    __syncthreads();
+    const int nxt = *chosen;
+    if (nxt < 0) {
+        if (tid == 0) {
+            state[0] = a.max_len; state[1] = 1;
+            if (cfg) { sn[0] = a.max_len; sn[1] = 1; }
+        }
+        return;
+    }
+    for (int d = tid; d < a.dim_emb * a.streams; d += NT) {
+        const float e = a.start[d];
+        a.x[(int64_t)b * a.streams * a.dim_emb + d] = e;
+        if (cfg) a.x[(int64_t)(b + 1) * a.streams * a.dim_emb + d] = e;
+    }
+    if (tid == 0) {
+        int* const dn = a.dialogues + SR * nxt;
+        state[0] = 0; state[1] = 0; state[2] = 0; state[3] = dn[0]; state[4] = nxt; state[5] = dn[1]; state[6] = dn[2];
+        dn[5] = b;
+        dn[3] = 1;
+        if (cfg) {
+            sn[0] = 0; sn[1] = 0; sn[2] = 0; sn[3] = dn[SR + 0]; sn[4] = nxt + 1; sn[5] = dn[1]; sn[6] = dn[2];
+            dn[SR + 5] = b + 1;
+            dn[SR + 3] = 1;
+        }
+    }
+}
+
+template <bool LOGP>
+__global__ __launch_bounds__(1024) void sample_per_kernel(const SampleArgs a, const PerArgs p)
+{
+    __shared__ __attribute__((aligned(16))) float lg[1024];
+    __shared__ __attribute__((aligned(16))) float ex[1024];
+    __shared__ float bv[16];
+    __shared__ int bi[16];
+    __shared__ int chosen;
+    sample_body_per<1024, LOGP>(a, p, blockIdx.x, lg, ex, bv, bi, &chosen);
+}
+
 // the log-prob epilogue alone: one block per row, no slot state (cvx_t2s_logprob_f32)
 __global__ __launch_bounds__(1024) void logprob_rows_kernel(const float* logits, const int64_t* tokens, int V, float* out)
 {
@@ -1392,7 +1535,8 @@ extern "C" int cvx_t2s_sample_f32(const float* logits, const float* uniforms, in
     return CVX_OK;
 }
 
-static int t2s_validate(const cvx_t2s_decoder* d, int32_t n_steps)
+// per_dialogue (cvx_t2s_decode_steps_per_dialogue): the sampling scalars of the descriptor are ignored and need not be valid
+static int t2s_validate(const cvx_t2s_decoder* d, int32_t n_steps, bool per_dialogue = false)
 {
     CVX_REQUIRE(d && d->layers && n_steps >= 0, "t2s_decode: null decoder");
     CVX_REQUIRE(d->dim > 0 && d->dim % 4 == 0 && d->dim <= T2S_MAX_DIM && d->inner == d->heads * 64 && d->depth > 0 &&
@@ -1400,7 +1544,7 @@ static int t2s_validate(const cvx_t2s_decoder* d, int32_t n_steps)
                 (d->streams == 1 || d->dim <= 1024) && d->vocab > 0 && d->vocab <= 1024 &&
                 d->ff_inner > 0 && d->ff_inner_pad >= d->ff_inner && d->ff_inner_pad % 4 == 0 && d->ff_inner_pad <= T2S_MAX_DIM &&
                 d->n_ctx >= 0 && d->n_ctx <= T2S_MAX_KEYS && d->max_len > 0 && d->max_len <= T2S_MAX_KEYS &&
-                d->temperature >= 0.f && d->batch >= 1 && d->batch <= T2S_MAX_BATCH &&
+                (per_dialogue || d->temperature >= 0.f) && d->batch >= 1 && d->batch <= T2S_MAX_BATCH &&
                 d->uniform_steps > 0 &&
                 d->ctx_rows > 0 && d->ctx_rows <= T2S_MAX_KEYS && d->n_ctx <= d->ctx_rows,
                 "t2s_decode: bad dimensions (dim=%d inner=%d heads=%d streams=%d dim_emb=%d vocab=%d ff=%d/%d n_ctx=%d/%d max_len=%d batch=%d)",
@@ -1415,8 +1559,10 @@ static int t2s_validate(const cvx_t2s_decoder* d, int32_t n_steps)
                 "t2s_decode: a dialogue queue under guidance holds record PAIRS (text context, null context): n_dialogues = %d must be "
                 "the even, positive number of records", d->n_dialogues);
     CVX_REQUIRE(d->n_dialogues >= 0, "t2s_decode: n_dialogues = %d", d->n_dialogues);
-    const int frc = t2s_filter_validate(d->filter_mode, d->top_k, d->top_p, d->vocab);
-    if (frc != CVX_OK) return frc;
+    if (!per_dialogue) {
+        const int frc = t2s_filter_validate(d->filter_mode, d->top_k, d->top_p, d->vocab);
+        if (frc != CVX_OK) return frc;
+    }
     CVX_REQUIRE(d->final_gamma && d->emb && d->rope_cos && d->rope_sin && d->uniforms && d->x && d->q && d->att && d->h &&
                 d->logits && d->tokens && d->state, "t2s_decode: null buffer");
     for (int l = 0; l < d->depth; ++l) {
@@ -1447,8 +1593,9 @@ static BeamArgs beam_args(const cvx_t2s_decoder* d, const cvx_t2s_beam* bm)
 // the step chain of cvx_t2s_decode_steps (logprobs == NULL) and cvx_t2s_decode_steps_scored: they differ in the sampling kernel only.
 // bm (cvx_t2s_beam_steps): the self-attention reads through the ancestry table, and the shortlist + merge kernels stand in for the sampling
 // kernel - one launch more per step; every other launch is the same.  bq (cvx_t2s_beam_queue_steps): the merge that refills its group.
+// per (cvx_t2s_decode_steps_per_dialogue): the sampling kernel that reads its settings from the per-dialogue table.
 static int t2s_decode_run(const cvx_t2s_decoder* d, int32_t n_steps, float* logprobs, cvx_stream_t s, const cvx_t2s_beam* bm = nullptr,
-                          const BeamQueueArgs* bq = nullptr)
+                          const BeamQueueArgs* bq = nullptr, const PerArgs* per = nullptr)
 {
     hipStream_t st = cvx_hip_stream(s);
     const float scale = 0.125f;        // dim_head ** -0.5
@@ -1508,6 +1655,11 @@ static int t2s_decode_run(const cvx_t2s_decoder* d, int32_t n_steps, float* logp
         SampleArgs sa{d->logits, d->uniforms, d->emb, d->x, d->tokens, d->state, d->queue, d->dialogues, d->start, nb, d->uniform_steps,
                       d->vocab, d->dim_emb, d->streams, d->max_len, d->top_k, d->vocab - 1, 1.0f / fmaxf(d->temperature, 1e-10f),
                       d->cfg_scale, d->top_p, logprobs};
+        if (per) {
+            if (logprobs) hipLaunchKernelGGL(sample_per_kernel<true>, dim3((unsigned)nb), dim3(1024), 0, st, sa, *per);
+            else hipLaunchKernelGGL(sample_per_kernel<false>, dim3((unsigned)nb), dim3(1024), 0, st, sa, *per);
+            continue;
+        }
         if (logprobs) {
             if (d->filter_mode == CVX_T2S_FILTER_TOP_P) hipLaunchKernelGGL((sample_kernel<FILT_TOP_P, true>), dim3((unsigned)nb), dim3(1024), 0, st, sa);
             else hipLaunchKernelGGL((sample_kernel<FILT_TOP_K, true>), dim3((unsigned)nb), dim3(1024), 0, st, sa);
@@ -1535,6 +1687,27 @@ extern "C" int cvx_t2s_decode_steps_scored(const cvx_t2s_decoder* d, const cvx_t
     CVX_REQUIRE(sc->logprob_len == d->max_len, "t2s_decode_scored: logprob_len = %d, the rows of logprobs are laid out like those of tokens "
                 "(max_len = %d floats)", sc->logprob_len, d->max_len);
     return t2s_decode_run(d, n_steps, sc->logprobs, s);
+}
+
+extern "C" int cvx_t2s_decode_steps_per_dialogue(const cvx_t2s_decoder* d, const cvx_t2s_scoring* sc, const cvx_t2s_per_dialogue* per,
+                                                 int32_t n_steps, cvx_stream_t s)
+{
+    CVX_REQUIRE(per && per->struct_size == sizeof(cvx_t2s_per_dialogue),
+                "t2s_decode_per_dialogue: cvx_t2s_per_dialogue.struct_size = %u, this library knows %u", per ? per->struct_size : 0u,
+                (unsigned)sizeof(cvx_t2s_per_dialogue));
+    CVX_REQUIRE(per->table && per->n_records >= 1, "t2s_decode_per_dialogue: null table or n_records = %d < 1", per->n_records);
+    CVX_REQUIRE(!sc || sc->struct_size == sizeof(cvx_t2s_scoring), "t2s_decode_per_dialogue: cvx_t2s_scoring.struct_size = %u, this library knows %u",
+                sc ? sc->struct_size : 0u, (unsigned)sizeof(cvx_t2s_scoring));
+    CVX_REQUIRE(!sc || sc->logprobs, "t2s_decode_per_dialogue: null logprobs");
+    const int rc = t2s_validate(d, n_steps, true);
+    if (rc != CVX_OK) return rc;
+    CVX_REQUIRE(!sc || sc->logprob_len == d->max_len, "t2s_decode_per_dialogue: logprob_len = %d, the rows of logprobs are laid out like those "
+                "of tokens (max_len = %d floats)", sc ? sc->logprob_len : 0, d->max_len);
+    // every record a slot can name has a row: the n_dialogues behind a queue; without one, slot b decodes dialogue b
+    CVX_REQUIRE(per->n_records >= d->n_dialogues && (d->queue || per->n_records >= d->batch),
+                "t2s_decode_per_dialogue: n_records = %d rows for %d dialogue records / %d slots", per->n_records, d->n_dialogues, d->batch);
+    const PerArgs pa{static_cast<const int*>(per->table), per->n_records};
+    return t2s_decode_run(d, n_steps, sc ? sc->logprobs : nullptr, s, nullptr, nullptr, &pa);
 }
 
 extern "C" int cvx_t2s_beam_steps(const cvx_t2s_decoder* d, const cvx_t2s_beam* bm, int32_t n_steps, cvx_stream_t s)

@@ -82,6 +82,8 @@ def build_parser() -> ArgumentParser:
     p.add_argument("--t2s_top_k", type=int, default=None, help="extension: an explicit k for --t2s_filter top_k (overrides the thres)")
     p.add_argument("--t2s_best_of", type=int, default=1, help="extension: decode this many candidates per turn through the continuously "
                    "refilled slots and keep the one the model finds most likely (largest mean token log-probability; 1 = off: today's files)")
+    p.add_argument("--t2s_best_of_temperatures", type=str, default=None, help="extension: T1,T2,... - --t2s_best_of with one temperature per "
+                   "candidate: candidate c of every turn is decoded at temperature c (implies --t2s_best_of = their number)")
     p.add_argument("--t2s_beam_size", type=int, default=0, help="extension: beam search with this many hypotheses per turn (1..16) instead of "
                    "sampling - deterministic: no draws, temperature and filter unused; not together with --t2s_best_of > 1 or guidance "
                    "(0 = off: sampling, today's files)")
@@ -202,6 +204,14 @@ def t2s_sampling_kwargs(args) -> dict:
         raise ValueError(f"--t2s_best_of {best_of}: at least 1")
     if best_of > 1:
         kw["best_of"] = best_of
+    if getattr(args, "t2s_best_of_temperatures", None):
+        temps = tuple(float(t) for t in str(args.t2s_best_of_temperatures).split(",") if t.strip())
+        if not temps or any(not t >= 0.0 for t in temps):
+            raise ValueError(f"--t2s_best_of_temperatures {args.t2s_best_of_temperatures}: a comma-separated list of temperatures >= 0")
+        if best_of > 1 and best_of != len(temps):
+            raise ValueError(f"--t2s_best_of {best_of} disagrees with the {len(temps)} --t2s_best_of_temperatures")
+        kw["best_of_temperatures"] = temps
+        best_of = len(temps)
     beam = int(getattr(args, "t2s_beam_size", 0))
     if beam:
         if not 1 <= beam <= 16:
@@ -218,18 +228,79 @@ def _candidate_salt(c: int) -> int:
     return 1 if c == 0 else 0x100 + int(c)
 
 
-def _predict_turns(work, t2s, device, seed: int, slots: int = 64, sampling=None) -> dict:
+T2S_SIDE_FIELDS = ("temperature", "filter", "filter_thres", "top_k", "cond_scale")
+
+
+def _turn_side_files(text_dir, name: str, k: int, src):
+    """The optional side files of one text turn -> (settings dict or None, prefix tokens or None).
+    `<stem>.t2s.json`: any of temperature, filter ("top_k" / "top_p"), filter_thres, top_k, cond_scale for this turn - they override the
+    --t2s_* flags.  `<stem>.prefix.semantic.npy`: tokens the turn's decode continues from, in the layout of `<name>.semantic.npy` (flat:
+    stream 1 then stream 2 on a two-output model, equally long).  <stem> is the turn's own file stem - `<name>.turn<k>` for a turn file,
+    `<name>` for a whole-utterance file; the turns of a `<name>.txt` look for `<name>.turn<k>.*` and then take the utterance's
+    `<name>.t2s.json` (the prefix `<name>.prefix.semantic.npy` goes to turn 0 only)."""
+    kind, v = src
+    if kind == "ids":
+        stems = [(v[:-len(".text_ids.npy")], True)]
+    elif text_dir is None:
+        return None, None
+    else:
+        stems = [(os.path.join(text_dir, f"{name}.turn{k}"), True), (os.path.join(text_dir, name), k == 0)]
+    settings = prefix = None
+    for stem, with_prefix in stems:
+        if settings is None and os.path.isfile(stem + ".t2s.json"):
+            with open(stem + ".t2s.json", "r", encoding="utf-8") as f:
+                settings = json.load(f)
+            unknown = sorted(set(settings) - set(T2S_SIDE_FIELDS)) if isinstance(settings, dict) else ["(not an object)"]
+            if unknown:
+                raise ValueError(f"{stem}.t2s.json: unknown fields {unknown}; known: {list(T2S_SIDE_FIELDS)}")
+        if prefix is None and with_prefix and os.path.isfile(stem + ".prefix.semantic.npy"):
+            prefix = np.load(stem + ".prefix.semantic.npy").astype(np.int64)
+    return settings, prefix
+
+
+def _turn_sampling(sampling: dict, side) -> dict:
+    """The facade keywords of ONE turn: the --t2s_* flags (t2s_sampling_kwargs) overridden by the turn's `.t2s.json`.  A filter named in
+    the side file drops the flags' thres / k of ANOTHER filter."""
+    kw = {k: sampling[k] for k in ("temprature", "cond_scale", "filter_logits_fn", "filter_fn_kwargs") if k in sampling}
+    side = side or {}
+    if "temperature" in side:
+        kw["temprature"] = float(side["temperature"])
+    if "cond_scale" in side:
+        kw["cond_scale"] = float(side["cond_scale"])
+    fkw = dict(kw.get("filter_fn_kwargs") or {})
+    if "filter" in side:
+        if side["filter"] not in ("top_k", "top_p"):
+            raise ValueError(f"t2s.json: filter must be 'top_k' or 'top_p', got {side['filter']!r}")
+        if side["filter"] != kw.get("filter_logits_fn", "top_k"):
+            fkw = {}
+        kw["filter_logits_fn"] = side["filter"]
+    if "filter_thres" in side:
+        fkw["thres"] = float(side["filter_thres"])
+    if "top_k" in side:
+        if kw.get("filter_logits_fn", "top_k") != "top_k":
+            raise ValueError("t2s.json: top_k goes with filter top_k")
+        fkw["k"] = int(side["top_k"])
+    kw["filter_fn_kwargs"] = fkw or None
+    return kw
+
+
+def _predict_turns(work, t2s, device, seed: int, slots: int = 64, sampling=None, text_dir=None) -> dict:
     """(name, turn) -> predicted semantic tokens (int64 numpy).  work: list of (name, turn, source).  Sources that are
     already tokens are read; the others are decoded by text2semantic on the GPU through `slots` decode slots, every turn
     with its OWN stream of uniforms (seeded from (--seed, name, turn)): the tokens do not depend on batching or ranks.
-    sampling: the --t2s_* flags as keywords (t2s_sampling_kwargs)."""
-    out, todo = {}, []
+    sampling: the --t2s_* flags as keywords (t2s_sampling_kwargs).  text_dir: where the turns' optional side files live
+    (_turn_side_files): per-turn settings and prefixes - the turns still share the slots (t2s.generate_many(settings=, prefixes=));
+    guided and unguided turns run as two calls.  Without side files nothing changes."""
+    out, todo, side = {}, [], {}
     for name, k, (kind, v) in work:
         if kind == "sem":
             out[(name, k)] = np.load(v).astype(np.int64)
         else:
             ids = torch.from_numpy(np.load(v).astype(np.int64)).reshape(1, -1) if kind == "ids" else _tokenize(v)
             todo.append((name, k, ids))
+            st, pre = _turn_side_files(text_dir, name, k, (kind, v))
+            if st is not None or pre is not None:
+                side[(name, k)] = (st, pre)
     if todo and t2s is None:
         raise RuntimeError("text sources need --t2s_ckpt")
     if todo:
@@ -242,6 +313,8 @@ def _predict_turns(work, t2s, device, seed: int, slots: int = 64, sampling=None)
         dec = t2s._get_t2s()
         S, V, L = dec.d["streams"], dec.d["vocab"], dec.max_length
         best_of = int((sampling or {}).get("best_of", 1))
+        if (sampling or {}).get("best_of_temperatures"):
+            best_of = len(sampling["best_of_temperatures"])
         win = max(1, WINDOW // best_of)
         for w in range(0, len(todo), win):
             part = todo[w:w + win]
@@ -257,10 +330,33 @@ def _predict_turns(work, t2s, device, seed: int, slots: int = 64, sampling=None)
                     g = torch.Generator(device=device).manual_seed(_stable_seed(seed, name, k, _candidate_salt(c)))
                     draws.append(torch.rand(L, S, V, device=device, generator=g))
                 uniforms.append(draws[0] if best_of == 1 else torch.stack(draws))
-            toks = t2s.synthesis_sample_text2semantic([ids.to(device) for _, _, ids in part], uniforms=uniforms, slots=slots,
-                                                      **(sampling or {}))
-            for (name, k, _), t in zip(part, toks):
-                out[(name, k)] = t.cpu().numpy().astype(np.int64)
+            if not any((name, k) in side for name, k, _ in part):
+                toks = t2s.synthesis_sample_text2semantic([ids.to(device) for _, _, ids in part], uniforms=uniforms, slots=slots,
+                                                          **(sampling or {}))
+                for (name, k, _), t in zip(part, toks):
+                    out[(name, k)] = t.cpu().numpy().astype(np.int64)
+                continue
+            # turns with side files: every turn's own keywords as lists; guided and unguided turns do not share a launch - two calls
+            per = [_turn_sampling(sampling or {}, side.get((name, k), (None, None))[0]) for name, k, _ in part]
+            rest = {k_: v for k_, v in (sampling or {}).items() if k_ not in ("temprature", "cond_scale", "filter_logits_fn", "filter_fn_kwargs")}
+            for guided in (False, True):
+                sel = [i for i, kw_ in enumerate(per) if (kw_.get("cond_scale", 1.0) > 1.0) == guided]
+                if not sel:
+                    continue
+                pres = []
+                for i in sel:
+                    pre = side.get((part[i][0], part[i][1]), (None, None))[1]
+                    if pre is not None and (pre.ndim > 2 or pre.size == 0 or pre.size % S or (pre.ndim == 2 and pre.shape[0] != S)):
+                        raise ValueError(f"{part[i][0]} turn {part[i][1]}: the prefix holds {pre.shape} tokens for {S} stream(s) of equal length")
+                    pres.append(None if pre is None else torch.from_numpy(pre.reshape(S, -1)))
+                toks = t2s.synthesis_sample_text2semantic([part[i][2].to(device) for i in sel], uniforms=[uniforms[i] for i in sel], slots=slots,
+                                                          temprature=[per[i].get("temprature", 1.0) for i in sel],
+                                                          cond_scale=[per[i].get("cond_scale", 1.0) for i in sel],
+                                                          filter_logits_fn=[per[i].get("filter_logits_fn", "top_k") for i in sel],
+                                                          filter_fn_kwargs=[per[i]["filter_fn_kwargs"] for i in sel],
+                                                          prefix=pres if any(p_ is not None for p_ in pres) else None, **rest)
+                for i, t in zip(sel, toks):
+                    out[(part[i][0], part[i][1])] = t.cpu().numpy().astype(np.int64)
     return out
 
 
@@ -304,6 +400,8 @@ def utterance_plan(text_dir: str, dialogue: bool, mode: str, have_t2s: bool, wor
     for ext in (".semantic.npy",) + ((".text_ids.npy", ".txt") if have_t2s else ()):
         for p in glob.glob(os.path.join(text_dir, "*" + ext)):
             stem = os.path.basename(p)[: -len(ext)]
+            if ext == ".semantic.npy" and stem.endswith(".prefix"):      # a turn's prefix (_turn_side_files), not an utterance
+                continue
             if multi_turn and ".turn" in stem and stem.rsplit(".turn", 1)[1].isdigit():
                 stem = stem.rsplit(".turn", 1)[0]
             stems.add(stem)
@@ -492,12 +590,12 @@ def run(dialogue: bool, argv=None) -> int:
     batch_log: list = []                     # (utterances, frames in the launch, generated frames, seconds) per batch -> last_stats
     load_s = 0.0
     if mode == "off":       # ---- text2semantic for this rank's utterances first (not timed, as in round 4), then ONE global packing
-        pred = _predict_turns(work, t2s, device, args.seed, sampling=t2s_kw)
+        pred = _predict_turns(work, t2s, device, args.seed, sampling=t2s_kw, text_dir=args.text_dir)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     batch_log_t[0] = t0
     if mode == "batch":     # ---- every turn of this rank through the continuously batched decode (timed), then ONE global packing
-        pred = _predict_turns(work, t2s, device, args.seed, sampling=t2s_kw)
+        pred = _predict_turns(work, t2s, device, args.seed, sampling=t2s_kw, text_dir=args.text_dir)
     head_start = not two_stage and len(mine) >= 2 * HEAD_START
     if head_start:
         # ---- a large directory: the model inputs of the first HEAD_START utterances are read, their fullest first-fit-decreasing bin
@@ -551,7 +649,7 @@ def run(dialogue: bool, argv=None) -> int:
                     else:
                         keep += b
                 pool = [pool[i] for i in sorted(keep)]
-        nfr = pl.run_two_stage(groups, lambda g: _predict_turns(g, t2s, device, args.seed, sampling=t2s_kw), solve, device,
+        nfr = pl.run_two_stage(groups, lambda g: _predict_turns(g, t2s, device, args.seed, sampling=t2s_kw, text_dir=args.text_dir), solve, device,
                                overlap=(mode == "on"), collate=collate)
         frames = sum(nfr)
     drain()

@@ -31,7 +31,8 @@ both, so q.k is unchanged) maps one onto the other - done once here at load time
 import ctypes as C
 import math
 import os
-from typing import Dict, Optional
+from collections.abc import Mapping
+from typing import Dict, NamedTuple, Optional
 
 import torch
 
@@ -170,6 +171,114 @@ def check_targets(targets, streams: int, vocab: int, max_length: int) -> list:
     return out
 
 
+class UtteranceSettings(NamedTuple):
+    """Sampling settings of ONE utterance of generate_many(settings=...): every field left None takes the call's scalar argument."""
+    temperature: Optional[float] = None
+    filter_logits_fn: Optional[object] = None
+    filter_fn_kwargs: Optional[dict] = None
+    cond_scale: Optional[float] = None
+
+
+SETTING_FIELDS = UtteranceSettings._fields
+
+
+def check_settings(settings, n: int, vocab: int, streams: int = 1, temperature: float = 1.0, filter_logits_fn="top_k", filter_fn_kwargs=None,
+                   cond_scale: float = 1.0) -> list:
+    """The per-utterance settings of generate_many resolved against the call's scalars: -> n tuples (temperature, (mode, k, thres),
+    cond_scale).  settings: n entries, each None (the scalars apply), a mapping or a record with any of the fields of UtteranceSettings
+    (an absent or None field takes the scalar; a filter_logits_fn without filter_fn_kwargs takes that filter's defaults, not the call's
+    kwargs of another filter).  ValueError for another length, an unknown field, a temperature < 0 (or NaN), whatever `filter_setting`
+    refuses, a cond_scale <= 1 in a guided call (the call's cond_scale > 1) and a cond_scale other than 1 in an unguided call: the slot-pair
+    layout of guidance belongs to the launch, so guided and unguided utterances do not share one - make two calls.  NotImplementedError for
+    guidance on a two-output model, as everywhere.  Pure host code."""
+    settings = list(settings)
+    if len(settings) != n:
+        raise ValueError(f"settings: {len(settings)} entries for {n} utterances")
+    guided = float(cond_scale) > 1.0
+    if guided and streams != 1:
+        raise NotImplementedError("guidance (cond_scale > 1) on a two-output model: the reference cannot run it (generate_batch)")
+    out = []
+    for j, e in enumerate(settings):
+        if e is None:
+            e = {}
+        elif isinstance(e, Mapping):
+            e = dict(e)
+        elif hasattr(e, "_asdict"):
+            e = e._asdict()
+        else:
+            e = {f: getattr(e, f) for f in SETTING_FIELDS if hasattr(e, f)}
+        unknown = sorted(set(e) - set(SETTING_FIELDS))
+        if unknown:
+            raise ValueError(f"settings[{j}]: unknown fields {unknown}; known: {list(SETTING_FIELDS)}")
+        t = float(temperature if e.get("temperature") is None else e["temperature"])
+        if not t >= 0.0:
+            raise ValueError(f"settings[{j}]: temperature = {t} must be >= 0")
+        if e.get("filter_logits_fn") is not None:
+            fn, kw = e["filter_logits_fn"], e.get("filter_fn_kwargs")
+        else:
+            fn, kw = filter_logits_fn, (filter_fn_kwargs if e.get("filter_fn_kwargs") is None else e["filter_fn_kwargs"])
+        try:
+            filt = filter_setting(fn, kw, vocab)
+        except ValueError as err:
+            raise ValueError(f"settings[{j}]: {err}") from None
+        c = float(cond_scale if e.get("cond_scale") is None else e["cond_scale"])
+        if guided and not c > 1.0:
+            raise ValueError(f"settings[{j}]: cond_scale = {c} in a guided call (cond_scale > 1): guided and unguided utterances do not share "
+                             "a launch - make two calls")
+        if not guided and c != 1.0:
+            if c > 1.0 and streams != 1:
+                raise NotImplementedError("guidance (cond_scale > 1) on a two-output model: the reference cannot run it (generate_batch)")
+            raise ValueError(f"settings[{j}]: cond_scale = {c} in an unguided call (cond_scale = 1): guided and unguided utterances do not "
+                             "share a launch - make two calls")
+        out.append((t, filt, c))
+    return out
+
+
+def settings_rows(resolved, prefix_lens=None) -> torch.Tensor:
+    """The rows of the device's settings table (cvx_t2s_per_dialogue; include/covomix_hip.h) for the tuples of check_settings: int32
+    [n, 8] holding [0] inv_temp = 1 / max(temperature, 1e-10) computed in fp32 - the bits cvx_t2s_decode_steps computes - [1] filter mode
+    [2] top_k [3] top_p [4] cond_scale (fp32 bits) [5] prefix length (default 0) [6], [7] 0."""
+    n = len(resolved)
+    rows = torch.zeros(n, _lib.T2S_PER_WORDS, dtype=torch.int32)
+    if n == 0:
+        return rows
+    f = lambda xs: torch.tensor(xs, dtype=torch.float64).to(torch.float32)       # (python floats round to fp32 as ctypes' c_float does)
+    inv = torch.ones(n, dtype=torch.float32) / torch.maximum(f([r[0] for r in resolved]), torch.tensor(1e-10, dtype=torch.float32))
+    rows[:, 0] = inv.view(torch.int32)
+    rows[:, 1] = torch.tensor([r[1][0] for r in resolved], dtype=torch.int32)
+    rows[:, 2] = torch.tensor([r[1][1] for r in resolved], dtype=torch.int32)
+    rows[:, 3] = f([r[1][2] for r in resolved]).view(torch.int32)
+    rows[:, 4] = f([r[2] for r in resolved]).view(torch.int32)
+    if prefix_lens is not None:
+        rows[:, 5] = torch.tensor([int(x) for x in prefix_lens], dtype=torch.int32)
+    return rows
+
+
+def check_prefixes(prefixes, n: int, streams: int, vocab: int, limits, forced=None) -> list:
+    """The prefixes of generate_many as int64 [S, P] host tensors (None: no prefix).  ValueError for another number of entries, whatever
+    `check_targets` refuses (shape, P < 1, a token outside [0, vocab)), P >= that utterance's step limit (nothing would be left to decode),
+    an eos inside a prefix (continuing past an end is not defined by the reference loop) and a prefix for an utterance that is forced."""
+    prefixes = list(prefixes)
+    if len(prefixes) != n:
+        raise ValueError(f"prefixes: {len(prefixes)} entries for {n} utterances")
+    out: list = [None] * n
+    for j, p in enumerate(prefixes):
+        if p is None:
+            continue
+        if forced is not None and forced[j] is not None:
+            raise ValueError(f"prefix {j}: the utterance is forced - its tokens are all given already")
+        try:
+            t = check_targets([p], streams, vocab, max(int(limits[j]), 1))[0]
+        except ValueError as err:
+            raise ValueError(f"prefix {j}: {err}") from None
+        if t.shape[1] >= int(limits[j]):
+            raise ValueError(f"prefix {j}: length {t.shape[1]} leaves nothing to decode below the step limit {int(limits[j])}")
+        if bool((t == vocab - 1).any()):
+            raise ValueError(f"prefix {j}: holds an eos (token {vocab - 1}); continuing past an end is not defined")
+        out[j] = t
+    return out
+
+
 def _dims(sd: Dict[str, torch.Tensor]) -> dict:
     dim = sd["token_emb.text.weight"].shape[1]
     dim_t = sd["start_token.speech"].shape[0]
@@ -295,7 +404,8 @@ class TextToSemanticDecoder:
                 self._layers[i].kv_c = L["kv_c"].data_ptr()
             self.buf.update(tokens=torch.zeros(dialogues, S, self.max_length, dtype=torch.int64, device=dev),
                             dialogues=torch.zeros(dialogues, SR, dtype=torch.int32, device=dev),
-                            queue=torch.zeros(2, dtype=torch.int32, device=dev))
+                            queue=torch.zeros(2, dtype=torch.int32, device=dev),
+                            per=torch.zeros(dialogues, _lib.T2S_PER_WORDS, dtype=torch.int32, device=dev))
             self.buf.pop("logprobs", None)
             self._dialogues, grown = dialogues, True
         if logprobs and "logprobs" not in self.buf:
@@ -379,10 +489,19 @@ class TextToSemanticDecoder:
             dec.queue, dec.dialogues, dec.start = b["queue"].data_ptr(), b["dialogues"].data_ptr(), self.start.data_ptr()
         return dec
 
-    def _launch_steps(self, temperature: float, batch: int, n: int, cfg_scale: float, queue: bool, filt, nd: int, scored: bool) -> None:
+    def _launch_steps(self, temperature: float, batch: int, n: int, cfg_scale: float, queue: bool, filt, nd: int, scored: bool,
+                      per: bool = False) -> None:
         """n token steps on the current stream.  scored: cvx_t2s_decode_steps_scored (log-probs of every step's token into
-        buf["logprobs"], forced dialogues honoured); else cvx_t2s_decode_steps, exactly as before that entry existed."""
+        buf["logprobs"], forced dialogues honoured); else cvx_t2s_decode_steps, exactly as before that entry existed.
+        per: cvx_t2s_decode_steps_per_dialogue - the settings come from buf["per"], one row per dialogue record; temperature and filt
+        are not looked at and cfg_scale only says whether the slots run in guided pairs."""
         dec = self._descriptor(temperature, batch, cfg_scale, queue, filt, nd)
+        if per:
+            sc = _lib.T2SScoring(C.sizeof(_lib.T2SScoring), self.max_length, self.buf["logprobs"].data_ptr()) if scored else None
+            pd = _lib.T2SPerDialogue(C.sizeof(_lib.T2SPerDialogue), self.buf["per"].shape[0], self.buf["per"].data_ptr())
+            _lib.check(_lib.load().cvx_t2s_decode_steps_per_dialogue(C.byref(dec), C.byref(sc) if scored else None, C.byref(pd), n, ops._stream()),
+                       "cvx_t2s_decode_steps_per_dialogue")
+            return
         if not scored:
             _lib.check(_lib.load().cvx_t2s_decode_steps(C.byref(dec), n, ops._stream()), "cvx_t2s_decode_steps")
             return
@@ -390,9 +509,9 @@ class TextToSemanticDecoder:
         _lib.check(_lib.load().cvx_t2s_decode_steps_scored(C.byref(dec), C.byref(sc), n, ops._stream()), "cvx_t2s_decode_steps_scored")
 
     def _run_steps(self, temperature: float, batch: int, n: int, cfg_scale: float = 1.0, queue: bool = False, filt=None, nd: int = 0,
-                   scored: bool = False) -> None:
+                   scored: bool = False, per: bool = False) -> None:
         """n token steps on the current stream without a graph."""
-        self._launch_steps(temperature, batch, n, cfg_scale, queue, filt, nd, scored)
+        self._launch_steps(temperature, batch, n, cfg_scale, queue, filt, nd, scored, per)
 
     def _uniform_view(self, n: int) -> torch.Tensor:
         """[n, steps, streams, vocab] view of the uniform draws of the first n dialogues"""
@@ -466,19 +585,24 @@ class TextToSemanticDecoder:
             self._pin_ev[pending].synchronize()      # (the helper stream's last copy: the buffers are reused by the next call)
         return self._read_state(nb)
 
-    def _graph(self, temperature: float, batch: int, cfg_scale: float = 1.0, queue: bool = False, filt=None, nd: int = 0, scored: bool = False):
+    def _graph(self, temperature: float, batch: int, cfg_scale: float = 1.0, queue: bool = False, filt=None, nd: int = 0, scored: bool = False,
+               per: bool = False):
         """The captured graph of CHUNK token steps for this (batch, stream CU count, mode, filter, scoring); captured on first use.  (nd, the
         number of dialogue records, is only validated by the C call: it is not part of the key.)  Capturing runs the
         steps once outside the capture (module load, kernel attributes): callers get their graph BEFORE they set up the decode state -
-        the warm-up runs on idle slot records (position max_length: the sampling kernel returns at once, every other kernel clamps)."""
+        the warm-up runs on idle slot records (position max_length: the sampling kernel returns at once, every other kernel clamps).
+        per: the per-dialogue chain, whose settings live in a device table - its key carries a "per" marker INSTEAD of (temperature, scale,
+        filter), so one graph per (batch, CUs, guided?, queue, scored) serves every mix of settings."""
         filt = filt or self._default_filter
         key = (temperature, batch, cfg_scale, ops.stream_cus(), queue, self._gen, filt, bool(scored))   # (the kernels' shape follows the CUs the stream owns)
+        if per:
+            key = ("per", batch, cfg_scale > 1.0, ops.stream_cus(), queue, self._gen, bool(scored))
         g = self._graphs.get(key)
         if g is not None:
             return g
 
         def launch():
-            self._launch_steps(temperature, batch, CHUNK, cfg_scale, queue, filt, nd, scored)
+            self._launch_steps(temperature, batch, CHUNK, cfg_scale, queue, filt, nd, scored, per)
         self.buf["state"].copy_(self._slot_records([]))
         launch()                                       # warm-up outside capture
         cur = torch.cuda.current_stream()
@@ -496,13 +620,13 @@ class TextToSemanticDecoder:
         return g
 
     def _run_chunk(self, temperature: float, batch: int = 1, cfg_scale: float = 1.0, queue: bool = False, filt=None, nd: int = 0,
-                   scored: bool = False) -> None:
+                   scored: bool = False, per: bool = False) -> None:
         """CHUNK token steps on the current stream: a graph replay of the per-launch path (the graph must exist - `_graph` - unless
         CVX_GRAPH=0 asks for plain launches)."""
         if os.environ.get("CVX_GRAPH", "1") != "1":
-            self._run_steps(temperature, batch, CHUNK, cfg_scale, queue, filt, nd, scored)
+            self._run_steps(temperature, batch, CHUNK, cfg_scale, queue, filt, nd, scored, per)
             return
-        self._graph(temperature, batch, cfg_scale, queue, filt, nd, scored).replay()
+        self._graph(temperature, batch, cfg_scale, queue, filt, nd, scored, per).replay()
 
     def _contexts(self, sources, rows=None) -> list:
         """encoder + the cross-attention k/v of the utterances into dialogue rows `rows` (default 0, 1, ...): [null | to_kv(enc)]
@@ -658,7 +782,8 @@ class TextToSemanticDecoder:
     @torch.no_grad()
     def generate_many(self, sources, uniforms=None, max_length: Optional[int] = None, temperature: float = 1.0,
                       generator: Optional[torch.Generator] = None, slots: int = 32, ignore_eos: bool = False, limits=None, on_done=None,
-                      cond_scale: float = 1.0, filter_logits_fn="top_k", filter_fn_kwargs=None, return_logprobs: bool = False, forced=None):
+                      cond_scale: float = 1.0, filter_logits_fn="top_k", filter_fn_kwargs=None, return_logprobs: bool = False, forced=None,
+                      settings=None, prefixes=None):
         """Decode ANY number of utterances through `slots` decode slots with continuous batching: every utterance runs the
         reference's loop (text2semantic.py:749-848) from position 0 to its first eos (:803-818) or its step limit, and the slot it
         ran in takes the next pending utterance in the sampling kernel of that very step (cvx_t2s_decoder.queue) - utterances end
@@ -679,7 +804,19 @@ class TextToSemanticDecoder:
         forced (with return_logprobs; `score_many` is the public form): a list with, per utterance, None (sampled as usual) or int64
         [S, L] tokens to SCORE instead of sampling - a forced dialogue (include/covomix_hip.h): the steps read these tokens, draw no
         uniforms (that utterance's entry of `uniforms` may be None), ignore every eos and stop after L steps whatever `limits` says;
-        its `streams` are the tokens given.  Forced and sampled utterances share the queue and the slots."""
+        its `streams` are the tokens given.  Forced and sampled utterances share the queue and the slots.
+        settings (default None: the call as it always was, graph for graph): one entry per utterance - None, a mapping or an
+        UtteranceSettings with any of temperature, filter_logits_fn, filter_fn_kwargs, cond_scale; what an entry leaves out takes the
+        call's scalar (`check_settings`).  Utterances with different settings share the slots, the queue and ONE captured graph: the
+        sampling kernel reads the settings of the dialogue a slot decodes from a device table (cvx_t2s_decode_steps_per_dialogue), and
+        every utterance gets, bit for bit, what it gets alone with its settings as the call's scalars.  Guided and unguided utterances do
+        not share a call (ValueError): the slot-pair layout belongs to the launch.
+        prefixes (default None): one entry per utterance - None, or int64 [S, P] tokens, 1 <= P < that utterance's step limit, none of
+        them an eos (`check_prefixes`): the decode CONTINUES from them.  They are copied into the utterance's token row; its first P steps
+        read them instead of sampling (no uniforms are read there; the uniforms stay indexed by position), and from position P on it
+        samples as ever - so a prefix cut from an earlier result, with the same uniforms, reproduces the rest of that result.  `streams`
+        starts with the prefix; under return_logprobs the positions below P hold the prefix tokens' teacher-forced log-probs (what
+        score_many gives them).  A prefix for a forced utterance is a ValueError."""
         d = self.d
         S, V = d["streams"], d["vocab"]
         n = len(sources)
@@ -700,6 +837,13 @@ class TextToSemanticDecoder:
         if cfg and S != 1:
             raise NotImplementedError("guidance (cond_scale > 1) on a two-output model: the reference cannot run it (generate_batch)")
         P = 2 if cfg else 1       # dialogue records (and decode slots) per utterance
+        per = settings is not None or prefixes is not None
+        resolved = None
+        if per:                   # (validated for the whole call before any window runs)
+            resolved = check_settings([None] * n if settings is None else settings, n, V, S, temperature, filter_logits_fn, filter_fn_kwargs,
+                                      cond_scale)
+            if prefixes is not None and len(list(prefixes)) != n:
+                raise ValueError(f"prefixes: {len(list(prefixes))} entries for {n} utterances")
         if n == 0:
             return []
         win = WINDOW // P
@@ -710,7 +854,9 @@ class TextToSemanticDecoder:
                                           generator, slots, ignore_eos, None if limits is None else limits[w:w + win],
                                           None if on_done is None else (lambda j, r, w=w: on_done(w + j, r)),
                                           cond_scale, filter_logits_fn, filter_fn_kwargs, return_logprobs,
-                                          None if forced is None else forced[w:w + win])
+                                          None if forced is None else forced[w:w + win],
+                                          None if settings is None else list(settings)[w:w + win],
+                                          None if prefixes is None else list(prefixes)[w:w + win])
             return out
         nb = P * max(1, min(int(slots) // P, MAX_BATCH // P, n))
         nb = nb if nb in (1, 2, 4) else min((nb + 7) // 8 * 8, MAX_BATCH)      # whole kernel groups (idle slots cost nothing)
@@ -728,10 +874,11 @@ class TextToSemanticDecoder:
         if forced is not None:
             lim = [forced[j].shape[1] if is_forced[j] else lim[j] for j in range(n)]
             span = max(span, max(lim))
+        pre = check_prefixes([None] * n if prefixes is None else prefixes, n, S, V, lim, forced) if per else [None] * n
         self._ensure(nb, nrec, max_len, scored)
         b = self.buf
         temperature = float(temperature)
-        self._graph(temperature, nb, cond_scale, True, filt, nrec, scored)
+        self._graph(temperature, nb, cond_scale, True, filt, nrec, scored, per)
         if cfg:                   # record 2u: the text context; record 2u + 1: the null key / value row only (every context key masked out)
             ctx = []
             for c in self._contexts(sources, range(0, nrec, 2)):
@@ -753,6 +900,12 @@ class TextToSemanticDecoder:
             for j in range(n):
                 if is_forced[j]:
                     b["tokens"][P * j, :, :lim[j]].copy_(ops.h2d(forced[j], self.device))
+        if per:                                            # one settings row per dialogue record (the odd record of a pair mirrors the even one)
+            b["per"][:nrec].copy_(ops.h2d(settings_rows(resolved, [0 if p is None else p.shape[1] for p in pre]).repeat_interleave(P, dim=0),
+                                          self.device))
+            for j, p in enumerate(pre):                    # the token row of a prefixed dialogue holds the prefix before its first step
+                if p is not None:
+                    b["tokens"][P * j, :, :p.shape[1]].copy_(ops.h2d(p, self.device))
         first = min(nb, nrec)     # records (= slots) that start at once; whole pairs under guidance (nb and nrec are even)
         rec = torch.tensor([[ctx[r], lim[r // P], flags[r // P], 1 if r < first else 0, 0, r if r < first else 0, 0, 0] for r in range(nrec)],
                            dtype=torch.int32)
@@ -810,7 +963,7 @@ class TextToSemanticDecoder:
         i, pending = 0, None
         cap = (sum(lim) + CHUNK - 1) // CHUNK + 4          # (one slot decoding everything: cannot be reached)
         while not all(seen) and i < cap:
-            self._run_chunk(temperature, nb, cond_scale, True, filt, nrec, scored)
+            self._run_chunk(temperature, nb, cond_scale, True, filt, nrec, scored, per)
             k = i & 1
             self._mirror_push(k, b["dialogues"][:nrec], via_helper)
             if pending is not None:

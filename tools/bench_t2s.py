@@ -3,7 +3,12 @@
 1 ... 64: encoder once, then N token steps through the graph-replayed decode loop (eos ignored so that the step count is fixed), then
 the continuous-batching path (generate_many) on utterances that END at different steps against the lock-step batch.
 Also prints the weight bytes a token step has to stream (the HBM/MALL roofline of a batch-1 decode).
-    TOKENS=512 SIDE=0 BATCHES=1,8,16,32,64 python tools/bench_t2s.py [comix|cosingle]"""
+    TOKENS=512 SIDE=0 BATCHES=1,8,16,32,64 python tools/bench_t2s.py [comix|cosingle]
+PER=1: instead, the per-dialogue sampling path (cvx_t2s_decode_steps_per_dialogue) against the scalar path on the full-size CoMix model,
+64 slots, eos ignored, STEPS (256) steps of graph replays: A = the scalar chain, B = every table row holding the same (default) setting,
+C = rows alternating top-k and top-p across the slots; A / B / C interleaved REPEATS (5) times in one process -> us per step, min /
+median / max of each, and the effective shader clock over the rounds (ops.clock_stamps).
+    PER=1 STEPS=256 REPEATS=5 OUT=profile.txt python tools/bench_t2s.py"""
 import os, sys, time, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import covomix_amd.synthetic as syn
@@ -16,6 +21,69 @@ which = sys.argv[1:] or ["cosingle", "comix"]
 if os.environ.get("SIDE", "0") == "1":          # on the 32-CU side stream of the CU partition (pipeline.py)
     torch.cuda.set_stream(ops.cu_partition(dev).side)
     print("on the side stream of the CU partition:", ops.stream_cus(), "CUs")
+
+
+def per_dialogue_ab():
+    """A / B / C interleaved, one process (see the module docstring)"""
+    import statistics
+    steps, reps, nb = int(os.environ.get("STEPS", "256")), int(os.environ.get("REPEATS", "5")), 64
+    sd = {k: torch.from_numpy(v) for k, v in syn.t2s_state_dict(syn.t2s_param_shapes(two_output=True, dim=512, dim_target=1024), seed=0).items()}
+    m = TextToSemanticDecoder(sd, dev, max_length=2048)
+    from covomix_amd.t2s import check_settings, settings_rows
+    g = torch.Generator().manual_seed(3)
+    srcs = [torch.randint(1, 30000, (1, 48), generator=g) for _ in range(nb)]
+    V, S = m.d["vocab"], m.d["streams"]
+    same = [{} for _ in range(nb)]
+    mixed = [{} if j % 2 == 0 else {"filter_logits_fn": "top_p", "filter_fn_kwargs": {"thres": 0.9}} for j in range(nb)]
+    rows = lambda st: settings_rows(check_settings(st, nb, V, S)).to(dev)
+    sides = (("A scalar path", None), ("B per-dialogue, one setting", rows(same)), ("C per-dialogue, top-k / top-p alternating", rows(mixed)))
+    m._ensure(nb, nb, steps)
+    m._graph(1.0, nb)
+    m._graph(1.0, nb, per=True)
+    rec = m._slot_records(m._contexts(srcs)).to(dev)
+    m.buf["uniforms"].uniform_(1e-6, 1 - 1e-6)
+    start = m.start[None, :].expand(nb, -1)
+    def run(table):                                      # slot b decodes dialogue b from position 0, no queue: `steps` steps whatever is sampled
+        m.buf["x"][:nb].copy_(start)
+        m.buf["state"].copy_(rec)
+        if table is not None:
+            m.buf["per"][:nb].copy_(table)
+        torch.cuda.synchronize(); t0 = time.perf_counter()
+        for _ in range(steps // CHUNK):
+            m._run_chunk(1.0, nb, per=table is not None)
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / steps * 1e6, m.buf["tokens"][:nb, :, :steps].clone()
+
+    ref = {}
+    for name, st in sides:                               # warm-up: graphs and buffers of every timed shape; and the results must agree
+        ref[name] = run(st)[1]
+    assert torch.equal(ref[sides[0][0]], ref[sides[1][0]]), "B decodes other tokens than A"
+    c0 = ops.clock_stamps()
+    t = {name: [] for name, _ in sides}
+    for _ in range(reps):
+        for name, st in sides:
+            t[name].append(run(st)[0])
+    clk = ops.clock_from_stamps(c0, ops.clock_stamps())
+    lines = [f"text2semantic, full-size CoMix (synthetic weights), {nb} slots, ignore_eos, {steps} steps (slot b decodes dialogue b, eos ignored): "
+             f"{steps // CHUNK} graph replays of {CHUNK} steps between two synchronisations / {steps}; {reps} rounds A B C A B C ...",
+             f"device: {torch.cuda.get_device_name(0)}; effective shader clock over the timed rounds (cycle counter / real time, "
+             f"{clk.get('cus', 0)} CUs): " + (f"{clk['mhz']:.0f} MHz" if clk else "not reported")]
+    for name, _ in sides:
+        v = sorted(t[name])
+        lines.append(f"  {name:45s} us/step  min {v[0]:8.1f}  median {statistics.median(v):8.1f}  max {v[-1]:8.1f}   all {[round(x, 1) for x in t[name]]}")
+    a, b_ = sorted(t[sides[0][0]]), sorted(t[sides[1][0]])
+    spread = a[-1] - a[0]
+    lines.append(f"  A's own spread {spread:.1f} us; B median - A median = {statistics.median(b_) - statistics.median(a):+.1f} us "
+                 f"({'inside' if a[0] - spread <= statistics.median(b_) <= a[-1] + spread else 'OUTSIDE'} A's min..max widened by that spread)")
+    print("\n".join(lines), flush=True)
+    if os.environ.get("OUT"):
+        with open(os.environ["OUT"], "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
+if os.environ.get("PER", "0") == "1":
+    per_dialogue_ab()
+    sys.exit(0)
 CFG = {"cosingle": dict(two_output=False, dim=512, dim_target=512), "comix": dict(two_output=True, dim=512, dim_target=1024)}
 for name in which:
     kw = CFG[name]
