@@ -38,6 +38,19 @@ constexpr int BUF_B = 2 * TILE_B;                  // A | W
 constexpr int DUMP_B = 2 * BUF_B;                  // dump area offset (8 KiB)
 constexpr int LDS_B = DUMP_B + 8 * 1024;
 
+// Which instances see the lane id through opaque per-tile copies (LEAN, see the kernel).  Without it the 256-row instances of every
+// epilogue but to_qkv's carried a private segment of 104-216 bytes (25-61 spilled VGPRs: lane-derived values hoisted out of the tile loop,
+// stored once and re-loaded ~35 times per tile), and so did the 192-row generic A | A2 instance (40 bytes); with it no instance has one
+// (tests/test_gemm_p8s_code_objects.py).  One switch per epilogue and tile height, so that a form that measures slower goes back alone
+// (profiles/r10_gemm_epilogues.txt): the 256-row launches gain 4-11 us each at 16,000 rows; the other 192-row instances never
+// spilled, had nothing to gain and measured 0-2.5 us slower in this form - they keep the plain lane id and the instruction text they had.
+__host__ __device__ constexpr bool epi_lean(int epi, int mi, bool has_a2)
+{
+    if (epi == EPI_QKV || epi == EPI_QKV_RS) return true;      // both heights (profiles/r08_qkv_vt_stores.txt)
+    if (mi == 8) return true;                                   // res_tw, gelu_rs, bias_tw (the bench step), res, gelu_split, bias, generic
+    return epi == EPI_GENERIC && has_a2;                        // (spilled; not reached by tools/gemm_p8_bench.py: not timed)
+}
+
 // the main loop for one output tile; SWAP selects the operand order of every MFMA (see the header)
 // first: this is the block's first tile (issue the six-quarter prologue); (m0n, n0n): the block's NEXT tile, whose first
 // six quarters take the place of the tail's dummy pieces (m0n < 0: no next tile), so that it starts without a prologue.
@@ -250,11 +263,11 @@ __global__ __launch_bounds__(512, 2) void gemm_f16x3_p8s_kernel(
         bool v_block = false;
         if constexpr (EPI == EPI_QKV || EPI == EPI_QKV_RS) v_block = n0 >= p.rope_cols;          // block-uniform: this tile holds V columns
         constexpr bool PERM = epi_perm(EPI);
-        // to_qkv (LEAN): the main loop and the epilogues each see the lane id through an opaque copy made per tile, and set_offsets through
+        // LEAN (epi_lean: per epilogue and tile height): the main loop and the epilogues each see the lane id through an opaque copy made per tile, and set_offsets through
         // one made where it runs.  Otherwise what they derive from it (the V^T lines, the permuted columns, the exchange's lane halves, the
         // lane's parts of the NEXT tile's DMA offsets) is hoisted out of the tile loop or the K loop, lives beside 128 accumulators and
-        // the fragments, and goes to scratch: 164 bytes per lane in the 256-row instance before, none now (tests/test_qkv_vt_stores.py).
-        constexpr bool LEAN = EPI == EPI_QKV || EPI == EPI_QKV_RS;
+        // the fragments, and goes to scratch: 164 bytes per lane in the 256-row qkv_rs instance before, none now (tests/test_qkv_vt_stores.py).
+        constexpr bool LEAN = epi_lean(EPI, MI, HAS_A2);
         int lane_e = lane, lane_m = lane;
         if constexpr (LEAN) asm volatile("" : "+v"(lane_m));
         if (v_block) {

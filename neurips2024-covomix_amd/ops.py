@@ -81,7 +81,8 @@ def _pair(x, rows=None, cols=None):
     """(hi_ptr, lo_ptr, ld) of a split pair: a (hi, lo) tuple (lo may be None) or a SplitIL."""
     if isinstance(x, SplitIL):
         assert (rows is None or x.rows == rows) and (cols is None or x.cols == cols), "SplitIL shape mismatch"
-        return x.buf.data_ptr(), x.buf.data_ptr() + 64, 2 * x.cols
+        assert x.buf.stride(1) == 1 and x.buf.stride(0) >= 2 * x.cols
+        return x.buf.data_ptr(), x.buf.data_ptr() + 64, x.buf.stride(0)          # (rows may be padded: a view into a wider buffer)
     hi, lo = x
     assert hi.dtype == torch.float16 and hi.stride(-1) == 1 and hi.is_cuda
     assert (rows is None or hi.shape[0] == rows) and (cols is None or hi.shape[-1] == cols)

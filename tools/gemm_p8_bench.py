@@ -5,7 +5,9 @@ skip: K-split A|A2 + bias), interleaved A and W.  Columns = cvx_gemm_split_io.fl
 16 + 128 large-problem kernel with 256-row tiles, 16 + 64 with 192-row tiles, 16 its own choice of height, 8 medium-problem kernel,
 0 the library's choice of kernel (+ 4 one tile per block; + 512 to_qkv's earlier 8-byte V^T stores; dev builds: + 256 main loop only).
 Per column: median and min of the interleaved rounds (ROUNDS=3).
-Env: M=16000, SHAPES=qkv,ff2, ZERO=1 (power probe), REPS=20."""
+Env: M=16000, SHAPES=qkv,ff2, ZERO=1 (power probe), REPS=10 (launches per timed round), DN=1 (out / ff1 / ff2 / skip in the deferred-norm forms a bench step
+runs: res_tw with the pair residual read and written in place, gelu_rs, bias_tw - acoustic.py; the in-place residual grows from launch
+to launch, the time does not depend on it)."""
 import math, os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from covomix_amd import ops
@@ -22,6 +24,7 @@ M = int(os.environ.get("M", "16000"))
 T = int(os.environ.get("T", "1000"))
 if M % T:
     T = M                                   # (one sequence: the RoPE table covers every row)
+DN = os.environ.get("DN") == "1"
 only = os.environ.get("SHAPES")
 variants = [int(v) for v in os.environ.get("VARIANTS", "144,80,16,8").split(",")]
 tot = {v: 0.0 for v in variants}
@@ -58,6 +61,19 @@ for (N, K, K1, name, cnt) in [(3072, 1024, 0, "qkv", 8), (1024, 1024, 0, "out", 
         Tp = (T + 31) // 32 * 32
         vt = (torch.zeros((M // T) * 16 * 64, Tp, dtype=torch.float16, device=dev), torch.zeros((M // T) * 16 * 64, Tp, dtype=torch.float16, device=dev))
         kw.update(rope=rope, rope_cols=2048, out_split=qk, vt_split=vt, write_f32=False)
+    elif DN and name in ("out", "ff2", "skip"):         # producers: pair residual read in place, raw twin, row sums of squares, no fp32 store
+        one = torch.ones(1, device=dev)
+        pair = ops.SplitIL(M, N, dev)
+        ops.split_act_f16(res if res is not None else torch.randn(M, N, generator=g).to(dev), pair)
+        kw.update(out_split=pair, c_scale=one, a_scale=one, c_rowsq=torch.empty(M, N // 64, device=dev), write_f32=False)
+        if name == "skip":
+            kw.update(a2_scale=one)
+        else:
+            kw.update(res_split=pair, res_scale=one)
+            if name == "ff2":
+                kw.update(bias=b)
+    elif DN and name == "ff1":                          # consumer: a factor per row on the accumulators
+        kw.update(bias=b, act=1, out_split=ops.SplitIL(M, N, dev), write_f32=False, a_row_scale=(0.5 + torch.rand(M, generator=g)).to(dev))
     elif name == "out":
         kw.update(residual=res)
     elif name == "ff1":
@@ -69,7 +85,7 @@ for (N, K, K1, name, cnt) in [(3072, 1024, 0, "qkv", 8), (1024, 1024, 0, "out", 
     for rep in range(int(os.environ.get("ROUNDS", "3")) + 1):          # interleaved A/B/C rounds; the first one is a warm-up
         for flags in variants:
             with ops.gemm_flags(flags):
-                t = timeit(fn, iters=10)
+                t = timeit(fn, iters=int(os.environ.get("REPS", "10")))
             if rep:
                 times[flags].append(t)
     mins = {v: min(ts) for v, ts in times.items()}
