@@ -247,7 +247,8 @@ int cvx_split_f16(const float* w, uint16_t* hi, uint16_t* lo, int64_t n, float s
  * set_scale_dev = a power of two that keeps |gamma| <= 1 (the consumer divides it out through a_scale_dev).  W is read once. */
 int cvx_split_f16_colscale_il(const float* W, int64_t ldw, int32_t N, int32_t K, const float* colscale, int64_t cs_ld,
                               const float* set_scale_dev, int64_t ss_ld, int32_t n_sets, float scale, uint16_t* out, cvx_stream_t s);
-/* the same with an additional DEVICE-resident factor (the pair holds w * scale * *scale_dev; scale_dev may be NULL) */
+/* the same with an additional DEVICE-resident factor (the pair holds w * scale * *scale_dev; scale_dev may be NULL).
+ * An interleaved pair (lo == hi + 32) needs n % 32 == 0: a partial last block of 32 would be stored past 2 * n halves (CVX_EINVAL). */
 int cvx_split_f16_dev(const float* w, uint16_t* hi, uint16_t* lo, int64_t n, float scale, const float* scale_dev, cvx_stream_t s);
 int cvx_gemm_f16x3(const cvx_gemm_args* a, const uint16_t* W_hi, const uint16_t* W_lo, float acc_scale,
                    const cvx_gemm_split_io* io, cvx_stream_t s);
@@ -280,7 +281,9 @@ int cvx_adarmsnorm_f32(const float* x, const float* gamma, const float* beta, fl
                        int64_t rows, int32_t D, int64_t rows_per_group, float scale, float eps,
                        cvx_stream_t s);
 /* the same; the split copy (y_hi, y_lo) holds y * *split_scale_dev (a power of two in DEVICE memory, NULL = 1: the
- * activation pre-scale of cvx_gemm_split_io.a_scale_dev).  The fp32 output y is never scaled. */
+ * activation pre-scale of cvx_gemm_split_io.a_scale_dev).  The fp32 output y is never scaled.
+ * An interleaved pair (y_lo == y_hi + 32) needs D % 32 == 0: the layout is addressed by flat offset, which is a row's own line of
+ * 2 * D halves only then (CVX_EINVAL otherwise; the same holds for cvx_adarmsnorm_f32). */
 /* out[r] = scale / max(sqrt(sum_{j < parts} rowsq[r * ld + j]), eps): the per-row factor of a deferred norm from the partial sums a
  * producer GEMM left (cvx_gemm_split_io.c_rowsq; F.normalize's eps clamp, acoustic.py:198-204).  parts <= 64, summed in index order. */
 int cvx_rownorm_scale_f32(const float* rowsq, int64_t rows, int32_t parts, int64_t ld, float scale, float eps, float* out, cvx_stream_t s);

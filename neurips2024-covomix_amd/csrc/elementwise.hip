@@ -492,6 +492,8 @@ extern "C" int cvx_adarmsnorm_scaled_f32(const float* x, const float* gamma, con
     _Float16* y_hi = reinterpret_cast<_Float16*>(y_hi_);
     _Float16* y_lo = reinterpret_cast<_Float16*>(y_lo_);
     CVX_REQUIRE(rows >= 0 && D > 0 && D % 4 == 0 && rows_per_group > 0, "adarmsnorm: bad shape rows=%ld D=%d", (long)rows, D);
+    // interleaved pair: store_split4 maps the flat offset row * D + col, which is the row's own line only when D % 32 == 0
+    CVX_REQUIRE(!(y_hi && y_lo == y_hi + 32) || D % 32 == 0, "adarmsnorm: an interleaved pair (y_lo == y_hi + 32) needs D %% 32 == 0 (D=%d)", D);
     if (rows == 0) return CVX_OK;
     hipStream_t st = cvx_hip_stream(s);
     dim3 grid((unsigned)((rows + 3) / 4));

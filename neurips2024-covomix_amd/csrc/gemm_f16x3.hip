@@ -444,6 +444,8 @@ extern "C" int cvx_split_f16_dev(const float* w, uint16_t* hi, uint16_t* lo, int
                                  cvx_stream_t s)
 {
     CVX_REQUIRE(w && hi && n >= 0, "split_f16: bad arguments");      // lo == NULL: plain fp16 cast (saturating)
+    // interleaved pair: element i lives at ((i >> 5) << 6) | (i & 31), so a partial last block of 32 would end past 2 * n halves
+    CVX_REQUIRE(lo != hi + 32 || n % 32 == 0, "split_f16: an interleaved pair (lo == hi + 32) needs n %% 32 == 0 (n=%ld)", (long)n);
     if (n == 0) return CVX_OK;
     CVX_REQUIRE_SAT(s);
     hipLaunchKernelGGL(split_f16_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, cvx_hip_stream(s),

@@ -374,7 +374,8 @@ def split_act_f16(x: torch.Tensor, hi=None, lo: Optional[torch.Tensor] = None, s
     assert x.is_contiguous()
     ensure_saturation_bound()
     if isinstance(hi, SplitIL):
-        h, l, _ = _pair(hi, x.shape[0], x.shape[1])
+        h, l, ld = _pair(hi, x.shape[0], x.shape[1])
+        assert ld == 2 * hi.cols, "split_act_f16: cvx_split_f16_dev takes no row stride (a SplitIL view into a wider buffer)"
         _lib.check(_lib.load().cvx_split_f16_dev(x.data_ptr(), h, l, x.numel(), 1.0, _sp(scale), _stream()), "cvx_split_f16")
         return hi
     if hi is None:
@@ -425,6 +426,7 @@ def adarmsnorm(x: torch.Tensor, gamma: torch.Tensor, beta: Optional[torch.Tensor
         ensure_saturation_bound()
         oh, ol, ld = _pair(out_split, rows if isinstance(out_split, SplitIL) else None, D)
         assert isinstance(out_split, SplitIL) or (out_split[0].is_contiguous() and out_split[0].numel() == x.numel())
+        assert not isinstance(out_split, SplitIL) or ld == 2 * D, "adarmsnorm: cvx_adarmsnorm_scaled_f32 takes no row stride (a SplitIL view into a wider buffer)"
     rpg = rows if rows_per_group is None else rows_per_group
     _lib.check(_lib.load().cvx_adarmsnorm_scaled_f32(x.data_ptr(), gamma.data_ptr(), _p(beta), _p(out), oh, ol, rows, D, rpg,
                                                      float(D) ** 0.5, eps, _sp(split_scale), _stream()), "cvx_adarmsnorm_f32")
