@@ -72,7 +72,9 @@ typedef const cvx_ctx* cvx_stream_t;
  * with its own size-carrying struct, cvx_t2s_beam_select_f32 - beam search on the decode slots; cvx_t2s_beam_queue_steps with
  * cvx_t2s_beam_queue - beam search through continuously refilled slot groups.  Still 113 (additive, one formerly ignored
  * flag bit; no struct or entry point changes): the V^T stores of a to_qkv launch of the eight-phase kernels go line-major, 16 bytes
- * per lane (same values, same addresses); CVX_GEMM_FLAG_VT_PIECES keeps the earlier store code selectable. */
+ * per lane (same values, same addresses); CVX_GEMM_FLAG_VT_PIECES keeps the earlier store code selectable.  Still 113 (a symbol and a
+ * struct added): cvx_t2s_decode_steps_mixed with cvx_t2s_mixed - guided and unguided dialogues in one slot pool; slot record [7], so
+ * far reserved, carries a slot's role there. */
 #define CVX_ABI_VERSION 113
 int         cvx_version(void);
 const char* cvx_last_error_string(void);
@@ -649,7 +651,7 @@ int cvx_wav_to_int16(const float* wav, int16_t* pcm, int64_t n, cvx_stream_t s);
  *       stream, [2] number of steps at that moment, [3] context rows (null row included) used when n_ctx == 0, so that one
  *       captured graph serves utterances of different text length, [4] the dialogue the slot decodes (indexes kv_c, uniforms,
  *       tokens; the caller writes the slot number there when there is no queue), [5] step limit and [6] flags of that
- *       dialogue (queue only; bit 0: an eos does not end it), [7] reserved; x must hold start_token and state[0..2] zeros
+ *       dialogue (queue only; bit 0: an eos does not end it), [7] reserved, 0 (cvx_t2s_decode_steps_mixed: the slot's role); x must hold start_token and state[0..2] zeros
  *       before a slot's first step.
  *   Continuous batching (queue != NULL; reference loop per dialogue: text2semantic.py:749-848, its exit :803-818): queue
  *       int32[2] = {next pending dialogue, number of dialogues}; dialogues int32[n][8]: the caller writes [0] context rows,
@@ -775,6 +777,48 @@ typedef struct cvx_t2s_per_dialogue {
 
 int cvx_t2s_decode_steps_per_dialogue(const cvx_t2s_decoder* dec, const cvx_t2s_scoring* scoring, const cvx_t2s_per_dialogue* per,
                                       int32_t n_steps, cvx_stream_t stream);
+
+/* Guided and unguided dialogues in ONE slot pool: the chain of cvx_t2s_decode_steps_per_dialogue (scoring NULL or not, the settings table
+ * always) in which the pair layout is a property of the dialogue RECORD, not of the launch.  Still ABI 113: a symbol and a struct added.
+ *   Dialogue records: flag bit 2 (CVX_T2S_FLAG_GUIDED, value 4) of record [2] makes record r the TEXT half of a guided utterance and
+ *       record r + 1 its NULL half: [0] context rows = 1, kv_c row 0 of that record = the learned null key / value, [1], [2] and the
+ *       settings row mirror those of record r.  An unguided utterance is one record.  queue[1] still counts records, and records may come
+ *       in any mixture and order.  Uniforms, token row and log-probs of a guided utterance are those of record r; the token and log-prob
+ *       rows of record r + 1 are unspecified (nothing in the chain reads them).
+ *   Slot records: [7] is the slot's role - 0 a single slot, p + 1 the text half whose null half is slot p, -(p + 1) the null half of slot
+ *       p.  Partners need not be neighbours.  dec->cfg_scale is not a layout switch here (> 1 is refused); the scale of a guided utterance
+ *       is word [4] of its settings row.
+ *   Sampling (one block per slot): an idle slot and a null half return at once; a single slot samples as the per-dialogue chain does
+ *       without guidance; a text half as it does under guidance, from null + (cond - null) * scale with the null half's logits row, and
+ *       feeds the token's embedding to both slots.  Prefixes, forced dialogues and log-probs as in cvx_t2s_decode_steps_per_dialogue.
+ *       A dialogue that ends (eos unless flag bit 0, or its step limit) gets [4] steps, [5] slot and then [3] status written into its
+ *       record - and into the null record of a pair, with [5] = the null half's slot - and its slot(s) idle: [0] = max_len, [1] = 1,
+ *       [7] = 0 (the null half's [7] is cleared by the scheduler launch that follows: its own block may still be reading it).  The
+ *       sampling launch does not touch the queue.
+ *   Scheduler (one block, one launch after the sampling launch of every step; the kernel boundary orders it behind every record write):
+ *       F = the idle slots ([0] >= max_len) in ascending order.  Loop: h = queue[0]; stop if h >= queue[1] or F is empty.  Record h
+ *       unguided: the lowest slot of F takes it, h += 1.  Guided: stop if h + 1 >= queue[1] (a pair is taken only if both records exist)
+ *       or F holds fewer than two slots (the head WAITS - strict queue order, no look-ahead); else the lowest slot of F becomes the text
+ *       half of record h, the next one the null half of record h + 1, h += 2.  A slot that takes a record starts at position 0 with
+ *       `start` as its input, [3]..[6] from the record, its role in [7]; the record gets [3] = 1 and [5] = the slot.  Serial and
+ *       deterministic: which slots an utterance runs in is a function of the records and of the step every utterance ends at.
+ *   n_steps == 0 runs the scheduler once and nothing else: with every slot idle ([0] = max_len) and queue = {0, n} that ARMS a call, so
+ *       the policy exists in one place.
+ *   mixed->n_guided: the number of guided utterances among the records (the host's count; the device reads the flags).
+ *   Bit identity: every utterance, guided or not, gets the tokens and log-probs it gets alone from cvx_t2s_decode_steps(_scored) with its
+ *   settings - whichever slots it runs in, whatever its neighbours are.
+ * No host synchronisation; graph-capturable; per step the launches of cvx_t2s_decode_steps plus one.  CVX_EINVAL, nothing launched:
+ * struct_size != sizeof(cvx_t2s_mixed), mixed, per or dec->queue NULL, dec->cfg_scale > 1, n_guided < 0 or 2 * n_guided >
+ * dec->n_dialogues, n_guided > 0 with streams != 1 or batch < 2, and everything cvx_t2s_decode_steps_per_dialogue refuses. */
+#define CVX_T2S_FLAG_GUIDED 4
+
+typedef struct cvx_t2s_mixed {
+    uint32_t struct_size;
+    int32_t n_guided;
+} cvx_t2s_mixed;
+
+int cvx_t2s_decode_steps_mixed(const cvx_t2s_decoder* dec, const cvx_t2s_scoring* scoring, const cvx_t2s_per_dialogue* per,
+                               const cvx_t2s_mixed* mixed, int32_t n_steps, cvx_stream_t stream);
 
 /* Beam search on the decode slots - the deterministic decode behind the reference's beam_search_decode flag, which its generate accepts
  * and never implements (text2semantic.py:673-677): the algorithm below is this library's definition.

@@ -165,6 +165,12 @@ class T2SPerDialogue(C.Structure):
 
 
 T2S_PER_WORDS = 8                                # 32-bit words per row of that table
+T2S_FLAG_GUIDED = 4                              # dialogue record [2], cvx_t2s_decode_steps_mixed: record r is the text half, r + 1 the null half
+
+
+class T2SMixed(C.Structure):
+    """cvx_t2s_mixed: struct_size = sizeof(this); n_guided = guided utterances among the dialogue records (two records each)"""
+    _fields_ = [("struct_size", C.c_uint32), ("n_guided", C.c_int32)]
 
 
 class T2SBeam(C.Structure):
@@ -228,6 +234,8 @@ SIGNATURES = {
     "cvx_t2s_decode_steps_scored": (C.c_int, [C.POINTER(T2SDecoder), C.POINTER(T2SScoring), C.c_int32, C.c_void_p]),
     "cvx_t2s_decode_steps_per_dialogue": (C.c_int, [C.POINTER(T2SDecoder), C.POINTER(T2SScoring), C.POINTER(T2SPerDialogue), C.c_int32,
                                                     C.c_void_p]),
+    "cvx_t2s_decode_steps_mixed": (C.c_int, [C.POINTER(T2SDecoder), C.POINTER(T2SScoring), C.POINTER(T2SPerDialogue), C.POINTER(T2SMixed),
+                                             C.c_int32, C.c_void_p]),
     "cvx_t2s_beam_steps": (C.c_int, [C.POINTER(T2SDecoder), C.POINTER(T2SBeam), C.c_int32, C.c_void_p]),
     "cvx_t2s_beam_queue_steps": (C.c_int, [C.POINTER(T2SDecoder), C.POINTER(T2SBeam), C.POINTER(T2SBeamQueue), C.c_int32, C.c_void_p]),
     "cvx_t2s_beam_select_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,

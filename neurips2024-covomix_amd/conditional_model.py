@@ -228,7 +228,7 @@ class CoVoMixModel:
     def synthesis_sample_text2semantic(self, grapheme_token_ids, temprature=1.0, cond_scale=1.0, beam_search_decode=False,
                                        prompt_mel=None, uniforms=None, generator=None, max_length=None, slots=64,
                                        filter_logits_fn="top_k", filter_fn_kwargs=None, return_logprobs=False, best_of=1,
-                                       beam_size=10, length_penalty=1.0, prefix=None, best_of_temperatures=None):
+                                       beam_size=10, length_penalty=1.0, prefix=None, best_of_temperatures=None, mixed_guidance=False):
         """reference conditional_model.py:313-321 -> TextToSemanticWrapper.sample (text2semantic.py:1237-1251): the
         sampled semantic tokens as one flat int64 tensor (two-output models: stream 1 then stream 2) on the input's
         device.  (`temprature` is the reference's spelling.)  `uniforms` / `generator` (optional) fix the U(0,1) draws
@@ -251,7 +251,9 @@ class CoVoMixModel:
         Per-utterance settings (extension; t2s.generate_many(settings=...)): with a LIST of texts, `temprature`, `cond_scale`,
         `filter_logits_fn` and `filter_fn_kwargs` may each be a list of the same length - utterance j then decodes with entry j, in the same
         slots and the same captured graph as the others, and gets what it gets alone with those values (lists whose entries are all equal
-        take the scalar path).  Guided and unguided utterances do not share a call (ValueError).
+        take the scalar path).  Guided and unguided utterances do not share a call (ValueError) - unless mixed_guidance=True (default
+        False): a list of cond_scale values may then hold 1 (unguided) beside values > 1 (guided), and all of them run through one slot
+        pool in one call (t2s.generate_many(mixed_guidance=True)) with the results they get one by one.
         prefix (extension): int64 [S, P] tokens the decode continues from (a list, None where an utterance has none, for a list of texts):
         the result starts with them (t2s.generate_many(prefixes=...)).
         best_of_temperatures (extension): a sequence of N temperatures - best_of = N with candidate c of every utterance decoded at
@@ -331,7 +333,8 @@ class CoVoMixModel:
                                           cond_scale=max(scales) if "cond_scale" in lists else float(cond_scale),
                                           filter_logits_fn="top_k" if "filter_logits_fn" in lists else filter_logits_fn,
                                           filter_fn_kwargs=None if "filter_logits_fn" in lists or "filter_fn_kwargs" in lists else filter_fn_kwargs,
-                                          return_logprobs=bool(return_logprobs) or N > 1, settings=sets, prefixes=pres)
+                                          return_logprobs=bool(return_logprobs) or N > 1, settings=sets, prefixes=pres,
+                                          **({"mixed_guidance": True} if mixed_guidance else {}))
             eos = self._t2s.d["vocab"] - 1
             out = []
             for j, i in enumerate(ids_l):
@@ -376,21 +379,31 @@ class CoVoMixModel:
 
     @ops.gated
     @torch.no_grad()
-    def score_text2semantic(self, grapheme_token_ids, streams, cond_scale=1.0):
+    def score_text2semantic(self, grapheme_token_ids, streams, cond_scale=1.0, mixed_guidance=False):
         """Teacher-forced scoring (extension; what the reference's evaluate_text2semantic measures through
         TextToSemantic.forward(..., return_loss=True)): the log-probability of every token of `streams` - int64 [S, L], the streams a
         sampling call returned - under the text: float32 [S, L] (t2s.score_many).  One utterance, or LISTS of texts and streams (-> a
-        list).  cond_scale > 1 scores under the guidance-combined logits and needs what sampling with it needs."""
+        list).  cond_scale > 1 scores under the guidance-combined logits and needs what sampling with it needs.  mixed_guidance=True with
+        lists: cond_scale may be a list as long as the texts, 1 (unguided) beside values > 1 (guided), scored in one call."""
         if not self.is_text2semantic:
             raise TypeError("this checkpoint is an acoustic model")
-        assert cond_scale >= 1., "cond_scale >= 1 (text2semantic.py:683)"
-        assert not (cond_scale > 1 and float(self.hparams.get("cond_drop_prob", 0.0)) == 0.0), \
+        scales = [float(c) for c in cond_scale] if isinstance(cond_scale, (list, tuple)) else [float(cond_scale)]
+        if isinstance(cond_scale, (list, tuple)) and not mixed_guidance:
+            raise ValueError("score_text2semantic: a list of cond_scale values needs mixed_guidance=True")
+        assert all(c >= 1. for c in scales), "cond_scale >= 1 (text2semantic.py:683)"
+        assert not (any(c > 1 for c in scales) and float(self.hparams.get("cond_drop_prob", 0.0)) == 0.0), \
             ("you need to train with conditional drop probability greater than 0 to use classifier free guidance at inference "
              "(text2semantic.py:684): this checkpoint's hyper_parameters['cond_drop_prob'] is 0 or absent")
         many = isinstance(grapheme_token_ids, (list, tuple))
         if many != isinstance(streams, (list, tuple)):
             raise ValueError("score_text2semantic: one utterance and its streams, or a list of each")
         dec = self._get_t2s()
+        if mixed_guidance:
+            if isinstance(cond_scale, (list, tuple)) and (not many or len(scales) != len(grapheme_token_ids)):
+                raise ValueError("score_text2semantic: a list of cond_scale values goes with a list of texts of the same length")
+            res = dec.score_many(list(grapheme_token_ids) if many else [grapheme_token_ids], list(streams) if many else [streams],
+                                 cond_scale=scales if isinstance(cond_scale, (list, tuple)) else scales[0], mixed_guidance=True)
+            return res if many else res[0]
         res = dec.score_many(list(grapheme_token_ids) if many else [grapheme_token_ids], list(streams) if many else [streams],
                              cond_scale=float(cond_scale))
         return res if many else res[0]

@@ -24,6 +24,9 @@
 //                       FORCED dialogues, which read given tokens instead of sampling (teacher-forced scoring).
 //   sample_per_kernel   sample_kernel with temperature, filter, guidance scale and a forced prefix length read per step from a table row of
 //                       the DIALOGUE the slot decodes (cvx_t2s_decode_steps_per_dialogue): utterances with different settings share the slots.
+//   sample_mixed_kernel, mixed_schedule_kernel   guided and unguided dialogues in one slot pool (cvx_t2s_decode_steps_mixed): a slot's
+//                       role (single / text half / null half) comes from its record, and a one-block launch after the sampling
+//                       kernel hands the idle slots the next records - a guided record takes two slots, wherever they are.
 // BEAM SEARCH (cvx_t2s_beam_steps; the algorithm: include/covomix_hip.h): the B hypotheses of an utterance sit in B neighbouring slots and
 // continue from each other's KV caches through an ancestry table - no cache row is ever copied:
 //   attn_owner_kernel      attn_kernel's body with key / value j read from the cache of slot owner[j] (the row staged in LDS);
@@ -1002,6 +1005,160 @@ __global__ __launch_bounds__(1024) void sample_per_kernel(const SampleArgs a, co
     sample_body_per<1024, LOGP>(a, p, blockIdx.x, lg, ex, bv, bi, &chosen);
 }
 
+// ---------------------------------------------------------------- guided and unguided dialogues in one slot pool
+// (cvx_t2s_decode_steps_mixed).  A SIBLING of sample_body_per for the reason given there: the instantiations above stay as they are.
+// Whether a slot is half of a guided pair is a property of the RECORD it decodes, carried in slot record [7] (its role):
+//    0           a single slot: sample_body_per without guidance (nrow == nullptr);
+//    p + 1       the text half of a pair whose null half is slot p (any slot: partners need not be neighbours): sample_body_per under
+//                guidance with nrow = the logits row of slot p and the scale of its own table row; it feeds both slots;
+//   -(p + 1)     the null half of slot p: its block returns at once, the text half moves its position.
+// What differs from sample_body_per beyond that: the token row of the null record is not written (nothing reads it), and the block that
+// ends a dialogue only writes the record(s) and puts its slot(s) into the idle state - it never touches the queue.  Handing out records
+// is the business of mixed_schedule_kernel, the launch that follows: a guided head needs TWO idle slots, which no single block can know.
+// The role of the null half is cleared by that launch too, not here: the null half's own block may be reading it in this launch, and
+// with the role unchanged every word a block decides by is either its own slot's or constant during the launch (no fences needed).
+template <int NT, bool LOGP>
+__device__ __forceinline__ void sample_body_mixed(const SampleArgs& a, const PerArgs& p, int b, float* lg, float* ex, float* bv, int* bi, int* chosen)
+{
+    const int tid = threadIdx.x;
+    int* const state = a.state + SR * b;
+    const int pos = aloadi(state);
+    if (pos >= a.max_len) return;                   // an idle slot
+    const int role = aloadi(state + 7);
+    if (role < 0) return;                           // the null half follows its partner (block-uniform)
+    const bool pair = role > 0;
+    const int pb = pair ? min(a.batch - 1, role - 1) : b;               // (a stray role indexes no slot outside the batch)
+    int* const sn = a.state + SR * pb;              // the null half's slot record (touched for a pair only)
+    const int64_t dlg = aloadi(state + 4);
+    const int* const row = p.table + (int64_t)PER_WORDS * min((int64_t)(p.n_records - 1), max((int64_t)0, dlg));
+    const float inv_temp = __int_as_float(row[0]);
+    const bool nucleus = row[1] == FILT_TOP_P;
+    const int top_k = min(a.V, max(1, row[2]));
+    const float top_p = __int_as_float(row[3]);
+    const float scale = __int_as_float(row[4]);
+    const int P = min(max(aloadi(state + 5), 0), max(0, row[5]));
+    const bool forced = LOGP ? (aloadi(state + 6) & 2) != 0 : false;
+    const bool given = forced || pos < P;
+    bool eos = false;
+    for (int s = 0; s < a.streams; ++s) {
+        const float* const lrow = a.logits + ((int64_t)b * a.streams + s) * a.V;
+        const float* const nrow = pair ? a.logits + ((int64_t)pb * a.streams + s) * a.V : nullptr;
+        int tok;
+        if (given) {
+            if (LOGP) stage_row<NT>(lrow, nrow, scale, a.V, lg);
+            tok = (int)min((int64_t)(a.V - 1), max((int64_t)0, a.tokens[(dlg * a.streams + s) * a.max_len + pos]));
+        } else {
+            const float* const urow = a.uniforms + ((dlg * a.uniform_steps + pos) * a.streams + s) * a.V;
+            if (nucleus) tok = sample_select<NT, FILT_TOP_P, false>(lrow, nrow, scale, urow, a.V, top_k, top_p, inv_temp, nullptr, lg, ex, bv, bi, chosen);
+            else tok = sample_select<NT, FILT_TOP_K, false>(lrow, nrow, scale, urow, a.V, top_k, top_p, inv_temp, nullptr, lg, ex, bv, bi, chosen);
+            if (tid == 0) a.tokens[(dlg * a.streams + s) * a.max_len + pos] = tok;
+        }
+        if (LOGP) {
+            const float lp = row_logprob<NT>(lg, a.V, tok, ex, bv);
+            if (tid == 0) a.logprobs[(dlg * a.streams + s) * a.max_len + pos] = lp;
+        }
+        eos = eos || (tok == a.eos_id && !given);
+        for (int d = tid; d < a.dim_emb; d += NT) {
+            const float e = a.emb[(int64_t)tok * a.dim_emb + d];
+            a.x[((int64_t)b * a.streams + s) * a.dim_emb + d] = e;
+            if (pair) a.x[((int64_t)pb * a.streams + s) * a.dim_emb + d] = e;
+        }
+        __syncthreads();
+    }
+    const bool ends_eos = eos && !(aloadi(state + 6) & 1);
+    const bool ends = ends_eos || pos + 1 >= aloadi(state + 5);
+    if (tid != 0) return;
+    if (!ends) {
+        state[0] = pos + 1;
+        if (pair) sn[0] = pos + 1;
+        return;
+    }
+    int* const dr = a.dialogues + SR * dlg;         // (the null record of a pair is the next one: the scheduler took both)
+    dr[4] = pos + 1;
+    dr[5] = b;
+    if (pair) { dr[SR + 4] = pos + 1; dr[SR + 5] = pb; }
+    __threadfence();
+    dr[3] = ends_eos ? 2 : 3;
+    if (pair) dr[SR + 3] = ends_eos ? 2 : 3;
+    state[0] = a.max_len; state[1] = 1; state[7] = 0;
+    if (pair) { sn[0] = a.max_len; sn[1] = 1; }     // (sn[7]: mixed_schedule_kernel, above)
+}
+
+template <bool LOGP>
+__global__ __launch_bounds__(1024) void sample_mixed_kernel(const SampleArgs a, const PerArgs p)
+{
+    __shared__ __attribute__((aligned(16))) float lg[1024];
+    __shared__ __attribute__((aligned(16))) float ex[1024];
+    __shared__ float bv[16];
+    __shared__ int bi[16];
+    __shared__ int chosen;
+    sample_body_mixed<1024, LOGP>(a, p, blockIdx.x, lg, ex, bv, bi, &chosen);
+}
+
+// The scheduler of the mixed pool: ONE block, launched after sample_mixed_kernel (the kernel boundary makes every record write of that
+// launch visible - no fence, no cross-block traffic).  Serial and deterministic, thread 0 (t2s.py: mixed_schedule replays it on the host):
+//   F = the idle slots (record [0] >= max_len) in ascending order; loop: h = queue[0]; stop if h >= queue[1] or F is empty; record h
+//   unguided: the lowest slot of F takes it, h += 1; guided (flag bit 2): stop if h + 1 >= queue[1] (never index past the records) or F
+//   holds fewer than two slots (the head waits: strict order); else the lowest slot of F becomes the text half of record h, the next one
+//   the null half of record h + 1, h += 2.
+// Re-arming a slot is sample_body_per's refill - position 0, [3]..[6] from the record, record [3] = 1 and [5] = the slot - plus the role
+// in [7]; all threads then copy `start` into the x rows of the armed slots.  Slots that stay idle get role 0 (the null half of a pair
+// that ended in the sampling launch still carries its role).  Plain stores only: nothing else runs beside this block.
+__global__ __launch_bounds__(1024) void mixed_schedule_kernel(const SampleArgs a)
+{
+    __shared__ int armed[T2S_MAX_BATCH];
+    __shared__ int n_armed;
+    __shared__ unsigned long long left;
+    const int tid = threadIdx.x;
+    if (tid < 64) {
+        const bool idle = tid < a.batch && aloadi(a.state + SR * tid) >= a.max_len;
+        unsigned long long F = __ballot(idle);
+        if (tid == 0) {
+            int h = aloadi(a.queue), cnt = 0;
+            const int n = aloadi(a.queue + 1);
+            while (F != 0ull && h >= 0 && h < n) {
+                int* const dn = a.dialogues + SR * (int64_t)h;
+                const int s0 = __ffsll((long long)F) - 1;
+                if (!(dn[2] & CVX_T2S_FLAG_GUIDED)) {
+                    F &= F - 1ull;
+                    int* const st = a.state + SR * s0;
+                    st[0] = 0; st[1] = 0; st[2] = 0; st[3] = dn[0]; st[4] = h; st[5] = dn[1]; st[6] = dn[2]; st[7] = 0;
+                    dn[5] = s0;
+                    dn[3] = 1;
+                    armed[cnt++] = s0;
+                    h += 1;
+                    continue;
+                }
+                if (h + 1 >= n || (F & (F - 1ull)) == 0ull) break;
+                F &= F - 1ull;
+                const int s1 = __ffsll((long long)F) - 1;
+                F &= F - 1ull;
+                int* const st = a.state + SR * s0;
+                int* const sn = a.state + SR * s1;
+                st[0] = 0; st[1] = 0; st[2] = 0; st[3] = dn[0]; st[4] = h; st[5] = dn[1]; st[6] = dn[2]; st[7] = s1 + 1;
+                sn[0] = 0; sn[1] = 0; sn[2] = 0; sn[3] = dn[SR + 0]; sn[4] = h + 1; sn[5] = dn[1]; sn[6] = dn[2]; sn[7] = -(s0 + 1);
+                dn[5] = s0;
+                dn[3] = 1;
+                dn[SR + 5] = s1;
+                dn[SR + 3] = 1;
+                armed[cnt++] = s0;
+                armed[cnt++] = s1;
+                h += 2;
+            }
+            if (cnt > 0) a.queue[0] = h;
+            n_armed = cnt;
+            left = F;
+        }
+    }
+    __syncthreads();
+    if (tid < a.batch && ((left >> tid) & 1ull) && aloadi(a.state + SR * tid + 7) != 0) a.state[SR * tid + 7] = 0;
+    const int cnt = n_armed, row = a.dim_emb * a.streams;
+    for (int i = tid; i < cnt * row; i += 1024) {
+        const int k = i / row, d = i - k * row;
+        a.x[(int64_t)armed[k] * row + d] = a.start[d];
+    }
+}
+
 // the log-prob epilogue alone: one block per row, no slot state (cvx_t2s_logprob_f32)
 __global__ __launch_bounds__(1024) void logprob_rows_kernel(const float* logits, const int64_t* tokens, int V, float* out)
 {
@@ -1594,8 +1751,10 @@ static BeamArgs beam_args(const cvx_t2s_decoder* d, const cvx_t2s_beam* bm)
 // bm (cvx_t2s_beam_steps): the self-attention reads through the ancestry table, and the shortlist + merge kernels stand in for the sampling
 // kernel - one launch more per step; every other launch is the same.  bq (cvx_t2s_beam_queue_steps): the merge that refills its group.
 // per (cvx_t2s_decode_steps_per_dialogue): the sampling kernel that reads its settings from the per-dialogue table.
+// mixed (cvx_t2s_decode_steps_mixed, with per): the sampling kernel that takes a slot's role from its record, then the scheduler - one
+// launch more per step; n_steps == 0 runs the scheduler alone, once.
 static int t2s_decode_run(const cvx_t2s_decoder* d, int32_t n_steps, float* logprobs, cvx_stream_t s, const cvx_t2s_beam* bm = nullptr,
-                          const BeamQueueArgs* bq = nullptr, const PerArgs* per = nullptr)
+                          const BeamQueueArgs* bq = nullptr, const PerArgs* per = nullptr, bool mixed = false)
 {
     hipStream_t st = cvx_hip_stream(s);
     const float scale = 0.125f;        // dim_head ** -0.5
@@ -1655,6 +1814,12 @@ static int t2s_decode_run(const cvx_t2s_decoder* d, int32_t n_steps, float* logp
         SampleArgs sa{d->logits, d->uniforms, d->emb, d->x, d->tokens, d->state, d->queue, d->dialogues, d->start, nb, d->uniform_steps,
                       d->vocab, d->dim_emb, d->streams, d->max_len, d->top_k, d->vocab - 1, 1.0f / fmaxf(d->temperature, 1e-10f),
                       d->cfg_scale, d->top_p, logprobs};
+        if (mixed) {
+            if (logprobs) hipLaunchKernelGGL(sample_mixed_kernel<true>, dim3((unsigned)nb), dim3(1024), 0, st, sa, *per);
+            else hipLaunchKernelGGL(sample_mixed_kernel<false>, dim3((unsigned)nb), dim3(1024), 0, st, sa, *per);
+            hipLaunchKernelGGL(mixed_schedule_kernel, dim3(1), dim3(1024), 0, st, sa);
+            continue;
+        }
         if (per) {
             if (logprobs) hipLaunchKernelGGL(sample_per_kernel<true>, dim3((unsigned)nb), dim3(1024), 0, st, sa, *per);
             else hipLaunchKernelGGL(sample_per_kernel<false>, dim3((unsigned)nb), dim3(1024), 0, st, sa, *per);
@@ -1665,6 +1830,11 @@ static int t2s_decode_run(const cvx_t2s_decoder* d, int32_t n_steps, float* logp
             else hipLaunchKernelGGL((sample_kernel<FILT_TOP_K, true>), dim3((unsigned)nb), dim3(1024), 0, st, sa);
         } else if (d->filter_mode == CVX_T2S_FILTER_TOP_P) hipLaunchKernelGGL(sample_kernel<FILT_TOP_P>, dim3((unsigned)nb), dim3(1024), 0, st, sa);
         else hipLaunchKernelGGL(sample_kernel<FILT_TOP_K>, dim3((unsigned)nb), dim3(1024), 0, st, sa);
+    }
+    if (mixed && n_steps == 0) {
+        const SampleArgs sa{d->logits, d->uniforms, d->emb, d->x, d->tokens, d->state, d->queue, d->dialogues, d->start, nb, d->uniform_steps,
+                            d->vocab, d->dim_emb, d->streams, d->max_len, d->top_k, d->vocab - 1, 1.0f, d->cfg_scale, d->top_p, logprobs};
+        hipLaunchKernelGGL(mixed_schedule_kernel, dim3(1), dim3(1024), 0, st, sa);
     }
     CVX_CHECK_LAUNCH("cvx_t2s_decode_steps");
     return CVX_OK;
@@ -1708,6 +1878,35 @@ extern "C" int cvx_t2s_decode_steps_per_dialogue(const cvx_t2s_decoder* d, const
                 "t2s_decode_per_dialogue: n_records = %d rows for %d dialogue records / %d slots", per->n_records, d->n_dialogues, d->batch);
     const PerArgs pa{static_cast<const int*>(per->table), per->n_records};
     return t2s_decode_run(d, n_steps, sc ? sc->logprobs : nullptr, s, nullptr, nullptr, &pa);
+}
+
+extern "C" int cvx_t2s_decode_steps_mixed(const cvx_t2s_decoder* d, const cvx_t2s_scoring* sc, const cvx_t2s_per_dialogue* per,
+                                          const cvx_t2s_mixed* mx, int32_t n_steps, cvx_stream_t s)
+{
+    CVX_REQUIRE(mx && mx->struct_size == sizeof(cvx_t2s_mixed), "t2s_decode_mixed: cvx_t2s_mixed.struct_size = %u, this library knows %u",
+                mx ? mx->struct_size : 0u, (unsigned)sizeof(cvx_t2s_mixed));
+    CVX_REQUIRE(per && per->struct_size == sizeof(cvx_t2s_per_dialogue),
+                "t2s_decode_mixed: cvx_t2s_per_dialogue.struct_size = %u, this library knows %u", per ? per->struct_size : 0u,
+                (unsigned)sizeof(cvx_t2s_per_dialogue));
+    CVX_REQUIRE(per->table && per->n_records >= 1, "t2s_decode_mixed: null table or n_records = %d < 1", per->n_records);
+    CVX_REQUIRE(!sc || sc->struct_size == sizeof(cvx_t2s_scoring), "t2s_decode_mixed: cvx_t2s_scoring.struct_size = %u, this library knows %u",
+                sc ? sc->struct_size : 0u, (unsigned)sizeof(cvx_t2s_scoring));
+    CVX_REQUIRE(!sc || sc->logprobs, "t2s_decode_mixed: null logprobs");
+    const int rc = t2s_validate(d, n_steps, true);
+    if (rc != CVX_OK) return rc;
+    CVX_REQUIRE(!sc || sc->logprob_len == d->max_len, "t2s_decode_mixed: logprob_len = %d, the rows of logprobs are laid out like those "
+                "of tokens (max_len = %d floats)", sc ? sc->logprob_len : 0, d->max_len);
+    CVX_REQUIRE(d->queue, "t2s_decode_mixed: the scheduler hands out records from the dialogue queue (queue must not be NULL)");
+    CVX_REQUIRE(!(d->cfg_scale > 1.f), "t2s_decode_mixed: cfg_scale = %g > 1 asks for the launch-wide pair layout; here the layout is per "
+                "record (flag bit 2) and the scale comes from the table", (double)d->cfg_scale);
+    CVX_REQUIRE(per->n_records >= d->n_dialogues, "t2s_decode_mixed: n_records = %d rows for %d dialogue records", per->n_records,
+                d->n_dialogues);
+    CVX_REQUIRE(mx->n_guided >= 0 && 2 * (int64_t)mx->n_guided <= d->n_dialogues,
+                "t2s_decode_mixed: n_guided = %d guided utterances take two records each of the %d", mx->n_guided, d->n_dialogues);
+    CVX_REQUIRE(mx->n_guided == 0 || (d->streams == 1 && d->batch >= 2),
+                "t2s_decode_mixed: guided records need a one-output model and two slots (streams = %d, batch = %d)", d->streams, d->batch);
+    const PerArgs pa{static_cast<const int*>(per->table), per->n_records};
+    return t2s_decode_run(d, n_steps, sc ? sc->logprobs : nullptr, s, nullptr, nullptr, &pa, true);
 }
 
 extern "C" int cvx_t2s_beam_steps(const cvx_t2s_decoder* d, const cvx_t2s_beam* bm, int32_t n_steps, cvx_stream_t s)

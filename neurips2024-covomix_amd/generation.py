@@ -84,6 +84,8 @@ def build_parser() -> ArgumentParser:
                    "refilled slots and keep the one the model finds most likely (largest mean token log-probability; 1 = off: today's files)")
     p.add_argument("--t2s_best_of_temperatures", type=str, default=None, help="extension: T1,T2,... - --t2s_best_of with one temperature per "
                    "candidate: candidate c of every turn is decoded at temperature c (implies --t2s_best_of = their number)")
+    p.add_argument("--t2s_mixed_guidance", action="store_true", help="extension: turns whose side files make some of them guided and "
+                   "others not are decoded in ONE call through one slot pool instead of two calls (the same files either way)")
     p.add_argument("--t2s_beam_size", type=int, default=0, help="extension: beam search with this many hypotheses per turn (1..16) instead of "
                    "sampling - deterministic: no draws, temperature and filter unused; not together with --t2s_best_of > 1 or guidance "
                    "(0 = off: sampling, today's files)")
@@ -219,6 +221,8 @@ def t2s_sampling_kwargs(args) -> dict:
         if best_of > 1 or kw.get("cond_scale", 1.0) > 1.0:
             raise ValueError("--t2s_beam_size does not combine with --t2s_best_of > 1 or guidance (--t2s_cond_scale > 1)")
         kw["beam_search_decode"], kw["beam_size"] = True, beam
+    if getattr(args, "t2s_mixed_guidance", False):
+        kw["mixed_guidance"] = True
     return kw
 
 
@@ -290,7 +294,7 @@ def _predict_turns(work, t2s, device, seed: int, slots: int = 64, sampling=None,
     with its OWN stream of uniforms (seeded from (--seed, name, turn)): the tokens do not depend on batching or ranks.
     sampling: the --t2s_* flags as keywords (t2s_sampling_kwargs).  text_dir: where the turns' optional side files live
     (_turn_side_files): per-turn settings and prefixes - the turns still share the slots (t2s.generate_many(settings=, prefixes=));
-    guided and unguided turns run as two calls.  Without side files nothing changes."""
+    guided and unguided turns run as two calls, or as one with --t2s_mixed_guidance.  Without side files nothing changes."""
     out, todo, side = {}, [], {}
     for name, k, (kind, v) in work:
         if kind == "sem":
@@ -336,11 +340,13 @@ def _predict_turns(work, t2s, device, seed: int, slots: int = 64, sampling=None,
                 for (name, k, _), t in zip(part, toks):
                     out[(name, k)] = t.cpu().numpy().astype(np.int64)
                 continue
-            # turns with side files: every turn's own keywords as lists; guided and unguided turns do not share a launch - two calls
+            # turns with side files: every turn's own keywords as lists; guided and unguided turns do not share a launch - two calls -
+            # unless --t2s_mixed_guidance puts them into one slot pool (one call, the same tokens)
             per = [_turn_sampling(sampling or {}, side.get((name, k), (None, None))[0]) for name, k, _ in part]
             rest = {k_: v for k_, v in (sampling or {}).items() if k_ not in ("temprature", "cond_scale", "filter_logits_fn", "filter_fn_kwargs")}
-            for guided in (False, True):
-                sel = [i for i, kw_ in enumerate(per) if (kw_.get("cond_scale", 1.0) > 1.0) == guided]
+            one_call = bool((sampling or {}).get("mixed_guidance"))
+            for guided in ((None,) if one_call else (False, True)):
+                sel = [i for i, kw_ in enumerate(per) if one_call or (kw_.get("cond_scale", 1.0) > 1.0) == guided]
                 if not sel:
                     continue
                 pres = []

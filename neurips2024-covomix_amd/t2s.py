@@ -23,6 +23,9 @@ through the same decode slots (score_many) and the mean token log-probability be
            of decode slots with CONTINUOUS BATCHING: an utterance that has sampled its eos (text2semantic.py:803-818) frees
            its slot, and the sampling kernel of that very step hands the slot the next pending utterance (device-side
            queue, no host round trip) - real dialogues end at different steps, and a lock-step batch would run half empty.
+           With mixed_guidance=True guided utterances (two slots each: text context / null context) and unguided ones (one slot)
+           share that pool: a one-block scheduler launch behind the sampling kernel hands idle slots to the queue head, a guided
+           utterance taking ANY two (cvx_t2s_decode_steps_mixed; `mixed_schedule` replays the policy on the host).
 
 The reference's rotary embedding rotates interleaved pairs (2i, 2i+1) (rotary_embedding_torch.py:25-41); the kernels
 rotate half-split pairs (i, i+32).  Permuting the rows of to_q and to_k inside every head (the same permutation on
@@ -183,19 +186,22 @@ SETTING_FIELDS = UtteranceSettings._fields
 
 
 def check_settings(settings, n: int, vocab: int, streams: int = 1, temperature: float = 1.0, filter_logits_fn="top_k", filter_fn_kwargs=None,
-                   cond_scale: float = 1.0) -> list:
+                   cond_scale: float = 1.0, mixed: bool = False) -> list:
     """The per-utterance settings of generate_many resolved against the call's scalars: -> n tuples (temperature, (mode, k, thres),
     cond_scale).  settings: n entries, each None (the scalars apply), a mapping or a record with any of the fields of UtteranceSettings
     (an absent or None field takes the scalar; a filter_logits_fn without filter_fn_kwargs takes that filter's defaults, not the call's
     kwargs of another filter).  ValueError for another length, an unknown field, a temperature < 0 (or NaN), whatever `filter_setting`
     refuses, a cond_scale <= 1 in a guided call (the call's cond_scale > 1) and a cond_scale other than 1 in an unguided call: the slot-pair
     layout of guidance belongs to the launch, so guided and unguided utterances do not share one - make two calls.  NotImplementedError for
-    guidance on a two-output model, as everywhere.  Pure host code."""
+    guidance on a two-output model, as everywhere.  Pure host code.
+    mixed (generate_many(mixed_guidance=True): the pair layout belongs to the dialogue record there): the call's cond_scale is only the
+    default, and every utterance may have a scale of exactly 1 (unguided) or > 1 (guided); any other value (< 1, NaN) is a ValueError,
+    and any scale > 1 on a two-output model a NotImplementedError."""
     settings = list(settings)
     if len(settings) != n:
         raise ValueError(f"settings: {len(settings)} entries for {n} utterances")
     guided = float(cond_scale) > 1.0
-    if guided and streams != 1:
+    if guided and streams != 1 and not mixed:
         raise NotImplementedError("guidance (cond_scale > 1) on a two-output model: the reference cannot run it (generate_batch)")
     out = []
     for j, e in enumerate(settings):
@@ -222,6 +228,13 @@ def check_settings(settings, n: int, vocab: int, streams: int = 1, temperature: 
         except ValueError as err:
             raise ValueError(f"settings[{j}]: {err}") from None
         c = float(cond_scale if e.get("cond_scale") is None else e["cond_scale"])
+        if mixed:
+            if not c >= 1.0:
+                raise ValueError(f"settings[{j}]: cond_scale = {c}: an utterance is unguided (exactly 1) or guided (> 1)")
+            if c > 1.0 and streams != 1:
+                raise NotImplementedError("guidance (cond_scale > 1) on a two-output model: the reference cannot run it (generate_batch)")
+            out.append((t, filt, c))
+            continue
         if guided and not c > 1.0:
             raise ValueError(f"settings[{j}]: cond_scale = {c} in a guided call (cond_scale > 1): guided and unguided utterances do not share "
                              "a launch - make two calls")
@@ -252,6 +265,74 @@ def settings_rows(resolved, prefix_lens=None) -> torch.Tensor:
     if prefix_lens is not None:
         rows[:, 5] = torch.tensor([int(x) for x in prefix_lens], dtype=torch.int32)
     return rows
+
+
+def mixed_records(kinds) -> list:
+    """The dialogue record of every utterance of a mixed call (cvx_t2s_decode_steps_mixed): a guided utterance (kinds[j] true) takes two
+    records - its text half, which is the one returned, and the null half behind it - an unguided one takes one.  -> n + 1 numbers, the
+    last one the number of records."""
+    first, r = [], 0
+    for g in kinds:
+        first.append(r)
+        r += 2 if g else 1
+    return first + [r]
+
+
+def mixed_windows(kinds, window: int = WINDOW) -> list:
+    """Utterance ranges [(begin, end), ...] of a mixed call cut so that every range holds at most `window` dialogue RECORDS and no
+    guided pair is cut: a range ends where the next utterance would not fit whole."""
+    out, begin, used = [], 0, 0
+    for j, g in enumerate(kinds):
+        need = 2 if g else 1
+        if used + need > window:
+            out.append((begin, j))
+            begin, used = j, 0
+        used += need
+    if begin < len(kinds):
+        out.append((begin, len(kinds)))
+    return out
+
+
+def mixed_schedule(kinds, lengths, slots: int, n_records: Optional[int] = None) -> list:
+    """The device's scheduler (mixed_schedule_kernel; include/covomix_hip.h, cvx_t2s_decode_steps_mixed) replayed on the host, given the
+    number of steps every utterance takes: -> per utterance (slot, null slot or None, start step), or None for an utterance that is
+    never taken.  kinds[j]: utterance j is guided; lengths[j] >= 1: its steps; slots: the decode slots.  The policy: after every step
+    (and once before the first: start step 0) the idle slots F in ascending order serve the queue head - an unguided record takes the
+    lowest slot of F; a guided one takes the two lowest (text half, null half) and WAITS, with everything behind it, while F holds fewer
+    than two.  An utterance that starts at step s with L steps frees its slot(s) for the scheduler run after step s + L.
+    n_records (default: all): the queue's record count - a guided head whose second record lies beyond it is never taken, nor is
+    anything behind it.  For tests and tools; the decode does not call it."""
+    n = len(kinds)
+    if len(lengths) != n or slots < 1 or any(int(x) < 1 for x in lengths):
+        raise ValueError("mixed_schedule: one length >= 1 per utterance and at least one slot")
+    first = mixed_records(kinds)
+    total = first[-1] if n_records is None else int(n_records)
+    out: list = [None] * n
+    free = list(range(int(slots)))
+    busy: list = []                        # (step at which the slots idle, slots)
+    h, t = 0, 0
+    while True:
+        while h < n and free and first[h] < total:
+            if not kinds[h]:
+                s0 = free.pop(0)
+                out[h] = (s0, None, t)
+                busy.append((t + int(lengths[h]), [s0]))
+            else:
+                if first[h] + 1 >= total or len(free) < 2:
+                    break
+                s0, s1 = free.pop(0), free.pop(0)
+                out[h] = (s0, s1, t)
+                busy.append((t + int(lengths[h]), [s0, s1]))
+            h += 1
+        if not busy:
+            break
+        t = min(e for e, _ in busy)
+        for e, ss in busy:
+            if e == t:
+                free += ss
+        busy = [x for x in busy if x[0] != t]
+        free.sort()
+    return out
 
 
 def check_prefixes(prefixes, n: int, streams: int, vocab: int, limits, forced=None) -> list:
@@ -490,15 +571,22 @@ class TextToSemanticDecoder:
         return dec
 
     def _launch_steps(self, temperature: float, batch: int, n: int, cfg_scale: float, queue: bool, filt, nd: int, scored: bool,
-                      per: bool = False) -> None:
+                      per: bool = False, mixed: Optional[int] = None) -> None:
         """n token steps on the current stream.  scored: cvx_t2s_decode_steps_scored (log-probs of every step's token into
         buf["logprobs"], forced dialogues honoured); else cvx_t2s_decode_steps, exactly as before that entry existed.
         per: cvx_t2s_decode_steps_per_dialogue - the settings come from buf["per"], one row per dialogue record; temperature and filt
-        are not looked at and cfg_scale only says whether the slots run in guided pairs."""
+        are not looked at and cfg_scale only says whether the slots run in guided pairs.
+        mixed (with per and queue): cvx_t2s_decode_steps_mixed with that many guided utterances among the nd records - the pair layout
+        comes from the records; n = 0 runs its scheduler alone, which arms idle slots."""
         dec = self._descriptor(temperature, batch, cfg_scale, queue, filt, nd)
         if per:
             sc = _lib.T2SScoring(C.sizeof(_lib.T2SScoring), self.max_length, self.buf["logprobs"].data_ptr()) if scored else None
             pd = _lib.T2SPerDialogue(C.sizeof(_lib.T2SPerDialogue), self.buf["per"].shape[0], self.buf["per"].data_ptr())
+            if mixed is not None:
+                mx = _lib.T2SMixed(C.sizeof(_lib.T2SMixed), int(mixed))
+                _lib.check(_lib.load().cvx_t2s_decode_steps_mixed(C.byref(dec), C.byref(sc) if scored else None, C.byref(pd), C.byref(mx), n,
+                                                                  ops._stream()), "cvx_t2s_decode_steps_mixed")
+                return
             _lib.check(_lib.load().cvx_t2s_decode_steps_per_dialogue(C.byref(dec), C.byref(sc) if scored else None, C.byref(pd), n, ops._stream()),
                        "cvx_t2s_decode_steps_per_dialogue")
             return
@@ -509,9 +597,9 @@ class TextToSemanticDecoder:
         _lib.check(_lib.load().cvx_t2s_decode_steps_scored(C.byref(dec), C.byref(sc), n, ops._stream()), "cvx_t2s_decode_steps_scored")
 
     def _run_steps(self, temperature: float, batch: int, n: int, cfg_scale: float = 1.0, queue: bool = False, filt=None, nd: int = 0,
-                   scored: bool = False, per: bool = False) -> None:
+                   scored: bool = False, per: bool = False, mixed: Optional[int] = None) -> None:
         """n token steps on the current stream without a graph."""
-        self._launch_steps(temperature, batch, n, cfg_scale, queue, filt, nd, scored, per)
+        self._launch_steps(temperature, batch, n, cfg_scale, queue, filt, nd, scored, per, mixed)
 
     def _uniform_view(self, n: int) -> torch.Tensor:
         """[n, steps, streams, vocab] view of the uniform draws of the first n dialogues"""
@@ -586,24 +674,30 @@ class TextToSemanticDecoder:
         return self._read_state(nb)
 
     def _graph(self, temperature: float, batch: int, cfg_scale: float = 1.0, queue: bool = False, filt=None, nd: int = 0, scored: bool = False,
-               per: bool = False):
+               per: bool = False, mixed: Optional[int] = None):
         """The captured graph of CHUNK token steps for this (batch, stream CU count, mode, filter, scoring); captured on first use.  (nd, the
         number of dialogue records, is only validated by the C call: it is not part of the key.)  Capturing runs the
         steps once outside the capture (module load, kernel attributes): callers get their graph BEFORE they set up the decode state -
         the warm-up runs on idle slot records (position max_length: the sampling kernel returns at once, every other kernel clamps).
         per: the per-dialogue chain, whose settings live in a device table - its key carries a "per" marker INSTEAD of (temperature, scale,
-        filter), so one graph per (batch, CUs, guided?, queue, scored) serves every mix of settings."""
+        filter), so one graph per (batch, CUs, guided?, queue, scored) serves every mix of settings.
+        mixed: the mixed chain (cvx_t2s_decode_steps_mixed) - its key is ("mixed", batch, CUs, scored): the launches depend on neither the
+        settings nor on how many utterances are guided."""
         filt = filt or self._default_filter
         key = (temperature, batch, cfg_scale, ops.stream_cus(), queue, self._gen, filt, bool(scored))   # (the kernels' shape follows the CUs the stream owns)
         if per:
             key = ("per", batch, cfg_scale > 1.0, ops.stream_cus(), queue, self._gen, bool(scored))
+        if mixed is not None:
+            key = ("mixed", batch, ops.stream_cus(), self._gen, bool(scored))
         g = self._graphs.get(key)
         if g is not None:
             return g
 
         def launch():
-            self._launch_steps(temperature, batch, CHUNK, cfg_scale, queue, filt, nd, scored, per)
+            self._launch_steps(temperature, batch, CHUNK, cfg_scale, queue, filt, nd, scored, per, mixed)
         self.buf["state"].copy_(self._slot_records([]))
+        if mixed is not None:                          # (the scheduler of the warm-up steps must find nothing to hand out)
+            self.buf["queue"].zero_()
         launch()                                       # warm-up outside capture
         cur = torch.cuda.current_stream()
         if self._cap is None:
@@ -620,13 +714,13 @@ class TextToSemanticDecoder:
         return g
 
     def _run_chunk(self, temperature: float, batch: int = 1, cfg_scale: float = 1.0, queue: bool = False, filt=None, nd: int = 0,
-                   scored: bool = False, per: bool = False) -> None:
+                   scored: bool = False, per: bool = False, mixed: Optional[int] = None) -> None:
         """CHUNK token steps on the current stream: a graph replay of the per-launch path (the graph must exist - `_graph` - unless
         CVX_GRAPH=0 asks for plain launches)."""
         if os.environ.get("CVX_GRAPH", "1") != "1":
-            self._run_steps(temperature, batch, CHUNK, cfg_scale, queue, filt, nd, scored, per)
+            self._run_steps(temperature, batch, CHUNK, cfg_scale, queue, filt, nd, scored, per, mixed)
             return
-        self._graph(temperature, batch, cfg_scale, queue, filt, nd, scored, per).replay()
+        self._graph(temperature, batch, cfg_scale, queue, filt, nd, scored, per, mixed).replay()
 
     def _contexts(self, sources, rows=None) -> list:
         """encoder + the cross-attention k/v of the utterances into dialogue rows `rows` (default 0, 1, ...): [null | to_kv(enc)]
@@ -783,7 +877,7 @@ class TextToSemanticDecoder:
     def generate_many(self, sources, uniforms=None, max_length: Optional[int] = None, temperature: float = 1.0,
                       generator: Optional[torch.Generator] = None, slots: int = 32, ignore_eos: bool = False, limits=None, on_done=None,
                       cond_scale: float = 1.0, filter_logits_fn="top_k", filter_fn_kwargs=None, return_logprobs: bool = False, forced=None,
-                      settings=None, prefixes=None):
+                      settings=None, prefixes=None, mixed_guidance: bool = False):
         """Decode ANY number of utterances through `slots` decode slots with continuous batching: every utterance runs the
         reference's loop (text2semantic.py:749-848) from position 0 to its first eos (:803-818) or its step limit, and the slot it
         ran in takes the next pending utterance in the sampling kernel of that very step (cvx_t2s_decoder.queue) - utterances end
@@ -810,13 +904,25 @@ class TextToSemanticDecoder:
         call's scalar (`check_settings`).  Utterances with different settings share the slots, the queue and ONE captured graph: the
         sampling kernel reads the settings of the dialogue a slot decodes from a device table (cvx_t2s_decode_steps_per_dialogue), and
         every utterance gets, bit for bit, what it gets alone with its settings as the call's scalars.  Guided and unguided utterances do
-        not share a call (ValueError): the slot-pair layout belongs to the launch.
+        not share a call (ValueError): the slot-pair layout belongs to the launch - unless mixed_guidance (below) is on.
         prefixes (default None): one entry per utterance - None, or int64 [S, P] tokens, 1 <= P < that utterance's step limit, none of
         them an eos (`check_prefixes`): the decode CONTINUES from them.  They are copied into the utterance's token row; its first P steps
         read them instead of sampling (no uniforms are read there; the uniforms stay indexed by position), and from position P on it
         samples as ever - so a prefix cut from an earlier result, with the same uniforms, reproduces the rest of that result.  `streams`
         starts with the prefix; under return_logprobs the positions below P hold the prefix tokens' teacher-forced log-probs (what
-        score_many gives them).  A prefix for a forced utterance is a ValueError."""
+        score_many gives them).  A prefix for a forced utterance is a ValueError.
+        mixed_guidance (default False: nothing changes, graph for graph): guided and unguided utterances share the call, the slots, the
+        queue and one captured graph (cvx_t2s_decode_steps_mixed).  cond_scale is then only the default of `settings`: an utterance whose
+        scale is exactly 1 is unguided and takes one dialogue record and one slot, one whose scale is > 1 is guided and takes two records
+        and two slots - ANY two: a one-block scheduler launch behind every sampling launch hands the idle slots out in queue order, and a
+        guided utterance at the head waits until two are idle (`mixed_schedule` replays that policy).  `slots` counts slots and must be
+        >= 2 when any utterance is guided; WINDOW counts records, and windows are cut on utterance boundaries (`mixed_windows`).
+        last_records stays one record per utterance (that of the text half) and gains, as a ninth entry, the slot of the null half of a
+        guided utterance (None for an unguided one).  Every other argument keeps its meaning, and every utterance gets, bit for bit, what
+        it gets alone."""
+        if mixed_guidance:
+            return self._generate_many_mixed(sources, uniforms, max_length, temperature, generator, slots, ignore_eos, limits, on_done,
+                                             cond_scale, filter_logits_fn, filter_fn_kwargs, return_logprobs, forced, settings, prefixes)
         d = self.d
         S, V = d["streams"], d["vocab"]
         n = len(sources)
@@ -964,6 +1070,160 @@ class TextToSemanticDecoder:
         cap = (sum(lim) + CHUNK - 1) // CHUNK + 4          # (one slot decoding everything: cannot be reached)
         while not all(seen) and i < cap:
             self._run_chunk(temperature, nb, cond_scale, True, filt, nrec, scored, per)
+            k = i & 1
+            self._mirror_push(k, b["dialogues"][:nrec], via_helper)
+            if pending is not None:
+                collect(self._mirror_pull(pending, nrec))
+            pending = k
+            i += 1
+        if not all(seen) and pending is not None:
+            collect(self._mirror_pull(pending, nrec))
+        if pending is not None:
+            self._pin_ev[pending].synchronize()
+        finish(True)
+        if not all(seen):
+            raise RuntimeError(f"text2semantic continuous decode: {seen.count(False)} of {n} utterances did not finish in {i} chunks")
+        return out
+
+    def _generate_many_mixed(self, sources, uniforms, max_length, temperature, generator, slots, ignore_eos, limits, on_done, cond_scale,
+                             filter_logits_fn, filter_fn_kwargs, return_logprobs, forced, settings, prefixes):
+        """generate_many(mixed_guidance=True): the records are laid out by prefix sum (`mixed_records`: one per unguided utterance; text
+        half and null half per guided one), everything that belongs to an utterance - uniforms, tokens, log-probs, prefix, forced tokens -
+        lives in its text record, the settings row is mirrored onto the null record, and the slots are armed by the device's scheduler (a
+        0-step call on idle slots), so the hand-out policy exists in one place."""
+        d = self.d
+        S, V = d["streams"], d["vocab"]
+        n = len(sources)
+        scored = bool(return_logprobs)
+        if forced is not None:
+            if not scored or len(forced) != n:
+                raise ValueError("forced: one entry per utterance, with return_logprobs=True")
+            if all(f is None for f in forced):
+                forced = None
+        if forced is not None:
+            forced = list(forced)
+            fi = [j for j in range(n) if forced[j] is not None]
+            for j, t in zip(fi, check_targets([forced[j] for j in fi], S, V, self.max_length)):
+                forced[j] = t
+        filter_setting(filter_logits_fn, filter_fn_kwargs, V)
+        resolved = check_settings([None] * n if settings is None else settings, n, V, S, temperature, filter_logits_fn, filter_fn_kwargs,
+                                  float(cond_scale), mixed=True)
+        if prefixes is not None and len(list(prefixes)) != n:
+            raise ValueError(f"prefixes: {len(list(prefixes))} entries for {n} utterances")
+        kinds = [r[2] > 1.0 for r in resolved]
+        if any(kinds) and int(slots) < 2:
+            raise ValueError(f"slots = {slots}: a guided utterance takes two decode slots")
+        if n == 0:
+            return []
+        wins = mixed_windows(kinds)
+        if len(wins) > 1:          # (the context k/v, uniforms and token rows of every queued record are resident: bounded windows)
+            out, recs = [], []
+            cut = lambda x, w0, w1: None if x is None else list(x)[w0:w1]
+            for w0, w1 in wins:
+                out += self._generate_many_mixed(sources[w0:w1], cut(uniforms, w0, w1), max_length, temperature, generator, slots, ignore_eos,
+                                                 cut(limits, w0, w1), None if on_done is None else (lambda j, r, w0=w0: on_done(w0 + j, r)),
+                                                 cond_scale, filter_logits_fn, filter_fn_kwargs, return_logprobs, cut(forced, w0, w1),
+                                                 cut(settings, w0, w1), cut(prefixes, w0, w1))
+                recs += self.last_records
+            self.last_records = recs
+            return out
+        first = mixed_records(kinds)
+        nrec, ng = first[-1], sum(kinds)
+        text = first[:-1]                                      # the record that carries utterance j
+        nulls = [text[j] + 1 for j in range(n) if kinds[j]]
+        nb = max(1, min(int(slots), MAX_BATCH, nrec))
+        max_len = min(int(max_length or self.max_length), self.max_length)
+        us = None
+        is_forced = [forced is not None and forced[j] is not None for j in range(n)]
+        if uniforms is not None:
+            us = [None if (u is None and is_forced[j]) else u.to(self.device, torch.float32).reshape(u.shape[0], S, V) for j, u in enumerate(uniforms)]
+            max_len = min([max_len] + [u.shape[0] for u in us if u is not None])
+        lim = [max_len] * n if limits is None else [max(1, min(int(x), max_len)) for x in limits]
+        if max_len <= 0:
+            raise ValueError("generate_many needs at least one step")
+        span = max_len
+        if forced is not None:
+            lim = [forced[j].shape[1] if is_forced[j] else lim[j] for j in range(n)]
+            span = max(span, max(lim))
+        pre = check_prefixes([None] * n if prefixes is None else prefixes, n, S, V, lim, forced)
+        self._ensure(nb, nrec, max_len, scored)
+        b = self.buf
+        self._graph(1.0, nb, 1.0, True, None, nrec, scored, True, ng)
+        ctx_text = self._contexts(sources, text)
+        ctx = [1] * nrec
+        for j in range(n):
+            ctx[text[j]] = ctx_text[j]
+        if nulls:                  # the null half: the learned null key / value row only (every context key masked out)
+            ni = ops.h2d(torch.tensor(nulls, dtype=torch.int64), self.device)
+            for L in self.dec:
+                L["kv_c"][:, 0].index_copy_(0, ni, L["null"][None, :].expand(len(nulls), -1))
+        uall = self._uniform_view(nrec)                        # the draws of utterance j live in its text record
+        if us is None:
+            if not all(is_forced):                             # (a forced dialogue reads no draws: a pure scoring call draws none)
+                ti = ops.h2d(torch.tensor(text, dtype=torch.int64), self.device)
+                uall[:, :max_len].index_copy_(0, ti, torch.rand(n, max_len, S, V, device=self.device, generator=generator))
+        else:
+            for j, u in enumerate(us):
+                if u is not None:
+                    uall[text[j], :max_len].copy_(u[:max_len])
+        flags = [(_lib.T2S_FLAG_FORCED if is_forced[j] else (_lib.T2S_FLAG_IGNORE_EOS if ignore_eos else 0)) |
+                 (_lib.T2S_FLAG_GUIDED if kinds[j] else 0) for j in range(n)]
+        for j in range(n):         # the token row of a forced / prefixed dialogue holds its tokens before its first step
+            if is_forced[j]:
+                b["tokens"][text[j], :, :lim[j]].copy_(ops.h2d(forced[j], self.device))
+            elif pre[j] is not None:
+                b["tokens"][text[j], :, :pre[j].shape[1]].copy_(ops.h2d(pre[j], self.device))
+        owner = [j for j in range(n) for _ in range(2 if kinds[j] else 1)]           # record -> utterance
+        rows = settings_rows(resolved, [0 if p_ is None else p_.shape[1] for p_ in pre])
+        b["per"][:nrec].copy_(ops.h2d(rows[torch.tensor(owner, dtype=torch.int64)].contiguous(), self.device))
+        rec = torch.tensor([[ctx[r], lim[owner[r]], flags[owner[r]], 0, 0, 0, 0, 0] for r in range(nrec)], dtype=torch.int32)
+        b["dialogues"][:nrec].copy_(rec)
+        b["queue"].copy_(torch.tensor([0, nrec], dtype=torch.int32))
+        b["state"].copy_(self._slot_records([]))
+        self._run_steps(1.0, nb, 0, 1.0, True, None, nrec, scored, True, ng)         # the scheduler alone: arms the first slots
+        self._mirror_setup()
+        via_helper = ops.is_partition_stream()
+        out: list = [None] * n
+        seen = [False] * n
+        tok_pin = torch.empty(n, S, span, dtype=torch.int64).pin_memory()
+        lp_pin = torch.empty(n, S, span, dtype=torch.float32).pin_memory() if scored else None
+        copies: list = []                                  # (j, steps, event) in flight on the helper stream
+        eos = V - 1
+
+        def finish(block: bool):
+            while copies and (block or copies[0][2].query()):
+                j, length, ev = copies.pop(0)
+                ev.synchronize()
+                streams = tok_pin[j, :, :length].clone()
+                after = (streams == eos).cumsum(dim=-1) > 0          # mask_after_eos (text2semantic.py:73-76)
+                after = torch.nn.functional.pad(after, (1, -1), value=False)
+                flat = streams.masked_fill(after, PAD_ID).reshape(-1)
+                out[j] = (flat[flat != PAD_ID], streams)
+                if scored:
+                    out[j] += (lp_pin[j, :, :length].clone(),)
+                if on_done is not None:
+                    on_done(j, out[j])
+
+        def collect(records):
+            self.last_records = [list(records[text[j]]) + [records[text[j] + 1][5] if kinds[j] else None] for j in range(n)]
+            fresh = [j for j in range(n) if not seen[j] and records[text[j]][3] >= 2]
+            if fresh:
+                with torch.cuda.stream(self._helper):
+                    for j in fresh:
+                        seen[j] = True
+                        length = records[text[j]][4]
+                        tok_pin[j, :, :length].copy_(b["tokens"][text[j], :, :length], non_blocking=True)
+                        if scored:
+                            lp_pin[j, :, :length].copy_(b["logprobs"][text[j], :, :length], non_blocking=True)
+                        ev = torch.cuda.Event()
+                        ev.record()
+                        copies.append((j, length, ev))
+            finish(False)
+
+        i, pending = 0, None
+        cap = (sum(lim) + CHUNK - 1) // CHUNK + 4          # (one slot decoding everything: cannot be reached)
+        while not all(seen) and i < cap:
+            self._run_chunk(1.0, nb, 1.0, True, None, nrec, scored, True, ng)
             k = i & 1
             self._mirror_push(k, b["dialogues"][:nrec], via_helper)
             if pending is not None:
@@ -1288,7 +1548,7 @@ class TextToSemanticDecoder:
             out += self._beam_queue_window(srcs[w:w + win], B, lim[w:w + win], float(length_penalty), int(slots))
         return out if return_beams else [h[0] for h in out]
 
-    def score_many(self, sources, targets, cond_scale: float = 1.0, slots: int = 64):
+    def score_many(self, sources, targets, cond_scale=1.0, slots: int = 64, mixed_guidance: bool = False):
         """Teacher-forced scoring: the log-probability the model gives every token of targets[j] under the text sources[j] - what the
         reference's TextToSemantic.forward(..., return_loss=True) averages (text2semantic.py), position by position.  targets[j]: int64
         [S, L_j], the `streams` that `generate` returns; -> list of float32 [S, L_j] host tensors: entry [s, t] is the log-softmax, at
@@ -1296,10 +1556,23 @@ class TextToSemanticDecoder:
         models).  The targets run as forced dialogues through `slots` continuously refilled decode slots, in windows of WINDOW records as
         generate_many; the values are bit-identical whatever the slots, the batch or the neighbours - and equal, bit for bit, the log-probs
         `generate(return_logprobs=True)` returned when it sampled those tokens.  ValueError for L_j < 1, L_j > max_length or a token
-        outside [0, vocab); NotImplementedError for guidance on a two-output model."""
+        outside [0, vocab); NotImplementedError for guidance on a two-output model.
+        mixed_guidance: cond_scale may be a list, one scale per utterance - 1 (unguided) or > 1 (guided) - and all of them are scored in
+        one generate_many(mixed_guidance=True) call."""
         sources, targets = list(sources), list(targets)
         if len(sources) != len(targets):
             raise ValueError(f"score_many: {len(sources)} sources, {len(targets)} targets")
+        if mixed_guidance:
+            scales = [float(c) for c in cond_scale] if isinstance(cond_scale, (list, tuple)) else [float(cond_scale)] * len(sources)
+            if len(scales) != len(sources):
+                raise ValueError(f"score_many: {len(scales)} cond_scale values for {len(sources)} utterances")
+            check_settings([{"cond_scale": c} for c in scales], len(scales), self.d["vocab"], self.d["streams"], mixed=True)
+            tg = check_targets(targets, self.d["streams"], self.d["vocab"], self.max_length)
+            if not tg:
+                return []
+            res = self.generate_many(sources, None, max(t.shape[1] for t in tg), 1.0, None, slots, return_logprobs=True, forced=tg,
+                                     settings=[{"cond_scale": c} for c in scales], mixed_guidance=True)
+            return [r[2] for r in res]
         if float(cond_scale) > 1.0 and self.d["streams"] != 1:
             raise NotImplementedError("guidance (cond_scale > 1) on a two-output model: the reference cannot run it (generate_batch)")
         tg = check_targets(targets, self.d["streams"], self.d["vocab"], self.max_length)

@@ -8,7 +8,12 @@ PER=1: instead, the per-dialogue sampling path (cvx_t2s_decode_steps_per_dialogu
 64 slots, eos ignored, STEPS (256) steps of graph replays: A = the scalar chain, B = every table row holding the same (default) setting,
 C = rows alternating top-k and top-p across the slots; A / B / C interleaved REPEATS (5) times in one process -> us per step, min /
 median / max of each, and the effective shader clock over the rounds (ops.clock_stamps).
-    PER=1 STEPS=256 REPEATS=5 OUT=profile.txt python tools/bench_t2s.py"""
+    PER=1 STEPS=256 REPEATS=5 OUT=profile.txt python tools/bench_t2s.py
+MIXED=1: the mixed slot pool (cvx_t2s_decode_steps_mixed) on the full-size CoSingle (one-output) model.  (a) us per step at 8 / 32 / 64
+slots, eos ignored, all records unguided: A = cvx_t2s_decode_steps_per_dialogue behind a queue, B = the mixed entry (one launch more per
+step: the scheduler), interleaved REPEATS times.  (b) 32 guided + 64 unguided utterances with step limits spread over 100..608, 64 slots:
+one generate_many(mixed_guidance=True) call against the two calls of the default path (guided, then unguided), wall time, interleaved.
+    MIXED=1 STEPS=256 REPEATS=5 OUT=profile.txt python tools/bench_t2s.py"""
 import os, sys, time, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import covomix_amd.synthetic as syn
@@ -81,8 +86,100 @@ def per_dialogue_ab():
             f.write("\n".join(lines) + "\n")
 
 
+def mixed_ab():
+    """(a) and (b) of MIXED=1 (see the module docstring)"""
+    import statistics
+    from covomix_amd.t2s import SR, check_settings, settings_rows
+    steps, reps = int(os.environ.get("STEPS", "256")), int(os.environ.get("REPEATS", "5"))
+    sd = {k: torch.from_numpy(v) for k, v in syn.t2s_state_dict(syn.t2s_param_shapes(two_output=False, dim=512, dim_target=512), seed=0).items()}
+    m = TextToSemanticDecoder(sd, dev, max_length=2048)
+    V, S = m.d["vocab"], m.d["streams"]
+    g = torch.Generator().manual_seed(3)
+    med = statistics.median
+    lines = [f"text2semantic, full-size CoSingle (synthetic weights), device: {torch.cuda.get_device_name(0)}",
+             f"(a) us per step, {steps} steps = {steps // CHUNK} graph replays of {CHUNK} steps between two synchronisations, eos ignored, every "
+             f"record unguided, one record per slot behind a queue; {reps} rounds A B A B ...: A = cvx_t2s_decode_steps_per_dialogue (34 launches "
+             "per step), B = cvx_t2s_decode_steps_mixed (35: + the scheduler)"]
+    for nb in (8, 32, 64):
+        srcs = [torch.randint(1, 30000, (1, 48), generator=g) for _ in range(nb)]
+        m._ensure(nb, nb, steps)
+        m._graph(1.0, nb, 1.0, True, None, nb, False, True)
+        m._graph(1.0, nb, 1.0, True, None, nb, False, True, 0)
+        ctx = m._contexts(srcs)
+        m.buf["uniforms"].uniform_(1e-6, 1 - 1e-6)
+        m.buf["per"][:nb].copy_(settings_rows(check_settings([None] * nb, nb, V, S)).to(dev))
+        lim, flag = min(steps + CHUNK, m._steps), 1                    # (never reached; eos ignored)
+        start = m.start[None, :].expand(nb, -1)
+
+        def run(mixed):
+            rec = torch.tensor([[ctx[r], lim, flag, 0 if mixed else 1, 0, 0 if mixed else r, 0, 0] for r in range(nb)], dtype=torch.int32)
+            m.buf["dialogues"][:nb].copy_(rec)
+            if mixed:                                                   # idle slots, armed by the scheduler alone (a 0-step call)
+                m.buf["queue"].copy_(torch.tensor([0, nb], dtype=torch.int32))
+                m.buf["state"].copy_(m._slot_records([]))
+                m._run_steps(1.0, nb, 0, 1.0, True, None, nb, False, True, 0)
+            else:
+                m.buf["queue"].copy_(torch.tensor([nb, nb], dtype=torch.int32))
+                st = m._slot_records(ctx).clone()
+                st[:nb, 5], st[:nb, 6] = lim, flag
+                m.buf["state"].copy_(st)
+                m.buf["x"][:nb].copy_(start)
+            torch.cuda.synchronize(); t0 = time.perf_counter()
+            for _ in range(steps // CHUNK):
+                m._run_chunk(1.0, nb, 1.0, True, None, nb, False, True, 0 if mixed else None)
+            torch.cuda.synchronize()
+            return (time.perf_counter() - t0) / steps * 1e6, m.buf["tokens"][:nb, :, :steps].clone()
+
+        ta, tb = run(False)[1], run(True)[1]
+        assert torch.equal(ta, tb), "the mixed entry decodes other tokens than the per-dialogue entry"
+        t = {"A": [], "B": []}
+        for _ in range(reps):
+            t["A"].append(run(False)[0])
+            t["B"].append(run(True)[0])
+        for k in "AB":
+            v = sorted(t[k])
+            lines.append(f"  {nb:2d} slots  {k}  min {v[0]:7.1f}  median {med(v):7.1f}  max {v[-1]:7.1f}   all {[round(x, 1) for x in t[k]]}")
+        lines.append(f"  {nb:2d} slots  B median - A median = {med(t['B']) - med(t['A']):+.1f} us per step (A's own spread {max(t['A']) - min(t['A']):.1f})")
+    # (b)
+    n, slots = 96, 64
+    kinds = [j % 3 == 0 for j in range(n)]
+    lims = torch.randint(100, 609, (n,), generator=g).tolist()
+    srcs = [torch.randint(1, 30000, (1, 48), generator=g) for _ in range(n)]
+    gi, ui = [j for j in range(n) if kinds[j]], [j for j in range(n) if not kinds[j]]
+    sets = [{"cond_scale": 2.0 if k else 1.0} for k in kinds]
+
+    def one_call(lm):
+        return m.generate_many(srcs, max_length=608, slots=slots, ignore_eos=True, limits=lm, settings=sets, mixed_guidance=True)
+
+    def two_calls(lm):
+        a = m.generate_many([srcs[j] for j in gi], max_length=608, slots=slots, ignore_eos=True, limits=[lm[j] for j in gi], cond_scale=2.0)
+        b = m.generate_many([srcs[j] for j in ui], max_length=608, slots=slots, ignore_eos=True, limits=[lm[j] for j in ui])
+        return a, b
+    one_call([20] * n); two_calls([20] * n)                            # graphs and buffers of the timed shapes
+    t = {"one": [], "two": []}
+    for _ in range(max(1, min(reps, 3))):
+        for name, fn in (("two", two_calls), ("one", one_call)):
+            torch.cuda.synchronize(); t0 = time.perf_counter()
+            fn(lims)
+            torch.cuda.synchronize()
+            t[name].append((time.perf_counter() - t0) * 1e3)
+    useful = sum(lims)
+    lines.append(f"(b) {len(gi)} guided (scale 2.0) + {len(ui)} unguided utterances, every third one guided, step limits 100..608 (sum {useful}), eos ignored, "
+                 f"{slots} slots, wall time of the call(s) with fresh random draws, encoder included; rounds two one two one ...")
+    lines.append(f"  two calls (guided: 32 slot pairs, then unguided: 64 slots)  ms  min {min(t['two']):8.1f}  median {med(t['two']):8.1f}   all {[round(x, 1) for x in t['two']]}")
+    lines.append(f"  one mixed call (64 slots, pairs wherever two are idle)      ms  min {min(t['one']):8.1f}  median {med(t['one']):8.1f}   all {[round(x, 1) for x in t['one']]}")
+    lines.append(f"  one / two (medians) = {med(t['one']) / med(t['two']):.3f}")
+    print("\n".join(lines), flush=True)
+    if os.environ.get("OUT"):
+        with open(os.environ["OUT"], "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
 if os.environ.get("PER", "0") == "1":
     per_dialogue_ab()
+    sys.exit(0)
+if os.environ.get("MIXED", "0") == "1":
+    mixed_ab()
     sys.exit(0)
 CFG = {"cosingle": dict(two_output=False, dim=512, dim_target=512), "comix": dict(two_output=True, dim=512, dim_target=1024)}
 for name in which:
