@@ -22,11 +22,11 @@ import torch
 import torch.nn.functional as F
 
 from conftest import rel_l2
+from gemm_guarded import NAN, Guarded as _Guarded, Pair as _Pair, PairIL as _PairIL, dev, vec as _vec
 
 pytestmark = pytest.mark.gpu
 
 NO_MEDIUM, ONE_TILE, TILE192, TILE256 = 16, 4, 64, 128
-NAN = float("nan")
 TOL = 1e-6
 
 
@@ -35,73 +35,6 @@ def ops():
     assert torch.cuda.is_available()
     import covomix_amd.ops as o
     return o
-
-
-def dev():
-    return torch.device("cuda:0")
-
-
-class _Guarded:
-    """a [rows, cols] view (`.v`) at the top left of a NaN-filled [rows + 1, cols + pad] buffer"""
-
-    def __init__(self, rows, cols, dtype=torch.float32, pad=64, data=None):
-        self.rows, self.cols = rows, cols
-        self.big = torch.full((rows + 1, cols + pad), NAN, dtype=dtype, device=dev())
-        self.v = self.big[:rows, :cols]
-        if data is not None:
-            self.v.copy_(data)
-
-    def guards_untouched(self):
-        return bool(torch.isnan(self.big[:, self.cols:]).all()) and bool(torch.isnan(self.big[self.rows]).all())
-
-
-def _vec(n, data):
-    """n elements at the head of a longer NaN-filled vector"""
-    big = torch.full((n + 64,), NAN, device=dev())
-    big[:n] = data
-    return big[:n]
-
-
-class _PairIL(_Guarded):
-    """an interleaved pair (ops.SplitIL: [hi 32 | lo 32] per 32 columns) whose lines sit inside a wider, taller NaN-filled buffer"""
-
-    def __init__(self, ops, rows, cols, x=None, scale=1.0):
-        super().__init__(rows, 2 * cols, torch.float16)
-        self.il = ops.SplitIL.__new__(ops.SplitIL)
-        self.il.rows, self.il.cols, self.il.buf = rows, cols, self.v
-        self.n = cols
-        if x is not None:
-            xs = (x.float() * scale).contiguous()
-            hi = xs.half()
-            lo = (xs - hi.float()).half()
-            t = self.v.unflatten(1, (cols // 32, 2, 32))
-            t[:, :, 0] = hi.reshape(rows, cols // 32, 32)
-            t[:, :, 1] = lo.reshape(rows, cols // 32, 32)
-
-    def halves(self):
-        t = self.v.unflatten(1, (self.n // 32, 2, 32))
-        return t[:, :, 0].reshape(self.rows, self.n), t[:, :, 1].reshape(self.rows, self.n)
-
-    def value(self):
-        h, l = self.halves()
-        return h.double() + l.double()
-
-
-class _Pair:
-    """a (hi, lo) pair of plain fp16 matrices, each inside its own guarded buffer"""
-
-    def __init__(self, rows, cols):
-        self.h, self.l = _Guarded(rows, cols, torch.float16), _Guarded(rows, cols, torch.float16)
-        self.pair = (self.h.v, self.l.v)
-
-    def halves(self):
-        return self.h.v, self.l.v
-
-    def value(self):
-        return self.h.v.double() + self.l.v.double()
-
-    def guards_untouched(self):
-        return self.h.guards_untouched() and self.l.guards_untouched()
 
 
 def _weights(ops, N, K, g):
