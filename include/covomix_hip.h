@@ -376,6 +376,23 @@ int cvx_gemm_skinny_f32(const float* A, int32_t lda, const float* W, int64_t ldw
  * y_mid = y + f0*dt/2, y1 = y + dt*f_mid); `out` may alias `y`. */
 int cvx_cfg_combine_axpy_f32(const float* f_c, const float* f_n, const float* y, float cond_scale,
                              float coef, float* out, float* out2, float* out3, int64_t n, cvx_stream_t s);
+/* CFG combine + one stage of an explicit Runge-Kutta step (fixed grid, at most 4 stages), one launch per field evaluation.
+ * Per element i of rows x dim (all tensors contiguous [rows, dim]):
+ *   v = f_c[i]
+ *   f_n != NULL:  s = row_scale ? row_scale[i / dim] : cond_scale ;  unless (row_scale && s == 1.0f):  v = v*(1+s) - s*f_n[i]
+ *   k_out != NULL: k_out[i] = v                                   (the combined field of this stage, kept for later stages)
+ *   o = y[i] ;  for j = 0 .. m-1 with w[j] != 0:  o += k_prev[j][i] * w[j] ;  if w[m] != 0:  o += v * w[m]
+ *   out[i] = o ;  out2, out3 = optional extra copies ;  `out` may alias `y`
+ * k_prev: HOST array of m device pointers (m <= 3), w: HOST array of m + 1 floats - the caller's fp32(dt * a_ji), or fp32(dt * b_j)
+ * on the last stage of a step.  A stage whose weight is exactly 0 is neither read nor added (its pointer may be NULL).
+ * row_scale: one guidance scale per ROW on the device (needs f_n); a row at exactly 1.0 takes f_c - the reference's branch
+ * (acoustic.py:423), which the formula does not reach continuously.  With m == 0, k_out == NULL and row_scale == NULL the result has
+ * the bits of cvx_cfg_combine_axpy_f32 with coef = w[0].  16-byte accesses when every pointer is 16-byte aligned.
+ * CVX_EINVAL, nothing launched: NULL f_c / y / out / w, m outside 0..3, NULL k_prev[j] with w[j] != 0, rows < 0, dim <= 0,
+ * row_scale without f_n. */
+int cvx_rk_stage_f32(const float* f_c, const float* f_n, const float* y, float cond_scale, const float* row_scale,
+                     const float* const* k_prev, const float* w, int32_t m, float* k_out, float* out, float* out2, float* out3,
+                     int64_t rows, int32_t dim, cvx_stream_t s);
 
 /* rows of [ emb(ids[m,0]) | emb(ids[m,1]) ... | cond[m,:] ]  -> out[M, S*E + Cc]
  * (the step-invariant columns of the to_embed input, acoustic.py:496-503).

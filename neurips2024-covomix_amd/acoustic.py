@@ -18,8 +18,10 @@ Python here only sequences kernel launches on torch's current stream and owns de
 """
 from __future__ import annotations
 
-from typing import Dict, List, Optional
+from dataclasses import dataclass
+from typing import Dict, List, Optional, Sequence, Tuple, Union
 
+import math
 import os
 
 import torch
@@ -255,6 +257,18 @@ class VectorField:
         self._ws[key] = ws
         return ws
 
+    def stage_buffers(self, ctx: dict, n: int) -> List[torch.Tensor]:
+        """n (<= 3) buffers [M1, dim_out] for the stored stages of a Runge-Kutta step (FlowMatchingSampler._integrate_stages).  They
+        belong to the batch shape's workspace and are made when a solver first asks for them: midpoint and Euler never do."""
+        ws, M1 = ctx["ws"], ctx["M1"]
+        whole = ws.get("whole", ws)                             # ragged batch: the capacity-sized workspace behind the row views
+        rows = whole["xin"].shape[0] if whole is not ws else M1
+        ks = whole.setdefault("rk_k", [])
+        assert 0 <= n <= 3
+        while len(ks) < n:
+            ks.append(torch.empty(rows, self.d["dim_out"], dtype=torch.float32, device=self.device))
+        return [k[:M1] for k in ks[:n]]
+
     def _rope_tables(self, pos: torch.Tensor) -> tuple:
         """(cos, sin) [len(pos), 32] of the half-split rotary embedding at the given positions (acoustic.py:120-137)."""
         ang = pos[:, None] * self.inv_freq[None, :]
@@ -277,6 +291,7 @@ class VectorField:
             rg = ops.Ragged(lengths, self.device, repeat=2 if use_null else 1)
             full = self._workspace(0, 0, ragged_rows=rg.M)
             ws = self._ws_cut(full, 0, rg.M, vt=None)            # row views of the capacity-sized buffers; V^T stays whole
+            ws["whole"] = full
             ws["rope"] = self._rope_tables(rg.positions())       # per-ROW tables: the to_qkv epilogue then runs with rope_T = M
         else:
             B, T, _ = cond.shape
@@ -685,12 +700,76 @@ class VectorField:
         return ws["pred"]
 
 
-def evaluation_times(nfe: int, method: str):
+@dataclass(frozen=True)
+class Tableau:
+    """Butcher tableau of an explicit Runge-Kutta method on the fixed grid: stage j evaluates the field at t0 + c[j] dt on
+    y + dt sum_i a[j-1][i] k_i, the step ends at y + dt sum_j b[j] k_j.  `a` holds the strictly lower-triangular rows (row j - 1 of
+    stage j: j entries), so a one-stage method has a = ().  At most MAX_STAGES stages (the stage kernel keeps three earlier ones).
+    Frozen and hashable: it is part of the keys of the per-grid tables and of the captured graphs."""
+    name: str
+    a: Tuple[Tuple[float, ...], ...]
+    b: Tuple[float, ...]
+    c: Tuple[float, ...]
+
+    MAX_STAGES = 4
+
+    def __post_init__(self):
+        try:
+            a = tuple(tuple(float(x) for x in row) for row in self.a)
+            b, c = tuple(float(x) for x in self.b), tuple(float(x) for x in self.c)
+        except TypeError as e:
+            raise ValueError(f"tableau {self.name!r}: a must be rows of numbers, b and c sequences of numbers") from e
+        for k, v in (("a", a), ("b", b), ("c", c)):
+            object.__setattr__(self, k, v)
+        n = len(b)
+        if not 1 <= n <= self.MAX_STAGES:
+            raise ValueError(f"tableau {self.name!r}: {n} stages, 1 to {self.MAX_STAGES} are supported")
+        if len(c) != n or len(a) != n - 1 or any(len(row) != j + 1 for j, row in enumerate(a)):
+            raise ValueError(f"tableau {self.name!r}: a must be the {n - 1} strictly lower-triangular rows (1, 2, ... entries) and c must have {n} entries")
+        if not all(math.isfinite(x) for x in b + c + tuple(x for row in a for x in row)):
+            raise ValueError(f"tableau {self.name!r}: non-finite entry")
+        if abs(sum(b) - 1.0) > 1e-12:
+            raise ValueError(f"tableau {self.name!r}: sum(b) = {sum(b)!r}, a consistent method needs 1")
+        for j in range(n):
+            row_sum = sum(a[j - 1]) if j else 0.0
+            if abs(c[j] - row_sum) > 1e-12:
+                raise ValueError(f"tableau {self.name!r}: c[{j}] = {c[j]!r} is not the sum of its row of a ({row_sum!r})")
+
+    @property
+    def stages(self) -> int:
+        return len(self.b)
+
+
+TABLEAUS = {t.name: t for t in (
+    Tableau("euler", (), (1.0,), (0.0,)),
+    Tableau("midpoint", ((0.5,),), (0.0, 1.0), (0.0, 0.5)),
+    Tableau("heun2", ((1.0,),), (0.5, 0.5), (0.0, 1.0)),
+    Tableau("heun3", ((1 / 3,), (0.0, 2 / 3)), (0.25, 0.0, 0.75), (0.0, 1 / 3, 2 / 3)),
+    # torchdiffeq's fixed-grid "rk4" is the 3/8 rule (the reference's torchdiffeq_ode_method, acoustic.py:560-591)
+    Tableau("rk4", ((1 / 3,), (-1 / 3, 1.0), (1.0, -1.0, 1.0)), (1 / 8, 3 / 8, 3 / 8, 1 / 8), (0.0, 1 / 3, 2 / 3, 1.0)),
+    Tableau("rk4_classic", ((0.5,), (0.0, 0.5), (0.0, 0.0, 1.0)), (1 / 6, 1 / 3, 1 / 3, 1 / 6), (0.0, 0.5, 0.5, 1.0)),
+)}
+
+
+def resolve_method(method) -> Tableau:
+    """The tableau of a solver given by name or as a Tableau; ValueError for anything else (an unknown name used to run Euler)."""
+    if isinstance(method, Tableau):
+        return method
+    if isinstance(method, str) and method in TABLEAUS:
+        return TABLEAUS[method]
+    raise ValueError(f"unknown ODE method {method!r}: one of {', '.join(TABLEAUS)} or a Tableau")
+
+
+def evaluation_times(nfe: int, method):
     """Fixed grid of the reference solver (torchdiffeq fixed-grid, options.step_size) as python floats
-    computed in fp32 exactly like the solver does: (t0, dt) per step, plus every time the field is evaluated at."""
-    steps = nfe // 2 if method == "midpoint" else nfe
-    if steps < 1 or (method == "midpoint" and nfe % 2):
-        raise ValueError(f"nfe={nfe} is not valid for method={method}")
+    computed in fp32 exactly like the solver does: (t0, dt) per step, plus every time the field is evaluated at -
+    t0 + fp32(c_j) dt per stage, the grid point t1 itself for a stage with c_j = 1 (as torchdiffeq's rk4 does).  One time per
+    evaluation: the last stage of a step and the first of the next may repeat a time (the per-time tables are indexed by evaluation)."""
+    tab = resolve_method(method)
+    n = tab.stages
+    if int(nfe) != nfe or nfe < n or nfe % n:
+        raise ValueError(f"nfe={nfe} is not valid for method={tab.name}: a positive multiple of its {n} stage(s)")
+    steps = nfe // n
     h = torch.tensor(1.0 / steps, dtype=torch.float32)
     grid = torch.arange(0, steps + 1, dtype=torch.float32) * h
     grid[-1] = 1.0
@@ -698,9 +777,13 @@ def evaluation_times(nfe: int, method: str):
     for a, b in zip(grid[:-1], grid[1:]):
         dt = b - a
         dts.append(float(dt))
-        times.append(float(a))
-        if method == "midpoint":
-            times.append(float(a + 0.5 * dt))
+        for c in tab.c:
+            if c == 0.0:
+                times.append(float(a))
+            elif c == 1.0:
+                times.append(float(b))
+            else:
+                times.append(float(a + torch.tensor(c, dtype=torch.float32) * dt))
     return torch.tensor(times, dtype=torch.float32), dts
 
 
@@ -708,18 +791,22 @@ class FlowMatchingSampler:
     """ConditionalFlowMatcherWrapper.sample (acoustic.py:597-688) on a VectorField.
 
     `nfe` counts CFG-combined field evaluations: the reference's ode_step_size=0.0625 midpoint
-    setting is nfe=32 (16 steps x 2).  method='euler' (nfe steps) is an extra the reference lacks."""
+    setting is nfe=32 (16 steps x 2).  `method`: the name of a built-in tableau (TABLEAUS: the reference's torchdiffeq_ode_method;
+    'euler' is an extra the reference lacks) or a Tableau; nfe must be a multiple of its stage count.  cond_scale may be one float
+    per utterance (extension: the reference takes one scalar per call)."""
 
-    def __init__(self, field: VectorField, nfe: int = 32, method: str = "midpoint"):
+    def __init__(self, field: VectorField, nfe: int = 32, method: Union[str, Tableau] = "midpoint"):
         self.field, self.nfe, self.method = field, nfe, method
+        resolve_method(method)
 
     # launch-bound regime (short / single utterances): the whole solve - ~2400 kernel launches for 32 NFE - is captured
     # once per input shape into a HIP graph and replayed (env CVX_GRAPH=0 disables, CVX_GRAPH_MAX_ROWS bounds the
     # batch size it applies to; large batches are GPU-bound and stay eager).
     GRAPH_CACHE = 4
 
-    def _integrate(self, phoneme_ids, cond, y, times_dev, dts, s: float, use_null: bool, lengths=None) -> None:
-        """prepare() + the fixed-grid loop; advances `y` in place (ragged batch: y, cond, ids packed, see prepare)."""
+    def _integrate(self, phoneme_ids, cond, y, times_dev, dts, s: float, use_null: bool, lengths=None, row_scale=None) -> None:
+        """prepare() + the fixed-grid loop; advances `y` in place (ragged batch: y, cond, ids packed, see prepare).
+        row_scale: one guidance scale per row of y on the device (then `s` is not used)."""
         f = self.field
         ctx = f.prepare(phoneme_ids, cond, times_dev, use_null, lengths=lengths, times_key=(int(self.nfe), str(self.method)))
         ws, M1 = ctx["ws"], ctx["M1"]
@@ -729,6 +816,9 @@ class FlowMatchingSampler:
         x_c.copy_(y.reshape(M1, -1))
         if use_null:
             x_n.copy_(x_c)
+        if row_scale is not None or self.method not in ("midpoint", "euler"):      # (an explicit Tableau is never equal to a name)
+            self._integrate_stages(ctx, y.reshape(M1, -1), dts, s, resolve_method(self.method), row_scale)
+            return ctx
         evaluate = f.evaluate
         e = 0
         for dt in dts:
@@ -742,10 +832,47 @@ class FlowMatchingSampler:
                 ops.cfg_combine_axpy(pred[:M1], pred[M1:] if use_null else None, y, s, dt, y, x_c, x_n)
         return ctx
 
+    def _integrate_stages(self, ctx: dict, y: torch.Tensor, dts, s: float, tab: Tableau, row_scale) -> None:
+        """The fixed-grid loop of any explicit tableau: one field evaluation and one cvx_rk_stage_f32 launch per stage.  The launch
+        after stage i combines the CFG branches into k_i and writes the next evaluation's input y + dt sum_l a[i+1][l] k_l - after
+        the last stage the step's result y + dt sum_l b[l] k_l, in place.  k_i is stored only when a later launch reads it (its b
+        or a later row of a is not 0): midpoint and Euler store nothing, Heun's third-order rule one stage, the fourth-order rules
+        three - buffers of the workspace, made on first use."""
+        f = self.field
+        ws, M1, use_null = ctx["ws"], ctx["M1"], ctx["use_null"]
+        x_c = ws["xin"][:M1]
+        x_n = ws["xin"][M1:] if use_null else None
+        n = tab.stages
+        rows = ((),) + tab.a + (tab.b,)          # rows[i + 1]: the weights the launch after stage i applies to k_0 .. k_i
+        keep = [i + 1 < n and any(rows[j][i] != 0.0 for j in range(i + 2, n + 1)) for i in range(n)]
+        bufs = iter(f.stage_buffers(ctx, sum(keep)))
+        k = [next(bufs) if keep[i] else None for i in range(n)]
+        e = 0
+        for dt in dts:
+            for i in range(n):
+                pred = f.evaluate(ctx, e); e += 1
+                coef, last = rows[i + 1], i + 1 == n
+                ops.rk_stage(pred[:M1], pred[M1:] if use_null else None, y, s, [dt * c for c in coef], y if last else x_c,
+                             k_prev=[k[l] if coef[l] != 0.0 else None for l in range(i)], k_out=k[i], row_scale=row_scale,
+                             out2=x_c if last else x_n, out3=x_n if last else None)
+
+    @staticmethod
+    def _scales(cond_scale, n: int):
+        """(scalar, per-utterance list or None) of a cond_scale given as one number or as one number per utterance; equal values
+        are the scalar."""
+        if not (isinstance(cond_scale, (list, tuple)) or getattr(cond_scale, "ndim", 0) > 0):
+            return float(cond_scale), None
+        vals = [float(v) for v in cond_scale]
+        if len(vals) != n:
+            raise ValueError(f"cond_scale: {len(vals)} values for {n} utterances")
+        if all(v == vals[0] for v in vals):
+            return vals[0], None
+        return 0.0, vals
+
     @ops.gated
     @torch.no_grad()
     def sample(self, *, phoneme_ids: torch.Tensor, cond: torch.Tensor, mask: Optional[torch.Tensor] = None,
-               cond_scale: float = 1.0, y0: Optional[torch.Tensor] = None) -> torch.Tensor:
+               cond_scale: Union[float, Sequence[float]] = 1.0, y0: Optional[torch.Tensor] = None) -> torch.Tensor:
         import os
         f, d = self.field, self.field.d
         dev = f.device
@@ -762,21 +889,25 @@ class FlowMatchingSampler:
         if tuple(y0.shape) != (B, T, d["dim_out"]):
             raise AssertionError(f"y0 must be [B,T,{d['dim_out']}] = {(B, T, d['dim_out'])}, got {tuple(y0.shape)}")
         y = y0.to(device=dev, dtype=torch.float32).contiguous().clone()
-        use_null = float(cond_scale) != 1.0          # acoustic.py:423
-        s = float(cond_scale)
+        s, per = self._scales(cond_scale, B)
+        use_null = s != 1.0 if per is None else True         # acoustic.py:423 (different scales: at least one is not 1)
+        # per-utterance scales: one float per row, read by the stage kernel (a row at 1.0 takes its conditional branch there)
+        row_scale = None if per is None else ops.h2d(torch.tensor(per, dtype=torch.float32).repeat_interleave(T), dev)
         times, dts = evaluation_times(self.nfe, self.method)
         rows = (2 * B if use_null else B) * T
         if os.environ.get("CVX_GRAPH", "1") == "0" or rows > int(os.environ.get("CVX_GRAPH_MAX_ROWS", "8192")):
-            self._integrate(phoneme_ids, cond, y, ops.h2d(times, dev), dts, s, use_null)
+            self._integrate(phoneme_ids, cond, y, ops.h2d(times, dev), dts, s, use_null, row_scale=row_scale)
             return y
         main = torch.cuda.current_stream()
-        # (the saturation flag of the launching stream is a kernel argument of the captured launches: one graph per stream)
-        key = (B, T, use_null, s, self.nfe, self.method, main.cuda_stream)
+        # (the saturation flag of the launching stream is a kernel argument of the captured launches: one graph per stream;
+        #  per-utterance scales sit in a buffer the graph reads: one graph serves every mix of them)
+        key = (B, T, use_null, s if per is None else "per-row", self.nfe, self.method, main.cuda_stream)
         cache = f.__dict__.setdefault("_graphs", {})
         ent = cache.get(key)
         if ent is None:
-            st = dict(ids=phoneme_ids.clone(), cond=cond.clone(), y=y.clone(), times=ops.h2d(times, dev))
-            ctx = self._integrate(st["ids"], st["cond"], st["y"], st["times"], dts, s, use_null)   # eager warm-up
+            st = dict(ids=phoneme_ids.clone(), cond=cond.clone(), y=y.clone(), times=ops.h2d(times, dev),
+                      row_scale=None if row_scale is None else row_scale.clone())
+            ctx = self._integrate(st["ids"], st["cond"], st["y"], st["times"], dts, s, use_null, row_scale=st["row_scale"])   # eager warm-up
             st["ws"] = ctx["ws"]             # keep this shape's workspace alive for as long as the graph is
             # (thread-local capture mode + the package's capture gate: another host thread driving its own model on this device
             #  must not break this capture, nor be broken by it - HIP rejects its synchronisations while a capture is open even
@@ -788,7 +919,8 @@ class FlowMatchingSampler:
                     self._cap = torch.cuda.Stream(device=dev)
                 ops.saturation_share(main, self._cap)    # the captured launches report into the calling stream's flag
                 with torch.cuda.graph(g, stream=self._cap, capture_error_mode="thread_local"):
-                    self._integrate(st["ids"], st["cond"], st["y"], st["times"], dts, s, use_null)
+                    self._integrate(st["ids"], st["cond"], st["y"], st["times"], dts, s, use_null, row_scale=st["row_scale"])
+            cache = f.__dict__.setdefault("_graphs", {})     # (the warm-up may have evicted a time grid and, with it, the cache)
             if len(cache) >= self.GRAPH_CACHE:
                 cache.pop(next(iter(cache)))
             ent = cache[key] = (g, st)
@@ -796,19 +928,22 @@ class FlowMatchingSampler:
         st["ids"].copy_(phoneme_ids)
         st["cond"].copy_(cond)
         st["y"].copy_(y)
+        if row_scale is not None:
+            st["row_scale"].copy_(row_scale)
         g.replay()
         return st["y"].clone()
 
     @ops.gated
     @torch.no_grad()
-    def sample_ragged(self, *, phoneme_ids: List[torch.Tensor], cond: List[torch.Tensor], cond_scale: float = 1.0,
+    def sample_ragged(self, *, phoneme_ids: List[torch.Tensor], cond: List[torch.Tensor], cond_scale: Union[float, Sequence[float]] = 1.0,
                       y0: Optional[List[torch.Tensor]] = None) -> List[torch.Tensor]:
         """The same solve for several utterances of DIFFERENT length in one launch sequence: utterance i is
         phoneme_ids[i] [T_i(, streams)], cond[i] [T_i, dim_cond] (y0[i] [T_i, dim_out]); returns the list of [T_i, dim_out]
         results.  The reference runs such utterances one at a time (monologue_generation.py:259-304) and its network has
         no padding mask (acoustic.py:313), so they are PACKED back to back - M = sum T_i rows - and the three operators
         that look along time (attention, rotary positions, ConvPositionEmbed) work per sequence (include/covomix_hip.h,
-        RAGGED BATCHES); every utterance gets the result of its own B = 1 run up to fp32 summation order."""
+        RAGGED BATCHES); every utterance gets the result of its own B = 1 run up to fp32 summation order.
+        cond_scale: one float, or one per utterance."""
         f, d = self.field, self.field.d
         dev = f.device
         n = len(cond)
@@ -829,8 +964,9 @@ class FlowMatchingSampler:
             y = torch.randn(cond_p.shape[0], d["dim_out"], device=dev, dtype=torch.float32)
         else:
             y = torch.cat([t.to(device=dev, dtype=torch.float32) for t in y0]).contiguous().clone()
-        use_null = float(cond_scale) != 1.0          # acoustic.py:423
+        s, per = self._scales(cond_scale, n)
+        use_null = s != 1.0 if per is None else True         # acoustic.py:423
+        row_scale = None if per is None else ops.h2d(torch.tensor(per, dtype=torch.float32).repeat_interleave(torch.tensor(lengths)), dev)
         times, dts = evaluation_times(self.nfe, self.method)
-        self._integrate(ids_p, cond_p, y, ops.h2d(times, dev), dts, float(cond_scale), use_null, lengths=lengths)
+        self._integrate(ids_p, cond_p, y, ops.h2d(times, dev), dts, s, use_null, lengths=lengths, row_scale=row_scale)
         return list(torch.split(y, lengths))
-

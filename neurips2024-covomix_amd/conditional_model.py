@@ -31,7 +31,7 @@ from typing import Dict, Optional
 import torch
 
 from . import ops
-from .acoustic import FlowMatchingSampler, VectorField
+from .acoustic import FlowMatchingSampler, VectorField, resolve_method
 
 _PREFIX = "cfm_wrapper.CoVoMix."
 _PREFIX_T2S = "cfm_wrapper.model."
@@ -73,9 +73,13 @@ def t2s_parameter_order(sd_keys) -> list:
 
 class CoVoMixModel:
     def __init__(self, state_dict: Dict[str, torch.Tensor], hparams: Optional[dict] = None,
-                 ema_shadow: Optional[list] = None, nfe: int = 32, ode_method: str = "midpoint",
+                 ema_shadow: Optional[list] = None, nfe: int = 32, ode_method="midpoint",
                  precision: Optional[str] = None):
-        """state_dict: un-prefixed CoVoMix parameter names (acoustic.py:326-406)."""
+        """state_dict: un-prefixed CoVoMix parameter names (acoustic.py:326-406).
+        ode_method: the reference's torchdiffeq_ode_method (acoustic.py:560-591) - the name of a built-in tableau (acoustic.TABLEAUS:
+        euler, midpoint, heun2, heun3, rk4 = torchdiffeq's 3/8 rule, rk4_classic) or an acoustic.Tableau; nfe counts field evaluations
+        and must be a multiple of the method's stages."""
+        resolve_method(ode_method)
         self.hparams = dict(hparams or {})
         self.is_text2semantic = "token_emb.text.weight" in state_dict
         if bool(self.hparams.get("text2semantic", self.is_text2semantic)) != self.is_text2semantic:
@@ -168,7 +172,9 @@ class CoVoMixModel:
         `y0` (optional) fixes the initial noise; parity is defined given y0.
         Extension: LISTS of per-utterance tensors (phoneme_ids[i] [T_i(, streams)], cond[i] [T_i, C], y0[i] [T_i, dim_out],
         lengths may differ) run as one packed ragged batch and return a list; each result equals that utterance's B = 1
-        call up to fp32 summation order (the reference loops over utterances, monologue_generation.py:259-304)."""
+        call up to fp32 summation order (the reference loops over utterances, monologue_generation.py:259-304).
+        Extension: cond_scale may be a sequence of one float per utterance (batched or ragged); an utterance at exactly 1.0 takes its
+        conditional branch alone, as a scalar call at 1.0 does (acoustic.py:423)."""
         from . import ops
         field = self._get_field()
         ragged = isinstance(cond, (list, tuple))     # extension: utterances of different length in one packed launch

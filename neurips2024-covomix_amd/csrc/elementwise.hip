@@ -2,6 +2,7 @@
 //   cvx_adarmsnorm_f32          AdaptiveRMSNorm / RMSNorm       (acoustic.py:165-204)
 //   cvx_dwconv31_gelu_res_f32   ConvPositionEmbed + residual    (acoustic.py:141-161, :508)
 //   cvx_cfg_combine_axpy_f32    CFG combine + ODE stage update  (acoustic.py:428; torchdiffeq midpoint)
+//   cvx_rk_stage_f32            CFG combine + one explicit Runge-Kutta stage, per-row guidance scale
 //   cvx_embed_gather_f32        step-invariant to_embed columns (acoustic.py:473-503)
 //   cvx_time_fourier_f32        LearnedSinusoidalPosEmb         (acoustic.py:107-111)
 //   cvx_wav_to_int16            mel_decode_to_wav tail          (monologue_generation.py:55-57)
@@ -388,6 +389,105 @@ __global__ __launch_bounds__(256) void cfg_axpy_kernel(const float* __restrict__
     if (out3) out3[i] = o;
 }
 
+// ---------------------------------------------------------------- CFG combine + one stage of an explicit Runge-Kutta step
+// cfg_axpy_kernel's combine and update, verbatim (same expressions, same contraction: with no stored stage, no k_out and no
+// row scales the bits are that kernel's), plus up to three stored stages, a per-row guidance scale and the combined field as
+// an output.  wk[j] of an unused or zero-weight stage is 0: such a stage is neither read nor added.
+struct RkStage {
+    const float* fc; const float* fn; const float* y; const float* row_scale;
+    const float* k0; const float* k1; const float* k2;
+    float wk0, wk1, wk2, wv, s;
+    float* k_out; float* out; float* out2; float* out3;          // out may alias y
+    int64_t n;
+    int dim;
+};
+
+// cfg_axpy_kernel's arithmetic as its gfx950 code has it (v_pk_mul_f32, v_sub_f32, v_fmac_f32): the two products of the combine are
+// rounded on their own and subtracted, the update is one fused multiply-add.  Spelled out, because the compiler contracts the
+// plain expressions differently from one lane of a float4 to the next.
+__device__ __forceinline__ float rk_cfg_combine(float v, float f, float s)
+{
+#pragma clang fp contract(off)
+    const float a = v * (1.0f + s), b = s * f;
+    return a - b;
+}
+
+template <int V>
+__device__ __forceinline__ void rk_stage_elems(const RkStage& a, int64_t i0)
+{
+    float v[V], o[V];
+    if constexpr (V == 4) {
+        const float4 t = *reinterpret_cast<const float4*>(a.fc + i0);
+        v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
+    } else v[0] = a.fc[i0];
+    if (a.fn) {
+        float f[V], s[V];
+        if constexpr (V == 4) {
+            const float4 t = *reinterpret_cast<const float4*>(a.fn + i0);
+            f[0] = t.x; f[1] = t.y; f[2] = t.z; f[3] = t.w;
+        } else f[0] = a.fn[i0];
+        if (a.row_scale) {
+            int64_t r = i0 / a.dim;
+            int rem = (int)(i0 - r * a.dim);
+#pragma unroll
+            for (int e = 0; e < V; ++e) {                           // (element i0 + e < n: its row is inside the table)
+                s[e] = a.row_scale[r];
+                if (++rem == a.dim) { rem = 0; ++r; }
+            }
+#pragma unroll
+            for (int e = 0; e < V; ++e)
+                if (s[e] != 1.0f) v[e] = rk_cfg_combine(v[e], f[e], s[e]);   // a row at exactly 1.0 takes f_c (acoustic.py:423)
+        } else {
+#pragma unroll
+            for (int e = 0; e < V; ++e) v[e] = rk_cfg_combine(v[e], f[e], a.s);
+        }
+    }
+    if constexpr (V == 4) {
+        const float4 t = *reinterpret_cast<const float4*>(a.y + i0);
+        o[0] = t.x; o[1] = t.y; o[2] = t.z; o[3] = t.w;
+    } else o[0] = a.y[i0];
+    if (a.k_out) {
+        if constexpr (V == 4) *reinterpret_cast<float4*>(a.k_out + i0) = make_float4(v[0], v[1], v[2], v[3]);
+        else a.k_out[i0] = v[0];
+    }
+#define RK_ADD_STAGE(K, W)                                                              \
+    if ((W) != 0.f) {                                                                   \
+        if constexpr (V == 4) {                                                         \
+            const float4 t = *reinterpret_cast<const float4*>((K) + i0);                \
+            o[0] = __builtin_fmaf(t.x, (W), o[0]); o[1] = __builtin_fmaf(t.y, (W), o[1]);   \
+            o[2] = __builtin_fmaf(t.z, (W), o[2]); o[3] = __builtin_fmaf(t.w, (W), o[3]);   \
+        } else o[0] = __builtin_fmaf((K)[i0], (W), o[0]);                               \
+    }
+    RK_ADD_STAGE(a.k0, a.wk0)
+    RK_ADD_STAGE(a.k1, a.wk1)
+    RK_ADD_STAGE(a.k2, a.wk2)
+#undef RK_ADD_STAGE
+    if (a.wv != 0.f) {
+#pragma unroll
+        for (int e = 0; e < V; ++e) o[e] = __builtin_fmaf(v[e], a.wv, o[e]);
+    }
+    if constexpr (V == 4) {
+        const float4 t = make_float4(o[0], o[1], o[2], o[3]);
+        *reinterpret_cast<float4*>(a.out + i0) = t;
+        if (a.out2) *reinterpret_cast<float4*>(a.out2 + i0) = t;
+        if (a.out3) *reinterpret_cast<float4*>(a.out3 + i0) = t;
+    } else {
+        a.out[i0] = o[0];
+        if (a.out2) a.out2[i0] = o[0];
+        if (a.out3) a.out3[i0] = o[0];
+    }
+}
+
+// V = 4: every base pointer is 16-byte aligned - one float4 per lane, the last n % 4 elements one at a time; V = 1 otherwise
+template <int V>
+__global__ __launch_bounds__(256) void rk_stage_kernel(const RkStage a)
+{
+    const int64_t i0 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * V;
+    if (i0 >= a.n) return;
+    if (V == 1 || i0 + V <= a.n) { rk_stage_elems<V>(a, i0); return; }
+    for (int64_t i = i0; i < a.n; ++i) rk_stage_elems<1>(a, i);
+}
+
 // ---------------------------------------------------------------- embedding gather
 __global__ __launch_bounds__(256) void embed_gather_kernel(const int64_t* __restrict__ ids, int S,
                                                           const float* __restrict__ table, int E, int n_rows_table,
@@ -658,6 +758,41 @@ extern "C" int cvx_cfg_combine_axpy_f32(const float* f_c, const float* f_n, cons
     hipLaunchKernelGGL(cfg_axpy_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, cvx_hip_stream(s),
                        f_c, f_n, y, cond_scale, coef, out, out2, out3, n);
     CVX_CHECK_LAUNCH("cvx_cfg_combine_axpy_f32");
+    return CVX_OK;
+}
+
+extern "C" int cvx_rk_stage_f32(const float* f_c, const float* f_n, const float* y, float cond_scale, const float* row_scale,
+                                const float* const* k_prev, const float* w, int32_t m, float* k_out, float* out, float* out2,
+                                float* out3, int64_t rows, int32_t dim, cvx_stream_t s)
+{
+    CVX_REQUIRE(f_c && y && out && w, "rk_stage: f_c, y, out and w must not be null");
+    CVX_REQUIRE(m >= 0 && m <= 3, "rk_stage: at most 3 stored stages (m=%d)", m);
+    CVX_REQUIRE(rows >= 0 && dim > 0, "rk_stage: bad shape (rows=%lld dim=%d)", (long long)rows, dim);
+    CVX_REQUIRE(!row_scale || f_n, "rk_stage: row_scale without f_n");
+    CVX_REQUIRE(m == 0 || k_prev, "rk_stage: k_prev is null");
+    RkStage a = {};
+    const float* k[3] = {nullptr, nullptr, nullptr};
+    float wk[3] = {0.f, 0.f, 0.f};
+    for (int j = 0; j < m; ++j) {
+        CVX_REQUIRE(k_prev[j] || w[j] == 0.f, "rk_stage: k_prev[%d] is null and its weight is not 0", j);
+        if (w[j] != 0.f) { k[j] = k_prev[j]; wk[j] = w[j]; }
+    }
+    CVX_REQUIRE(rows <= (int64_t)0x7fffffffffffLL / dim, "rk_stage: rows x dim too large");
+    a.fc = f_c; a.fn = f_n; a.y = y; a.row_scale = row_scale;
+    a.k0 = k[0]; a.k1 = k[1]; a.k2 = k[2];
+    a.wk0 = wk[0]; a.wk1 = wk[1]; a.wk2 = wk[2]; a.wv = w[m]; a.s = cond_scale;
+    a.k_out = k_out; a.out = out; a.out2 = out2; a.out3 = out3;
+    a.n = rows * dim; a.dim = dim;
+    if (a.n == 0) return CVX_OK;
+    uintptr_t bits = (uintptr_t)f_c | (uintptr_t)f_n | (uintptr_t)y | (uintptr_t)k[0] | (uintptr_t)k[1] | (uintptr_t)k[2] |
+                     (uintptr_t)k_out | (uintptr_t)out | (uintptr_t)out2 | (uintptr_t)out3;
+    const bool vec = (bits & 15) == 0;
+    const int64_t threads = vec ? (a.n + 3) / 4 : a.n;
+    const int64_t blocks = (threads + 255) / 256;
+    CVX_REQUIRE(blocks <= 0x7fffffffLL, "rk_stage: rows x dim too large for one launch");
+    if (vec) hipLaunchKernelGGL(rk_stage_kernel<4>, dim3((unsigned)blocks), dim3(256), 0, cvx_hip_stream(s), a);
+    else hipLaunchKernelGGL(rk_stage_kernel<1>, dim3((unsigned)blocks), dim3(256), 0, cvx_hip_stream(s), a);
+    CVX_CHECK_LAUNCH("cvx_rk_stage_f32");
     return CVX_OK;
 }
 

@@ -37,6 +37,7 @@ import numpy as np
 import torch
 
 from . import assembly, dp
+from .acoustic import evaluation_times
 from .conditional_model import CoVoMixModel
 from .vocoder import AttrDict, Generator
 
@@ -71,6 +72,9 @@ def build_parser() -> ArgumentParser:
     p.add_argument("--km_path", type=str, default=None, help="k-means model (joblib) for --hubert_ckpt")
     p.add_argument("--nfe", type=int, default=32, help="extension: CFG-combined field evaluations of the midpoint solver (32 = the "
                    "reference's ode_step_size 0.0625, acoustic.py:586-591; 64 = BASELINE config 5's 64-step setting)")
+    p.add_argument("--ode_method", type=str, default="midpoint", help="extension: the fixed-grid solver (the reference's "
+                   "torchdiffeq_ode_method, acoustic.py:560-591): euler, midpoint, heun2, heun3, rk4 (torchdiffeq's 3/8 rule) or rk4_classic; "
+                   "--nfe must be a multiple of its stages (1, 2, 2, 3, 4, 4)")
     p.add_argument("--t2s_temperature", type=float, default=None, help="extension: sampling temperature of the text2semantic decode "
                    "(default: the reference's 1.0)")
     p.add_argument("--t2s_cond_scale", type=float, default=None, help="extension: classifier-free guidance of the text2semantic decode "
@@ -427,6 +431,7 @@ def run(dialogue: bool, argv=None) -> int:
     from . import ops
     import sys
     args = build_parser().parse_args(argv)
+    evaluation_times(int(args.nfe), args.ode_method)              # (ValueError before anything loads: unknown method, nfe no multiple of its stages)
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:          # spawn our own ranks (hifi-gan/train.py:268-278 does the same)
         rc = dp.launch_ranks(os.path.abspath(sys.argv[0]), list(sys.argv[1:] if argv is None else argv), args.gpus)
         if rc:
@@ -458,7 +463,7 @@ def run(dialogue: bool, argv=None) -> int:
     model = CoVoMixModel.load_from_checkpoint(args.acous_ckpt, base_dir="", batch_size=16, num_workers=0)
     model.eval()
     model = model.to(device)
-    model.nfe = int(args.nfe)
+    model.nfe, model.ode_method = int(args.nfe), args.ode_method
     t2s_kw = t2s_sampling_kwargs(args)
     if rank == 0:
         with open(os.path.join(args.saved_dir, "config.txt"), "w") as f:

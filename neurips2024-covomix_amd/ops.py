@@ -890,6 +890,24 @@ def cfg_combine_axpy(f_c, f_n, y, cond_scale: float, coef: float, out, out2=None
                "cvx_cfg_combine_axpy_f32")
 
 
+def rk_stage(f_c, f_n, y, cond_scale: float, weights, out, *, k_prev=(), k_out=None, row_scale=None, out2=None, out3=None) -> None:
+    """CFG combine + one stage of an explicit Runge-Kutta step (cvx_rk_stage_f32): out = y + sum_j k_prev[j] * weights[j] + v * weights[m],
+    v = the combined field (also written to k_out when given).  f_c, y, out ... [rows, dim]; weights: m + 1 floats for the m = len(k_prev)
+    stored stages and this one (a stage whose weight is 0 may be None); row_scale [rows]: one guidance scale per row."""
+    _chk_f32(f_c, f_n, y, out, out2, out3, k_out, row_scale, *k_prev)
+    n, m = y.numel(), len(k_prev)
+    dim = y.shape[-1]
+    rows = n // dim if dim else 0
+    assert len(weights) == m + 1 and f_c.numel() == n and out.numel() == n and (f_n is None or f_n.numel() == n)
+    assert row_scale is None or (row_scale.numel() == rows and row_scale.is_contiguous())
+    for t in (f_c, f_n, y, out, out2, out3, k_out, *k_prev):
+        assert t is None or (t.is_contiguous() and t.numel() == n)
+    kp = (C.c_void_p * max(m, 1))(*[_p(t) for t in k_prev])
+    w = (C.c_float * (m + 1))(*[float(x) for x in weights])
+    _lib.check(_lib.load().cvx_rk_stage_f32(f_c.data_ptr(), _p(f_n), y.data_ptr(), cond_scale, _p(row_scale), kp, w, m, _p(k_out),
+                                            out.data_ptr(), _p(out2), _p(out3), rows, dim, _stream()), "cvx_rk_stage_f32")
+
+
 def embed_gather(ids: Optional[torch.Tensor], streams: int, table: torch.Tensor, cond: Optional[torch.Tensor],
                  cond_row: Optional[torch.Tensor], cond_dim: int, null_id: int, out: torch.Tensor, M: int) -> torch.Tensor:
     _chk_f32(table, cond, cond_row, out)
