@@ -36,6 +36,9 @@
 // cvx_t2s_beam_queue_steps runs a LIST of utterances through the groups: beam_merge_queue_kernel ends an utterance, takes the next pending
 // one from a device-side queue and re-arms the whole group inside the same launch; the history is then kept per utterance
 // (beam_backtrack_queue_kernel).
+// ONE BODY PER STEP: the three sampling kernels instantiate sample_step, the two merge kernels beam_merge_step, the two back-track kernels
+// beam_backtrack_step.  What such sharing does to a kernel is read from the compiler (tools/kernel_text_diff.py against the parent's
+// assembly), not assumed: the default chain's kernels keep their instruction text (tests/test_t2s_code_objects.py holds their resources).
 // The reference rotates ALL cached keys again every step with rotary_embedding_torch's interleaved pairs
 // (rotary_embedding_torch.py:146-157); rotating a key once at its own position when it enters the cache is the same
 // arithmetic.  Interleaved pairs (2i, 2i+1) become half-split pairs (i, i+32) by permuting the rows of to_q / to_k
@@ -682,40 +685,12 @@ __device__ __forceinline__ void stage_row(const float* lrow, const float* nrow, 
     __syncthreads();
 }
 
-// log-softmax of the staged row lg[0, V) at entry tok: lp = (lg[tok] - m) - logf(sum_j expf(lg[j] - m)), m = the row maximum (exact in any
-// order).  The sum is a function of the row alone - whatever NT, the slot, the batch or the launch: ex[j] = expf(lg[j] - m) for j < V and 0
+// The maximum m of the staged row lg[0, V) (every thread; exact in any order) and sum_j expf(lg[j] - m) (the threads of the first wave).
+// The sum is a function of the row alone - whatever NT, the slot, the batch or the launch: ex[j] = expf(lg[j] - m) for j < V and 0
 // up to 1024; lane t of the first wave adds ex[t], ex[t + 64], ..., ex[t + 960] in that order, then the xor butterfly 32, 16, 8, 4, 2, 1
 // over the 64 lanes.  lg: the row (as sample_select / stage_row left it, already synchronised), ex: 1024 floats, bv: 16 floats of LDS.
-// The result is valid in thread 0; the caller synchronises before lg, ex or bv are written again.
-template <int NT>
-__device__ __forceinline__ float row_logprob(const float* lg, int V, int tok, float* ex, float* bv)
-{
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    float m = -INFINITY;
-    for (int i = tid; i < V; i += NT) m = fmaxf(m, lg[i]);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
-    if (lane == 0) bv[wid] = m;
-    __syncthreads();
-    m = bv[0];
-    for (int w = 1; w < NT / 64; ++w) m = fmaxf(m, bv[w]);
-    for (int i = tid; i < 1024; i += NT) ex[i] = i < V ? expf(lg[i] - m) : 0.f;
-    __syncthreads();
-    float lp = 0.f;
-    if (tid < 64) {
-        float sum = 0.f;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) sum += ex[tid + 64 * i];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
-        lp = (lg[tok] - m) - logf(sum);
-    }
-    return lp;
-}
-
-// row_logprob's m (every thread) and sum (the threads of the first wave) alone: the same operations in the same order, so the beam shortlist
-// takes every entry's log-prob from the same bits.  (A copy, not a call from row_logprob: splitting that function changes the schedule of the
-// scoring kernels, which stay as they were.)
+// The ONE definition behind cvx_t2s_logprob_f32, the scoring epilogue and the beam shortlist, which promise each other the same bits.
+// The caller synchronises before lg, ex or bv are written again.
 template <int NT>
 __device__ __forceinline__ float row_expsum(const float* lg, int V, float* ex, float* bv, float& m)
 {
@@ -740,54 +715,119 @@ __device__ __forceinline__ float row_expsum(const float* lg, int V, float* ex, f
     return sum;
 }
 
-template <int NT, int FILT, bool LOGP>
-__device__ __forceinline__ void sample_body(const SampleArgs& a, int b, float* lg, float* ex, float* bv, int* bi, int* chosen)
+// log-softmax of the staged row at entry tok: lp = (lg[tok] - m) - logf(sum), valid in thread 0
+template <int NT>
+__device__ __forceinline__ float row_logprob(const float* lg, int V, int tok, float* ex, float* bv)
+{
+    float m;
+    const float sum = row_expsum<NT>(lg, V, ex, bv, m);
+    return threadIdx.x < 64 ? (lg[tok] - m) - logf(sum) : 0.f;
+}
+
+// per-dialogue settings (cvx_t2s_decode_steps_per_dialogue, cvx_t2s_decode_steps_mixed)
+struct PerArgs {
+    const int* table;        // [n_records][PER_WORDS] 32-bit words: [0] float inv_temp [1] int filter mode [2] int top_k [3] float top_p
+                             //                                     [4] float cfg_scale [5] int prefix_len [6], [7] reserved
+    int n_records;
+};
+constexpr int PER_WORDS = 8;
+
+// The slot of the null half beside text half b: b + 1 in the launch-wide pair layout, slot pb in the mixed pool.  Spelled out at every use:
+// with b + 1 routed through a variable the compiler schedules the default kernels differently (1,260 -> 1,257 instructions).
+template <bool MIXED> __device__ __forceinline__ int null_slot(int b, int pb)
+{
+    if constexpr (MIXED) return pb;
+    else return b + 1;
+}
+
+// The sampling step of slot b: ONE body behind sample_kernel, sample_per_kernel and sample_mixed_kernel (NT threads, all of the block).
+// Per output stream: the token (sample_select, or read from the token row on a given step), its log-prob (LOGP), the embedding = the next
+// input; then the eos bookkeeping and, behind a dialogue queue, the refill.  What the parameters choose:
+//   FILT, PER   the SETTINGS.  !PER: temperature, top_k, top_p and the guidance scale from SampleArgs, the filter from FILT.  PER: from the
+//               settings row of the DIALOGUE the slot decodes (slot record [4]) - a refilled slot picks up the new dialogue's settings because
+//               it now names that dialogue - with the filter chosen at run time (block-uniform: a branch around the two sample_select
+//               forms) and a forced prefix: while pos < prefix_len the step is a given step.
+//   LOGP        the log-prob epilogue and the FORCED flag (bit 1): every step of such a dialogue is a given step.
+//               A GIVEN step reads its token from the dialogue's token row (clamped into [0, V)), reads no uniforms, and its eos ends nothing.
+//   MIXED       the PAIRING.  !MIXED: cfg_scale > 1 is the launch's layout - slots (2u, 2u + 1) decode the records (dlg, dlg + 1), the odd
+//               block returns at once and the even one feeds both slots and writes the null record's token row too.  MIXED: slot record [7]
+//               is the slot's role - 0 single, p + 1 the text half of a pair whose null half is slot p (any slot: partners need not be
+//               neighbours), -(p + 1) the null half of slot p, whose block returns at once; the null record's token row is not written
+//               (nothing reads it).
+//               And the TAIL.  !MIXED: without a queue the slot record moves on; with one, a block that ends its dialogue takes the next
+//               pending one.  MIXED: such a block only writes the record(s) and idles its slot(s) - it never touches the queue.  Handing out
+//               records is the business of mixed_schedule_kernel, the launch that follows: a guided head needs TWO idle slots, which no
+//               single block can know.  That launch clears the null half's role too, not this one: the null half's own block may be reading
+//               it now, and with the role unchanged every word a block decides by is its own slot's or constant during the launch (no fences).
+// lg, ex: 1024 floats (ex: FILT_TOP_P, PER or LOGP only), bv / bi: 16 entries, chosen: one int of LDS.
+template <int NT, int FILT, bool LOGP, bool PER, bool MIXED>
+__device__ __forceinline__ void sample_step(const SampleArgs& a, const PerArgs& p, int b, float* lg, float* ex, float* bv, int* bi, int* chosen)
 {
     const int tid = threadIdx.x;
-    const bool cfg = a.cfg_scale > 1.0f;
+    const bool cfg = !MIXED && a.cfg_scale > 1.0f;
     if (cfg && (b & 1)) return;                     // the null-context slot follows its partner (block-uniform)
     int* const state = a.state + SR * b;
     const int pos = aloadi(state);
-    if (pos >= a.max_len) return;                   // (block-uniform; also: an idle slot of a drained queue)
+    if (pos >= a.max_len) return;                   // (block-uniform) an idle slot: a drained queue, or past its last step
+    const int role = MIXED ? aloadi(state + 7) : 0;
+    if (MIXED && role < 0) return;                  // the null half follows its partner (block-uniform)
+    const bool pair = MIXED ? role > 0 : cfg;
+    const int pb = MIXED && pair ? min(a.batch - 1, role - 1) : b;      // (a stray role indexes no slot outside the batch)
+    int* const sn = MIXED ? a.state + SR * pb : state + SR;             // the null half's slot record (touched for a pair only)
     const int64_t dlg = aloadi(state + 4);          // the dialogue this slot decodes (== b without a queue)
-    // FORCED (flag bit 1, the LOGP instantiations only): the token row already holds the dialogue's tokens - nothing is sampled, the row's
-    // uniforms are not read, and only the step limit ends the dialogue (block-uniform: every thread reads the record)
+    // PER: the dialogue's settings (block-uniform: every thread reads the same row).  A stray record number reads row 0 / the last row, and
+    // stray values cannot index anything: top_k is clamped into [1, V], an unknown mode is top-k, P is clamped into [0, step limit]
+    const int* const row = PER ? p.table + (int64_t)PER_WORDS * min((int64_t)(p.n_records - 1), max((int64_t)0, dlg)) : nullptr;
+    const float inv_temp = PER ? __int_as_float(row[0]) : a.inv_temp;
+    const bool nucleus = PER ? row[1] == FILT_TOP_P : FILT == FILT_TOP_P;
+    const int top_k = PER ? min(a.V, max(1, row[2])) : a.top_k;
+    const float top_p = PER ? __int_as_float(row[3]) : a.top_p;
+    const float scale = PER ? __int_as_float(row[4]) : a.cfg_scale;
+    const int plim = (MIXED || a.queue) ? aloadi(state + 5) : a.max_len;    // (without a queue the slot record's limit is the caller's business)
+    const int P = PER ? min(max(plim, 0), max(0, row[5])) : 0;
+    // (block-uniform: every thread reads the record.)  !PER: `given` must be the constant-folded `forced` - pos is loaded, so a `pos < 0` that
+    // can never hold would stay in the default kernel (1,260 -> 1,319 instructions, another VGPR granule)
     const bool forced = LOGP ? (aloadi(state + 6) & 2) != 0 : false;
+    const bool given = PER ? forced || pos < P : forced;
     bool eos = false;
     for (int s = 0; s < a.streams; ++s) {
         const float* const lrow = a.logits + ((int64_t)b * a.streams + s) * a.V;
-        const float* const nrow = cfg ? a.logits + ((int64_t)(b + 1) * a.streams + s) * a.V : nullptr;
+        const float* const nrow = pair ? a.logits + ((int64_t)null_slot<MIXED>(b, pb) * a.streams + s) * a.V : nullptr;
         int tok;
-        if (LOGP && forced) {
-            stage_row<NT>(lrow, nrow, a.cfg_scale, a.V, lg);
+        if (given) {
+            if (LOGP) stage_row<NT>(lrow, nrow, scale, a.V, lg);          // (without the epilogue nothing reads the row)
             // (the host refuses tokens outside [0, V); the clamp keeps a stray one from indexing emb)
             tok = (int)min((int64_t)(a.V - 1), max((int64_t)0, a.tokens[(dlg * a.streams + s) * a.max_len + pos]));
         } else {
-            tok = sample_select<NT, FILT, false>(lrow, nrow, a.cfg_scale, a.uniforms + ((dlg * a.uniform_steps + pos) * a.streams + s) * a.V,
-                                                 a.V, a.top_k, a.top_p, a.inv_temp, nullptr, lg, ex, bv, bi, chosen);
+            const float* const urow = a.uniforms + ((dlg * a.uniform_steps + pos) * a.streams + s) * a.V;
+            if constexpr (!PER) tok = sample_select<NT, FILT, false>(lrow, nrow, scale, urow, a.V, top_k, top_p, inv_temp, nullptr, lg, ex, bv, bi, chosen);
+            else if (nucleus) tok = sample_select<NT, FILT_TOP_P, false>(lrow, nrow, scale, urow, a.V, top_k, top_p, inv_temp, nullptr, lg, ex, bv, bi, chosen);
+            else tok = sample_select<NT, FILT_TOP_K, false>(lrow, nrow, scale, urow, a.V, top_k, top_p, inv_temp, nullptr, lg, ex, bv, bi, chosen);
             if (tid == 0) a.tokens[(dlg * a.streams + s) * a.max_len + pos] = tok;
         }
         if (LOGP) {          // of the row the filter saw: before the filter, the temperature and the noise
             const float lp = row_logprob<NT>(lg, a.V, tok, ex, bv);
             if (tid == 0) a.logprobs[(dlg * a.streams + s) * a.max_len + pos] = lp;
         }
-        eos = eos || (tok == a.eos_id);
+        // a given eos ends nothing: PER leaves it out here, !PER in ends_eos below, where given == forced.  (One form for both - all eos here,
+        // `&& !given` below - is the same function and moved sample_per_kernel<false> by 9 instructions: the default chain's text is kept.)
+        eos = eos || (tok == a.eos_id && !(PER && given));
         for (int d = tid; d < a.dim_emb; d += NT) {
             const float e = a.emb[(int64_t)tok * a.dim_emb + d];
             a.x[((int64_t)b * a.streams + s) * a.dim_emb + d] = e;
-            if (cfg) a.x[((int64_t)(b + 1) * a.streams + s) * a.dim_emb + d] = e;
+            if (pair) a.x[((int64_t)null_slot<MIXED>(b, pb) * a.streams + s) * a.dim_emb + d] = e;
         }
-        if (cfg && tid == 0) a.tokens[((dlg + 1) * a.streams + s) * a.max_len + pos] = tok;
+        if (!MIXED && pair && tid == 0) a.tokens[((dlg + 1) * a.streams + s) * a.max_len + pos] = tok;
         __syncthreads();
     }
-    if (a.queue == nullptr) {
+    if (!MIXED && a.queue == nullptr) {
         if (LOGP && forced) {       // the slot record's step limit ends a forced dialogue: done, its length, and the slot idles
             if (tid == 0) {
                 const bool last = pos + 1 >= aloadi(state + 5);
                 const int np = last ? a.max_len : pos + 1;
                 if (last) { state[1] = 1; state[2] = pos + 1; }
                 state[0] = np;
-                if (cfg) { int* const sn = state + SR; if (last) { sn[1] = 1; sn[2] = pos + 1; } sn[0] = np; }
+                if (pair) { if (last) { sn[1] = 1; sn[2] = pos + 1; } sn[0] = np; }
             }
             return;
         }
@@ -795,56 +835,58 @@ __device__ __forceinline__ void sample_body(const SampleArgs& a, int b, float* l
             int done = aloadi(state + 1), len = aloadi(state + 2);
             if (eos && done == 0) { done = 1; len = pos + 1; state[1] = 1; state[2] = len; }
             state[0] = pos + 1;
-            if (cfg) { int* const sn = state + SR; sn[1] = done; sn[2] = len; sn[0] = pos + 1; }
+            if (pair) { sn[1] = done; sn[2] = len; sn[0] = pos + 1; }
         }
         return;
     }
     // continuous batching: the dialogue ends with its first eos (text2semantic.py:803-818) or at its step limit; the slot then
     // takes the next pending dialogue: position 0, the start token as input, that dialogue's context / uniforms / token rows.
-    // Guidance: the even slot decides for the pair; the pair's dialogue records are (dlg, dlg + 1) and the queue hands out two records
+    // A pair: the text half decides for both; the pair's dialogue records are (dlg, dlg + 1) and the queue hands out two records
     // at a time.  A pair is taken only when BOTH of its records exist (nxt + 1 < n), so a refill never indexes past the n dialogues
     // whatever the caller put into queue[1].
-    int* const sn = state + SR;                     // the null-context slot of a guided pair (touched under cfg only)
-    const bool ends_eos = eos && !(aloadi(state + 6) & 1) && !forced;
+    const bool ends_eos = eos && !(aloadi(state + 6) & 1) && !(!PER && forced);
     const bool ends = ends_eos || pos + 1 >= aloadi(state + 5);        // (block-uniform: `eos` comes from LDS, the record is read by all)
     if (!ends) {
-        if (tid == 0) { state[0] = pos + 1; if (cfg) sn[0] = pos + 1; }
+        if (tid == 0) { state[0] = pos + 1; if (pair) sn[0] = pos + 1; }
         return;
     }
     if (tid == 0) {
         int* const dr = a.dialogues + SR * dlg;
         dr[4] = pos + 1;
         dr[5] = b;
-        if (cfg) { dr[SR + 4] = pos + 1; dr[SR + 5] = b + 1; }
+        if (pair) { dr[SR + 4] = pos + 1; dr[SR + 5] = null_slot<MIXED>(b, pb); }
         __threadfence();
         dr[3] = ends_eos ? 2 : 3;
-        if (cfg) dr[SR + 3] = ends_eos ? 2 : 3;
-        const int take = cfg ? 2 : 1;
-        const int nxt = atomicAdd(a.queue, take);
-        *chosen = nxt + take - 1 < aloadi(a.queue + 1) ? nxt : -1;
+        if (pair) dr[SR + 3] = ends_eos ? 2 : 3;
+        if constexpr (!MIXED) {
+            const int take = pair ? 2 : 1;
+            const int nxt = atomicAdd(a.queue, take);
+            *chosen = nxt + take - 1 < aloadi(a.queue + 1) ? nxt : -1;
+        }
     }
-    __syncthreads();
-    const int nxt = *chosen;
+    int nxt = -1;
+    if constexpr (!MIXED) { __syncthreads(); nxt = *chosen; }
     if (nxt < 0) {                                  // nothing pending: the slot idles (every kernel clamps / skips at max_len)
         if (tid == 0) {
             state[0] = a.max_len; state[1] = 1;
-            if (cfg) { sn[0] = a.max_len; sn[1] = 1; }
+            if (MIXED) state[7] = 0;                // (sn[7]: mixed_schedule_kernel, above)
+            if (pair) { sn[0] = a.max_len; sn[1] = 1; }
         }
         return;
     }
     for (int d = tid; d < a.dim_emb * a.streams; d += NT) {
         const float e = a.start[d];
         a.x[(int64_t)b * a.streams * a.dim_emb + d] = e;
-        if (cfg) a.x[(int64_t)(b + 1) * a.streams * a.dim_emb + d] = e;
+        if (pair) a.x[(int64_t)null_slot<MIXED>(b, pb) * a.streams * a.dim_emb + d] = e;
     }
     if (tid == 0) {
         int* const dn = a.dialogues + SR * nxt;
         state[0] = 0; state[1] = 0; state[2] = 0; state[3] = dn[0]; state[4] = nxt; state[5] = dn[1]; state[6] = dn[2];
         dn[5] = b;
         dn[3] = 1;
-        if (cfg) {
+        if (pair) {
             sn[0] = 0; sn[1] = 0; sn[2] = 0; sn[3] = dn[SR + 0]; sn[4] = nxt + 1; sn[5] = dn[1]; sn[6] = dn[2];
-            dn[SR + 5] = b + 1;
+            dn[SR + 5] = null_slot<MIXED>(b, pb);
             dn[SR + 3] = 1;
         }
     }
@@ -861,139 +903,10 @@ __global__ __launch_bounds__(1024) void sample_kernel(const SampleArgs a)
     __shared__ float bv[16];
     __shared__ int bi[16];
     __shared__ int chosen;
-    sample_body<1024, FILT, LOGP>(a, blockIdx.x, lg, ex, bv, bi, &chosen);
+    sample_step<1024, FILT, LOGP, false, false>(a, PerArgs{nullptr, 0}, blockIdx.x, lg, ex, bv, bi, &chosen);
 }
 
-// ---------------------------------------------------------------- per-dialogue settings and forced prefixes
-// (cvx_t2s_decode_steps_per_dialogue).  A SIBLING of sample_body, not a flag on it: sharing a body can move the schedule of the existing
-// instantiations (row_expsum above), and those stay as they are.  What differs from sample_body:
-//   - inverse temperature, filter mode, top_k, top_p and the guidance scale come from the settings row of the DIALOGUE the slot decodes
-//     (slot record [4]), so a refilled slot picks up the new dialogue's settings because it now names that dialogue;
-//   - the filter is chosen at run time (block-uniform): a branch around the two sample_select forms, the second LDS array always present;
-//   - prefix_len P: while pos < P the step is a forced step - the token comes from the dialogue's token row (clamped into [0, V)), no
-//     uniforms are read, its eos does not end the dialogue - in BOTH instantiations; from P on the step samples, uniforms indexed by pos.
-// Everything else - eos bookkeeping, the refill from the queue, the guided pair's mirroring - is sample_body's, statement for statement.
-struct PerArgs {
-    const int* table;        // [n_records][PER_WORDS] 32-bit words: [0] float inv_temp [1] int filter mode [2] int top_k [3] float top_p
-                             //                                     [4] float cfg_scale [5] int prefix_len [6], [7] reserved
-    int n_records;
-};
-constexpr int PER_WORDS = 8;
-
-template <int NT, bool LOGP>
-__device__ __forceinline__ void sample_body_per(const SampleArgs& a, const PerArgs& p, int b, float* lg, float* ex, float* bv, int* bi, int* chosen)
-{
-    const int tid = threadIdx.x;
-    const bool cfg = a.cfg_scale > 1.0f;            // the launch's LAYOUT (slot pairs); the scale itself is the dialogue's
-    if (cfg && (b & 1)) return;
-    int* const state = a.state + SR * b;
-    const int pos = aloadi(state);
-    if (pos >= a.max_len) return;
-    const int64_t dlg = aloadi(state + 4);
-    // the dialogue's settings (block-uniform: every thread reads the same row).  A stray record number reads row 0 / the last row, and
-    // stray values cannot index anything: top_k is clamped into [1, V], an unknown mode is top-k, P is clamped into [0, step limit]
-    const int* const row = p.table + (int64_t)PER_WORDS * min((int64_t)(p.n_records - 1), max((int64_t)0, dlg));
-    const float inv_temp = __int_as_float(row[0]);
-    const bool nucleus = row[1] == FILT_TOP_P;
-    const int top_k = min(a.V, max(1, row[2]));
-    const float top_p = __int_as_float(row[3]);
-    const float scale = __int_as_float(row[4]);
-    const int plim = a.queue ? aloadi(state + 5) : a.max_len;           // (without a queue the slot record's limit is the caller's business)
-    const int P = min(max(plim, 0), max(0, row[5]));
-    const bool forced = LOGP ? (aloadi(state + 6) & 2) != 0 : false;
-    const bool given = forced || pos < P;           // this step reads its token (block-uniform)
-    bool eos = false;
-    for (int s = 0; s < a.streams; ++s) {
-        const float* const lrow = a.logits + ((int64_t)b * a.streams + s) * a.V;
-        const float* const nrow = cfg ? a.logits + ((int64_t)(b + 1) * a.streams + s) * a.V : nullptr;
-        int tok;
-        if (given) {
-            if (LOGP) stage_row<NT>(lrow, nrow, scale, a.V, lg);
-            tok = (int)min((int64_t)(a.V - 1), max((int64_t)0, a.tokens[(dlg * a.streams + s) * a.max_len + pos]));
-        } else {
-            const float* const urow = a.uniforms + ((dlg * a.uniform_steps + pos) * a.streams + s) * a.V;
-            if (nucleus) tok = sample_select<NT, FILT_TOP_P, false>(lrow, nrow, scale, urow, a.V, top_k, top_p, inv_temp, nullptr, lg, ex, bv, bi, chosen);
-            else tok = sample_select<NT, FILT_TOP_K, false>(lrow, nrow, scale, urow, a.V, top_k, top_p, inv_temp, nullptr, lg, ex, bv, bi, chosen);
-            if (tid == 0) a.tokens[(dlg * a.streams + s) * a.max_len + pos] = tok;
-        }
-        if (LOGP) {
-            const float lp = row_logprob<NT>(lg, a.V, tok, ex, bv);
-            if (tid == 0) a.logprobs[(dlg * a.streams + s) * a.max_len + pos] = lp;
-        }
-        eos = eos || (tok == a.eos_id && !given);   // (an eos that was given - forced or inside the prefix - ends nothing)
-        for (int d = tid; d < a.dim_emb; d += NT) {
-            const float e = a.emb[(int64_t)tok * a.dim_emb + d];
-            a.x[((int64_t)b * a.streams + s) * a.dim_emb + d] = e;
-            if (cfg) a.x[((int64_t)(b + 1) * a.streams + s) * a.dim_emb + d] = e;
-        }
-        if (cfg && tid == 0) a.tokens[((dlg + 1) * a.streams + s) * a.max_len + pos] = tok;
-        __syncthreads();
-    }
-    if (a.queue == nullptr) {
-        if (LOGP && forced) {
-            if (tid == 0) {
-                const bool last = pos + 1 >= aloadi(state + 5);
-                const int np = last ? a.max_len : pos + 1;
-                if (last) { state[1] = 1; state[2] = pos + 1; }
-                state[0] = np;
-                if (cfg) { int* const sn = state + SR; if (last) { sn[1] = 1; sn[2] = pos + 1; } sn[0] = np; }
-            }
-            return;
-        }
-        if (tid == 0) {
-            int done = aloadi(state + 1), len = aloadi(state + 2);
-            if (eos && done == 0) { done = 1; len = pos + 1; state[1] = 1; state[2] = len; }
-            state[0] = pos + 1;
-            if (cfg) { int* const sn = state + SR; sn[1] = done; sn[2] = len; sn[0] = pos + 1; }
-        }
-        return;
-    }
-    int* const sn = state + SR;
-    const bool ends_eos = eos && !(aloadi(state + 6) & 1);             // (`eos` already leaves out the given tokens)
-    const bool ends = ends_eos || pos + 1 >= aloadi(state + 5);
-    if (!ends) {
-        if (tid == 0) { state[0] = pos + 1; if (cfg) sn[0] = pos + 1; }
-        return;
-    }
-    if (tid == 0) {
-        int* const dr = a.dialogues + SR * dlg;
-        dr[4] = pos + 1;
-        dr[5] = b;
-        if (cfg) { dr[SR + 4] = pos + 1; dr[SR + 5] = b + 1; }
-        __threadfence();
-        dr[3] = ends_eos ? 2 : 3;
-        if (cfg) dr[SR + 3] = ends_eos ? 2 : 3;
-        const int take = cfg ? 2 : 1;
-        const int nxt = atomicAdd(a.queue, take);
-        *chosen = nxt + take - 1 < aloadi(a.queue + 1) ? nxt : -1;
-    }
-    __syncthreads();
-    const int nxt = *chosen;
-    if (nxt < 0) {
-        if (tid == 0) {
-            state[0] = a.max_len; state[1] = 1;
-            if (cfg) { sn[0] = a.max_len; sn[1] = 1; }
-        }
-        return;
-    }
-    for (int d = tid; d < a.dim_emb * a.streams; d += NT) {
-        const float e = a.start[d];
-        a.x[(int64_t)b * a.streams * a.dim_emb + d] = e;
-        if (cfg) a.x[(int64_t)(b + 1) * a.streams * a.dim_emb + d] = e;
-    }
-    if (tid == 0) {
-        int* const dn = a.dialogues + SR * nxt;
-        state[0] = 0; state[1] = 0; state[2] = 0; state[3] = dn[0]; state[4] = nxt; state[5] = dn[1]; state[6] = dn[2];
-        dn[5] = b;
-        dn[3] = 1;
-        if (cfg) {
-            sn[0] = 0; sn[1] = 0; sn[2] = 0; sn[3] = dn[SR + 0]; sn[4] = nxt + 1; sn[5] = dn[1]; sn[6] = dn[2];
-            dn[SR + 5] = b + 1;
-            dn[SR + 3] = 1;
-        }
-    }
-}
-
+// settings per dialogue and forced prefixes (cvx_t2s_decode_steps_per_dialogue)
 template <bool LOGP>
 __global__ __launch_bounds__(1024) void sample_per_kernel(const SampleArgs a, const PerArgs p)
 {
@@ -1002,88 +915,10 @@ __global__ __launch_bounds__(1024) void sample_per_kernel(const SampleArgs a, co
     __shared__ float bv[16];
     __shared__ int bi[16];
     __shared__ int chosen;
-    sample_body_per<1024, LOGP>(a, p, blockIdx.x, lg, ex, bv, bi, &chosen);
+    sample_step<1024, FILT_TOP_K, LOGP, true, false>(a, p, blockIdx.x, lg, ex, bv, bi, &chosen);
 }
 
-// ---------------------------------------------------------------- guided and unguided dialogues in one slot pool
-// (cvx_t2s_decode_steps_mixed).  A SIBLING of sample_body_per for the reason given there: the instantiations above stay as they are.
-// Whether a slot is half of a guided pair is a property of the RECORD it decodes, carried in slot record [7] (its role):
-//    0           a single slot: sample_body_per without guidance (nrow == nullptr);
-//    p + 1       the text half of a pair whose null half is slot p (any slot: partners need not be neighbours): sample_body_per under
-//                guidance with nrow = the logits row of slot p and the scale of its own table row; it feeds both slots;
-//   -(p + 1)     the null half of slot p: its block returns at once, the text half moves its position.
-// What differs from sample_body_per beyond that: the token row of the null record is not written (nothing reads it), and the block that
-// ends a dialogue only writes the record(s) and puts its slot(s) into the idle state - it never touches the queue.  Handing out records
-// is the business of mixed_schedule_kernel, the launch that follows: a guided head needs TWO idle slots, which no single block can know.
-// The role of the null half is cleared by that launch too, not here: the null half's own block may be reading it in this launch, and
-// with the role unchanged every word a block decides by is either its own slot's or constant during the launch (no fences needed).
-template <int NT, bool LOGP>
-__device__ __forceinline__ void sample_body_mixed(const SampleArgs& a, const PerArgs& p, int b, float* lg, float* ex, float* bv, int* bi, int* chosen)
-{
-    const int tid = threadIdx.x;
-    int* const state = a.state + SR * b;
-    const int pos = aloadi(state);
-    if (pos >= a.max_len) return;                   // an idle slot
-    const int role = aloadi(state + 7);
-    if (role < 0) return;                           // the null half follows its partner (block-uniform)
-    const bool pair = role > 0;
-    const int pb = pair ? min(a.batch - 1, role - 1) : b;               // (a stray role indexes no slot outside the batch)
-    int* const sn = a.state + SR * pb;              // the null half's slot record (touched for a pair only)
-    const int64_t dlg = aloadi(state + 4);
-    const int* const row = p.table + (int64_t)PER_WORDS * min((int64_t)(p.n_records - 1), max((int64_t)0, dlg));
-    const float inv_temp = __int_as_float(row[0]);
-    const bool nucleus = row[1] == FILT_TOP_P;
-    const int top_k = min(a.V, max(1, row[2]));
-    const float top_p = __int_as_float(row[3]);
-    const float scale = __int_as_float(row[4]);
-    const int P = min(max(aloadi(state + 5), 0), max(0, row[5]));
-    const bool forced = LOGP ? (aloadi(state + 6) & 2) != 0 : false;
-    const bool given = forced || pos < P;
-    bool eos = false;
-    for (int s = 0; s < a.streams; ++s) {
-        const float* const lrow = a.logits + ((int64_t)b * a.streams + s) * a.V;
-        const float* const nrow = pair ? a.logits + ((int64_t)pb * a.streams + s) * a.V : nullptr;
-        int tok;
-        if (given) {
-            if (LOGP) stage_row<NT>(lrow, nrow, scale, a.V, lg);
-            tok = (int)min((int64_t)(a.V - 1), max((int64_t)0, a.tokens[(dlg * a.streams + s) * a.max_len + pos]));
-        } else {
-            const float* const urow = a.uniforms + ((dlg * a.uniform_steps + pos) * a.streams + s) * a.V;
-            if (nucleus) tok = sample_select<NT, FILT_TOP_P, false>(lrow, nrow, scale, urow, a.V, top_k, top_p, inv_temp, nullptr, lg, ex, bv, bi, chosen);
-            else tok = sample_select<NT, FILT_TOP_K, false>(lrow, nrow, scale, urow, a.V, top_k, top_p, inv_temp, nullptr, lg, ex, bv, bi, chosen);
-            if (tid == 0) a.tokens[(dlg * a.streams + s) * a.max_len + pos] = tok;
-        }
-        if (LOGP) {
-            const float lp = row_logprob<NT>(lg, a.V, tok, ex, bv);
-            if (tid == 0) a.logprobs[(dlg * a.streams + s) * a.max_len + pos] = lp;
-        }
-        eos = eos || (tok == a.eos_id && !given);
-        for (int d = tid; d < a.dim_emb; d += NT) {
-            const float e = a.emb[(int64_t)tok * a.dim_emb + d];
-            a.x[((int64_t)b * a.streams + s) * a.dim_emb + d] = e;
-            if (pair) a.x[((int64_t)pb * a.streams + s) * a.dim_emb + d] = e;
-        }
-        __syncthreads();
-    }
-    const bool ends_eos = eos && !(aloadi(state + 6) & 1);
-    const bool ends = ends_eos || pos + 1 >= aloadi(state + 5);
-    if (tid != 0) return;
-    if (!ends) {
-        state[0] = pos + 1;
-        if (pair) sn[0] = pos + 1;
-        return;
-    }
-    int* const dr = a.dialogues + SR * dlg;         // (the null record of a pair is the next one: the scheduler took both)
-    dr[4] = pos + 1;
-    dr[5] = b;
-    if (pair) { dr[SR + 4] = pos + 1; dr[SR + 5] = pb; }
-    __threadfence();
-    dr[3] = ends_eos ? 2 : 3;
-    if (pair) dr[SR + 3] = ends_eos ? 2 : 3;
-    state[0] = a.max_len; state[1] = 1; state[7] = 0;
-    if (pair) { sn[0] = a.max_len; sn[1] = 1; }     // (sn[7]: mixed_schedule_kernel, above)
-}
-
+// guided and unguided dialogues in one slot pool (cvx_t2s_decode_steps_mixed)
 template <bool LOGP>
 __global__ __launch_bounds__(1024) void sample_mixed_kernel(const SampleArgs a, const PerArgs p)
 {
@@ -1092,7 +927,7 @@ __global__ __launch_bounds__(1024) void sample_mixed_kernel(const SampleArgs a, 
     __shared__ float bv[16];
     __shared__ int bi[16];
     __shared__ int chosen;
-    sample_body_mixed<1024, LOGP>(a, p, blockIdx.x, lg, ex, bv, bi, &chosen);
+    sample_step<1024, FILT_TOP_K, LOGP, true, true>(a, p, blockIdx.x, lg, ex, bv, bi, &chosen);
 }
 
 // The scheduler of the mixed pool: ONE block, launched after sample_mixed_kernel (the kernel boundary makes every record write of that
@@ -1101,7 +936,7 @@ __global__ __launch_bounds__(1024) void sample_mixed_kernel(const SampleArgs a, 
 //   unguided: the lowest slot of F takes it, h += 1; guided (flag bit 2): stop if h + 1 >= queue[1] (never index past the records) or F
 //   holds fewer than two slots (the head waits: strict order); else the lowest slot of F becomes the text half of record h, the next one
 //   the null half of record h + 1, h += 2.
-// Re-arming a slot is sample_body_per's refill - position 0, [3]..[6] from the record, record [3] = 1 and [5] = the slot - plus the role
+// Re-arming a slot is sample_step's refill - position 0, [3]..[6] from the record, record [3] = 1 and [5] = the slot - plus the role
 // in [7]; all threads then copy `start` into the x rows of the armed slots.  Slots that stay idle get role 0 (the null half of a pair
 // that ended in the sampling launch still carries its role).  Plain stores only: nothing else runs beside this block.
 __global__ __launch_bounds__(1024) void mixed_schedule_kernel(const SampleArgs a)
@@ -1386,7 +1221,36 @@ __global__ __launch_bounds__(1024) void beam_shortlist_kernel(const BeamArgs a)
     beam_shortlist<1024>(lg, a.V, min(a.B, a.V), ex, bv, &ls, a.short_lp + row * BEAM_MAX, a.short_tok + row * BEAM_MAX);
 }
 
-__global__ __launch_bounds__(1024) void beam_merge_kernel(const BeamArgs a)
+// what the QUEUE forms of the merge and the back-track need beyond BeamArgs (cvx_t2s_beam_queue_steps: beam search through continuously
+// refilled groups); a second kernel argument, as attn_owner_kernel's table
+struct BeamQueueArgs {
+    int* queue;              // {next pending utterance, number of utterances}
+    int* utterances;         // [n][SR]: in [0] context rows [1] step limit; out [3] status [4] steps decoded [5] the group it ran in
+    const float* start;      // [streams * dim_emb] start token: the input of every slot of a re-armed group
+    int* parents;            // [n][max_len][B] - history by UTTERANCE (a group decodes several, one after the other)
+    int* hist_tok;           // [n][max_len][B][streams]
+    float* hist_lp;
+    float* final_scores;     // [n][B]: scores / steps / finished flags of the B hypotheses when the utterance ended
+    int* final_steps;
+    uint8_t* final_fin;
+    int64_t* tokens;         // [n * B][streams][max_len] (back-track)
+    float* logprobs;
+    int n, ctx_rows;         // (n: the back-track's thread count; the merge reads queue[1])
+};
+
+// where step t of hypothesis i is kept: by slot ([max_len][batch], group g's slots start at g B), or by utterance g ([n][max_len][B])
+template <bool QUEUE> __device__ __forceinline__ int64_t beam_hist_index(const BeamArgs& a, int g, int t, int i)
+{
+    return QUEUE ? ((int64_t)g * a.max_len + t) * a.B + i : (int64_t)t * a.batch + g * a.B + i;
+}
+
+// One selection step of group u = blockIdx.x (1024 threads): the B best candidates, their back-pointers into the history, the scores and
+// slot records, then the next inputs and the next ancestry rows.  ONE body behind beam_merge_kernel and beam_merge_queue_kernel.  QUEUE: the
+// history is indexed by the group's utterance (group record [3]) and, when the utterance ends, the same launch writes its finals, status and
+// steps, takes the next pending one from the queue (one atomicAdd) and re-arms the whole group at position 0; with none left the group ends
+// as without a queue.
+template <bool QUEUE>
+__device__ __forceinline__ void beam_merge_step(const BeamArgs& a, const BeamQueueArgs& qa)
 {
     __shared__ float bv[16];
     __shared__ int bi[16];
@@ -1397,7 +1261,11 @@ __global__ __launch_bounds__(1024) void beam_merge_kernel(const BeamArgs a)
     const int u = blockIdx.x, base = u * B;
     int* const gs = a.groups + 4 * u;
     const int t = aloadi(gs);
-    if (aloadi(gs + 1) != 0 || t < 0 || t >= min(aloadi(gs + 2), a.max_len)) return;       // (block-uniform) ended, or nothing to decode
+    // (a refilled group's limit comes from an utterance record: at least one step)
+    const int lim = QUEUE ? min(max(aloadi(gs + 2), 1), a.max_len) : min(aloadi(gs + 2), a.max_len);
+    if (aloadi(gs + 1) != 0 || t < 0 || t >= lim) return;                  // (block-uniform) ended or idle, or nothing to decode
+    // the history's first index: the group, or its utterance (a stray record stays inside the n utterances)
+    const int hg = QUEUE ? min(max(aloadi(gs + 3), 0), max(aloadi(qa.queue + 1) - 1, 0)) : u;
     if (tid < B) {
         sc[tid] = a.scores[base + tid];
         fin[tid] = a.finished[base + tid] ? 1 : 0;
@@ -1410,23 +1278,70 @@ __global__ __launch_bounds__(1024) void beam_merge_kernel(const BeamArgs a)
     BeamPick r;
     if (tid < B) {
         r = beam_pick(sel[tid], tid, sc, fin, sl_lp, sl_tok, B, S, a.V - 1);
-        const int64_t h = (int64_t)t * a.batch + base + tid;
-        a.parents[h] = r.parent;
-        a.hist_tok[h * S] = r.tok0; a.hist_lp[h * S] = r.lp0;
-        if (S == 2) { a.hist_tok[h * S + 1] = r.tok1; a.hist_lp[h * S + 1] = r.lp1; }
+        const int64_t h = beam_hist_index<QUEUE>(a, hg, t, tid);
+        int* const parents = QUEUE ? qa.parents : a.parents;
+        int* const hist_tok = QUEUE ? qa.hist_tok : a.hist_tok;
+        float* const hist_lp = QUEUE ? qa.hist_lp : a.hist_lp;
+        parents[h] = r.parent;
+        hist_tok[h * S] = r.tok0; hist_lp[h * S] = r.lp0;
+        if (S == 2) { hist_tok[h * S + 1] = r.tok1; hist_lp[h * S + 1] = r.lp1; }
         n_par[tid] = r.parent; n_fin[tid] = r.fin; n_tok[tid][0] = r.tok0; n_tok[tid][1] = r.tok1;
     }
     __syncthreads();                                    // (every old score / flag / length has been read)
     bool all_fin = true;
     for (int i = 0; i < B; ++i) all_fin = all_fin && n_fin[i] != 0;
-    const bool ends = all_fin || t + 1 >= min(aloadi(gs + 2), a.max_len);
+    const bool ends = all_fin || t + 1 >= lim;
+    // a finished hypothesis keeps the steps it took; at the end of the utterance the others took all t + 1
+    int steps = 0;
+    if (tid < B) steps = r.fin ? (sel[tid] >= 0 && fin[r.parent] ? len[r.parent] : (sel[tid] >= 0 ? t + 1 : 0)) : (ends ? t + 1 : 0);
+    if constexpr (QUEUE) {
+        if (ends) {                                     // the utterance's finals, status and steps; then the next pending one
+            __shared__ int chosen;
+            if (tid < B) {
+                const int64_t f = (int64_t)hg * B + tid;
+                qa.final_scores[f] = r.score;
+                qa.final_steps[f] = steps;
+                qa.final_fin[f] = (uint8_t)r.fin;
+            }
+            if (tid == 0) {
+                int* const ur = qa.utterances + SR * hg;
+                ur[4] = t + 1;
+                ur[5] = u;
+                __threadfence();
+                ur[3] = all_fin ? 2 : 3;
+                const int nxt = atomicAdd(qa.queue, 1);
+                chosen = nxt >= 0 && nxt < aloadi(qa.queue + 1) ? nxt : -1;
+            }
+            __syncthreads();
+            const int nxt = chosen;
+            if (nxt >= 0) {
+                // re-arm the group on utterance nxt: position 0, the start token, hypothesis 0 alone live.  The cache and owner rows of the
+                // ended utterance stay where they are: the new one's owner rows name only positions it has written itself
+                int* const un = qa.utterances + SR * nxt;
+                for (int idx = tid; idx < B * S * a.dim_emb; idx += 1024) a.x[(int64_t)base * S * a.dim_emb + idx] = qa.start[idx % (S * a.dim_emb)];
+                if (tid < B) {
+                    const int slot = base + tid;
+                    int* const st = a.state + SR * slot;
+                    a.scores[slot] = tid == 0 ? 0.f : -__builtin_inff();
+                    a.finished[slot] = 0;
+                    st[0] = 0; st[1] = 0; st[2] = 0; st[3] = min(max(aloadi(un), 1), qa.ctx_rows); st[4] = nxt;
+                    a.owner[(int64_t)slot * a.max_len] = slot;      // (parity 0, position 0)
+                }
+                if (tid == 0) {
+                    gs[0] = 0; gs[1] = 0; gs[2] = min(max(aloadi(un + 1), 1), a.max_len); gs[3] = nxt;
+                    un[5] = u;
+                    un[3] = 1;
+                }
+                return;
+            }
+        }
+    }
     if (tid < B) {
         const int slot = base + tid;
         int* const st = a.state + SR * slot;
         a.scores[slot] = r.score;
         a.finished[slot] = (uint8_t)r.fin;
-        // a finished hypothesis keeps the steps it took; the slots of an ended utterance idle at max_len (the attention kernel's idle exit)
-        const int steps = r.fin ? (sel[tid] >= 0 && fin[r.parent] ? len[r.parent] : (sel[tid] >= 0 ? t + 1 : 0)) : (ends ? t + 1 : 0);
+        // the slots of an ended utterance idle at max_len, as a finished hypothesis does (the attention kernel's idle exit)
         st[0] = (r.fin || ends) ? a.max_len : t + 1;
         st[1] = (r.fin || ends) ? 1 : 0;
         st[2] = steps;
@@ -1449,173 +1364,36 @@ __global__ __launch_bounds__(1024) void beam_merge_kernel(const BeamArgs a)
     }
 }
 
-// tokens / logprobs [slot][streams][max_len] of every hypothesis from the back-pointers: one thread per slot walks its ancestry
-__global__ __launch_bounds__(64) void beam_backtrack_kernel(const BeamArgs a)
-{
-    const int slot = blockIdx.x * 64 + threadIdx.x;
-    if (slot >= a.batch) return;
-    const int base = slot / a.B * a.B, S = a.streams;
-    const int T = min(max(aloadi(a.groups + 4 * (slot / a.B)), 0), a.max_len);
-    int cur = slot - base;
-    for (int t = T - 1; t >= 0; --t) {
-        const int64_t h = (int64_t)t * a.batch + base + cur;
-        for (int s = 0; s < S; ++s) {
-            a.tokens[((int64_t)slot * S + s) * a.max_len + t] = a.hist_tok[h * S + s];
-            a.logprobs[((int64_t)slot * S + s) * a.max_len + t] = a.hist_lp[h * S + s];
-        }
-        cur = min(max(aloadi(a.parents + h), 0), a.B - 1);
-    }
-}
+__global__ __launch_bounds__(1024) void beam_merge_kernel(const BeamArgs a) { beam_merge_step<false>(a, BeamQueueArgs{}); }
+__global__ __launch_bounds__(1024) void beam_merge_queue_kernel(const BeamArgs a, const BeamQueueArgs qa) { beam_merge_step<true>(a, qa); }
 
-// ---------------------------------------------------------------- beam search through continuously refilled groups (cvx_t2s_beam_queue_steps)
-// what beam_merge_queue_kernel and beam_backtrack_queue_kernel need beyond BeamArgs (a second kernel argument, as attn_owner_kernel's table)
-struct BeamQueueArgs {
-    int* queue;              // {next pending utterance, number of utterances}
-    int* utterances;         // [n][SR]: in [0] context rows [1] step limit; out [3] status [4] steps decoded [5] the group it ran in
-    const float* start;      // [streams * dim_emb] start token: the input of every slot of a re-armed group
-    int* parents;            // [n][max_len][B] - history by UTTERANCE (a group decodes several, one after the other)
-    int* hist_tok;           // [n][max_len][B][streams]
-    float* hist_lp;
-    float* final_scores;     // [n][B]: scores / steps / finished flags of the B hypotheses when the utterance ended
-    int* final_steps;
-    uint8_t* final_fin;
-    int64_t* tokens;         // [n * B][streams][max_len] (back-track)
-    float* logprobs;
-    int n, ctx_rows;         // (n: the back-track's thread count; the merge reads queue[1])
-};
-
-// beam_merge_kernel (a copy: sharing the body through a template moved the parent's schedule) with the history indexed by the group's
-// utterance (group record [3]) and, when the utterance ends, the refill of the whole group inside the same launch: finals, status and steps
-// of the ended utterance, the next pending one from the queue (one atomicAdd), and the group re-armed at position 0 - or idle when none is left
-__global__ __launch_bounds__(1024) void beam_merge_queue_kernel(const BeamArgs a, const BeamQueueArgs qa)
-{
-    __shared__ float bv[16];
-    __shared__ int bi[16];
-    __shared__ float sc[BEAM_MAX];
-    __shared__ int fin[BEAM_MAX], len[BEAM_MAX], sel[BEAM_MAX];
-    __shared__ int n_par[BEAM_MAX], n_fin[BEAM_MAX], n_tok[BEAM_MAX][2];
-    __shared__ int chosen;
-    const int tid = threadIdx.x, B = a.B, S = a.streams;
-    const int u = blockIdx.x, base = u * B;
-    int* const gs = a.groups + 4 * u;
-    const int t = aloadi(gs);
-    const int lim = min(max(aloadi(gs + 2), 1), a.max_len);
-    if (aloadi(gs + 1) != 0 || t < 0 || t >= lim) return;                  // (block-uniform) idle, or nothing to decode
-    const int utt = min(max(aloadi(gs + 3), 0), max(aloadi(qa.queue + 1) - 1, 0));   // (a stray record stays inside the n utterances)
-    if (tid < B) {
-        sc[tid] = a.scores[base + tid];
-        fin[tid] = a.finished[base + tid] ? 1 : 0;
-        len[tid] = aloadi(a.state + SR * (base + tid) + 2);
-    }
-    __syncthreads();
-    const float* const sl_lp = a.short_lp + (int64_t)base * S * BEAM_MAX;
-    const int* const sl_tok = a.short_tok + (int64_t)base * S * BEAM_MAX;
-    beam_merge<1024>(sc, fin, sl_lp, B, S, min(B, a.V), bv, bi, sel);
-    BeamPick r;
-    if (tid < B) {
-        r = beam_pick(sel[tid], tid, sc, fin, sl_lp, sl_tok, B, S, a.V - 1);
-        const int64_t h = ((int64_t)utt * a.max_len + t) * B + tid;
-        qa.parents[h] = r.parent;
-        qa.hist_tok[h * S] = r.tok0; qa.hist_lp[h * S] = r.lp0;
-        if (S == 2) { qa.hist_tok[h * S + 1] = r.tok1; qa.hist_lp[h * S + 1] = r.lp1; }
-        n_par[tid] = r.parent; n_fin[tid] = r.fin; n_tok[tid][0] = r.tok0; n_tok[tid][1] = r.tok1;
-    }
-    __syncthreads();                                    // (every old score / flag / length has been read)
-    bool all_fin = true;
-    for (int i = 0; i < B; ++i) all_fin = all_fin && n_fin[i] != 0;
-    const bool ends = all_fin || t + 1 >= lim;
-    if (!ends) {
-        if (tid < B) {
-            const int slot = base + tid;
-            int* const st = a.state + SR * slot;
-            a.scores[slot] = r.score;
-            a.finished[slot] = (uint8_t)r.fin;
-            st[0] = r.fin ? a.max_len : t + 1;
-            st[1] = r.fin ? 1 : 0;
-            st[2] = r.fin ? (sel[tid] >= 0 && fin[r.parent] ? len[r.parent] : (sel[tid] >= 0 ? t + 1 : 0)) : 0;
-        }
-        if (tid == 0) gs[0] = t + 1;
-        // the next input of every live hypothesis, and its row of the ancestry table: the parent's row for positions 0..t, then itself
-        for (int idx = tid; idx < B * S * a.dim_emb; idx += 1024) {
-            const int i = idx / (S * a.dim_emb), rem = idx - i * (S * a.dim_emb), s = rem / a.dim_emb, d = rem - s * a.dim_emb;
-            if (!n_fin[i]) a.x[((int64_t)(base + i) * S + s) * a.dim_emb + d] = a.emb[(int64_t)n_tok[i][s] * a.dim_emb + d];
-        }
-        const int* const src = a.owner + (int64_t)(t & 1) * a.batch * a.max_len;
-        int* const dst = a.owner + (int64_t)((t + 1) & 1) * a.batch * a.max_len;
-        for (int i = 0; i < B; ++i) {
-            if (n_fin[i]) continue;
-            const int* const sr = src + (int64_t)(base + n_par[i]) * a.max_len;
-            int* const dr = dst + (int64_t)(base + i) * a.max_len;
-            for (int j = tid; j <= t; j += 1024) dr[j] = aloadi(sr + j);
-            if (tid == 0) dr[t + 1] = base + i;         // (t + 1 < max_len: the utterance has not ended)
-        }
-        return;
-    }
-    // the utterance ends: its finals (a finished hypothesis keeps the steps it took, the others took all t + 1), status and steps
-    if (tid < B) {
-        const int64_t f = (int64_t)utt * B + tid;
-        qa.final_scores[f] = r.score;
-        qa.final_steps[f] = r.fin ? (sel[tid] >= 0 && fin[r.parent] ? len[r.parent] : (sel[tid] >= 0 ? t + 1 : 0)) : t + 1;
-        qa.final_fin[f] = (uint8_t)r.fin;
-    }
-    if (tid == 0) {
-        int* const ur = qa.utterances + SR * utt;
-        ur[4] = t + 1;
-        ur[5] = u;
-        __threadfence();
-        ur[3] = all_fin ? 2 : 3;
-        const int nxt = atomicAdd(qa.queue, 1);
-        chosen = nxt >= 0 && nxt < aloadi(qa.queue + 1) ? nxt : -1;
-    }
-    __syncthreads();
-    const int nxt = chosen;
-    if (nxt < 0) {                                      // nothing pending: the group ends as in the lock-step chain, its slots idle at max_len
-        if (tid < B) {
-            const int slot = base + tid;
-            int* const st = a.state + SR * slot;
-            a.scores[slot] = r.score;
-            a.finished[slot] = (uint8_t)r.fin;
-            st[0] = a.max_len; st[1] = 1; st[2] = qa.final_steps[(int64_t)utt * B + tid];
-        }
-        if (tid == 0) { gs[0] = t + 1; gs[1] = 1; }
-        return;
-    }
-    // re-arm the group on utterance nxt: position 0, the start token, hypothesis 0 alone live.  The cache and owner rows of the ended utterance
-    // stay where they are: the new one's owner rows name only positions it has written itself
-    int* const un = qa.utterances + SR * nxt;
-    for (int idx = tid; idx < B * S * a.dim_emb; idx += 1024) a.x[(int64_t)base * S * a.dim_emb + idx] = qa.start[idx % (S * a.dim_emb)];
-    if (tid < B) {
-        const int slot = base + tid;
-        int* const st = a.state + SR * slot;
-        a.scores[slot] = tid == 0 ? 0.f : -__builtin_inff();
-        a.finished[slot] = 0;
-        st[0] = 0; st[1] = 0; st[2] = 0; st[3] = min(max(aloadi(un), 1), qa.ctx_rows); st[4] = nxt;
-        a.owner[(int64_t)slot * a.max_len] = slot;      // (parity 0, position 0)
-    }
-    if (tid == 0) {
-        gs[0] = 0; gs[1] = 0; gs[2] = min(max(aloadi(un + 1), 1), a.max_len); gs[3] = nxt;
-        un[5] = u;
-        un[3] = 1;
-    }
-}
-
-// tokens / logprobs [utterance * B + hypothesis][streams][max_len] from the per-utterance back-pointers: one thread per (utterance, hypothesis)
-__global__ __launch_bounds__(64) void beam_backtrack_queue_kernel(const BeamArgs a, const BeamQueueArgs qa)
+// tokens / logprobs [row][streams][max_len] from the back-pointers: one thread per row walks its ancestry.  A row is a slot of group g
+// (steps: group record [0]) or, with QUEUE, hypothesis row - g B of utterance g (steps: utterance record [4])
+template <bool QUEUE>
+__device__ __forceinline__ void beam_backtrack_step(const BeamArgs& a, const BeamQueueArgs& qa)
 {
     const int row = blockIdx.x * 64 + threadIdx.x;
-    if (row >= qa.n * a.B) return;
-    const int utt = row / a.B, S = a.streams;
-    const int T = min(max(aloadi(qa.utterances + SR * utt + 4), 0), a.max_len);
-    int cur = row - utt * a.B;
+    if (row >= (QUEUE ? qa.n * a.B : a.batch)) return;
+    const int g = row / a.B, S = a.streams;
+    const int T = min(max(aloadi(QUEUE ? qa.utterances + SR * g + 4 : a.groups + 4 * g), 0), a.max_len);
+    const int* const parents = QUEUE ? qa.parents : a.parents;
+    const int* const hist_tok = QUEUE ? qa.hist_tok : a.hist_tok;
+    const float* const hist_lp = QUEUE ? qa.hist_lp : a.hist_lp;
+    int64_t* const tokens = QUEUE ? qa.tokens : a.tokens;
+    float* const logprobs = QUEUE ? qa.logprobs : a.logprobs;
+    int cur = row - g * a.B;
     for (int t = T - 1; t >= 0; --t) {
-        const int64_t h = ((int64_t)utt * a.max_len + t) * a.B + cur;
+        const int64_t h = beam_hist_index<QUEUE>(a, g, t, cur);
         for (int s = 0; s < S; ++s) {
-            qa.tokens[((int64_t)row * S + s) * a.max_len + t] = qa.hist_tok[h * S + s];
-            qa.logprobs[((int64_t)row * S + s) * a.max_len + t] = qa.hist_lp[h * S + s];
+            tokens[((int64_t)row * S + s) * a.max_len + t] = hist_tok[h * S + s];
+            logprobs[((int64_t)row * S + s) * a.max_len + t] = hist_lp[h * S + s];
         }
-        cur = min(max(aloadi(qa.parents + h), 0), a.B - 1);
+        cur = min(max(aloadi(parents + h), 0), a.B - 1);
     }
 }
+
+__global__ __launch_bounds__(64) void beam_backtrack_kernel(const BeamArgs a) { beam_backtrack_step<false>(a, BeamQueueArgs{}); }
+__global__ __launch_bounds__(64) void beam_backtrack_queue_kernel(const BeamArgs a, const BeamQueueArgs qa) { beam_backtrack_step<true>(a, qa); }
 
 __global__ __launch_bounds__(256) void geglu_kernel(const float* __restrict__ h, float* __restrict__ out, int64_t rows,
                                                    int F, int64_t ld_out)
@@ -1747,18 +1525,38 @@ static BeamArgs beam_args(const cvx_t2s_decoder* d, const cvx_t2s_beam* bm)
                     d->streams, d->max_len};
 }
 
-// the step chain of cvx_t2s_decode_steps (logprobs == NULL) and cvx_t2s_decode_steps_scored: they differ in the sampling kernel only.
-// bm (cvx_t2s_beam_steps): the self-attention reads through the ancestry table, and the shortlist + merge kernels stand in for the sampling
-// kernel - one launch more per step; every other launch is the same.  bq (cvx_t2s_beam_queue_steps): the merge that refills its group.
-// per (cvx_t2s_decode_steps_per_dialogue): the sampling kernel that reads its settings from the per-dialogue table.
-// mixed (cvx_t2s_decode_steps_mixed, with per): the sampling kernel that takes a slot's role from its record, then the scheduler - one
-// launch more per step; n_steps == 0 runs the scheduler alone, once.
-static int t2s_decode_run(const cvx_t2s_decoder* d, int32_t n_steps, float* logprobs, cvx_stream_t s, const cvx_t2s_beam* bm = nullptr,
-                          const BeamQueueArgs* bq = nullptr, const PerArgs* per = nullptr, bool mixed = false)
+static SampleArgs sample_args(const cvx_t2s_decoder* d, float* logprobs)
+{
+    return SampleArgs{d->logits, d->uniforms, d->emb, d->x, d->tokens, d->state, d->queue, d->dialogues, d->start, d->batch, d->uniform_steps,
+                      d->vocab, d->dim_emb, d->streams, d->max_len, d->top_k, d->vocab - 1, 1.0f / fmaxf(d->temperature, 1e-10f),
+                      d->cfg_scale, d->top_p, logprobs};
+}
+
+// which selection follows the logits of a step; the entry points fill it through the checks below
+struct T2sSelect {
+    enum Kind {
+        SAMPLE,              // cvx_t2s_decode_steps, cvx_t2s_decode_steps_scored: sample_kernel
+        PER,                 // cvx_t2s_decode_steps_per_dialogue: sample_per_kernel, its settings from the per-dialogue table
+        MIXED,               // cvx_t2s_decode_steps_mixed: sample_mixed_kernel takes a slot's role from its record, then the scheduler - one
+                             // launch more per step; n_steps == 0 runs the scheduler alone, once
+        BEAM,                // cvx_t2s_beam_steps: the self-attention reads through the ancestry table, and the shortlist + merge kernels stand in
+                             // for the sampling kernel - one launch more per step; every other launch is the same
+        BEAM_QUEUE           // cvx_t2s_beam_queue_steps: the merge that refills its group
+    } kind;
+    float* logprobs;         // SAMPLE / PER / MIXED: non-NULL picks the scoring instantiation
+    PerArgs per;             // PER / MIXED
+    const cvx_t2s_beam* bm;  // BEAM / BEAM_QUEUE
+    BeamQueueArgs bq;        // BEAM_QUEUE
+};
+
+// the step chain of every cvx_t2s_*_steps* entry point: they differ in what follows the logits only
+static int t2s_decode_run(const cvx_t2s_decoder* d, int32_t n_steps, const T2sSelect& sel, cvx_stream_t s)
 {
     hipStream_t st = cvx_hip_stream(s);
     const float scale = 0.125f;        // dim_head ** -0.5
     const int nb = d->batch;
+    const bool beam = sel.kind == T2sSelect::BEAM || sel.kind == T2sSelect::BEAM_QUEUE;
+    const dim3 slots((unsigned)nb), block(1024);
     // ONE row pair per wave everywhere since the kernel holds 118 VGPRs (four blocks per CU): 64 slots 462 vs 480 us per CoMix step with two
     // pairs (170 VGPRs, two blocks), 32-CU side stream at 8 slots 434 vs 439 (round 5, at two blocks per CU either way, two pairs won there:
     // 760 vs 813).
@@ -1774,7 +1572,7 @@ static int t2s_decode_run(const cvx_t2s_decoder* d, int32_t n_steps, float* logp
             g.cache_stride = cache_stride; g.state = d->state; g.max_len = d->max_len;
             launch_gemv<MODE_QKV>(g, 3 * d->inner / 2, nb, st);
             AttnArgs at{d->q, L.k_cache, L.v_cache, d->inner, cache_stride, d->att, d->state, -1, 0, scale, d->max_len};
-            if (bm) hipLaunchKernelGGL(attn_owner_kernel, dim3((unsigned)d->heads, (unsigned)nb), dim3(256), 0, st, at, (const int*)bm->owner);
+            if (beam) hipLaunchKernelGGL(attn_owner_kernel, dim3((unsigned)d->heads, (unsigned)nb), dim3(256), 0, st, at, (const int*)sel.bm->owner);
             else hipLaunchKernelGGL(attn_kernel, dim3((unsigned)d->heads, (unsigned)nb), dim3(256), 0, st, at);
             g = GemvArgs{};
             g.W = L.wo_s; g.ldw = d->inner; g.x = d->att; g.x_stride = d->inner; g.y = d->x; g.y_stride = d->dim; g.N = d->dim; g.K = d->inner;
@@ -1804,129 +1602,139 @@ static int t2s_decode_run(const cvx_t2s_decoder* d, int32_t n_steps, float* logp
         g.W = d->emb; g.ldw = d->dim_emb; g.x = d->x; g.x_stride = d->dim; g.gamma = d->final_gamma; g.y = d->logits;
         g.y_stride = d->streams * d->vocab; g.N = d->vocab; g.K = d->dim_emb; g.streams = d->streams;
         launch_gemv<MODE_LOGITS>(g, d->streams * ((d->vocab + 1) / 2), nb, st);
-        if (bm) {
-            const BeamArgs ba = beam_args(d, bm);
-            hipLaunchKernelGGL(beam_shortlist_kernel, dim3((unsigned)(nb * d->streams)), dim3(1024), 0, st, ba);
-            if (bq) hipLaunchKernelGGL(beam_merge_queue_kernel, dim3((unsigned)(nb / bm->beam_size)), dim3(1024), 0, st, ba, *bq);
-            else hipLaunchKernelGGL(beam_merge_kernel, dim3((unsigned)(nb / bm->beam_size)), dim3(1024), 0, st, ba);
+        if (beam) {
+            const BeamArgs ba = beam_args(d, sel.bm);
+            const dim3 groups((unsigned)(nb / sel.bm->beam_size));
+            hipLaunchKernelGGL(beam_shortlist_kernel, dim3((unsigned)(nb * d->streams)), block, 0, st, ba);
+            if (sel.kind == T2sSelect::BEAM_QUEUE) hipLaunchKernelGGL(beam_merge_queue_kernel, groups, block, 0, st, ba, sel.bq);
+            else hipLaunchKernelGGL(beam_merge_kernel, groups, block, 0, st, ba);
             continue;
         }
-        SampleArgs sa{d->logits, d->uniforms, d->emb, d->x, d->tokens, d->state, d->queue, d->dialogues, d->start, nb, d->uniform_steps,
-                      d->vocab, d->dim_emb, d->streams, d->max_len, d->top_k, d->vocab - 1, 1.0f / fmaxf(d->temperature, 1e-10f),
-                      d->cfg_scale, d->top_p, logprobs};
-        if (mixed) {
-            if (logprobs) hipLaunchKernelGGL(sample_mixed_kernel<true>, dim3((unsigned)nb), dim3(1024), 0, st, sa, *per);
-            else hipLaunchKernelGGL(sample_mixed_kernel<false>, dim3((unsigned)nb), dim3(1024), 0, st, sa, *per);
-            hipLaunchKernelGGL(mixed_schedule_kernel, dim3(1), dim3(1024), 0, st, sa);
-            continue;
-        }
-        if (per) {
-            if (logprobs) hipLaunchKernelGGL(sample_per_kernel<true>, dim3((unsigned)nb), dim3(1024), 0, st, sa, *per);
-            else hipLaunchKernelGGL(sample_per_kernel<false>, dim3((unsigned)nb), dim3(1024), 0, st, sa, *per);
-            continue;
-        }
-        if (logprobs) {
-            if (d->filter_mode == CVX_T2S_FILTER_TOP_P) hipLaunchKernelGGL((sample_kernel<FILT_TOP_P, true>), dim3((unsigned)nb), dim3(1024), 0, st, sa);
-            else hipLaunchKernelGGL((sample_kernel<FILT_TOP_K, true>), dim3((unsigned)nb), dim3(1024), 0, st, sa);
-        } else if (d->filter_mode == CVX_T2S_FILTER_TOP_P) hipLaunchKernelGGL(sample_kernel<FILT_TOP_P>, dim3((unsigned)nb), dim3(1024), 0, st, sa);
-        else hipLaunchKernelGGL(sample_kernel<FILT_TOP_K>, dim3((unsigned)nb), dim3(1024), 0, st, sa);
+        const SampleArgs sa = sample_args(d, sel.logprobs);
+        const bool top_p = d->filter_mode == CVX_T2S_FILTER_TOP_P;
+        if (sel.kind == T2sSelect::MIXED) {
+            if (sel.logprobs) hipLaunchKernelGGL(sample_mixed_kernel<true>, slots, block, 0, st, sa, sel.per);
+            else hipLaunchKernelGGL(sample_mixed_kernel<false>, slots, block, 0, st, sa, sel.per);
+            hipLaunchKernelGGL(mixed_schedule_kernel, dim3(1), block, 0, st, sa);
+        } else if (sel.kind == T2sSelect::PER) {
+            if (sel.logprobs) hipLaunchKernelGGL(sample_per_kernel<true>, slots, block, 0, st, sa, sel.per);
+            else hipLaunchKernelGGL(sample_per_kernel<false>, slots, block, 0, st, sa, sel.per);
+        } else if (sel.logprobs) {
+            if (top_p) hipLaunchKernelGGL((sample_kernel<FILT_TOP_P, true>), slots, block, 0, st, sa);
+            else hipLaunchKernelGGL((sample_kernel<FILT_TOP_K, true>), slots, block, 0, st, sa);
+        } else if (top_p) hipLaunchKernelGGL(sample_kernel<FILT_TOP_P>, slots, block, 0, st, sa);
+        else hipLaunchKernelGGL(sample_kernel<FILT_TOP_K>, slots, block, 0, st, sa);
     }
-    if (mixed && n_steps == 0) {
-        const SampleArgs sa{d->logits, d->uniforms, d->emb, d->x, d->tokens, d->state, d->queue, d->dialogues, d->start, nb, d->uniform_steps,
-                            d->vocab, d->dim_emb, d->streams, d->max_len, d->top_k, d->vocab - 1, 1.0f, d->cfg_scale, d->top_p, logprobs};
-        hipLaunchKernelGGL(mixed_schedule_kernel, dim3(1), dim3(1024), 0, st, sa);
-    }
+    if (sel.kind == T2sSelect::MIXED && n_steps == 0) hipLaunchKernelGGL(mixed_schedule_kernel, dim3(1), block, 0, st, sample_args(d, sel.logprobs));
     CVX_CHECK_LAUNCH("cvx_t2s_decode_steps");
+    return CVX_OK;
+}
+
+// ---- the argument checks the entry points share.  `who`: the entry point's name in the message.  Each runs behind t2s_validate (it reads the
+// descriptor), refuses with CVX_EINVAL before anything is launched, and fills its part of the selection.
+#define T2S_TRY(call)                        \
+    do {                                     \
+        const int rc_ = (call);              \
+        if (rc_ != CVX_OK) return rc_;       \
+    } while (0)
+
+template <class T>
+static int t2s_struct_size(const char* who, const char* type, const T* p)
+{
+    CVX_REQUIRE(p && p->struct_size == sizeof(T), "%s: %s.struct_size = %u, this library knows %u", who, type, p ? p->struct_size : 0u,
+                (unsigned)sizeof(T));
+    return CVX_OK;
+}
+
+// cvx_t2s_scoring; optional: none (NULL) leaves the log-prob epilogue off
+static int t2s_scoring_block(const char* who, const cvx_t2s_decoder* d, const cvx_t2s_scoring* sc, bool optional, T2sSelect& sel)
+{
+    if (optional && !sc) return CVX_OK;
+    T2S_TRY(t2s_struct_size(who, "cvx_t2s_scoring", sc));
+    CVX_REQUIRE(sc->logprobs, "%s: null logprobs", who);
+    CVX_REQUIRE(sc->logprob_len == d->max_len, "%s: logprob_len = %d, the rows of logprobs are laid out like those of tokens (max_len = %d floats)",
+                who, sc->logprob_len, d->max_len);
+    sel.logprobs = sc->logprobs;
+    return CVX_OK;
+}
+
+// cvx_t2s_per_dialogue: every record a slot can name has a row - the n_dialogues behind a queue; without one, slot b decodes dialogue b
+static int t2s_per_dialogue_block(const char* who, const cvx_t2s_decoder* d, const cvx_t2s_per_dialogue* per, T2sSelect& sel)
+{
+    T2S_TRY(t2s_struct_size(who, "cvx_t2s_per_dialogue", per));
+    CVX_REQUIRE(per->table && per->n_records >= 1, "%s: null table or n_records = %d < 1", who, per->n_records);
+    CVX_REQUIRE(per->n_records >= d->n_dialogues && (d->queue || per->n_records >= d->batch),
+                "%s: n_records = %d rows for %d dialogue records / %d slots", who, per->n_records, d->n_dialogues, d->batch);
+    sel.per = PerArgs{static_cast<const int*>(per->table), per->n_records};
+    return CVX_OK;
+}
+
+// cvx_t2s_beam
+static int t2s_beam_block(const char* who, const cvx_t2s_decoder* d, const cvx_t2s_beam* bm, T2sSelect& sel)
+{
+    T2S_TRY(t2s_struct_size(who, "cvx_t2s_beam", bm));
+    CVX_REQUIRE(!d->queue, "%s: the dialogue queue of the sampled decode cannot feed beam groups (dec->queue must be NULL)", who);
+    CVX_REQUIRE(!(d->cfg_scale > 1.f), "%s: guidance (cfg_scale > 1) is not built for beam search", who);
+    CVX_REQUIRE(bm->beam_size >= 1 && bm->beam_size <= BEAM_MAX && d->batch % bm->beam_size == 0,
+                "%s: beam_size = %d outside [1, %d] or no divisor of batch = %d", who, bm->beam_size, BEAM_MAX, d->batch);
+    CVX_REQUIRE(bm->hist_len == d->max_len, "%s: hist_len = %d, the history arrays and logprobs hold max_len = %d steps", who, bm->hist_len,
+                d->max_len);
+    CVX_REQUIRE(bm->scores && bm->finished && bm->owner && bm->groups && bm->parents && bm->hist_tokens && bm->hist_logprobs && bm->short_lp &&
+                bm->short_tokens && bm->logprobs, "%s: null pointer in cvx_t2s_beam", who);
+    sel.bm = bm;
     return CVX_OK;
 }
 
 extern "C" int cvx_t2s_decode_steps(const cvx_t2s_decoder* d, int32_t n_steps, cvx_stream_t s)
 {
-    const int rc = t2s_validate(d, n_steps);
-    if (rc != CVX_OK) return rc;
-    return t2s_decode_run(d, n_steps, nullptr, s);
+    T2S_TRY(t2s_validate(d, n_steps));
+    return t2s_decode_run(d, n_steps, T2sSelect{T2sSelect::SAMPLE}, s);
 }
 
 extern "C" int cvx_t2s_decode_steps_scored(const cvx_t2s_decoder* d, const cvx_t2s_scoring* sc, int32_t n_steps, cvx_stream_t s)
 {
-    CVX_REQUIRE(sc && sc->struct_size == sizeof(cvx_t2s_scoring), "t2s_decode_scored: cvx_t2s_scoring.struct_size = %u, this library knows %u",
-                sc ? sc->struct_size : 0u, (unsigned)sizeof(cvx_t2s_scoring));
-    CVX_REQUIRE(sc->logprobs, "t2s_decode_scored: null logprobs");
-    const int rc = t2s_validate(d, n_steps);
-    if (rc != CVX_OK) return rc;
-    CVX_REQUIRE(sc->logprob_len == d->max_len, "t2s_decode_scored: logprob_len = %d, the rows of logprobs are laid out like those of tokens "
-                "(max_len = %d floats)", sc->logprob_len, d->max_len);
-    return t2s_decode_run(d, n_steps, sc->logprobs, s);
+    T2sSelect sel{T2sSelect::SAMPLE};
+    T2S_TRY(t2s_validate(d, n_steps));
+    T2S_TRY(t2s_scoring_block("t2s_decode_scored", d, sc, false, sel));
+    return t2s_decode_run(d, n_steps, sel, s);
 }
 
 extern "C" int cvx_t2s_decode_steps_per_dialogue(const cvx_t2s_decoder* d, const cvx_t2s_scoring* sc, const cvx_t2s_per_dialogue* per,
                                                  int32_t n_steps, cvx_stream_t s)
 {
-    CVX_REQUIRE(per && per->struct_size == sizeof(cvx_t2s_per_dialogue),
-                "t2s_decode_per_dialogue: cvx_t2s_per_dialogue.struct_size = %u, this library knows %u", per ? per->struct_size : 0u,
-                (unsigned)sizeof(cvx_t2s_per_dialogue));
-    CVX_REQUIRE(per->table && per->n_records >= 1, "t2s_decode_per_dialogue: null table or n_records = %d < 1", per->n_records);
-    CVX_REQUIRE(!sc || sc->struct_size == sizeof(cvx_t2s_scoring), "t2s_decode_per_dialogue: cvx_t2s_scoring.struct_size = %u, this library knows %u",
-                sc ? sc->struct_size : 0u, (unsigned)sizeof(cvx_t2s_scoring));
-    CVX_REQUIRE(!sc || sc->logprobs, "t2s_decode_per_dialogue: null logprobs");
-    const int rc = t2s_validate(d, n_steps, true);
-    if (rc != CVX_OK) return rc;
-    CVX_REQUIRE(!sc || sc->logprob_len == d->max_len, "t2s_decode_per_dialogue: logprob_len = %d, the rows of logprobs are laid out like those "
-                "of tokens (max_len = %d floats)", sc ? sc->logprob_len : 0, d->max_len);
-    // every record a slot can name has a row: the n_dialogues behind a queue; without one, slot b decodes dialogue b
-    CVX_REQUIRE(per->n_records >= d->n_dialogues && (d->queue || per->n_records >= d->batch),
-                "t2s_decode_per_dialogue: n_records = %d rows for %d dialogue records / %d slots", per->n_records, d->n_dialogues, d->batch);
-    const PerArgs pa{static_cast<const int*>(per->table), per->n_records};
-    return t2s_decode_run(d, n_steps, sc ? sc->logprobs : nullptr, s, nullptr, nullptr, &pa);
+    const char* const who = "t2s_decode_per_dialogue";
+    T2sSelect sel{T2sSelect::PER};
+    T2S_TRY(t2s_validate(d, n_steps, true));
+    T2S_TRY(t2s_per_dialogue_block(who, d, per, sel));
+    T2S_TRY(t2s_scoring_block(who, d, sc, true, sel));
+    return t2s_decode_run(d, n_steps, sel, s);
 }
 
 extern "C" int cvx_t2s_decode_steps_mixed(const cvx_t2s_decoder* d, const cvx_t2s_scoring* sc, const cvx_t2s_per_dialogue* per,
                                           const cvx_t2s_mixed* mx, int32_t n_steps, cvx_stream_t s)
 {
-    CVX_REQUIRE(mx && mx->struct_size == sizeof(cvx_t2s_mixed), "t2s_decode_mixed: cvx_t2s_mixed.struct_size = %u, this library knows %u",
-                mx ? mx->struct_size : 0u, (unsigned)sizeof(cvx_t2s_mixed));
-    CVX_REQUIRE(per && per->struct_size == sizeof(cvx_t2s_per_dialogue),
-                "t2s_decode_mixed: cvx_t2s_per_dialogue.struct_size = %u, this library knows %u", per ? per->struct_size : 0u,
-                (unsigned)sizeof(cvx_t2s_per_dialogue));
-    CVX_REQUIRE(per->table && per->n_records >= 1, "t2s_decode_mixed: null table or n_records = %d < 1", per->n_records);
-    CVX_REQUIRE(!sc || sc->struct_size == sizeof(cvx_t2s_scoring), "t2s_decode_mixed: cvx_t2s_scoring.struct_size = %u, this library knows %u",
-                sc ? sc->struct_size : 0u, (unsigned)sizeof(cvx_t2s_scoring));
-    CVX_REQUIRE(!sc || sc->logprobs, "t2s_decode_mixed: null logprobs");
-    const int rc = t2s_validate(d, n_steps, true);
-    if (rc != CVX_OK) return rc;
-    CVX_REQUIRE(!sc || sc->logprob_len == d->max_len, "t2s_decode_mixed: logprob_len = %d, the rows of logprobs are laid out like those "
-                "of tokens (max_len = %d floats)", sc ? sc->logprob_len : 0, d->max_len);
+    const char* const who = "t2s_decode_mixed";
+    T2sSelect sel{T2sSelect::MIXED};
+    T2S_TRY(t2s_validate(d, n_steps, true));
+    T2S_TRY(t2s_struct_size(who, "cvx_t2s_mixed", mx));
     CVX_REQUIRE(d->queue, "t2s_decode_mixed: the scheduler hands out records from the dialogue queue (queue must not be NULL)");
     CVX_REQUIRE(!(d->cfg_scale > 1.f), "t2s_decode_mixed: cfg_scale = %g > 1 asks for the launch-wide pair layout; here the layout is per "
                 "record (flag bit 2) and the scale comes from the table", (double)d->cfg_scale);
-    CVX_REQUIRE(per->n_records >= d->n_dialogues, "t2s_decode_mixed: n_records = %d rows for %d dialogue records", per->n_records,
-                d->n_dialogues);
+    T2S_TRY(t2s_per_dialogue_block(who, d, per, sel));
+    T2S_TRY(t2s_scoring_block(who, d, sc, true, sel));
     CVX_REQUIRE(mx->n_guided >= 0 && 2 * (int64_t)mx->n_guided <= d->n_dialogues,
                 "t2s_decode_mixed: n_guided = %d guided utterances take two records each of the %d", mx->n_guided, d->n_dialogues);
     CVX_REQUIRE(mx->n_guided == 0 || (d->streams == 1 && d->batch >= 2),
                 "t2s_decode_mixed: guided records need a one-output model and two slots (streams = %d, batch = %d)", d->streams, d->batch);
-    const PerArgs pa{static_cast<const int*>(per->table), per->n_records};
-    return t2s_decode_run(d, n_steps, sc ? sc->logprobs : nullptr, s, nullptr, nullptr, &pa, true);
+    return t2s_decode_run(d, n_steps, sel, s);
 }
 
 extern "C" int cvx_t2s_beam_steps(const cvx_t2s_decoder* d, const cvx_t2s_beam* bm, int32_t n_steps, cvx_stream_t s)
 {
-    CVX_REQUIRE(bm && bm->struct_size == sizeof(cvx_t2s_beam), "t2s_beam_steps: cvx_t2s_beam.struct_size = %u, this library knows %u",
-                bm ? bm->struct_size : 0u, (unsigned)sizeof(cvx_t2s_beam));
-    const int rc = t2s_validate(d, n_steps);
-    if (rc != CVX_OK) return rc;
-    CVX_REQUIRE(!d->queue, "t2s_beam_steps: a dialogue queue cannot feed beam groups (queue must be NULL)");
-    CVX_REQUIRE(!(d->cfg_scale > 1.f), "t2s_beam_steps: guidance (cfg_scale > 1) is not built for beam search");
-    CVX_REQUIRE(bm->beam_size >= 1 && bm->beam_size <= BEAM_MAX && d->batch % bm->beam_size == 0,
-                "t2s_beam_steps: beam_size = %d outside [1, %d] or no divisor of batch = %d", bm->beam_size, BEAM_MAX, d->batch);
-    CVX_REQUIRE(bm->hist_len == d->max_len, "t2s_beam_steps: hist_len = %d, the back-pointer arrays and logprobs hold max_len = %d steps",
-                bm->hist_len, d->max_len);
-    CVX_REQUIRE(bm->scores && bm->finished && bm->owner && bm->groups && bm->parents && bm->hist_tokens && bm->hist_logprobs && bm->short_lp &&
-                bm->short_tokens && bm->logprobs, "t2s_beam_steps: null pointer in cvx_t2s_beam");
-    if (n_steps > 0) {
-        const int rr = t2s_decode_run(d, n_steps, nullptr, s, bm);
-        if (rr != CVX_OK) return rr;
-    }
+    T2sSelect sel{T2sSelect::BEAM};
+    T2S_TRY(t2s_validate(d, n_steps));
+    T2S_TRY(t2s_beam_block("t2s_beam_steps", d, bm, sel));
+    if (n_steps > 0) T2S_TRY(t2s_decode_run(d, n_steps, sel, s));
     if (bm->backtrack) {
         hipLaunchKernelGGL(beam_backtrack_kernel, dim3((unsigned)((d->batch + 63) / 64)), dim3(64), 0, cvx_hip_stream(s), beam_args(d, bm));
         CVX_CHECK_LAUNCH("cvx_t2s_beam_steps");
@@ -1937,33 +1745,20 @@ extern "C" int cvx_t2s_beam_steps(const cvx_t2s_decoder* d, const cvx_t2s_beam* 
 extern "C" int cvx_t2s_beam_queue_steps(const cvx_t2s_decoder* d, const cvx_t2s_beam* bm, const cvx_t2s_beam_queue* bq, int32_t n_steps,
                                         cvx_stream_t s)
 {
-    CVX_REQUIRE(bm && bm->struct_size == sizeof(cvx_t2s_beam), "t2s_beam_queue_steps: cvx_t2s_beam.struct_size = %u, this library knows %u",
-                bm ? bm->struct_size : 0u, (unsigned)sizeof(cvx_t2s_beam));
-    CVX_REQUIRE(bq && bq->struct_size == sizeof(cvx_t2s_beam_queue),
-                "t2s_beam_queue_steps: cvx_t2s_beam_queue.struct_size = %u, this library knows %u", bq ? bq->struct_size : 0u,
-                (unsigned)sizeof(cvx_t2s_beam_queue));
-    const int rc = t2s_validate(d, n_steps);
-    if (rc != CVX_OK) return rc;
-    CVX_REQUIRE(!d->queue, "t2s_beam_queue_steps: the dialogue queue of the sampled decode plays no part (dec->queue must be NULL)");
-    CVX_REQUIRE(!(d->cfg_scale > 1.f), "t2s_beam_queue_steps: guidance (cfg_scale > 1) is not built for beam search");
-    CVX_REQUIRE(bm->beam_size >= 1 && bm->beam_size <= BEAM_MAX && d->batch % bm->beam_size == 0,
-                "t2s_beam_queue_steps: beam_size = %d outside [1, %d] or no divisor of batch = %d", bm->beam_size, BEAM_MAX, d->batch);
-    CVX_REQUIRE(bm->hist_len == d->max_len, "t2s_beam_queue_steps: hist_len = %d, the history arrays hold max_len = %d steps per utterance",
-                bm->hist_len, d->max_len);
+    const char* const who = "t2s_beam_queue_steps";
+    T2sSelect sel{T2sSelect::BEAM_QUEUE};
+    T2S_TRY(t2s_validate(d, n_steps));
+    T2S_TRY(t2s_beam_block(who, d, bm, sel));
+    T2S_TRY(t2s_struct_size(who, "cvx_t2s_beam_queue", bq));
     CVX_REQUIRE(bq->n_utterances >= 1, "t2s_beam_queue_steps: n_utterances = %d", bq->n_utterances);
-    CVX_REQUIRE(bm->scores && bm->finished && bm->owner && bm->groups && bm->parents && bm->hist_tokens && bm->hist_logprobs && bm->short_lp &&
-                bm->short_tokens && bm->logprobs, "t2s_beam_queue_steps: null pointer in cvx_t2s_beam");
     CVX_REQUIRE(bq->queue && bq->utterances && bq->start && bq->parents && bq->hist_tokens && bq->hist_logprobs && bq->final_scores &&
                 bq->final_steps && bq->final_finished && bq->tokens && bq->logprobs, "t2s_beam_queue_steps: null pointer in cvx_t2s_beam_queue");
-    const BeamQueueArgs qa{bq->queue, bq->utterances, bq->start, bq->parents, bq->hist_tokens, bq->hist_logprobs, bq->final_scores,
+    sel.bq = BeamQueueArgs{bq->queue, bq->utterances, bq->start, bq->parents, bq->hist_tokens, bq->hist_logprobs, bq->final_scores,
                            bq->final_steps, bq->final_finished, bq->tokens, bq->logprobs, bq->n_utterances, d->ctx_rows};
-    if (n_steps > 0) {
-        const int rr = t2s_decode_run(d, n_steps, nullptr, s, bm, &qa);
-        if (rr != CVX_OK) return rr;
-    }
+    if (n_steps > 0) T2S_TRY(t2s_decode_run(d, n_steps, sel, s));
     if (bm->backtrack) {
         hipLaunchKernelGGL(beam_backtrack_queue_kernel, dim3((unsigned)(((int64_t)bq->n_utterances * bm->beam_size + 63) / 64)), dim3(64), 0,
-                           cvx_hip_stream(s), beam_args(d, bm), qa);
+                           cvx_hip_stream(s), beam_args(d, bm), sel.bq);
         CVX_CHECK_LAUNCH("cvx_t2s_beam_queue_steps");
     }
     return CVX_OK;
