@@ -74,7 +74,8 @@ typedef const cvx_ctx* cvx_stream_t;
  * flag bit; no struct or entry point changes): the V^T stores of a to_qkv launch of the eight-phase kernels go line-major, 16 bytes
  * per lane (same values, same addresses); CVX_GEMM_FLAG_VT_PIECES keeps the earlier store code selectable.  Still 113 (a symbol and a
  * struct added): cvx_t2s_decode_steps_mixed with cvx_t2s_mixed - guided and unguided dialogues in one slot pool; slot record [7], so
- * far reserved, carries a slot's role there. */
+ * far reserved, carries a slot's role there.  Still 113 (two symbols added, no struct changed): cvx_t2s_beam_guided_steps and
+ * cvx_t2s_beam_guided_queue_steps - beam search under classifier-free guidance, on the structs of the unguided entry points. */
 #define CVX_ABI_VERSION 113
 int         cvx_version(void);
 const char* cvx_last_error_string(void);
@@ -931,6 +932,51 @@ typedef struct cvx_t2s_beam_queue {
 
 int cvx_t2s_beam_queue_steps(const cvx_t2s_decoder* dec, const cvx_t2s_beam* beam, const cvx_t2s_beam_queue* bq, int32_t n_steps,
                              cvx_stream_t stream);
+
+/* Beam search UNDER CLASSIFIER-FREE GUIDANCE (dec->cfg_scale > 1, one-output models: streams == 1): the algorithm of cvx_t2s_beam_steps
+ * with S = 1, where a hypothesis is a SLOT PAIR with one ancestry, as a guided utterance of the sampled decode is a slot pair.
+ *   Layout: hypothesis h of the launch sits in slots 2h (the TEXT half: decodes with the text context) and 2h + 1 (the NULL half: decodes
+ *       with the learned null key / value only).  Utterance u owns hypotheses [u B, (u + 1) B) = slots [2 u B, 2 (u + 1) B);
+ *       dec->batch = utterances * 2 B <= 64, 1 <= B <= 16.  H = dec->batch / 2 hypotheses, G = H / B groups.
+ *   Indexed BY SLOT (dec->batch rows, as in cvx_t2s_beam_steps): the slot records dec->state, owner int32 [2][batch][max_len], dec->x,
+ *       dec->logits and the self-attention caches.
+ *   Indexed BY HYPOTHESIS (H rows where cvx_t2s_beam_steps has batch rows): scores fp32 [H], finished uint8 [H], parents int32 [max_len][H]
+ *       (index inside the group), hist_tokens int32 / hist_logprobs fp32 [max_len][H][1], short_lp fp32 / short_tokens int32 [H][1][16],
+ *       the back-tracked dec->tokens int64 [H][1][max_len] and logprobs fp32 [H][1][max_len]; groups int32 [G][4] as before.
+ *   The caller writes, before step 0: both slot records of hypothesis h of utterance u - text half {0, 0, 0, context rows of u, kv_c row of
+ *       u's [null | context] block, ...}, null half {0, 0, 0, 1, a kv_c row whose row 0 holds the learned null key / value, ...} (the rows a
+ *       guided pair of cvx_t2s_decode_steps uses; the B hypotheses of an utterance may share both); x of both slots = the start token; the
+ *       identity ancestry owner[*][slot][*] = slot; scores {0, -inf, ...} per utterance, finished 0, groups {0, 0, limit, 0}.  Idle groups:
+ *       groups [1] = 1 and both slots of every hypothesis at position max_len.
+ *   One step: g[j] = n[j] + (c[j] - n[j]) * scale in fp32 in this operation order (no contraction), c = the logits row of the text half, n
+ *       that of the null half, scale = dec->cfg_scale; lp[j] = log_softmax of g exactly as defined under "Log-probabilities" above - the
+ *       row and the function the scored decode uses under guidance, so lp carries the bits cvx_t2s_decode_steps_scored gives a forced
+ *       dialogue pair with the same prefix.  Shortlist, candidates, order key q, selection, ties, dead and finished hypotheses, the end of
+ *       an utterance: cvx_t2s_beam_steps with S = 1, over hypotheses.
+ *   The selection writes, for BOTH halves of new hypothesis i with parent p: the slot records ([0] position, or max_len for a finished
+ *       hypothesis and for an ended utterance - both slots idle together; [1], [2] as in cvx_t2s_beam_steps); the next input - the chosen
+ *       token's embedding row into both x rows; and the next ancestry rows - the text slot's row is the parent's TEXT row for positions
+ *       0..pos, then the text slot itself; the null slot's row is the parent's NULL row, then the null slot itself.  The self-attention
+ *       kernel is the one of cvx_t2s_beam_steps, one block row per slot.
+ *   Per step: the launches of cvx_t2s_beam_steps, no more.  No host synchronisation, graph-capturable.  backtrack as in cvx_t2s_beam_steps,
+ *       one thread per hypothesis.
+ * CVX_EINVAL (nothing is launched): dec->cfg_scale not > 1 (NaN included; cvx_t2s_beam_steps is the unguided entry), streams != 1,
+ * n_ctx != 0, dec->queue != NULL, beam_size outside [1, 16], batch % (2 beam_size) != 0, hist_len != max_len, struct_size != sizeof, a
+ * NULL pointer, and everything cvx_t2s_decode_steps refuses. */
+int cvx_t2s_beam_guided_steps(const cvx_t2s_decoder* dec, const cvx_t2s_beam* beam, int32_t n_steps, cvx_stream_t stream);
+
+/* cvx_t2s_beam_queue_steps under guidance: the G = dec->batch / (2 B) groups of cvx_t2s_beam_guided_steps, refilled from a list of n
+ * utterances.  `beam` as for cvx_t2s_beam_guided_steps (groups record [3] = the utterance), `bq` as for cvx_t2s_beam_queue_steps: its
+ * arrays are by utterance and hypothesis already ([n][hist_len][B]..., [n][B], [n * B][1][max_len]).  Utterance j owns TWO kv_c rows, as a
+ * guided record pair of the sampled decode does: row 2 j holds [null | context of j] (utterance record [0] = its context rows), row 2 j + 1
+ * holds the learned null key / value in its row 0.  The caller starts group g on utterance g: text slots {0, 0, 0, context rows, 2 g, ...},
+ * null slots {0, 0, 0, 1, 2 g + 1, ...}, owner[0][slot][0] = slot for both halves.  A refilled group re-arms BOTH halves of its B
+ * hypotheses: x = start, position 0, [1] = [2] = 0, owner[0][slot][0] = slot, text half [3] = context rows (clamped into [1, ctx_rows]) and
+ * [4] = 2 * utterance, null half [3] = 1 and [4] = 2 * utterance + 1.  Everything else, the finals and the back-track included, is
+ * cvx_t2s_beam_queue_steps; an utterance gets, bit for bit, what cvx_t2s_beam_guided_steps gives it alone.  CVX_EINVAL: what
+ * cvx_t2s_beam_guided_steps and cvx_t2s_beam_queue_steps refuse (with cfg_scale not > 1 refused here, cfg_scale > 1 there). */
+int cvx_t2s_beam_guided_queue_steps(const cvx_t2s_decoder* dec, const cvx_t2s_beam* beam, const cvx_t2s_beam_queue* bq, int32_t n_steps,
+                                    cvx_stream_t stream);
 
 /* The selection step alone (the device functions cvx_t2s_beam_steps selects with; no slot state): groups G of beam_size B hypotheses,
  * logits [G * B, streams, V] fp32, scores_in [G * B], finished_in uint8 [G * B] -> per new slot: parents (index inside the group), tokens

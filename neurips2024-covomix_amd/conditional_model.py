@@ -234,7 +234,8 @@ class CoVoMixModel:
     def synthesis_sample_text2semantic(self, grapheme_token_ids, temprature=1.0, cond_scale=1.0, beam_search_decode=False,
                                        prompt_mel=None, uniforms=None, generator=None, max_length=None, slots=64,
                                        filter_logits_fn="top_k", filter_fn_kwargs=None, return_logprobs=False, best_of=1,
-                                       beam_size=10, length_penalty=1.0, prefix=None, best_of_temperatures=None, mixed_guidance=False):
+                                       beam_size=10, length_penalty=1.0, prefix=None, best_of_temperatures=None, mixed_guidance=False,
+                                       guided_beam=False):
         """reference conditional_model.py:313-321 -> TextToSemanticWrapper.sample (text2semantic.py:1237-1251): the
         sampled semantic tokens as one flat int64 tensor (two-output models: stream 1 then stream 2) on the input's
         device.  (`temprature` is the reference's spelling.)  `uniforms` / `generator` (optional) fix the U(0,1) draws
@@ -253,7 +254,10 @@ class CoVoMixModel:
         with `beam_size` hypotheses (default 10, the reference's; 1..16) - t2s.generate_beam: deterministic, so `temprature` and
         `filter_*` are unused, and `uniforms`, `generator` or best_of > 1 with it are a ValueError; returns the tokens of the hypothesis with
         the largest cumulative log-probability / (tokens scored) ** length_penalty (or the tuple under return_logprobs; lists run in
-        lock-step waves of 64 // beam_size utterances).  Guided beams (cond_scale > 1) are not built: NotImplementedError.
+        lock-step waves of 64 // beam_size utterances).  Beam search under guidance (cond_scale > 1) is opt-in: guided_beam=True (default
+        False) runs t2s.generate_beam(cond_scale=...) - every hypothesis a slot pair, waves of 64 // (2 * beam_size) utterances, one-output
+        models - and without the switch the combination stays a NotImplementedError; guided_beam=True with cond_scale == 1 is the plain
+        beam call.
         Per-utterance settings (extension; t2s.generate_many(settings=...)): with a LIST of texts, `temprature`, `cond_scale`,
         `filter_logits_fn` and `filter_fn_kwargs` may each be a list of the same length - utterance j then decodes with entry j, in the same
         slots and the same captured graph as the others, and gets what it gets alone with those values (lists whose entries are all equal
@@ -300,10 +304,17 @@ class CoVoMixModel:
             if not (isinstance(best_of, int) and not isinstance(best_of, bool) and best_of == 1):
                 raise ValueError("beam search already keeps beam_size hypotheses: best_of > 1 does not combine with it")
             check_beam_size(beam_size)
+            if cond_scale > 1 and not guided_beam:
+                raise NotImplementedError("beam search under guidance (cond_scale > 1) is opt-in: pass guided_beam=True (every hypothesis "
+                                          "then takes a slot pair, text context / null context, sharing one ancestry)")
             if cond_scale > 1:
-                raise NotImplementedError("beam search under guidance (cond_scale > 1) is not built: a guided hypothesis would need a slot "
-                                          "pair (text context / null context) sharing one ancestry")
-            res = self._get_t2s().generate_beam(list(ids) if many else ids, beam_size, max_length, float(length_penalty))
+                from .t2s import _dims
+                if _dims(self.active_state_dict())["streams"] != 1:          # (from the weights: refused whatever the device)
+                    raise NotImplementedError("guidance (cond_scale > 1) on a two-output model: the reference cannot run it")
+                res = self._get_t2s().generate_beam(list(ids) if many else ids, beam_size, max_length, float(length_penalty),
+                                                    cond_scale=float(cond_scale))
+            else:
+                res = self._get_t2s().generate_beam(list(ids) if many else ids, beam_size, max_length, float(length_penalty))
             pick = (lambda r, i: tuple(t.to(i.device) for t in r[:3])) if return_logprobs else (lambda r, i: r[0].to(i.device))
             return [pick(r, i) for r, i in zip(res, ids)] if many else pick(res, ids)
         if best_of_temperatures is not None:

@@ -36,7 +36,16 @@
 // cvx_t2s_beam_queue_steps runs a LIST of utterances through the groups: beam_merge_queue_kernel ends an utterance, takes the next pending
 // one from a device-side queue and re-arms the whole group inside the same launch; the history is then kept per utterance
 // (beam_backtrack_queue_kernel).
-// ONE BODY PER STEP: the three sampling kernels instantiate sample_step, the two merge kernels beam_merge_step, the two back-track kernels
+// BEAM SEARCH UNDER GUIDANCE (cvx_t2s_beam_guided_steps, cvx_t2s_beam_guided_queue_steps): a hypothesis is a slot PAIR - slot 2h with the text
+// context, slot 2h + 1 with the null context - with one score, one history and one ancestry; the chain and attn_owner_kernel (one block row
+// per slot) are those of the beam search:
+//   beam_shortlist_guided_kernel   one block per live hypothesis: stage_row's null + (cond - null) * scale over the logits rows of both halves -
+//                          the row the guided scoring path takes its log-probs from - then the shortlist;
+//   beam_merge_guided_kernel, beam_merge_guided_queue_kernel   beam_merge_step<QUEUE, GUIDED = true>: the selection over hypotheses; slot
+//                          records, the next input (one embedding row into both x rows) and the ancestry rows (text row from the parent's text
+//                          row, null row from its null row) for both halves; the queue form re-arms both halves of a refilled group.
+//                          The back-track kernels are shared: their rows are hypotheses either way.
+// ONE BODY PER STEP: the three sampling kernels instantiate sample_step, the four merge kernels beam_merge_step, the two back-track kernels
 // beam_backtrack_step.  What such sharing does to a kernel is read from the compiler (tools/kernel_text_diff.py against the parent's
 // assembly), not assumed: the default chain's kernels keep their instruction text (tests/test_t2s_code_objects.py holds their resources).
 // The reference rotates ALL cached keys again every step with rotary_embedding_torch's interleaved pairs
@@ -1221,6 +1230,21 @@ __global__ __launch_bounds__(1024) void beam_shortlist_kernel(const BeamArgs a)
     beam_shortlist<1024>(lg, a.V, min(a.B, a.V), ex, bv, &ls, a.short_lp + row * BEAM_MAX, a.short_tok + row * BEAM_MAX);
 }
 
+// The shortlist of a GUIDED hypothesis (cvx_t2s_beam_guided_steps): one block per hypothesis h = slots 2h (text context) and 2h + 1 (null
+// context); the row is stage_row's null + (cond - null) * scale - the row the guided scoring path takes its log-probs from - and the
+// shortlist is kept by hypothesis.  (BeamArgs.batch counts HYPOTHESES in the guided chain: half the slots.)
+__global__ __launch_bounds__(1024) void beam_shortlist_guided_kernel(const BeamArgs a, const float scale)
+{
+    __shared__ __attribute__((aligned(16))) float lg[1024];
+    __shared__ __attribute__((aligned(16))) float ex[1024];
+    __shared__ float bv[16];
+    __shared__ float ls;
+    const int h = blockIdx.x;
+    if (aloadi(a.state + SR * (2 * h)) >= a.max_len) return;          // (block-uniform) finished, ended or idle: both halves idle together
+    stage_row<1024>(a.logits + (int64_t)(2 * h) * a.V, a.logits + (int64_t)(2 * h + 1) * a.V, scale, a.V, lg);
+    beam_shortlist<1024>(lg, a.V, min(a.B, a.V), ex, bv, &ls, a.short_lp + h * BEAM_MAX, a.short_tok + h * BEAM_MAX);
+}
+
 // what the QUEUE forms of the merge and the back-track need beyond BeamArgs (cvx_t2s_beam_queue_steps: beam search through continuously
 // refilled groups); a second kernel argument, as attn_owner_kernel's table
 struct BeamQueueArgs {
@@ -1249,9 +1273,15 @@ template <bool QUEUE> __device__ __forceinline__ int64_t beam_hist_index(const B
 // history is indexed by the group's utterance (group record [3]) and, when the utterance ends, the same launch writes its finals, status and
 // steps, takes the next pending one from the queue (one atomicAdd) and re-arms the whole group at position 0; with none left the group ends
 // as without a queue.
-template <bool QUEUE>
+// GUIDED (cvx_t2s_beam_guided_steps): a hypothesis is a slot PAIR - hypothesis h in slots 2h (text context) and 2h + 1 (null context) - with
+// one score, one flag and one history entry; a.batch counts hypotheses, one stream.  Whatever is kept by SLOT is written for both halves:
+// the slot records, the next input (the same embedding row) and the ancestry rows (the text row continues the parent's text row, the null
+// row the parent's null row).  A re-armed group gives the text half the utterance's context rows and kv_c row 2 * utterance, the null half one
+// context row (the learned null key / value) and kv_c row 2 * utterance + 1.
+template <bool QUEUE, bool GUIDED = false>
 __device__ __forceinline__ void beam_merge_step(const BeamArgs& a, const BeamQueueArgs& qa)
 {
+    constexpr int P = GUIDED ? 2 : 1;                   // slots per hypothesis
     __shared__ float bv[16];
     __shared__ int bi[16];
     __shared__ float sc[BEAM_MAX];
@@ -1269,7 +1299,7 @@ __device__ __forceinline__ void beam_merge_step(const BeamArgs& a, const BeamQue
     if (tid < B) {
         sc[tid] = a.scores[base + tid];
         fin[tid] = a.finished[base + tid] ? 1 : 0;
-        len[tid] = aloadi(a.state + SR * (base + tid) + 2);
+        len[tid] = aloadi(a.state + SR * (base + tid) * P + 2);
     }
     __syncthreads();
     const float* const sl_lp = a.short_lp + (int64_t)base * S * BEAM_MAX;
@@ -1318,14 +1348,19 @@ __device__ __forceinline__ void beam_merge_step(const BeamArgs& a, const BeamQue
                 // re-arm the group on utterance nxt: position 0, the start token, hypothesis 0 alone live.  The cache and owner rows of the
                 // ended utterance stay where they are: the new one's owner rows name only positions it has written itself
                 int* const un = qa.utterances + SR * nxt;
-                for (int idx = tid; idx < B * S * a.dim_emb; idx += 1024) a.x[(int64_t)base * S * a.dim_emb + idx] = qa.start[idx % (S * a.dim_emb)];
+                for (int idx = tid; idx < B * P * S * a.dim_emb; idx += 1024)
+                    a.x[(int64_t)base * P * S * a.dim_emb + idx] = qa.start[idx % (S * a.dim_emb)];
                 if (tid < B) {
-                    const int slot = base + tid;
+                    const int slot = (base + tid) * P;              // (GUIDED: the text half; base + tid is the hypothesis)
                     int* const st = a.state + SR * slot;
-                    a.scores[slot] = tid == 0 ? 0.f : -__builtin_inff();
-                    a.finished[slot] = 0;
-                    st[0] = 0; st[1] = 0; st[2] = 0; st[3] = min(max(aloadi(un), 1), qa.ctx_rows); st[4] = nxt;
+                    a.scores[base + tid] = tid == 0 ? 0.f : -__builtin_inff();
+                    a.finished[base + tid] = 0;
+                    st[0] = 0; st[1] = 0; st[2] = 0; st[3] = min(max(aloadi(un), 1), qa.ctx_rows); st[4] = nxt * P;
                     a.owner[(int64_t)slot * a.max_len] = slot;      // (parity 0, position 0)
+                    if constexpr (GUIDED) {
+                        st[SR] = 0; st[SR + 1] = 0; st[SR + 2] = 0; st[SR + 3] = 1; st[SR + 4] = nxt * 2 + 1;
+                        a.owner[(int64_t)(slot + 1) * a.max_len] = slot + 1;
+                    }
                 }
                 if (tid == 0) {
                     gs[0] = 0; gs[1] = 0; gs[2] = min(max(aloadi(un + 1), 1), a.max_len); gs[3] = nxt;
@@ -1337,35 +1372,53 @@ __device__ __forceinline__ void beam_merge_step(const BeamArgs& a, const BeamQue
         }
     }
     if (tid < B) {
-        const int slot = base + tid;
+        const int slot = (base + tid) * P;                  // (GUIDED: the text half; base + tid is the hypothesis)
         int* const st = a.state + SR * slot;
-        a.scores[slot] = r.score;
-        a.finished[slot] = (uint8_t)r.fin;
+        a.scores[base + tid] = r.score;
+        a.finished[base + tid] = (uint8_t)r.fin;
         // the slots of an ended utterance idle at max_len, as a finished hypothesis does (the attention kernel's idle exit)
         st[0] = (r.fin || ends) ? a.max_len : t + 1;
         st[1] = (r.fin || ends) ? 1 : 0;
         st[2] = steps;
+        if constexpr (GUIDED) {
+            st[SR] = (r.fin || ends) ? a.max_len : t + 1;
+            st[SR + 1] = (r.fin || ends) ? 1 : 0;
+            st[SR + 2] = steps;
+        }
     }
     if (tid == 0) { gs[0] = t + 1; if (ends) gs[1] = 1; }
     if (ends) return;
     // the next input of every live hypothesis, and its row of the ancestry table: the parent's row for positions 0..t, then itself
-    for (int idx = tid; idx < B * S * a.dim_emb; idx += 1024) {
-        const int i = idx / (S * a.dim_emb), rem = idx - i * (S * a.dim_emb), s = rem / a.dim_emb, d = rem - s * a.dim_emb;
-        if (!n_fin[i]) a.x[((int64_t)(base + i) * S + s) * a.dim_emb + d] = a.emb[(int64_t)n_tok[i][s] * a.dim_emb + d];
+    if constexpr (GUIDED) {
+        // (one stream: row r of the group's 2 B slots belongs to hypothesis r / 2; both halves take the same embedding row)
+        for (int idx = tid; idx < B * 2 * a.dim_emb; idx += 1024) {
+            const int r2 = idx / a.dim_emb, d = idx - r2 * a.dim_emb, i = r2 >> 1;
+            if (!n_fin[i]) a.x[((int64_t)base * 2 + r2) * a.dim_emb + d] = a.emb[(int64_t)n_tok[i][0] * a.dim_emb + d];
+        }
+    } else {
+        for (int idx = tid; idx < B * S * a.dim_emb; idx += 1024) {
+            const int i = idx / (S * a.dim_emb), rem = idx - i * (S * a.dim_emb), s = rem / a.dim_emb, d = rem - s * a.dim_emb;
+            if (!n_fin[i]) a.x[((int64_t)(base + i) * S + s) * a.dim_emb + d] = a.emb[(int64_t)n_tok[i][s] * a.dim_emb + d];
+        }
     }
-    const int* const src = a.owner + (int64_t)(t & 1) * a.batch * a.max_len;
-    int* const dst = a.owner + (int64_t)((t + 1) & 1) * a.batch * a.max_len;
+    const int* const src = a.owner + (int64_t)(t & 1) * a.batch * P * a.max_len;
+    int* const dst = a.owner + (int64_t)((t + 1) & 1) * a.batch * P * a.max_len;
     for (int i = 0; i < B; ++i) {
         if (n_fin[i]) continue;
-        const int* const sr = src + (int64_t)(base + n_par[i]) * a.max_len;
-        int* const dr = dst + (int64_t)(base + i) * a.max_len;
-        for (int j = tid; j <= t; j += 1024) dr[j] = aloadi(sr + j);
-        if (tid == 0) dr[t + 1] = base + i;             // (t + 1 < max_len: the utterance has not ended)
+#pragma unroll
+        for (int half = 0; half < P; ++half) {
+            const int* const sr = src + (int64_t)((base + n_par[i]) * P + half) * a.max_len;
+            int* const dr = dst + (int64_t)((base + i) * P + half) * a.max_len;
+            for (int j = tid; j <= t; j += 1024) dr[j] = aloadi(sr + j);
+            if (tid == 0) dr[t + 1] = (base + i) * P + half;     // (t + 1 < max_len: the utterance has not ended)
+        }
     }
 }
 
 __global__ __launch_bounds__(1024) void beam_merge_kernel(const BeamArgs a) { beam_merge_step<false>(a, BeamQueueArgs{}); }
 __global__ __launch_bounds__(1024) void beam_merge_queue_kernel(const BeamArgs a, const BeamQueueArgs qa) { beam_merge_step<true>(a, qa); }
+__global__ __launch_bounds__(1024) void beam_merge_guided_kernel(const BeamArgs a) { beam_merge_step<false, true>(a, BeamQueueArgs{}); }
+__global__ __launch_bounds__(1024) void beam_merge_guided_queue_kernel(const BeamArgs a, const BeamQueueArgs qa) { beam_merge_step<true, true>(a, qa); }
 
 // tokens / logprobs [row][streams][max_len] from the back-pointers: one thread per row walks its ancestry.  A row is a slot of group g
 // (steps: group record [0]) or, with QUEUE, hypothesis row - g B of utterance g (steps: utterance record [4])
@@ -1518,11 +1571,12 @@ extern "C" int cvx_t2s_logprob_f32(const float* logits, const int64_t* tokens, i
     return CVX_OK;
 }
 
-static BeamArgs beam_args(const cvx_t2s_decoder* d, const cvx_t2s_beam* bm)
+// guided: BeamArgs.batch counts hypotheses - slot pairs - not slots
+static BeamArgs beam_args(const cvx_t2s_decoder* d, const cvx_t2s_beam* bm, bool guided = false)
 {
     return BeamArgs{d->logits, d->emb, d->x, d->state, bm->scores, bm->finished, bm->owner, bm->groups, bm->parents, bm->hist_tokens,
-                    bm->hist_logprobs, bm->short_lp, bm->short_tokens, d->tokens, bm->logprobs, d->batch, bm->beam_size, d->vocab, d->dim_emb,
-                    d->streams, d->max_len};
+                    bm->hist_logprobs, bm->short_lp, bm->short_tokens, d->tokens, bm->logprobs, guided ? d->batch / 2 : d->batch, bm->beam_size,
+                    d->vocab, d->dim_emb, d->streams, d->max_len};
 }
 
 static SampleArgs sample_args(const cvx_t2s_decoder* d, float* logprobs)
@@ -1547,6 +1601,8 @@ struct T2sSelect {
     PerArgs per;             // PER / MIXED
     const cvx_t2s_beam* bm;  // BEAM / BEAM_QUEUE
     BeamQueueArgs bq;        // BEAM_QUEUE
+    bool guided;             // BEAM / BEAM_QUEUE: cvx_t2s_beam_guided_steps / _queue_steps - a hypothesis is a slot pair, the shortlist reads the
+                             // guidance-combined row; the same number of launches
 };
 
 // the step chain of every cvx_t2s_*_steps* entry point: they differ in what follows the logits only
@@ -1602,6 +1658,14 @@ static int t2s_decode_run(const cvx_t2s_decoder* d, int32_t n_steps, const T2sSe
         g.W = d->emb; g.ldw = d->dim_emb; g.x = d->x; g.x_stride = d->dim; g.gamma = d->final_gamma; g.y = d->logits;
         g.y_stride = d->streams * d->vocab; g.N = d->vocab; g.K = d->dim_emb; g.streams = d->streams;
         launch_gemv<MODE_LOGITS>(g, d->streams * ((d->vocab + 1) / 2), nb, st);
+        if (beam && sel.guided) {
+            const BeamArgs ba = beam_args(d, sel.bm, true);
+            const dim3 groups((unsigned)(ba.batch / sel.bm->beam_size));
+            hipLaunchKernelGGL(beam_shortlist_guided_kernel, dim3((unsigned)ba.batch), block, 0, st, ba, d->cfg_scale);
+            if (sel.kind == T2sSelect::BEAM_QUEUE) hipLaunchKernelGGL(beam_merge_guided_queue_kernel, groups, block, 0, st, ba, sel.bq);
+            else hipLaunchKernelGGL(beam_merge_guided_kernel, groups, block, 0, st, ba);
+            continue;
+        }
         if (beam) {
             const BeamArgs ba = beam_args(d, sel.bm);
             const dim3 groups((unsigned)(nb / sel.bm->beam_size));
@@ -1669,19 +1733,29 @@ static int t2s_per_dialogue_block(const char* who, const cvx_t2s_decoder* d, con
     return CVX_OK;
 }
 
-// cvx_t2s_beam
-static int t2s_beam_block(const char* who, const cvx_t2s_decoder* d, const cvx_t2s_beam* bm, T2sSelect& sel)
+// cvx_t2s_beam.  guided: the entry points whose hypotheses are slot pairs (t2s_validate has held cfg_scale > 1 to one stream, an even
+// batch and n_ctx == 0)
+static int t2s_beam_block(const char* who, const cvx_t2s_decoder* d, const cvx_t2s_beam* bm, T2sSelect& sel, bool guided = false)
 {
     T2S_TRY(t2s_struct_size(who, "cvx_t2s_beam", bm));
     CVX_REQUIRE(!d->queue, "%s: the dialogue queue of the sampled decode cannot feed beam groups (dec->queue must be NULL)", who);
-    CVX_REQUIRE(!(d->cfg_scale > 1.f), "%s: guidance (cfg_scale > 1) is not built for beam search", who);
-    CVX_REQUIRE(bm->beam_size >= 1 && bm->beam_size <= BEAM_MAX && d->batch % bm->beam_size == 0,
-                "%s: beam_size = %d outside [1, %d] or no divisor of batch = %d", who, bm->beam_size, BEAM_MAX, d->batch);
+    if (guided)
+        CVX_REQUIRE(d->cfg_scale > 1.f && d->streams == 1 && d->n_ctx == 0,
+                    "%s: cfg_scale = %g must be > 1 (cvx_t2s_beam_steps is the unguided entry) on a one-output model with per-slot context "
+                    "rows (streams = %d, n_ctx = %d)", who, (double)d->cfg_scale, d->streams, d->n_ctx);
+    else
+        CVX_REQUIRE(!(d->cfg_scale > 1.f), "%s: guidance (cfg_scale > 1) runs through %s", who,
+                    sel.kind == T2sSelect::BEAM_QUEUE ? "cvx_t2s_beam_guided_queue_steps" : "cvx_t2s_beam_guided_steps");
+    const int per = guided ? 2 : 1;                    // slots per hypothesis
+    CVX_REQUIRE(bm->beam_size >= 1 && bm->beam_size <= BEAM_MAX && d->batch % (per * bm->beam_size) == 0,
+                "%s: beam_size = %d outside [1, %d], or %d slots per utterance do not divide batch = %d", who, bm->beam_size, BEAM_MAX,
+                per * bm->beam_size, d->batch);
     CVX_REQUIRE(bm->hist_len == d->max_len, "%s: hist_len = %d, the history arrays and logprobs hold max_len = %d steps", who, bm->hist_len,
                 d->max_len);
     CVX_REQUIRE(bm->scores && bm->finished && bm->owner && bm->groups && bm->parents && bm->hist_tokens && bm->hist_logprobs && bm->short_lp &&
                 bm->short_tokens && bm->logprobs, "%s: null pointer in cvx_t2s_beam", who);
     sel.bm = bm;
+    sel.guided = guided;
     return CVX_OK;
 }
 
@@ -1729,15 +1803,49 @@ extern "C" int cvx_t2s_decode_steps_mixed(const cvx_t2s_decoder* d, const cvx_t2
     return t2s_decode_run(d, n_steps, sel, s);
 }
 
-extern "C" int cvx_t2s_beam_steps(const cvx_t2s_decoder* d, const cvx_t2s_beam* bm, int32_t n_steps, cvx_stream_t s)
+// cvx_t2s_beam_steps and cvx_t2s_beam_guided_steps: the checks, the steps, the back-track (one thread per hypothesis)
+static int t2s_beam_steps(const char* who, const cvx_t2s_decoder* d, const cvx_t2s_beam* bm, int32_t n_steps, bool guided, cvx_stream_t s)
 {
     T2sSelect sel{T2sSelect::BEAM};
     T2S_TRY(t2s_validate(d, n_steps));
-    T2S_TRY(t2s_beam_block("t2s_beam_steps", d, bm, sel));
+    T2S_TRY(t2s_beam_block(who, d, bm, sel, guided));
     if (n_steps > 0) T2S_TRY(t2s_decode_run(d, n_steps, sel, s));
     if (bm->backtrack) {
-        hipLaunchKernelGGL(beam_backtrack_kernel, dim3((unsigned)((d->batch + 63) / 64)), dim3(64), 0, cvx_hip_stream(s), beam_args(d, bm));
-        CVX_CHECK_LAUNCH("cvx_t2s_beam_steps");
+        const BeamArgs ba = beam_args(d, bm, guided);
+        hipLaunchKernelGGL(beam_backtrack_kernel, dim3((unsigned)((ba.batch + 63) / 64)), dim3(64), 0, cvx_hip_stream(s), ba);
+        CVX_CHECK_LAUNCH(who);
+    }
+    return CVX_OK;
+}
+
+extern "C" int cvx_t2s_beam_steps(const cvx_t2s_decoder* d, const cvx_t2s_beam* bm, int32_t n_steps, cvx_stream_t s)
+{
+    return t2s_beam_steps("t2s_beam_steps", d, bm, n_steps, false, s);
+}
+
+extern "C" int cvx_t2s_beam_guided_steps(const cvx_t2s_decoder* d, const cvx_t2s_beam* bm, int32_t n_steps, cvx_stream_t s)
+{
+    return t2s_beam_steps("t2s_beam_guided_steps", d, bm, n_steps, true, s);
+}
+
+// cvx_t2s_beam_queue_steps and cvx_t2s_beam_guided_queue_steps
+static int t2s_beam_queue_steps(const char* who, const cvx_t2s_decoder* d, const cvx_t2s_beam* bm, const cvx_t2s_beam_queue* bq, int32_t n_steps,
+                                bool guided, cvx_stream_t s)
+{
+    T2sSelect sel{T2sSelect::BEAM_QUEUE};
+    T2S_TRY(t2s_validate(d, n_steps));
+    T2S_TRY(t2s_beam_block(who, d, bm, sel, guided));
+    T2S_TRY(t2s_struct_size(who, "cvx_t2s_beam_queue", bq));
+    CVX_REQUIRE(bq->n_utterances >= 1, "%s: n_utterances = %d", who, bq->n_utterances);
+    CVX_REQUIRE(bq->queue && bq->utterances && bq->start && bq->parents && bq->hist_tokens && bq->hist_logprobs && bq->final_scores &&
+                bq->final_steps && bq->final_finished && bq->tokens && bq->logprobs, "%s: null pointer in cvx_t2s_beam_queue", who);
+    sel.bq = BeamQueueArgs{bq->queue, bq->utterances, bq->start, bq->parents, bq->hist_tokens, bq->hist_logprobs, bq->final_scores,
+                           bq->final_steps, bq->final_finished, bq->tokens, bq->logprobs, bq->n_utterances, d->ctx_rows};
+    if (n_steps > 0) T2S_TRY(t2s_decode_run(d, n_steps, sel, s));
+    if (bm->backtrack) {
+        hipLaunchKernelGGL(beam_backtrack_queue_kernel, dim3((unsigned)(((int64_t)bq->n_utterances * bm->beam_size + 63) / 64)), dim3(64), 0,
+                           cvx_hip_stream(s), beam_args(d, bm, guided), sel.bq);
+        CVX_CHECK_LAUNCH(who);
     }
     return CVX_OK;
 }
@@ -1745,23 +1853,13 @@ extern "C" int cvx_t2s_beam_steps(const cvx_t2s_decoder* d, const cvx_t2s_beam* 
 extern "C" int cvx_t2s_beam_queue_steps(const cvx_t2s_decoder* d, const cvx_t2s_beam* bm, const cvx_t2s_beam_queue* bq, int32_t n_steps,
                                         cvx_stream_t s)
 {
-    const char* const who = "t2s_beam_queue_steps";
-    T2sSelect sel{T2sSelect::BEAM_QUEUE};
-    T2S_TRY(t2s_validate(d, n_steps));
-    T2S_TRY(t2s_beam_block(who, d, bm, sel));
-    T2S_TRY(t2s_struct_size(who, "cvx_t2s_beam_queue", bq));
-    CVX_REQUIRE(bq->n_utterances >= 1, "t2s_beam_queue_steps: n_utterances = %d", bq->n_utterances);
-    CVX_REQUIRE(bq->queue && bq->utterances && bq->start && bq->parents && bq->hist_tokens && bq->hist_logprobs && bq->final_scores &&
-                bq->final_steps && bq->final_finished && bq->tokens && bq->logprobs, "t2s_beam_queue_steps: null pointer in cvx_t2s_beam_queue");
-    sel.bq = BeamQueueArgs{bq->queue, bq->utterances, bq->start, bq->parents, bq->hist_tokens, bq->hist_logprobs, bq->final_scores,
-                           bq->final_steps, bq->final_finished, bq->tokens, bq->logprobs, bq->n_utterances, d->ctx_rows};
-    if (n_steps > 0) T2S_TRY(t2s_decode_run(d, n_steps, sel, s));
-    if (bm->backtrack) {
-        hipLaunchKernelGGL(beam_backtrack_queue_kernel, dim3((unsigned)(((int64_t)bq->n_utterances * bm->beam_size + 63) / 64)), dim3(64), 0,
-                           cvx_hip_stream(s), beam_args(d, bm), sel.bq);
-        CVX_CHECK_LAUNCH("cvx_t2s_beam_queue_steps");
-    }
-    return CVX_OK;
+    return t2s_beam_queue_steps("t2s_beam_queue_steps", d, bm, bq, n_steps, false, s);
+}
+
+extern "C" int cvx_t2s_beam_guided_queue_steps(const cvx_t2s_decoder* d, const cvx_t2s_beam* bm, const cvx_t2s_beam_queue* bq, int32_t n_steps,
+                                               cvx_stream_t s)
+{
+    return t2s_beam_queue_steps("t2s_beam_guided_queue_steps", d, bm, bq, n_steps, true, s);
 }
 
 extern "C" int cvx_t2s_beam_select_f32(const float* logits, const float* scores_in, const uint8_t* finished_in, int32_t groups,

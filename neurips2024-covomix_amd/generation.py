@@ -93,6 +93,8 @@ def build_parser() -> ArgumentParser:
     p.add_argument("--t2s_beam_size", type=int, default=0, help="extension: beam search with this many hypotheses per turn (1..16) instead of "
                    "sampling - deterministic: no draws, temperature and filter unused; not together with --t2s_best_of > 1 or guidance "
                    "(0 = off: sampling, today's files)")
+    p.add_argument("--t2s_beam_guided", action="store_true", help="extension: lets --t2s_beam_size run under guidance (--t2s_cond_scale > 1): "
+                   "every hypothesis takes a slot pair, so a wave holds half as many turns (one-output models)")
     p.add_argument("--gpus", type=int, default=1, help="extension: from a plain shell, start this many ranks (one per GPU, "
                    "utterances sharded; under torch.distributed.run the launcher's WORLD_SIZE is used instead)")
     return p
@@ -222,9 +224,13 @@ def t2s_sampling_kwargs(args) -> dict:
     if beam:
         if not 1 <= beam <= 16:
             raise ValueError(f"--t2s_beam_size {beam}: 0 (sampling) or 1..16")
-        if best_of > 1 or kw.get("cond_scale", 1.0) > 1.0:
-            raise ValueError("--t2s_beam_size does not combine with --t2s_best_of > 1 or guidance (--t2s_cond_scale > 1)")
+        guided_beam = bool(getattr(args, "t2s_beam_guided", False))
+        if best_of > 1 or (kw.get("cond_scale", 1.0) > 1.0 and not guided_beam):
+            raise ValueError("--t2s_beam_size does not combine with --t2s_best_of > 1 or, without --t2s_beam_guided, guidance "
+                             "(--t2s_cond_scale > 1)")
         kw["beam_search_decode"], kw["beam_size"] = True, beam
+        if guided_beam:
+            kw["guided_beam"] = True
     if getattr(args, "t2s_mixed_guidance", False):
         kw["mixed_guidance"] = True
     return kw

@@ -125,6 +125,14 @@ def check_beam_size(beam_size) -> int:
     return beam_size
 
 
+def check_beam_scale(cond_scale) -> float:
+    """the guidance scale of a beam search: 1 (unguided) or > 1 (guided)"""
+    scale = float(cond_scale)
+    if not scale >= 1.0:
+        raise ValueError(f"beam search: cond_scale = {cond_scale} must be >= 1")
+    return scale
+
+
 def beam_backtrack(parents, tokens, logprobs, slot: int, steps: int):
     """The sequence of the hypothesis that sits in `slot` after `steps` steps, from the back-pointer records of the selection step:
     parents [T, B] (the slot the hypothesis came from), tokens [T, B, S], logprobs [T, B, S] -> (tokens [S, steps], logprobs [S, steps],
@@ -1240,6 +1248,13 @@ class TextToSemanticDecoder:
         return out
 
     # ------------------------------------------------------------------ beam search
+    def _beam_scale(self, cond_scale) -> float:
+        """check_beam_scale, and guidance is for one-output models (as in generate_batch)"""
+        scale = check_beam_scale(cond_scale)
+        if scale > 1.0 and self.d["streams"] != 1:
+            raise NotImplementedError("guidance (cond_scale > 1) on a two-output model: the reference cannot run it (generate_batch)")
+        return scale
+
     def _ensure_beam(self) -> dict:
         """Device state of the beam chain (cvx_t2s_beam), for the decode buffers' current slot capacity: allocated on first use, and again
         when those buffers were re-allocated.  Nothing else holds its addresses but the beam graphs."""
@@ -1253,13 +1268,17 @@ class TextToSemanticDecoder:
                           short_lp=f32(n * S * BEAM_MAX), short_tokens=i32(n * S * BEAM_MAX), logprobs=f32(n, S, L))
         return self._beam
 
-    def _launch_beam(self, batch: int, beam_size: int, n: int, backtrack: bool = False) -> None:
-        """n steps of the beam chain (cvx_t2s_beam_steps) on the current stream; backtrack: then tokens / log-probs from the back-pointers"""
+    def _launch_beam(self, batch: int, beam_size: int, n: int, backtrack: bool = False, scale: float = 1.0) -> None:
+        """n steps of the beam chain (cvx_t2s_beam_steps) on the current stream; backtrack: then tokens / log-probs from the back-pointers.
+        scale > 1: the guided chain (cvx_t2s_beam_guided_steps) - `batch` slots are batch / 2 hypotheses."""
         bm = self._ensure_beam()
-        dec = self._descriptor(1.0, batch)
+        dec = self._descriptor(1.0, batch, scale)
         bs = _lib.T2SBeam(C.sizeof(_lib.T2SBeam), beam_size, self.max_length, 1 if backtrack else 0,
                           *[bm[k].data_ptr() for k in ("scores", "finished", "owner", "groups", "parents", "hist_tokens", "hist_logprobs",
                                                       "short_lp", "short_tokens", "logprobs")])
+        if scale > 1.0:
+            _lib.check(_lib.load().cvx_t2s_beam_guided_steps(C.byref(dec), C.byref(bs), n, ops._stream()), "cvx_t2s_beam_guided_steps")
+            return
         _lib.check(_lib.load().cvx_t2s_beam_steps(C.byref(dec), C.byref(bs), n, ops._stream()), "cvx_t2s_beam_steps")
 
     def _beam_idle(self) -> None:
@@ -1269,15 +1288,17 @@ class TextToSemanticDecoder:
         g[:, 1] = 1
         self._ensure_beam()["groups"].copy_(g)
 
-    def _beam_graph(self, batch: int, beam_size: int):
-        """The captured graph of CHUNK beam steps for this (batch, beam size, stream CU count); `_graph`'s procedure, a key of its own shape."""
+    def _beam_graph(self, batch: int, beam_size: int, scale: float = 1.0):
+        """The captured graph of CHUNK beam steps for this (batch, beam size, stream CU count); `_graph`'s procedure, a key of its own shape.
+        The guided chain (scale > 1) has graphs of its own kind, "beamg", whose key carries the scale (a kernel argument)."""
         self._ensure_beam()
-        key = ("beam", beam_size, batch, ops.stream_cus(), self._gen)
+        key = ("beamg", beam_size, batch, float(scale), ops.stream_cus(), self._gen) if scale > 1.0 else \
+            ("beam", beam_size, batch, ops.stream_cus(), self._gen)
         g = self._graphs.get(key)
         if g is not None:
             return g
         self._beam_idle()
-        self._launch_beam(batch, beam_size, CHUNK)       # warm-up outside capture
+        self._launch_beam(batch, beam_size, CHUNK, scale=scale)       # warm-up outside capture
         cur = torch.cuda.current_stream()
         if self._cap is None:
             self._cap = torch.cuda.Stream(device=self.device)
@@ -1286,28 +1307,41 @@ class TextToSemanticDecoder:
             cur.synchronize()
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g, stream=self._cap, capture_error_mode="thread_local"):
-                self._launch_beam(batch, beam_size, CHUNK)
+                self._launch_beam(batch, beam_size, CHUNK, scale=scale)
         if len(self._graphs) >= 8:
             self._graphs.clear()
         self._graphs[key] = g
         return g
 
-    def _beam_wave(self, sources, B: int, max_len: int, length_penalty: float) -> list:
-        """One lock-step wave: utterance u in slots [u B, (u + 1) B).  -> per utterance the list of its B hypotheses, best first."""
+    def _beam_wave(self, sources, B: int, max_len: int, length_penalty: float, scale: float = 1.0) -> list:
+        """One lock-step wave: utterance u in slots [u B, (u + 1) B).  -> per utterance the list of its B hypotheses, best first.
+        scale > 1 (guided): hypothesis h is the slot pair (2h, 2h + 1) - text context / null context - and utterance u owns the kv_c rows
+        2u (its context) and 2u + 1 (the null key / value alone), as in _generate_guided; everything kept per hypothesis (scores, history,
+        back-tracked rows) has nh = n B rows, everything per slot nb = 2 nh."""
         d = self.d
         S, n = d["streams"], len(sources)
-        nb = n * B
+        guided = scale > 1.0
+        nh = n * B
+        nb = 2 * nh if guided else nh
         self._ensure(nb, nb, 0)
         bm = self._ensure_beam()
         use_graph = os.environ.get("CVX_GRAPH", "1") == "1"
         if use_graph:
-            self._beam_graph(nb, B)
-        ctx = self._contexts(sources)
-        rows = [[0, 0, 0, ctx[i // B], i // B, 0, 0, 0] if i < nb else [self.max_length, 1, 0, 1, 0, 0, 0, 0] for i in range(self._slots)]
+            self._beam_graph(nb, B, scale)
+        if guided:
+            ctx = self._contexts(sources, range(0, 2 * n, 2))
+            for L in self.dec:
+                L["kv_c"][1:2 * n:2, 0].copy_(L["null"][None, :].expand(n, -1))
+            idle = [self.max_length, 1, 0, 1, 0, 0, 0, 0]
+            rows = [([0, 0, 0, 1, 2 * (i // (2 * B)) + 1, 0, 0, 0] if i & 1 else [0, 0, 0, ctx[i // (2 * B)], 2 * (i // (2 * B)), 0, 0, 0])
+                    if i < nb else idle for i in range(self._slots)]
+        else:
+            ctx = self._contexts(sources)
+            rows = [[0, 0, 0, ctx[i // B], i // B, 0, 0, 0] if i < nb else [self.max_length, 1, 0, 1, 0, 0, 0, 0] for i in range(self._slots)]
         self.buf["state"].copy_(torch.tensor(rows, dtype=torch.int32))
         self.buf["x"][:nb].copy_(self.start[None, :].expand(nb, -1))
         sc = torch.full((self._slots,), -math.inf)
-        sc[0:nb:B] = 0.0                                   # before step 0 only hypothesis 0 of an utterance is live
+        sc[0:nh:B] = 0.0                                   # before step 0 only hypothesis 0 of an utterance is live
         bm["scores"].copy_(sc)
         bm["finished"].zero_()
         bm["owner"].copy_(torch.arange(self._slots, dtype=torch.int32)[None, :, None].expand(2, -1, self.max_length).reshape(-1))
@@ -1321,9 +1355,9 @@ class TextToSemanticDecoder:
         steps, i, pending = 0, 0, None
         while steps < max_len:
             if use_graph:
-                self._beam_graph(nb, B).replay()
+                self._beam_graph(nb, B, scale).replay()
             else:
-                self._launch_beam(nb, B, CHUNK)
+                self._launch_beam(nb, B, CHUNK, scale=scale)
             steps += CHUNK
             k = i & 1
             self._mirror_push(k, self.buf["state"][:nb], via_helper)
@@ -1333,8 +1367,9 @@ class TextToSemanticDecoder:
             i += 1
         if pending is not None:
             self._pin_ev[pending].synchronize()
-        self._launch_beam(nb, B, 0, backtrack=True)
-        st = self._read_state(nb)
+        self._launch_beam(nb, B, 0, backtrack=True, scale=scale)
+        st = self._read_state(nb)[::2 if guided else 1]    # (per hypothesis: the text half's record)
+        nb = nh                                            # from here on rows are hypotheses
         scores, groups = bm["scores"][:nb].cpu(), bm["groups"][:n].tolist()
         tokens, logprobs = self.buf["tokens"][:nb].cpu(), bm["logprobs"][:nb].cpu()
         eos = d["vocab"] - 1
@@ -1359,7 +1394,7 @@ class TextToSemanticDecoder:
     @ops.gated
     @torch.no_grad()
     def generate_beam(self, sources, beam_size: int = 10, max_length: Optional[int] = None, length_penalty: float = 1.0,
-                      return_beams: bool = False):
+                      return_beams: bool = False, cond_scale: float = 1.0):
         """Beam search (the algorithm: include/covomix_hip.h, cvx_t2s_beam_steps): deterministic, no draws - temperature, logit filter and
         uniforms play no part.  Every step keeps the beam_size hypotheses with the largest cumulative log-probability (fp32); a hypothesis
         that takes an eos in any stream is finished and competes with its score unchanged; the utterance ends when all are finished or after
@@ -1372,17 +1407,22 @@ class TextToSemanticDecoder:
         the selection kept, and logprobs equal, bit for bit, what score_many gives for `streams`.  return_beams: the list of all beam_size
         hypotheses instead, best first (dead ones, score -inf, last).  `last_beam` keeps, per utterance of the call, the records of the search
         (tests, tools): steps, the slots best first (`order`), their lengths and scores, and the back-pointers parents [steps, B], tokens /
-        logprobs [steps, B, S] (beam_backtrack turns them into sequences)."""
+        logprobs [steps, B, S] (beam_backtrack turns them into sequences).
+        cond_scale > 1 (one-output models): beam search under classifier-free guidance (cvx_t2s_beam_guided_steps) - every hypothesis is a
+        slot pair (text context, null context), the search ranks by the log-softmax of null + (cond - null) * cond_scale, and logprobs
+        equal, bit for bit, score_many(..., cond_scale=cond_scale); waves hold MAX_BATCH // (2 * beam_size) utterances.  Return values and
+        `last_beam` have the same shape.  ValueError for cond_scale < 1, NotImplementedError for a two-output model."""
         B = check_beam_size(beam_size)
+        scale = self._beam_scale(cond_scale)
         one = torch.is_tensor(sources)
         srcs = [sources] if one else list(sources)
         max_len = min(int(max_length or self.max_length), self.max_length)
         if max_len < 1:
             raise ValueError("generate_beam needs at least one step")
         self.last_beam = []
-        per, out = MAX_BATCH // B, []
+        per, out = MAX_BATCH // (2 * B if scale > 1.0 else B), []
         for w in range(0, len(srcs), per):
-            out += self._beam_wave(srcs[w:w + per], B, max_len, float(length_penalty))
+            out += self._beam_wave(srcs[w:w + per], B, max_len, float(length_penalty), scale)
         res = out if return_beams else [h[0] for h in out]
         return res[0] if one else res
 
@@ -1394,7 +1434,7 @@ class TextToSemanticDecoder:
         bq = getattr(self, "_beamq", None)
         if bq is not None and bq["gen"] == self._gen and bq["records"] >= records:
             return bq
-        for key in [k for k in self._graphs if k[0] == "beamq"]:
+        for key in [k for k in self._graphs if k[0] in ("beamq", "beamqg")]:
             del self._graphs[key]
         R, n, L, S, dev = max(records, 8), self._slots, self.max_length, self.d["streams"], self.device
         i32 = lambda *s: torch.zeros(*s, dtype=torch.int32, device=dev)
@@ -1407,28 +1447,33 @@ class TextToSemanticDecoder:
                            slot_ids=torch.arange(n, dtype=torch.int32, device=dev))
         return self._beamq
 
-    def _launch_beam_queue(self, batch: int, beam_size: int, n_utt: int, n: int, backtrack: bool = False) -> None:
+    def _launch_beam_queue(self, batch: int, beam_size: int, n_utt: int, n: int, backtrack: bool = False, scale: float = 1.0) -> None:
         """n steps of the refilled beam chain (cvx_t2s_beam_queue_steps) on the current stream; backtrack: then tokens / log-probs of every
-        (utterance, hypothesis) from the per-utterance back-pointers"""
+        (utterance, hypothesis) from the per-utterance back-pointers.  scale > 1: cvx_t2s_beam_guided_queue_steps."""
         bm, bq = self._ensure_beam(), self._beamq
-        dec = self._descriptor(1.0, batch)
+        dec = self._descriptor(1.0, batch, scale)
         bs = _lib.T2SBeam(C.sizeof(_lib.T2SBeam), beam_size, self.max_length, 1 if backtrack else 0, bm["scores"].data_ptr(),
                           bm["finished"].data_ptr(), bq["owner"].data_ptr(),
                           *[bm[k].data_ptr() for k in ("groups", "parents", "hist_tokens", "hist_logprobs", "short_lp", "short_tokens", "logprobs")])
         qs = _lib.T2SBeamQueue(C.sizeof(_lib.T2SBeamQueue), n_utt, bq["queue"].data_ptr(), bq["utterances"].data_ptr(), self.start.data_ptr(),
                                *[bq[k].data_ptr() for k in ("parents", "hist_tokens", "hist_logprobs", "final_scores", "final_steps",
                                                            "final_finished", "tokens", "logprobs")])
+        if scale > 1.0:
+            _lib.check(_lib.load().cvx_t2s_beam_guided_queue_steps(C.byref(dec), C.byref(bs), C.byref(qs), n, ops._stream()),
+                       "cvx_t2s_beam_guided_queue_steps")
+            return
         _lib.check(_lib.load().cvx_t2s_beam_queue_steps(C.byref(dec), C.byref(bs), C.byref(qs), n, ops._stream()), "cvx_t2s_beam_queue_steps")
 
-    def _beam_queue_graph(self, batch: int, beam_size: int):
+    def _beam_queue_graph(self, batch: int, beam_size: int, scale: float = 1.0):
         """The captured graph of CHUNK steps of the refilled beam chain; `_beam_graph`'s procedure.  (The number of utterances sizes the
-        back-track launch only, which is not part of the graph: the steps read the device-side queue.)"""
-        key = ("beamq", beam_size, batch, ops.stream_cus(), self._gen)
+        back-track launch only, which is not part of the graph: the steps read the device-side queue.)  Guided: kind "beamqg", with the scale."""
+        key = ("beamqg", beam_size, batch, float(scale), ops.stream_cus(), self._gen) if scale > 1.0 else \
+            ("beamq", beam_size, batch, ops.stream_cus(), self._gen)
         g = self._graphs.get(key)
         if g is not None:
             return g
         self._beam_idle()
-        self._launch_beam_queue(batch, beam_size, 1, CHUNK)       # warm-up outside capture
+        self._launch_beam_queue(batch, beam_size, 1, CHUNK, scale=scale)       # warm-up outside capture
         cur = torch.cuda.current_stream()
         if self._cap is None:
             self._cap = torch.cuda.Stream(device=self.device)
@@ -1437,29 +1482,39 @@ class TextToSemanticDecoder:
             cur.synchronize()
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g, stream=self._cap, capture_error_mode="thread_local"):
-                self._launch_beam_queue(batch, beam_size, 1, CHUNK)
+                self._launch_beam_queue(batch, beam_size, 1, CHUNK, scale=scale)
         if len(self._graphs) >= 8:
             self._graphs.clear()
         self._graphs[key] = g
         return g
 
-    def _beam_queue_window(self, sources, B: int, lim: list, length_penalty: float, slots: int) -> list:
-        """One window of generate_beam_many: its utterances' contexts resident, the groups refilled on the device until all have ended."""
+    def _beam_queue_window(self, sources, B: int, lim: list, length_penalty: float, slots: int, scale: float = 1.0) -> list:
+        """One window of generate_beam_many: its utterances' contexts resident, the groups refilled on the device until all have ended.
+        scale > 1 (guided): a group is 2 B slots - the pairs of _beam_wave - and utterance j owns the kv_c rows 2j and 2j + 1."""
         d = self.d
         S, n, L = d["streams"], len(sources), self.max_length
-        G = max(1, min(slots // B, MAX_BATCH // B, n))
-        nb = G * B                                         # (the buffers hold whole 8-slot kernel groups: _ensure)
-        self._ensure(nb, n, 0)
+        guided = scale > 1.0
+        P = 2 if guided else 1                             # slots per hypothesis
+        G = max(1, min(slots // (P * B), MAX_BATCH // (P * B), n))
+        nb = G * B * P                                     # (the buffers hold whole 8-slot kernel groups: _ensure)
+        self._ensure(nb, n * P, 0)
         bm, bq = self._ensure_beam(), self._ensure_beam_queue(max(n * B, WINDOW))
         use_graph = os.environ.get("CVX_GRAPH", "1") == "1"
         if use_graph:
-            self._beam_queue_graph(nb, B)
-        ctx = self._contexts(sources)
-        rows = [[0, 0, 0, ctx[i // B], i // B, 0, 0, 0] if i < nb else [L, 1, 0, 1, 0, 0, 0, 0] for i in range(self._slots)]
+            self._beam_queue_graph(nb, B, scale)
+        if guided:
+            ctx = self._contexts(sources, range(0, 2 * n, 2))
+            for Ld in self.dec:
+                Ld["kv_c"][1:2 * n:2, 0].copy_(Ld["null"][None, :].expand(n, -1))
+            rows = [([0, 0, 0, 1, 2 * (i // (2 * B)) + 1, 0, 0, 0] if i & 1 else [0, 0, 0, ctx[i // (2 * B)], 2 * (i // (2 * B)), 0, 0, 0])
+                    if i < nb else [L, 1, 0, 1, 0, 0, 0, 0] for i in range(self._slots)]
+        else:
+            ctx = self._contexts(sources)
+            rows = [[0, 0, 0, ctx[i // B], i // B, 0, 0, 0] if i < nb else [L, 1, 0, 1, 0, 0, 0, 0] for i in range(self._slots)]
         self.buf["state"].copy_(torch.tensor(rows, dtype=torch.int32))
         self.buf["x"][:nb].copy_(self.start[None, :].expand(nb, -1))
         sc = torch.full((self._slots,), -math.inf)
-        sc[0:nb:B] = 0.0                                   # before step 0 only hypothesis 0 of an utterance is live
+        sc[0:G * B:B] = 0.0                                # before step 0 only hypothesis 0 of an utterance is live
         bm["scores"].copy_(sc)
         bm["finished"].zero_()
         g = torch.zeros(self._slots, 4, dtype=torch.int32)
@@ -1479,9 +1534,9 @@ class TextToSemanticDecoder:
         cap = (sum(lim) + CHUNK - 1) // CHUNK + 4          # (one group decoding everything: cannot be reached)
         while not done(rec) and i < cap:
             if use_graph:
-                self._beam_queue_graph(nb, B).replay()
+                self._beam_queue_graph(nb, B, scale).replay()
             else:
-                self._launch_beam_queue(nb, B, n, CHUNK)
+                self._launch_beam_queue(nb, B, n, CHUNK, scale=scale)
             k = i & 1
             self._mirror_push(k, bq["utterances"][:n], via_helper)
             if pending is not None:
@@ -1495,7 +1550,7 @@ class TextToSemanticDecoder:
         if not done(rec):
             left = n if rec is None else sum(1 for row in rec if row[3] < 2)
             raise RuntimeError(f"text2semantic refilled beam decode: {left} of {n} utterances did not finish in {i} chunks")
-        self._launch_beam_queue(nb, B, n, 0, backtrack=True)
+        self._launch_beam_queue(nb, B, n, 0, backtrack=True, scale=scale)
         scores, lengths_all = bq["final_scores"][:n * B].cpu(), bq["final_steps"][:n * B].tolist()
         tokens, logprobs = bq["tokens"][:n * B].cpu(), bq["logprobs"][:n * B].cpu()
         hist = lambda name, *tail: bq[name][:n * L * B * math.prod(tail)].view(n, L, B, *tail)
@@ -1522,7 +1577,7 @@ class TextToSemanticDecoder:
     @ops.gated
     @torch.no_grad()
     def generate_beam_many(self, sources, beam_size: int = 10, max_length: Optional[int] = None, length_penalty: float = 1.0,
-                           return_beams: bool = False, slots: int = 64, limits=None):
+                           return_beams: bool = False, slots: int = 64, limits=None, cond_scale: float = 1.0):
         """generate_beam for ANY number of utterances through continuously refilled slot GROUPS (cvx_t2s_beam_queue_steps): slots // beam_size
         groups (at most MAX_BATCH // beam_size) of beam_size neighbouring slots; a group whose utterance has ended - all hypotheses finished,
         or its step limit - takes the next pending utterance inside the selection kernel of that very step, as generate_many's slots do.
@@ -1530,12 +1585,16 @@ class TextToSemanticDecoder:
         max_length for all).  Windows of WINDOW // beam_size utterances (a record is a hypothesis), one packed encoder pass each.
         Returns what generate_beam returns for a list, in input order, host tensors; `last_beam` keeps generate_beam's record per utterance
         plus `status` (2: all hypotheses finished, 3: step limit) and `group` (the group it ran in).
-        ValueError (before any device work): beam_size outside 1..16, slots < beam_size, limits of another length than sources."""
+        cond_scale > 1 (one-output models): the guided search of generate_beam(cond_scale=...) through slots // (2 * beam_size) groups of
+        slot pairs (cvx_t2s_beam_guided_queue_steps); every utterance again equals generate_beam(cond_scale=...) alone, bit for bit.
+        ValueError (before any device work): beam_size outside 1..16, slots that hold no group (slots < beam_size, or < 2 * beam_size under
+        guidance), cond_scale < 1, limits of another length than sources.  NotImplementedError: guidance on a two-output model."""
         B = check_beam_size(beam_size)
+        scale = self._beam_scale(cond_scale)
         srcs = list(sources)
         n = len(srcs)
-        if int(slots) < B:
-            raise ValueError(f"generate_beam_many: slots = {slots} hold no group of beam_size = {B}")
+        if int(slots) < (2 * B if scale > 1.0 else B):
+            raise ValueError(f"generate_beam_many: slots = {slots} hold no {'guided ' if scale > 1.0 else ''}group of beam_size = {B}")
         if limits is not None and len(limits) != n:
             raise ValueError(f"generate_beam_many: {len(limits)} limits for {n} utterances")
         max_len = min(int(max_length or self.max_length), self.max_length)
@@ -1545,7 +1604,7 @@ class TextToSemanticDecoder:
         self.last_beam = []
         out, win = [], max(1, WINDOW // B)
         for w in range(0, n, win):
-            out += self._beam_queue_window(srcs[w:w + win], B, lim[w:w + win], float(length_penalty), int(slots))
+            out += self._beam_queue_window(srcs[w:w + win], B, lim[w:w + win], float(length_penalty), int(slots), scale)
         return out if return_beams else [h[0] for h in out]
 
     def score_many(self, sources, targets, cond_scale=1.0, slots: int = 64, mixed_guidance: bool = False):

@@ -13,7 +13,15 @@ MIXED=1: the mixed slot pool (cvx_t2s_decode_steps_mixed) on the full-size CoSin
 slots, eos ignored, all records unguided: A = cvx_t2s_decode_steps_per_dialogue behind a queue, B = the mixed entry (one launch more per
 step: the scheduler), interleaved REPEATS times.  (b) 32 guided + 64 unguided utterances with step limits spread over 100..608, 64 slots:
 one generate_many(mixed_guidance=True) call against the two calls of the default path (guided, then unguided), wall time, interleaved.
-    MIXED=1 STEPS=256 REPEATS=5 OUT=profile.txt python tools/bench_t2s.py"""
+    MIXED=1 STEPS=256 REPEATS=5 OUT=profile.txt python tools/bench_t2s.py
+BEAM=1: beam search (generate_beam, graph replay) on the full-size CoSingle model with the eos embedding row zeroed - its logit is then 0
+at every step, far below the shortlists, so no hypothesis finishes and every call runs STEPS (256) steps (checked).  us per beam step = the
+wall time of the call / STEPS (the encoder pass, the arming copies and the back-track included, the same for every side).  PARTS (a,b,c):
+(a) unguided, beam size 10 x 6 utterances = 60 slots; (b) guided (scale 1.5), beam size 10 x 3 utterances = the same 60 slots - (a) and (b)
+interleaved REPEATS times in one process; (c) generate_beam_many(cond_scale=1.5) against generate_beam(cond_scale=1.5) in lock-step waves of
+3 utterances (each wave to its longest limit) on 24 utterances with step limits 100..608.  PARTS=a runs on a commit without guided beams
+too: fresh processes of two commits, alternating, compare them.
+    BEAM=1 PARTS=a,b,c STEPS=256 REPEATS=5 OUT=profile.txt python tools/bench_t2s.py"""
 import os, sys, time, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import covomix_amd.synthetic as syn
@@ -175,8 +183,82 @@ def mixed_ab():
             f.write("\n".join(lines) + "\n")
 
 
+def beam_ab():
+    """(a), (b), (c) of BEAM=1 (see the module docstring)"""
+    import statistics
+    med = statistics.median
+    steps, reps, B = int(os.environ.get("STEPS", "256")), int(os.environ.get("REPEATS", "5")), 10
+    parts = [p.strip() for p in os.environ.get("PARTS", "a,b,c").split(",")]
+    sd = {k: torch.from_numpy(v) for k, v in syn.t2s_state_dict(syn.t2s_param_shapes(two_output=False, dim=512, dim_target=512), seed=0).items()}
+    E = sd["semantic_token_emb.weight"].clone()
+    E[-1] = 0.0
+    sd["semantic_token_emb.weight"] = E
+    m = TextToSemanticDecoder(sd, dev, max_length=2048)
+    g = torch.Generator().manual_seed(3)
+    srcs = [torch.randint(1, 30000, (1, 48), generator=g) for _ in range(24)]
+    lines = [f"text2semantic beam search, full-size CoSingle (synthetic weights, eos row zeroed: no hypothesis finishes), beam size {B}, "
+             f"device: {torch.cuda.get_device_name(0)}"]
+
+    def run(n, scale):
+        kw = {"cond_scale": scale} if scale > 1.0 else {}
+        torch.cuda.synchronize(); t0 = time.perf_counter()
+        m.generate_beam(srcs[:n], beam_size=B, max_length=steps, **kw)
+        torch.cuda.synchronize(); dt = time.perf_counter() - t0
+        assert all(r["steps"] == steps for r in m.last_beam), "an utterance ended early: the step count is not fixed"
+        return dt / steps * 1e6
+
+    sides = [(k, name, n, scale) for k, name, n, scale in (("a", "(a) unguided, 6 utterances = 60 slots", 6, 1.0),
+                                                            ("b", "(b) guided 1.5, 3 utterances = 60 slots", 3, 1.5)) if k in parts]
+    if sides:
+        for _, _, n, scale in sides:                         # graphs and buffers of the timed shapes
+            run(n, scale)
+        c0 = ops.clock_stamps()
+        t = {k: [] for k, _, _, _ in sides}
+        for _ in range(reps):
+            for k, _, n, scale in sides:
+                t[k].append(run(n, scale))
+        clk = ops.clock_from_stamps(c0, ops.clock_stamps())
+        lines.append(f"us per beam step = wall time of generate_beam / {steps} steps ({steps // CHUNK} graph replays of {CHUNK} steps; encoder, arming and "
+                     f"back-track included); {reps} rounds {' '.join(k for k, _, _, _ in sides)} ...; effective shader clock over the timed rounds "
+                     f"({clk.get('cus', 0)} CUs): " + (f"{clk['mhz']:.0f} MHz" if clk else "not reported"))
+        for k, name, _, _ in sides:
+            v = sorted(t[k])
+            lines.append(f"  {name:42s} us/step  min {v[0]:8.1f}  median {med(v):8.1f}  max {v[-1]:8.1f}   all {[round(x, 1) for x in t[k]]}")
+        if "a" in t and "b" in t:
+            lines.append(f"  (b) median / (a) median = {med(t['b']) / med(t['a']):.3f}; per hypothesis-step: (a) {med(t['a']) / 60 * 1e3:.0f} ns at 60 "
+                         f"hypotheses, (b) {med(t['b']) / 30 * 1e3:.0f} ns at 30")
+    if "c" in parts:
+        n, per, scale = 24, 3, 1.5
+        lims = torch.randint(100, 609, (n,), generator=g).tolist()
+        many = lambda l: m.generate_beam_many(srcs, beam_size=B, max_length=608, limits=l, cond_scale=scale)
+        waves = lambda l: [m.generate_beam(srcs[w:w + per], beam_size=B, max_length=max(l[w:w + per]), cond_scale=scale) for w in range(0, n, per)]
+        many([20] * n); waves([20] * n)                        # graphs and buffers of the timed shapes
+        t = {"many": [], "waves": []}
+        c0 = ops.clock_stamps()
+        for _ in range(max(1, min(reps, 3))):
+            for name, fn in (("waves", waves), ("many", many)):
+                torch.cuda.synchronize(); t0 = time.perf_counter()
+                fn(lims)
+                torch.cuda.synchronize()
+                t[name].append((time.perf_counter() - t0) * 1e3)
+            assert all(r["steps"] == l for r, l in zip(m.last_beam, lims)), "an utterance ended before its limit"
+        clk = ops.clock_from_stamps(c0, ops.clock_stamps())
+        lines.append(f"(c) guided (scale {scale}), {n} utterances, step limits 100..608 (sum {sum(lims)}), 60 of 64 slots = 3 groups of 10 slot pairs; wall "
+                     f"time, encoder included; rounds waves many ...; effective shader clock: " + (f"{clk['mhz']:.0f} MHz" if clk else "not reported"))
+        lines.append(f"  lock-step waves of {per} (each to its longest limit)   ms  min {min(t['waves']):8.1f}  median {med(t['waves']):8.1f}   all {[round(x, 1) for x in t['waves']]}")
+        lines.append(f"  generate_beam_many (refilled groups)              ms  min {min(t['many']):8.1f}  median {med(t['many']):8.1f}   all {[round(x, 1) for x in t['many']]}")
+        lines.append(f"  many / waves (medians) = {med(t['many']) / med(t['waves']):.3f}")
+    print("\n".join(lines), flush=True)
+    if os.environ.get("OUT"):
+        with open(os.environ["OUT"], "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
 if os.environ.get("PER", "0") == "1":
     per_dialogue_ab()
+    sys.exit(0)
+if os.environ.get("BEAM", "0") == "1":
+    beam_ab()
     sys.exit(0)
 if os.environ.get("MIXED", "0") == "1":
     mixed_ab()
