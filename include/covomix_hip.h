@@ -394,6 +394,29 @@ int cvx_cfg_combine_axpy_f32(const float* f_c, const float* f_n, const float* y,
 int cvx_rk_stage_f32(const float* f_c, const float* f_n, const float* y, float cond_scale, const float* row_scale,
                      const float* const* k_prev, const float* w, int32_t m, float* k_out, float* out, float* out2, float* out3,
                      int64_t rows, int32_t dim, cvx_stream_t s);
+/* The LAST stage of a step with the embedded error estimate.  Everything cvx_rk_stage_f32 does - out, out2, out3 and k_out have that
+ * kernel's bits for the same arguments - plus, per element, with v the combined field and o the new state of this launch:
+ *   delta = 0 ;  for j = 0 .. m-1 with we[j] != 0:  delta = fma(k_prev[j][i], we[j], delta) ;  if we[m] != 0:  delta = fma(v, we[m], delta)
+ * we: HOST array of m + 1 floats, the caller's fp32(dt * (b_j - b_err_j)): delta is the local error of the lower-order solution on
+ * the same stages.  A stage whose w[j] is 0 and whose we[j] is not must still be given (midpoint's k_0).
+ * A block owns one chunk of at most CVX_RK_ERR_ROWS consecutive rows of ONE sequence, counted from that sequence's first row (the
+ * last chunk of a sequence is short), and writes partials[block] = (sum delta^2, sum o^2) over its chunk: per-thread sums in element
+ * order, 64-lane butterfly, the four waves in wave order through LDS - no atomics, a function of the chunk's own rows only.
+ * map_dev: DEVICE int32 [blocks][3] = (first row, rows, sequence) per block; map_host: the same table on the HOST, checked here:
+ * the chunks must tile [0, rows) in order, 1 .. CVX_RK_ERR_ROWS rows each, sequences ascending, a short chunk ending its sequence.
+ * partials: DEVICE float [blocks][2] of this step, 8-byte aligned.  16-byte accesses when every pointer is 16-byte aligned and
+ * dim % 4 == 0 (every chunk then starts on a 16-byte boundary), 4-byte accesses otherwise; the sums may differ between the two forms.
+ * CVX_EINVAL, nothing launched: whatever cvx_rk_stage_f32 refuses; NULL we, map_dev, map_host or partials; NULL k_prev[j] with
+ * we[j] != 0; a map that does not tile the launch's rows as described. */
+#define CVX_RK_ERR_ROWS 32
+int cvx_rk_stage_err_f32(const float* f_c, const float* f_n, const float* y, float cond_scale, const float* row_scale,
+                         const float* const* k_prev, const float* w, const float* we, int32_t m, float* k_out, float* out, float* out2,
+                         float* out3, int64_t rows, int32_t dim, const int32_t* map_dev, const int32_t* map_host, int32_t blocks,
+                         float* partials, cvx_stream_t s);
+/* err[step][q] = (sum delta^2, sum o^2) of sequence q at every step: the partials [steps][blocks][2] of the blocks the map gives to
+ * q, added in block order by one thread.  One launch at the end of a solve.  err: DEVICE float [steps][n_seq][2], 8-byte aligned. */
+int cvx_rk_err_finish_f32(const float* partials, const int32_t* map_dev, int32_t blocks, int32_t steps, int32_t n_seq, float* err,
+                          cvx_stream_t s);
 
 /* rows of [ emb(ids[m,0]) | emb(ids[m,1]) ... | cond[m,:] ]  -> out[M, S*E + Cc]
  * (the step-invariant columns of the to_embed input, acoustic.py:496-503).

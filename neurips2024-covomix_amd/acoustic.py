@@ -18,7 +18,7 @@ Python here only sequences kernel launches on torch's current stream and owns de
 """
 from __future__ import annotations
 
-from dataclasses import dataclass
+from dataclasses import dataclass, field
 from typing import Dict, List, Optional, Sequence, Tuple, Union
 
 import math
@@ -705,11 +705,15 @@ class Tableau:
     """Butcher tableau of an explicit Runge-Kutta method on the fixed grid: stage j evaluates the field at t0 + c[j] dt on
     y + dt sum_i a[j-1][i] k_i, the step ends at y + dt sum_j b[j] k_j.  `a` holds the strictly lower-triangular rows (row j - 1 of
     stage j: j entries), so a one-stage method has a = ().  At most MAX_STAGES stages (the stage kernel keeps three earlier ones).
-    Frozen and hashable: it is part of the keys of the per-grid tables and of the captured graphs."""
+    Frozen and hashable: it is part of the keys of the per-grid tables and of the captured graphs.
+    b_err (optional): the weights of a LOWER-order solution on the same stages - an embedded pair.  dt sum_j (b[j] - b_err[j]) k_j is
+    then the local error of that lower-order solution (FlowMatchingSampler.sample(return_error=True)).  It does not change the solve
+    and takes no part in equality or the hash: the time tables and graphs of a tableau serve it with any b_err."""
     name: str
     a: Tuple[Tuple[float, ...], ...]
     b: Tuple[float, ...]
     c: Tuple[float, ...]
+    b_err: Optional[Tuple[float, ...]] = field(default=None, compare=False)
 
     MAX_STAGES = 4
 
@@ -734,20 +738,48 @@ class Tableau:
             row_sum = sum(a[j - 1]) if j else 0.0
             if abs(c[j] - row_sum) > 1e-12:
                 raise ValueError(f"tableau {self.name!r}: c[{j}] = {c[j]!r} is not the sum of its row of a ({row_sum!r})")
+        if self.b_err is not None:
+            try:
+                be = tuple(float(x) for x in self.b_err)
+            except TypeError as e:
+                raise ValueError(f"tableau {self.name!r}: b_err must be a sequence of numbers") from e
+            object.__setattr__(self, "b_err", be)
+            if len(be) != n or not all(math.isfinite(x) for x in be):
+                raise ValueError(f"tableau {self.name!r}: b_err must have {n} finite entries")
+            if abs(sum(be) - 1.0) > 1e-12:
+                raise ValueError(f"tableau {self.name!r}: sum(b_err) = {sum(be)!r}, a consistent method needs 1")
+            if be == b:
+                raise ValueError(f"tableau {self.name!r}: b_err equals b - the estimate would be 0")
 
     @property
     def stages(self) -> int:
         return len(self.b)
 
+    @property
+    def err_order(self) -> Optional[int]:
+        """Order q of the solution b_err gives (None without b_err): 1, 2 with sum b_err_j c_j = 1/2, 3 with the two third-order
+        conditions on top.  The estimate of a step is O(dt^(q+1))."""
+        if self.b_err is None:
+            return None
+        n, be, c = self.stages, self.b_err, self.c
+        ac = [sum(self.a[j - 1][i] * c[i] for i in range(j)) if j else 0.0 for j in range(n)]
+        dot = lambda u, v: sum(x * y for x, y in zip(u, v))
+        if abs(dot(be, c) - 0.5) > 1e-12:
+            return 1
+        if abs(dot(be, [x * x for x in c]) - 1 / 3) > 1e-12 or abs(dot(be, ac) - 1 / 6) > 1e-12:
+            return 2
+        return 3
+
 
 TABLEAUS = {t.name: t for t in (
+    # b_err (last argument): Euler's step inside midpoint and Heun (order 1), a second-order rule on the stages of the others
     Tableau("euler", (), (1.0,), (0.0,)),
-    Tableau("midpoint", ((0.5,),), (0.0, 1.0), (0.0, 0.5)),
-    Tableau("heun2", ((1.0,),), (0.5, 0.5), (0.0, 1.0)),
-    Tableau("heun3", ((1 / 3,), (0.0, 2 / 3)), (0.25, 0.0, 0.75), (0.0, 1 / 3, 2 / 3)),
+    Tableau("midpoint", ((0.5,),), (0.0, 1.0), (0.0, 0.5), (1.0, 0.0)),
+    Tableau("heun2", ((1.0,),), (0.5, 0.5), (0.0, 1.0), (1.0, 0.0)),
+    Tableau("heun3", ((1 / 3,), (0.0, 2 / 3)), (0.25, 0.0, 0.75), (0.0, 1 / 3, 2 / 3), (0.0, 0.5, 0.5)),
     # torchdiffeq's fixed-grid "rk4" is the 3/8 rule (the reference's torchdiffeq_ode_method, acoustic.py:560-591)
-    Tableau("rk4", ((1 / 3,), (-1 / 3, 1.0), (1.0, -1.0, 1.0)), (1 / 8, 3 / 8, 3 / 8, 1 / 8), (0.0, 1 / 3, 2 / 3, 1.0)),
-    Tableau("rk4_classic", ((0.5,), (0.0, 0.5), (0.0, 0.0, 1.0)), (1 / 6, 1 / 3, 1 / 3, 1 / 6), (0.0, 0.5, 0.5, 1.0)),
+    Tableau("rk4", ((1 / 3,), (-1 / 3, 1.0), (1.0, -1.0, 1.0)), (1 / 8, 3 / 8, 3 / 8, 1 / 8), (0.0, 1 / 3, 2 / 3, 1.0), (0.0, 0.5, 0.5, 0.0)),
+    Tableau("rk4_classic", ((0.5,), (0.0, 0.5), (0.0, 0.0, 1.0)), (1 / 6, 1 / 3, 1 / 3, 1 / 6), (0.0, 0.5, 0.5, 1.0), (0.0, 1.0, 0.0, 0.0)),
 )}
 
 
@@ -760,21 +792,98 @@ def resolve_method(method) -> Tableau:
     raise ValueError(f"unknown ODE method {method!r}: one of {', '.join(TABLEAUS)} or a Tableau")
 
 
-def evaluation_times(nfe: int, method):
-    """Fixed grid of the reference solver (torchdiffeq fixed-grid, options.step_size) as python floats
-    computed in fp32 exactly like the solver does: (t0, dt) per step, plus every time the field is evaluated at -
-    t0 + fp32(c_j) dt per stage, the grid point t1 itself for a stage with c_j = 1 (as torchdiffeq's rk4 does).  One time per
-    evaluation: the last stage of a step and the first of the next may repeat a time (the per-time tables are indexed by evaluation)."""
-    tab = resolve_method(method)
+SWAY_MAX = 2.0 / (math.pi - 2.0)        # t' = u + s (cos(pi u / 2) - 1 + u) is monotone on [0, 1] for -1 <= s <= 2 / (pi - 2)
+
+
+def _steps_of(nfe: int, tab: Tableau) -> int:
     n = tab.stages
     if int(nfe) != nfe or nfe < n or nfe % n:
         raise ValueError(f"nfe={nfe} is not valid for method={tab.name}: a positive multiple of its {n} stage(s)")
-    steps = nfe // n
-    h = torch.tensor(1.0 / steps, dtype=torch.float32)
-    grid = torch.arange(0, steps + 1, dtype=torch.float32) * h
-    grid[-1] = 1.0
+    return int(nfe) // n
+
+
+def time_grid(spec, steps: int) -> Tuple[float, ...]:
+    """The steps + 1 grid points of a solve on [0, 1] as python floats that fp32 holds exactly: 0.0 first, 1.0 last, strictly increasing.
+    spec: 'uniform' (the reference's grid: arange(steps + 1) * fp32(1 / steps) in fp32, the last point set to 1), 'sway:<s>'
+    (t' = u + s (cos(pi u / 2) - 1 + u) on u = j / steps, -1 <= s <= 2 / (pi - 2): s < 0 takes small steps first - F5-TTS's sway
+    sampling), 'cosine' (t' = (1 - cos(pi u)) / 2: small steps at both ends), or an explicit sequence of steps + 1 numbers (rounded to
+    fp32).  sway and cosine are computed in fp64 and rounded to fp32 ('sway:0' need not have the uniform grid's bits).  ValueError,
+    naming the entry: wrong length, a non-finite value, ends other than 0 and 1, not strictly increasing."""
+    if int(steps) != steps or steps < 1:
+        raise ValueError(f"time grid: steps={steps!r}, a positive integer is needed")
+    steps = int(steps)
+    if isinstance(spec, str):
+        if spec == "uniform":
+            g = torch.arange(0, steps + 1, dtype=torch.float32) * torch.tensor(1.0 / steps, dtype=torch.float32)
+            g[-1] = 1.0
+            vals = g.tolist()
+        elif spec == "cosine" or spec.startswith("sway:"):
+            if spec == "cosine":
+                fn = lambda u: (1.0 - math.cos(math.pi * u)) / 2.0
+            else:
+                try:
+                    sw = float(spec[5:])
+                except ValueError:
+                    raise ValueError(f"time grid {spec!r}: sway:<s> needs a number") from None
+                if not -1.0 <= sw <= SWAY_MAX:             # (NaN fails both comparisons)
+                    raise ValueError(f"time grid {spec!r}: s must lie in [-1, 2 / (pi - 2) = {SWAY_MAX:.6f}], where the map is monotone")
+                fn = lambda u: u + sw * (math.cos(math.pi * u / 2.0) - 1.0 + u)
+            vals = [fn(j / steps) for j in range(steps + 1)]
+            vals[0], vals[-1] = 0.0, 1.0
+        else:
+            raise ValueError(f"unknown time grid {spec!r}: uniform, cosine, sway:<s> or a sequence of steps + 1 numbers")
+    else:
+        try:
+            vals = [float(x) for x in spec]
+        except (TypeError, ValueError) as e:
+            raise ValueError(f"time grid: {spec!r} is neither a grid's name nor a sequence of numbers") from e
+        if len(vals) != steps + 1:
+            raise ValueError(f"time grid: {len(vals)} points for {steps} steps, {steps + 1} are needed")
+    for j, v in enumerate(vals):
+        if not math.isfinite(v):
+            raise ValueError(f"time grid: entry {j} is {v!r}")
+    vals = torch.tensor(vals, dtype=torch.float64).to(torch.float32).tolist()
+    if vals[0] != 0.0:
+        raise ValueError(f"time grid: entry 0 is {vals[0]!r}, the grid starts at 0")
+    if vals[-1] != 1.0:
+        raise ValueError(f"time grid: entry {steps} is {vals[-1]!r}, the grid ends at 1")
+    for j in range(steps):
+        if not vals[j] < vals[j + 1]:
+            raise ValueError(f"time grid: entry {j + 1} ({vals[j + 1]!r}) is not above entry {j} ({vals[j]!r}) in fp32")
+    return tuple(vals)
+
+
+def resolve_grid(grid, nfe: int, method) -> Optional[Tuple[float, ...]]:
+    """None for the uniform grid (None, 'uniform', or its points given explicitly: existing callers keep their table and graph keys),
+    otherwise the validated grid as a hashable tuple - with every refusal of time_grid and of evaluation_times."""
+    if grid is None or (isinstance(grid, str) and grid == "uniform"):
+        return None
+    tab = resolve_method(method)
+    g = time_grid(grid, _steps_of(nfe, tab))
+    if g == time_grid("uniform", len(g) - 1):
+        return None
+    evaluation_times(nfe, tab, g)
+    return g
+
+
+def evaluation_times(nfe: int, method, grid=None):
+    """Fixed grid of the reference solver (torchdiffeq fixed-grid, options.step_size) as python floats
+    computed in fp32 exactly like the solver does: (t0, dt) per step, plus every time the field is evaluated at -
+    t0 + fp32(c_j) dt per stage, the grid point t1 itself for a stage with c_j = 1 (as torchdiffeq's rk4 does).  One time per
+    evaluation: the last stage of a step and the first of the next may repeat a time (the per-time tables are indexed by evaluation).
+    grid: None / 'uniform', or anything time_grid takes - the same fp32 arithmetic on its points.  ValueError if a step of a given
+    grid is so small that a stage time with 0 < c_j < 1 rounds onto t0 or t1."""
+    tab = resolve_method(method)
+    steps = _steps_of(nfe, tab)
+    given = not (grid is None or (isinstance(grid, str) and grid == "uniform"))
+    if given:
+        grid = torch.tensor(time_grid(grid, steps), dtype=torch.float32)
+    else:
+        h = torch.tensor(1.0 / steps, dtype=torch.float32)
+        grid = torch.arange(0, steps + 1, dtype=torch.float32) * h
+        grid[-1] = 1.0
     times, dts = [], []
-    for a, b in zip(grid[:-1], grid[1:]):
+    for j, (a, b) in enumerate(zip(grid[:-1], grid[1:])):
         dt = b - a
         dts.append(float(dt))
         for c in tab.c:
@@ -783,8 +892,60 @@ def evaluation_times(nfe: int, method):
             elif c == 1.0:
                 times.append(float(b))
             else:
-                times.append(float(a + torch.tensor(c, dtype=torch.float32) * dt))
+                t = float(a + torch.tensor(c, dtype=torch.float32) * dt)
+                if given and 0.0 < c < 1.0 and not float(a) < t < float(b):
+                    raise ValueError(f"time grid: entry {j + 1} ({float(b)!r}) is so close to entry {j} ({float(a)!r}) that the stage at "
+                                     f"c = {c!r} of {tab.name} falls onto a grid point in fp32")
+                times.append(t)
     return torch.tensor(times, dtype=torch.float32), dts
+
+
+@dataclass(frozen=True)
+class SolveError:
+    """The embedded error estimate of one solve.  delta_rms[k, i]: root mean square over utterance i's elements of
+    delta = dt_k sum_j (b_j - b_err_j) k_j at step k - the local error of the order-`order` solution on the method's stages,
+    O(dt^(order + 1)); state_rms[k, i]: the same mean of the state after step k.  fp64 CPU tensors [steps, utterances]."""
+    grid: Tuple[float, ...]
+    method: Union[str, Tableau]
+    order: int
+    delta_rms: torch.Tensor
+    state_rms: torch.Tensor
+
+
+def fit_time_grid(error: SolveError, steps: int, reduce: str = "rms") -> Tuple[float, ...]:
+    """A grid of `steps` steps that equidistributes the measured local error: with E_k the `reduce` ('rms', 'mean' or 'max') over the
+    utterances of error.delta_rms[k], h_k the steps of error.grid and q = error.order, the density rho_k = E_k^(1 / (q + 1)) / h_k is
+    constant on step k (a step of length h there has local error ~ (rho h)^(q + 1)); F is its integral and the new points are
+    F^-1(j F(1) / steps), piecewise linear.  fp64 on the host, rounded to fp32, ends exactly 0 and 1, refused like an explicit grid.
+    Equal E_k on a uniform grid give the uniform points (up to the fp32 rounding of j / steps)."""
+    d = error.delta_rms.to(torch.float64)
+    if d.ndim != 2 or d.shape[0] != len(error.grid) - 1 or d.shape[1] < 1 or not bool(torch.isfinite(d).all()):
+        raise ValueError("fit_time_grid: delta_rms must be a finite [steps, utterances] table on error.grid")
+    if reduce == "rms":
+        E = d.square().mean(dim=1).sqrt()
+    elif reduce == "mean":
+        E = d.mean(dim=1)
+    elif reduce == "max":
+        E = d.amax(dim=1)
+    else:
+        raise ValueError(f"fit_time_grid: reduce={reduce!r}: rms, mean or max")
+    old = [float(t) for t in error.grid]
+    E = [max(float(e), 1e-300) for e in E]
+    p = 1.0 / (int(error.order) + 1)
+    F = [0.0]
+    for e in E:
+        F.append(F[-1] + e ** p)                       # rho_k h_k
+    new, k = [], 0
+    for j in range(steps + 1):
+        tgt = j * F[-1] / steps
+        while k + 1 < len(E) and F[k + 1] < tgt:
+            k += 1
+        new.append(old[k] + (old[k + 1] - old[k]) * min(max((tgt - F[k]) / (F[k + 1] - F[k]), 0.0), 1.0))
+    new[0], new[-1] = 0.0, 1.0
+    g = time_grid(new, steps)
+    tab = resolve_method(error.method)
+    evaluation_times(steps * tab.stages, tab, g)
+    return g
 
 
 class FlowMatchingSampler:
@@ -793,22 +954,28 @@ class FlowMatchingSampler:
     `nfe` counts CFG-combined field evaluations: the reference's ode_step_size=0.0625 midpoint
     setting is nfe=32 (16 steps x 2).  `method`: the name of a built-in tableau (TABLEAUS: the reference's torchdiffeq_ode_method;
     'euler' is an extra the reference lacks) or a Tableau; nfe must be a multiple of its stage count.  cond_scale may be one float
-    per utterance (extension: the reference takes one scalar per call)."""
+    per utterance (extension: the reference takes one scalar per call).  `grid`: the time grid (time_grid: 'uniform', 'sway:<s>',
+    'cosine' or the points) - fixed before the solve starts, like everything that depends on the evaluation times."""
 
-    def __init__(self, field: VectorField, nfe: int = 32, method: Union[str, Tableau] = "midpoint"):
+    def __init__(self, field: VectorField, nfe: int = 32, method: Union[str, Tableau] = "midpoint", grid="uniform"):
         self.field, self.nfe, self.method = field, nfe, method
         resolve_method(method)
+        self.grid = resolve_grid(grid, nfe, method)      # None: uniform; otherwise a tuple - part of the table and graph keys
 
     # launch-bound regime (short / single utterances): the whole solve - ~2400 kernel launches for 32 NFE - is captured
     # once per input shape into a HIP graph and replayed (env CVX_GRAPH=0 disables, CVX_GRAPH_MAX_ROWS bounds the
     # batch size it applies to; large batches are GPU-bound and stay eager).
     GRAPH_CACHE = 4
 
-    def _integrate(self, phoneme_ids, cond, y, times_dev, dts, s: float, use_null: bool, lengths=None, row_scale=None) -> None:
+    def _times_key(self) -> tuple:
+        return (int(self.nfe), str(self.method)) + (() if self.grid is None else (self.grid,))
+
+    def _integrate(self, phoneme_ids, cond, y, times_dev, dts, s: float, use_null: bool, lengths=None, row_scale=None, err=None) -> None:
         """prepare() + the fixed-grid loop; advances `y` in place (ragged batch: y, cond, ids packed, see prepare).
-        row_scale: one guidance scale per row of y on the device (then `s` is not used)."""
+        row_scale: one guidance scale per row of y on the device (then `s` is not used).  err: the buffers of the embedded error
+        estimate (_error_state) - the generic stage loop then runs for every method."""
         f = self.field
-        ctx = f.prepare(phoneme_ids, cond, times_dev, use_null, lengths=lengths, times_key=(int(self.nfe), str(self.method)))
+        ctx = f.prepare(phoneme_ids, cond, times_dev, use_null, lengths=lengths, times_key=self._times_key())
         ws, M1 = ctx["ws"], ctx["M1"]
         xin = ws["xin"]
         x_c = xin[:M1]
@@ -816,8 +983,8 @@ class FlowMatchingSampler:
         x_c.copy_(y.reshape(M1, -1))
         if use_null:
             x_n.copy_(x_c)
-        if row_scale is not None or self.method not in ("midpoint", "euler"):      # (an explicit Tableau is never equal to a name)
-            self._integrate_stages(ctx, y.reshape(M1, -1), dts, s, resolve_method(self.method), row_scale)
+        if row_scale is not None or err is not None or self.method not in ("midpoint", "euler"):      # (an explicit Tableau is never equal to a name)
+            self._integrate_stages(ctx, y.reshape(M1, -1), dts, s, resolve_method(self.method), row_scale, err)
             return ctx
         evaluate = f.evaluate
         e = 0
@@ -832,29 +999,64 @@ class FlowMatchingSampler:
                 ops.cfg_combine_axpy(pred[:M1], pred[M1:] if use_null else None, y, s, dt, y, x_c, x_n)
         return ctx
 
-    def _integrate_stages(self, ctx: dict, y: torch.Tensor, dts, s: float, tab: Tableau, row_scale) -> None:
+    def _integrate_stages(self, ctx: dict, y: torch.Tensor, dts, s: float, tab: Tableau, row_scale, err=None) -> None:
         """The fixed-grid loop of any explicit tableau: one field evaluation and one cvx_rk_stage_f32 launch per stage.  The launch
         after stage i combines the CFG branches into k_i and writes the next evaluation's input y + dt sum_l a[i+1][l] k_l - after
         the last stage the step's result y + dt sum_l b[l] k_l, in place.  k_i is stored only when a later launch reads it (its b
         or a later row of a is not 0): midpoint and Euler store nothing, Heun's third-order rule one stage, the fourth-order rules
-        three - buffers of the workspace, made on first use."""
+        three - buffers of the workspace, made on first use.
+        err: the last launch of every step is cvx_rk_stage_err_f32 (the same bits in y) with the weights dt (b_j - b_err_j); a stage
+        those weights read is stored as well (midpoint's k_0), and one cvx_rk_err_finish_f32 launch ends the solve."""
         f = self.field
         ws, M1, use_null = ctx["ws"], ctx["M1"], ctx["use_null"]
         x_c = ws["xin"][:M1]
         x_n = ws["xin"][M1:] if use_null else None
         n = tab.stages
         rows = ((),) + tab.a + (tab.b,)          # rows[i + 1]: the weights the launch after stage i applies to k_0 .. k_i
-        keep = [i + 1 < n and any(rows[j][i] != 0.0 for j in range(i + 2, n + 1)) for i in range(n)]
+        db = [b - be for b, be in zip(tab.b, tab.b_err)] if err is not None else [0.0] * n
+        keep = [i + 1 < n and (db[i] != 0.0 or any(rows[j][i] != 0.0 for j in range(i + 2, n + 1))) for i in range(n)]
         bufs = iter(f.stage_buffers(ctx, sum(keep)))
         k = [next(bufs) if keep[i] else None for i in range(n)]
         e = 0
-        for dt in dts:
+        for step, dt in enumerate(dts):
             for i in range(n):
                 pred = f.evaluate(ctx, e); e += 1
                 coef, last = rows[i + 1], i + 1 == n
+                if last and err is not None:
+                    ops.rk_stage_err(pred[:M1], pred[M1:] if use_null else None, y, s, [dt * c for c in coef], [dt * c for c in db], y,
+                                     err["map"], err["partials"][step], k_prev=[k[l] if (coef[l] != 0.0 or db[l] != 0.0) else None for l in range(i)],
+                                     row_scale=row_scale, out2=x_c, out3=x_n)
+                    continue
                 ops.rk_stage(pred[:M1], pred[M1:] if use_null else None, y, s, [dt * c for c in coef], y if last else x_c,
                              k_prev=[k[l] if coef[l] != 0.0 else None for l in range(i)], k_out=k[i], row_scale=row_scale,
                              out2=x_c if last else x_n, out3=x_n if last else None)
+        if err is not None:
+            ops.rk_err_finish(err["partials"], err["map"], err["sums"])
+
+    def _error_state(self, lengths: List[int], return_error: bool) -> Optional[dict]:
+        """The device buffers of the embedded error estimate for sequences of these lengths: the block map of the last-stage kernel,
+        its partial sums per (step, block) and the sums per (step, sequence).  Made once per call - or once per captured graph, whose
+        static state they are - before the loop starts."""
+        if not return_error:
+            return None
+        tab = resolve_method(self.method)
+        if tab.b_err is None:
+            raise ValueError(f"return_error: method {tab.name!r} has no embedded pair (Tableau.b_err)")
+        dev, steps = self.field.device, len(self._grid_points()) - 1
+        emap = ops.RkErrMap(lengths, dev)
+        return dict(map=emap, partials=torch.zeros(steps, emap.blocks, 2, dtype=torch.float32, device=dev),
+                    sums=torch.zeros(steps, emap.n_seq, 2, dtype=torch.float32, device=dev))
+
+    def _grid_points(self) -> Tuple[float, ...]:
+        return self.grid if self.grid is not None else time_grid("uniform", _steps_of(self.nfe, resolve_method(self.method)))
+
+    def _solve_error(self, err: dict, lengths: List[int]) -> SolveError:
+        """the two tables of a finished solve on the host (one synchronising copy)"""
+        tab = resolve_method(self.method)
+        sums = err["sums"].cpu().double()                                           # [steps, sequences, 2]
+        count = torch.tensor([L * self.field.d["dim_out"] for L in lengths], dtype=torch.float64)
+        return SolveError(grid=self._grid_points(), method=self.method, order=tab.err_order,
+                          delta_rms=(sums[..., 0] / count).sqrt(), state_rms=(sums[..., 1] / count).sqrt())
 
     @staticmethod
     def _scales(cond_scale, n: int):
@@ -872,7 +1074,8 @@ class FlowMatchingSampler:
     @ops.gated
     @torch.no_grad()
     def sample(self, *, phoneme_ids: torch.Tensor, cond: torch.Tensor, mask: Optional[torch.Tensor] = None,
-               cond_scale: Union[float, Sequence[float]] = 1.0, y0: Optional[torch.Tensor] = None) -> torch.Tensor:
+               cond_scale: Union[float, Sequence[float]] = 1.0, y0: Optional[torch.Tensor] = None, return_error: bool = False):
+        """return_error: also measure the embedded error estimate - the result is (y, SolveError), y with the bits of the plain call."""
         import os
         f, d = self.field, self.field.d
         dev = f.device
@@ -893,21 +1096,26 @@ class FlowMatchingSampler:
         use_null = s != 1.0 if per is None else True         # acoustic.py:423 (different scales: at least one is not 1)
         # per-utterance scales: one float per row, read by the stage kernel (a row at 1.0 takes its conditional branch there)
         row_scale = None if per is None else ops.h2d(torch.tensor(per, dtype=torch.float32).repeat_interleave(T), dev)
-        times, dts = evaluation_times(self.nfe, self.method)
+        times, dts = evaluation_times(self.nfe, self.method, self.grid)
         rows = (2 * B if use_null else B) * T
         if os.environ.get("CVX_GRAPH", "1") == "0" or rows > int(os.environ.get("CVX_GRAPH_MAX_ROWS", "8192")):
-            self._integrate(phoneme_ids, cond, y, ops.h2d(times, dev), dts, s, use_null, row_scale=row_scale)
-            return y
+            err = self._error_state([T] * B, return_error)
+            self._integrate(phoneme_ids, cond, y, ops.h2d(times, dev), dts, s, use_null, row_scale=row_scale, err=err)
+            return (y, self._solve_error(err, [T] * B)) if return_error else y
         main = torch.cuda.current_stream()
         # (the saturation flag of the launching stream is a kernel argument of the captured launches: one graph per stream;
         #  per-utterance scales sit in a buffer the graph reads: one graph serves every mix of them)
         key = (B, T, use_null, s if per is None else "per-row", self.nfe, self.method, main.cuda_stream)
+        if self.grid is not None:            # (the uniform grid keeps the key it always had)
+            key += (self.grid,)
+        if return_error:                     # (b_err takes no part in a Tableau's equality)
+            key += ("error", resolve_method(self.method).b_err)
         cache = f.__dict__.setdefault("_graphs", {})
         ent = cache.get(key)
         if ent is None:
             st = dict(ids=phoneme_ids.clone(), cond=cond.clone(), y=y.clone(), times=ops.h2d(times, dev),
-                      row_scale=None if row_scale is None else row_scale.clone())
-            ctx = self._integrate(st["ids"], st["cond"], st["y"], st["times"], dts, s, use_null, row_scale=st["row_scale"])   # eager warm-up
+                      row_scale=None if row_scale is None else row_scale.clone(), err=self._error_state([T] * B, return_error))
+            ctx = self._integrate(st["ids"], st["cond"], st["y"], st["times"], dts, s, use_null, row_scale=st["row_scale"], err=st["err"])   # eager warm-up
             st["ws"] = ctx["ws"]             # keep this shape's workspace alive for as long as the graph is
             # (thread-local capture mode + the package's capture gate: another host thread driving its own model on this device
             #  must not break this capture, nor be broken by it - HIP rejects its synchronisations while a capture is open even
@@ -919,7 +1127,7 @@ class FlowMatchingSampler:
                     self._cap = torch.cuda.Stream(device=dev)
                 ops.saturation_share(main, self._cap)    # the captured launches report into the calling stream's flag
                 with torch.cuda.graph(g, stream=self._cap, capture_error_mode="thread_local"):
-                    self._integrate(st["ids"], st["cond"], st["y"], st["times"], dts, s, use_null, row_scale=st["row_scale"])
+                    self._integrate(st["ids"], st["cond"], st["y"], st["times"], dts, s, use_null, row_scale=st["row_scale"], err=st["err"])
             cache = f.__dict__.setdefault("_graphs", {})     # (the warm-up may have evicted a time grid and, with it, the cache)
             if len(cache) >= self.GRAPH_CACHE:
                 cache.pop(next(iter(cache)))
@@ -931,23 +1139,27 @@ class FlowMatchingSampler:
         if row_scale is not None:
             st["row_scale"].copy_(row_scale)
         g.replay()
+        if return_error:
+            return st["y"].clone(), self._solve_error(st["err"], [T] * B)
         return st["y"].clone()
 
     @ops.gated
     @torch.no_grad()
     def sample_ragged(self, *, phoneme_ids: List[torch.Tensor], cond: List[torch.Tensor], cond_scale: Union[float, Sequence[float]] = 1.0,
-                      y0: Optional[List[torch.Tensor]] = None) -> List[torch.Tensor]:
+                      y0: Optional[List[torch.Tensor]] = None, return_error: bool = False):
         """The same solve for several utterances of DIFFERENT length in one launch sequence: utterance i is
         phoneme_ids[i] [T_i(, streams)], cond[i] [T_i, dim_cond] (y0[i] [T_i, dim_out]); returns the list of [T_i, dim_out]
         results.  The reference runs such utterances one at a time (monologue_generation.py:259-304) and its network has
         no padding mask (acoustic.py:313), so they are PACKED back to back - M = sum T_i rows - and the three operators
         that look along time (attention, rotary positions, ConvPositionEmbed) work per sequence (include/covomix_hip.h,
         RAGGED BATCHES); every utterance gets the result of its own B = 1 run up to fp32 summation order.
-        cond_scale: one float, or one per utterance."""
+        cond_scale: one float, or one per utterance.  return_error: the result is (list, SolveError), as in sample()."""
         f, d = self.field, self.field.d
         dev = f.device
         n = len(cond)
         if n == 0:
+            if return_error:
+                raise ValueError("return_error: no utterance to measure")
             return []
         lengths = [int(c.shape[0]) for c in cond]
         for i in range(n):
@@ -967,6 +1179,8 @@ class FlowMatchingSampler:
         s, per = self._scales(cond_scale, n)
         use_null = s != 1.0 if per is None else True         # acoustic.py:423
         row_scale = None if per is None else ops.h2d(torch.tensor(per, dtype=torch.float32).repeat_interleave(torch.tensor(lengths)), dev)
-        times, dts = evaluation_times(self.nfe, self.method)
-        self._integrate(ids_p, cond_p, y, ops.h2d(times, dev), dts, s, use_null, lengths=lengths, row_scale=row_scale)
-        return list(torch.split(y, lengths))
+        times, dts = evaluation_times(self.nfe, self.method, self.grid)
+        err = self._error_state(lengths, return_error)
+        self._integrate(ids_p, cond_p, y, ops.h2d(times, dev), dts, s, use_null, lengths=lengths, row_scale=row_scale, err=err)
+        out = list(torch.split(y, lengths))
+        return (out, self._solve_error(err, lengths)) if return_error else out

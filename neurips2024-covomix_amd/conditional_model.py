@@ -31,7 +31,7 @@ from typing import Dict, Optional
 import torch
 
 from . import ops
-from .acoustic import FlowMatchingSampler, VectorField, resolve_method
+from .acoustic import FlowMatchingSampler, VectorField, resolve_grid, resolve_method
 
 _PREFIX = "cfm_wrapper.CoVoMix."
 _PREFIX_T2S = "cfm_wrapper.model."
@@ -74,12 +74,16 @@ def t2s_parameter_order(sd_keys) -> list:
 class CoVoMixModel:
     def __init__(self, state_dict: Dict[str, torch.Tensor], hparams: Optional[dict] = None,
                  ema_shadow: Optional[list] = None, nfe: int = 32, ode_method="midpoint",
-                 precision: Optional[str] = None):
+                 precision: Optional[str] = None, ode_grid="uniform", ode_error: bool = False):
         """state_dict: un-prefixed CoVoMix parameter names (acoustic.py:326-406).
         ode_method: the reference's torchdiffeq_ode_method (acoustic.py:560-591) - the name of a built-in tableau (acoustic.TABLEAUS:
         euler, midpoint, heun2, heun3, rk4 = torchdiffeq's 3/8 rule, rk4_classic) or an acoustic.Tableau; nfe counts field evaluations
-        and must be a multiple of the method's stages."""
+        and must be a multiple of the method's stages.
+        ode_grid: the time grid of the solve (acoustic.time_grid: 'uniform', 'sway:<s>', 'cosine' or nfe / stages + 1 points).
+        ode_error: every synthesis_sample also measures the method's embedded error estimate and leaves it in last_solve_error
+        (acoustic.SolveError); the result is the same, bit for bit."""
         resolve_method(ode_method)
+        resolve_grid(ode_grid, nfe, ode_method)
         self.hparams = dict(hparams or {})
         self.is_text2semantic = "token_emb.text.weight" in state_dict
         if bool(self.hparams.get("text2semantic", self.is_text2semantic)) != self.is_text2semantic:
@@ -99,6 +103,8 @@ class CoVoMixModel:
         self._use_ema = False
         self.device = torch.device("cpu")
         self.nfe, self.ode_method = nfe, ode_method
+        self.ode_grid, self.ode_error = ode_grid, bool(ode_error)
+        self.last_solve_error = None
         self.precision = precision or os.environ.get("CVX_PRECISION", "f16x3")
         self._field: Optional[VectorField] = None
         self._field_fp32: Optional[VectorField] = None      # built only if a split-precision call ever saturates
@@ -180,11 +186,15 @@ class CoVoMixModel:
         ragged = isinstance(cond, (list, tuple))     # extension: utterances of different length in one packed launch
 
         def run(f):
-            sampler = FlowMatchingSampler(f, nfe=self.nfe, method=self.ode_method)
+            sampler = FlowMatchingSampler(f, nfe=self.nfe, method=self.ode_method, grid=self.ode_grid)
             if ragged:
-                return sampler.sample_ragged(phoneme_ids=list(phoneme_ids), cond=list(cond), cond_scale=cond_scale,
-                                             y0=None if y0 is None else list(y0))
-            return sampler.sample(phoneme_ids=phoneme_ids, cond=cond, mask=mask, cond_scale=cond_scale, y0=y0)
+                res = sampler.sample_ragged(phoneme_ids=list(phoneme_ids), cond=list(cond), cond_scale=cond_scale,
+                                            y0=None if y0 is None else list(y0), return_error=self.ode_error)
+            else:
+                res = sampler.sample(phoneme_ids=phoneme_ids, cond=cond, mask=mask, cond_scale=cond_scale, y0=y0, return_error=self.ode_error)
+            if self.ode_error:
+                res, self.last_solve_error = res
+            return res
         # Split-precision activations live in a window of 2^12 around the RMS the gain model predicts (acoustic.py,
         # _activation_scales).  A checkpoint with an outlier row / channel can leave it: the kernels then clamp and raise the
         # device's sticky saturation flag (include/covomix_hip.h).  One flag read per call (the only host synchronisation of

@@ -3,6 +3,8 @@
 //   cvx_dwconv31_gelu_res_f32   ConvPositionEmbed + residual    (acoustic.py:141-161, :508)
 //   cvx_cfg_combine_axpy_f32    CFG combine + ODE stage update  (acoustic.py:428; torchdiffeq midpoint)
 //   cvx_rk_stage_f32            CFG combine + one explicit Runge-Kutta stage, per-row guidance scale
+//   cvx_rk_stage_err_f32        the last stage of a step + the embedded error estimate's sums per chunk of a sequence
+//   cvx_rk_err_finish_f32       chunk sums -> one (sum delta^2, sum o^2) per (step, sequence)
 //   cvx_embed_gather_f32        step-invariant to_embed columns (acoustic.py:473-503)
 //   cvx_time_fourier_f32        LearnedSinusoidalPosEmb         (acoustic.py:107-111)
 //   cvx_wav_to_int16            mel_decode_to_wav tail          (monologue_generation.py:55-57)
@@ -412,8 +414,9 @@ __device__ __forceinline__ float rk_cfg_combine(float v, float f, float s)
     return a - b;
 }
 
-template <int V>
-__device__ __forceinline__ void rk_stage_elems(const RkStage& a, int64_t i0)
+// KEEP (the error-estimate kernel): vo receives the combined field of the V elements from i0, then their new state (what `out` receives)
+template <int V, bool KEEP = false>
+__device__ __forceinline__ void rk_stage_elems(const RkStage& a, int64_t i0, float* vo = nullptr)
 {
     float v[V], o[V];
     if constexpr (V == 4) {
@@ -476,6 +479,10 @@ __device__ __forceinline__ void rk_stage_elems(const RkStage& a, int64_t i0)
         if (a.out2) a.out2[i0] = o[0];
         if (a.out3) a.out3[i0] = o[0];
     }
+    if constexpr (KEEP) {
+#pragma unroll
+        for (int e = 0; e < V; ++e) { vo[e] = v[e]; vo[V + e] = o[e]; }
+    }
 }
 
 // V = 4: every base pointer is 16-byte aligned - one float4 per lane, the last n % 4 elements one at a time; V = 1 otherwise
@@ -486,6 +493,84 @@ __global__ __launch_bounds__(256) void rk_stage_kernel(const RkStage a)
     if (i0 >= a.n) return;
     if (V == 1 || i0 + V <= a.n) { rk_stage_elems<V>(a, i0); return; }
     for (int64_t i = i0; i < a.n; ++i) rk_stage_elems<1>(a, i);
+}
+
+// ---------------------------------------------------------------- the last stage of a step + the embedded error estimate
+// rk_stage_elems on a block's chunk of rows, plus per element delta = sum_j k_j we_j (stored stages first, in j order, then this
+// launch's v; a zero weight is neither read nor added; the first term is fma(k, we, 0) = the rounded product) and the two sums
+// of squares.  A block owns one chunk of at most CVX_RK_ERR_ROWS consecutive rows of ONE sequence, counted from that sequence's
+// first row: thread t takes the chunk's elements (t + 256 i) V ... in i order, so what a thread adds, and in which order, depends on
+// the chunk's own rows only - not on where the sequence lies in the batch.  Lane sums (wave_sum), then the four waves in wave order
+// through LDS: one fixed tree, no atomics.
+struct RkErr {
+    const float* e0; const float* e1; const float* e2;
+    float we0, we1, we2, wev;
+    const int32_t* map;          // per block: first row, rows, sequence
+    float2* partials;            // per block: (sum delta^2, sum o^2)
+};
+
+template <int V>
+__device__ __forceinline__ void rk_err_elems(const RkStage& a, const RkErr& e, int64_t i0, float& sd, float& so)
+{
+    float vo[2 * V], d[V];
+    rk_stage_elems<V, true>(a, i0, vo);
+    const float *v = vo, *o = vo + V;
+#pragma unroll
+    for (int l = 0; l < V; ++l) d[l] = 0.f;
+#define RK_ERR_STAGE(K, W)                                                              \
+    if ((W) != 0.f) {                                                                   \
+        if constexpr (V == 4) {                                                         \
+            const float4 t = *reinterpret_cast<const float4*>((K) + i0);                \
+            d[0] = __builtin_fmaf(t.x, (W), d[0]); d[1] = __builtin_fmaf(t.y, (W), d[1]);   \
+            d[2] = __builtin_fmaf(t.z, (W), d[2]); d[3] = __builtin_fmaf(t.w, (W), d[3]);   \
+        } else d[0] = __builtin_fmaf((K)[i0], (W), d[0]);                               \
+    }
+    RK_ERR_STAGE(e.e0, e.we0)
+    RK_ERR_STAGE(e.e1, e.we1)
+    RK_ERR_STAGE(e.e2, e.we2)
+#undef RK_ERR_STAGE
+    if (e.wev != 0.f) {
+#pragma unroll
+        for (int l = 0; l < V; ++l) d[l] = __builtin_fmaf(v[l], e.wev, d[l]);
+    }
+#pragma unroll
+    for (int l = 0; l < V; ++l) {
+        sd = __builtin_fmaf(d[l], d[l], sd);
+        so = __builtin_fmaf(o[l], o[l], so);
+    }
+}
+
+// V = 4: every base pointer is 16-byte aligned and dim % 4 == 0 (every chunk then starts and ends on a float4); V = 1 otherwise
+template <int V>
+__global__ __launch_bounds__(256) void rk_err_stage_kernel(const RkStage a, const RkErr e)
+{
+    __shared__ float red[8];
+    const int32_t* mp = e.map + 3 * (int64_t)blockIdx.x;
+    const int64_t base = (int64_t)mp[0] * a.dim;
+    const int64_t cnt = (base >= 0 && base < a.n) ? ((int64_t)mp[1] * a.dim < a.n - base ? (int64_t)mp[1] * a.dim : a.n - base) : 0;   // (never past the launch's rows)
+    float sd = 0.f, so = 0.f;
+    for (int64_t i = (int64_t)threadIdx.x * V; i < cnt; i += 256 * V) rk_err_elems<V>(a, e, base + i, sd, so);
+    sd = wave_sum(sd);
+    so = wave_sum(so);
+    const int wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) { red[wave] = sd; red[4 + wave] = so; }
+    __syncthreads();
+    if (threadIdx.x == 0)
+        e.partials[blockIdx.x] = make_float2(((red[0] + red[1]) + red[2]) + red[3], ((red[4] + red[5]) + red[6]) + red[7]);
+}
+
+// one thread per (step, sequence): the chunk sums of the blocks the map gives to that sequence, in block order
+__global__ __launch_bounds__(256) void rk_err_finish_kernel(const float2* __restrict__ partials, const int32_t* __restrict__ map,
+                                                            float2* __restrict__ err, int steps, int n_seq, int blocks)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= steps * n_seq) return;
+    const int step = i / n_seq, q = i - step * n_seq;
+    const float2* p = partials + (int64_t)step * blocks;
+    float sd = 0.f, so = 0.f;
+    for (int b = 0; b < blocks; ++b)
+        if (map[3 * b + 2] == q) { sd += p[b].x; so += p[b].y; }
+    err[i] = make_float2(sd, so);
 }
 
 // ---------------------------------------------------------------- embedding gather
@@ -761,16 +846,16 @@ extern "C" int cvx_cfg_combine_axpy_f32(const float* f_c, const float* f_n, cons
     return CVX_OK;
 }
 
-extern "C" int cvx_rk_stage_f32(const float* f_c, const float* f_n, const float* y, float cond_scale, const float* row_scale,
-                                const float* const* k_prev, const float* w, int32_t m, float* k_out, float* out, float* out2,
-                                float* out3, int64_t rows, int32_t dim, cvx_stream_t s)
+// the argument checks of both stage entry points; *vec: every pointer of the launch is 16-byte aligned
+static int rk_stage_args(RkStage& a, bool* vec, const float* f_c, const float* f_n, const float* y, float cond_scale, const float* row_scale,
+                         const float* const* k_prev, const float* w, int32_t m, float* k_out, float* out, float* out2, float* out3,
+                         int64_t rows, int32_t dim)
 {
     CVX_REQUIRE(f_c && y && out && w, "rk_stage: f_c, y, out and w must not be null");
     CVX_REQUIRE(m >= 0 && m <= 3, "rk_stage: at most 3 stored stages (m=%d)", m);
     CVX_REQUIRE(rows >= 0 && dim > 0, "rk_stage: bad shape (rows=%lld dim=%d)", (long long)rows, dim);
     CVX_REQUIRE(!row_scale || f_n, "rk_stage: row_scale without f_n");
     CVX_REQUIRE(m == 0 || k_prev, "rk_stage: k_prev is null");
-    RkStage a = {};
     const float* k[3] = {nullptr, nullptr, nullptr};
     float wk[3] = {0.f, 0.f, 0.f};
     for (int j = 0; j < m; ++j) {
@@ -783,16 +868,86 @@ extern "C" int cvx_rk_stage_f32(const float* f_c, const float* f_n, const float*
     a.wk0 = wk[0]; a.wk1 = wk[1]; a.wk2 = wk[2]; a.wv = w[m]; a.s = cond_scale;
     a.k_out = k_out; a.out = out; a.out2 = out2; a.out3 = out3;
     a.n = rows * dim; a.dim = dim;
-    if (a.n == 0) return CVX_OK;
     uintptr_t bits = (uintptr_t)f_c | (uintptr_t)f_n | (uintptr_t)y | (uintptr_t)k[0] | (uintptr_t)k[1] | (uintptr_t)k[2] |
                      (uintptr_t)k_out | (uintptr_t)out | (uintptr_t)out2 | (uintptr_t)out3;
-    const bool vec = (bits & 15) == 0;
+    *vec = (bits & 15) == 0;
+    return CVX_OK;
+}
+
+extern "C" int cvx_rk_stage_f32(const float* f_c, const float* f_n, const float* y, float cond_scale, const float* row_scale,
+                                const float* const* k_prev, const float* w, int32_t m, float* k_out, float* out, float* out2,
+                                float* out3, int64_t rows, int32_t dim, cvx_stream_t s)
+{
+    RkStage a = {};
+    bool vec = false;
+    const int rc = rk_stage_args(a, &vec, f_c, f_n, y, cond_scale, row_scale, k_prev, w, m, k_out, out, out2, out3, rows, dim);
+    if (rc != CVX_OK) return rc;
+    if (a.n == 0) return CVX_OK;
     const int64_t threads = vec ? (a.n + 3) / 4 : a.n;
     const int64_t blocks = (threads + 255) / 256;
     CVX_REQUIRE(blocks <= 0x7fffffffLL, "rk_stage: rows x dim too large for one launch");
     if (vec) hipLaunchKernelGGL(rk_stage_kernel<4>, dim3((unsigned)blocks), dim3(256), 0, cvx_hip_stream(s), a);
     else hipLaunchKernelGGL(rk_stage_kernel<1>, dim3((unsigned)blocks), dim3(256), 0, cvx_hip_stream(s), a);
     CVX_CHECK_LAUNCH("cvx_rk_stage_f32");
+    return CVX_OK;
+}
+
+extern "C" int cvx_rk_stage_err_f32(const float* f_c, const float* f_n, const float* y, float cond_scale, const float* row_scale,
+                                    const float* const* k_prev, const float* w, const float* we, int32_t m, float* k_out, float* out,
+                                    float* out2, float* out3, int64_t rows, int32_t dim, const int32_t* map_dev, const int32_t* map_host,
+                                    int32_t blocks, float* partials, cvx_stream_t s)
+{
+    RkStage a = {};
+    bool vec = false;
+    const int rc = rk_stage_args(a, &vec, f_c, f_n, y, cond_scale, row_scale, k_prev, w, m, k_out, out, out2, out3, rows, dim);
+    if (rc != CVX_OK) return rc;
+    CVX_REQUIRE(we && map_dev && map_host && partials, "rk_stage_err: we, the map (device and host copy) and partials must not be null");
+    CVX_REQUIRE(((uintptr_t)map_dev & 3) == 0 && ((uintptr_t)partials & 7) == 0, "rk_stage_err: map 4-byte, partials 8-byte aligned");
+    CVX_REQUIRE(blocks >= 0 && rows <= 0x7fffffffLL, "rk_stage_err: bad block count %d / rows beyond int32", blocks);
+    RkErr e = {};
+    const float* k[3] = {nullptr, nullptr, nullptr};
+    float wk[3] = {0.f, 0.f, 0.f};
+    for (int j = 0; j < m; ++j) {
+        CVX_REQUIRE(k_prev[j] || we[j] == 0.f, "rk_stage_err: k_prev[%d] is null and its error weight is not 0", j);
+        if (we[j] != 0.f) { k[j] = k_prev[j]; wk[j] = we[j]; }
+    }
+    // the chunks must tile [0, rows) in order, each 1 .. CVX_RK_ERR_ROWS rows of one sequence, sequences in ascending order; a chunk
+    // shorter than CVX_RK_ERR_ROWS ends its sequence (chunks are counted from a sequence's first row)
+    int64_t next = 0;
+    for (int b = 0; b < blocks; ++b) {
+        const int32_t r0 = map_host[3 * b], nr = map_host[3 * b + 1], q = map_host[3 * b + 2];
+        CVX_REQUIRE(r0 == next && nr >= 1 && nr <= CVX_RK_ERR_ROWS && q >= 0, "rk_stage_err: map entry %d (first row %d, rows %d, sequence %d) "
+                    "does not continue at row %lld with 1..%d rows", b, r0, nr, q, (long long)next, CVX_RK_ERR_ROWS);
+        if (b > 0) {
+            const int32_t pq = map_host[3 * b - 1], pn = map_host[3 * b - 2];
+            CVX_REQUIRE(q == pq ? pn == CVX_RK_ERR_ROWS : q > pq, "rk_stage_err: map entry %d: sequence %d after %d (a short chunk ends its sequence)", b, q, pq);
+        }
+        next += nr;
+    }
+    CVX_REQUIRE(next == rows, "rk_stage_err: the map covers %lld rows, the launch has %lld", (long long)next, (long long)rows);
+    if (a.n == 0) return CVX_OK;
+    e.e0 = k[0]; e.e1 = k[1]; e.e2 = k[2];
+    e.we0 = wk[0]; e.we1 = wk[1]; e.we2 = wk[2]; e.wev = we[m];
+    e.map = map_dev; e.partials = reinterpret_cast<float2*>(partials);
+    vec = vec && (((uintptr_t)k[0] | (uintptr_t)k[1] | (uintptr_t)k[2]) & 15) == 0 && dim % 4 == 0;
+    if (vec) hipLaunchKernelGGL(rk_err_stage_kernel<4>, dim3((unsigned)blocks), dim3(256), 0, cvx_hip_stream(s), a, e);
+    else hipLaunchKernelGGL(rk_err_stage_kernel<1>, dim3((unsigned)blocks), dim3(256), 0, cvx_hip_stream(s), a, e);
+    CVX_CHECK_LAUNCH("cvx_rk_stage_err_f32");
+    return CVX_OK;
+}
+
+extern "C" int cvx_rk_err_finish_f32(const float* partials, const int32_t* map_dev, int32_t blocks, int32_t steps, int32_t n_seq, float* err,
+                                     cvx_stream_t s)
+{
+    CVX_REQUIRE(partials && map_dev && err, "rk_err_finish: partials, map and err must not be null");
+    CVX_REQUIRE(((uintptr_t)partials & 7) == 0 && ((uintptr_t)err & 7) == 0 && ((uintptr_t)map_dev & 3) == 0, "rk_err_finish: 8-byte aligned partials and err");
+    CVX_REQUIRE(blocks >= 0 && steps >= 0 && n_seq >= 0 && (int64_t)steps * n_seq <= 0x7fffffffLL && (int64_t)steps * blocks <= 0x7fffffffLL,
+                "rk_err_finish: bad sizes (blocks=%d steps=%d sequences=%d)", blocks, steps, n_seq);
+    const int64_t n = (int64_t)steps * n_seq;
+    if (n == 0) return CVX_OK;
+    hipLaunchKernelGGL(rk_err_finish_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, cvx_hip_stream(s),
+                       reinterpret_cast<const float2*>(partials), map_dev, reinterpret_cast<float2*>(err), steps, n_seq, blocks);
+    CVX_CHECK_LAUNCH("cvx_rk_err_finish_f32");
     return CVX_OK;
 }
 

@@ -37,7 +37,7 @@ import numpy as np
 import torch
 
 from . import assembly, dp
-from .acoustic import evaluation_times
+from .acoustic import evaluation_times, resolve_grid, resolve_method
 from .conditional_model import CoVoMixModel
 from .vocoder import AttrDict, Generator
 
@@ -75,6 +75,12 @@ def build_parser() -> ArgumentParser:
     p.add_argument("--ode_method", type=str, default="midpoint", help="extension: the fixed-grid solver (the reference's "
                    "torchdiffeq_ode_method, acoustic.py:560-591): euler, midpoint, heun2, heun3, rk4 (torchdiffeq's 3/8 rule) or rk4_classic; "
                    "--nfe must be a multiple of its stages (1, 2, 2, 3, 4, 4)")
+    p.add_argument("--ode_grid", type=str, default="uniform", help="extension: the time grid of the solve - uniform (the reference's), "
+                   "cosine, sway:<s> (-1 <= s <= 1.75: s < 0 steps finely first), or the path of a JSON list of nfe / stages + 1 points as "
+                   "tools/fit_time_grid.py writes it")
+    p.add_argument("--ode_error_json", type=str, default=None, help="extension: also measure the method's embedded error estimate and "
+                   "write, per utterance, the grid and the delta_rms / state_rms tables per step (acoustic.SolveError) to this file; the "
+                   "audio is the same bit for bit (ranks other than 0 append .rank<r>)")
     p.add_argument("--t2s_temperature", type=float, default=None, help="extension: sampling temperature of the text2semantic decode "
                    "(default: the reference's 1.0)")
     p.add_argument("--t2s_cond_scale", type=float, default=None, help="extension: classifier-free guidance of the text2semantic decode "
@@ -431,6 +437,19 @@ def utterance_plan(text_dir: str, dialogue: bool, mode: str, have_t2s: bool, wor
     return names, sources, plan
 
 
+def ode_grid_argument(spec: str):
+    """--ode_grid: a grid's name as it is, the JSON list of a file otherwise"""
+    if spec in ("uniform", "cosine") or spec.startswith("sway:"):
+        return spec
+    if not os.path.isfile(spec):
+        raise ValueError(f"--ode_grid {spec!r}: neither uniform, cosine, sway:<s> nor a file")
+    with open(spec) as f:
+        pts = json.load(f)
+    if not isinstance(pts, list):
+        raise ValueError(f"--ode_grid {spec!r}: the file must hold one JSON list of grid points")
+    return tuple(pts)
+
+
 def run(dialogue: bool, argv=None) -> int:
     import time
     from scipy.io.wavfile import write
@@ -438,6 +457,9 @@ def run(dialogue: bool, argv=None) -> int:
     import sys
     args = build_parser().parse_args(argv)
     evaluation_times(int(args.nfe), args.ode_method)              # (ValueError before anything loads: unknown method, nfe no multiple of its stages)
+    ode_grid = resolve_grid(ode_grid_argument(args.ode_grid), int(args.nfe), args.ode_method) or "uniform"
+    if args.ode_error_json and resolve_method(args.ode_method).b_err is None:
+        raise ValueError(f"--ode_error_json: --ode_method {args.ode_method} has no embedded error estimate")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:          # spawn our own ranks (hifi-gan/train.py:268-278 does the same)
         rc = dp.launch_ranks(os.path.abspath(sys.argv[0]), list(sys.argv[1:] if argv is None else argv), args.gpus)
         if rc:
@@ -470,6 +492,8 @@ def run(dialogue: bool, argv=None) -> int:
     model.eval()
     model = model.to(device)
     model.nfe, model.ode_method = int(args.nfe), args.ode_method
+    model.ode_grid, model.ode_error = ode_grid, bool(args.ode_error_json)
+    solve_errors: dict = {}                  # --ode_error_json: utterance -> segment -> tables
     t2s_kw = t2s_sampling_kwargs(args)
     if rank == 0:
         with open(os.path.join(args.saved_dir, "config.txt"), "w") as f:
@@ -527,6 +551,11 @@ def run(dialogue: bool, argv=None) -> int:
         else:
             sampled = model.synthesis_sample(phoneme_ids=[up(it[0]) for it in its], cond=[up(it[1]) for it in its],
                                              mask=[it[2] for it in its], cond_scale=COND_SCALE, y0=y0)
+        if model.ode_error:                   # (one column per utterance of the batch, in the batch's order)
+            se = model.last_solve_error
+            for j, (_, (n, seg)) in enumerate(batch):
+                solve_errors.setdefault(n, {})[seg] = dict(grid=list(se.grid), method=str(args.ode_method), order=se.order,
+                                                           delta_rms=se.delta_rms[:, j].tolist(), state_rms=se.state_rms[:, j].tolist())
         # vocoder: the generated frames of every utterance of the batch (:299-300: mask is a suffix) go through HiFi-GAN in
         # ONE ragged call (zero-padded to the longest, per-item lengths: every item gets its B = 1 waveform); one int16 cast
         # and one device-to-host copy per batch, sliced per utterance on the host
@@ -680,6 +709,9 @@ def run(dialogue: bool, argv=None) -> int:
         write(out, 8000, audio)
         print("Saved wavfile", out)
         done += 1
+    if args.ode_error_json:
+        with open(args.ode_error_json + (f".rank{rank}" if rank else ""), "w") as f:
+            json.dump({n: [segs[k] for k in sorted(segs)] for n, segs in sorted(solve_errors.items())}, f, indent=1)
     print(f"rank {rank}: {done} utterances, {frames} generated frames in {elapsed:.3f} s ({frames / max(elapsed, 1e-9):.1f} frames/s, "
           f"{'text2semantic + ' if mode != 'off' else ''}sampling + vocoder, excluding model load; --pipeline {mode})")
     run.last_stats = dict(utterances=done, frames=frames, seconds=elapsed, pipeline=mode, load_seconds=load_s, batches=batch_log,

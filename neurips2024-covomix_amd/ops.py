@@ -7,7 +7,7 @@ import os as _os
 import functools
 import threading
 from contextlib import contextmanager
-from typing import Optional
+from typing import Optional, Sequence
 
 import torch
 
@@ -890,10 +890,8 @@ def cfg_combine_axpy(f_c, f_n, y, cond_scale: float, coef: float, out, out2=None
                "cvx_cfg_combine_axpy_f32")
 
 
-def rk_stage(f_c, f_n, y, cond_scale: float, weights, out, *, k_prev=(), k_out=None, row_scale=None, out2=None, out3=None) -> None:
-    """CFG combine + one stage of an explicit Runge-Kutta step (cvx_rk_stage_f32): out = y + sum_j k_prev[j] * weights[j] + v * weights[m],
-    v = the combined field (also written to k_out when given).  f_c, y, out ... [rows, dim]; weights: m + 1 floats for the m = len(k_prev)
-    stored stages and this one (a stage whose weight is 0 may be None); row_scale [rows]: one guidance scale per row."""
+def _rk_stage_args(f_c, f_n, y, weights, out, k_prev, k_out, row_scale, out2, out3):
+    """the checks both stage kernels share -> (rows, dim, m, host array of the stage pointers, host array of the weights)"""
     _chk_f32(f_c, f_n, y, out, out2, out3, k_out, row_scale, *k_prev)
     n, m = y.numel(), len(k_prev)
     dim = y.shape[-1]
@@ -904,8 +902,63 @@ def rk_stage(f_c, f_n, y, cond_scale: float, weights, out, *, k_prev=(), k_out=N
         assert t is None or (t.is_contiguous() and t.numel() == n)
     kp = (C.c_void_p * max(m, 1))(*[_p(t) for t in k_prev])
     w = (C.c_float * (m + 1))(*[float(x) for x in weights])
+    return rows, dim, m, kp, w
+
+
+def rk_stage(f_c, f_n, y, cond_scale: float, weights, out, *, k_prev=(), k_out=None, row_scale=None, out2=None, out3=None) -> None:
+    """CFG combine + one stage of an explicit Runge-Kutta step (cvx_rk_stage_f32): out = y + sum_j k_prev[j] * weights[j] + v * weights[m],
+    v = the combined field (also written to k_out when given).  f_c, y, out ... [rows, dim]; weights: m + 1 floats for the m = len(k_prev)
+    stored stages and this one (a stage whose weight is 0 may be None); row_scale [rows]: one guidance scale per row."""
+    rows, dim, m, kp, w = _rk_stage_args(f_c, f_n, y, weights, out, k_prev, k_out, row_scale, out2, out3)
     _lib.check(_lib.load().cvx_rk_stage_f32(f_c.data_ptr(), _p(f_n), y.data_ptr(), cond_scale, _p(row_scale), kp, w, m, _p(k_out),
                                             out.data_ptr(), _p(out2), _p(out3), rows, dim, _stream()), "cvx_rk_stage_f32")
+
+
+RK_ERR_ROWS = 32          # CVX_RK_ERR_ROWS of include/covomix_hip.h: rows of one sequence a block of the error-estimate stage owns
+
+
+class RkErrMap:
+    """The block -> (first row, rows, sequence) table of cvx_rk_stage_err_f32 for sequences of the given lengths packed back to back:
+    every sequence is cut into chunks of RK_ERR_ROWS rows counted from its own first row (the last one short).  int32 on the host
+    (the library checks it against the launch's rows) and on the device (the kernels read it)."""
+
+    def __init__(self, lengths: Sequence[int], device):
+        ent = []
+        r0 = 0
+        for q, L in enumerate(lengths):
+            L = int(L)
+            if L < 1:
+                raise ValueError(f"sequence {q} has {L} rows")
+            for c in range(0, L, RK_ERR_ROWS):
+                ent.append((r0 + c, min(RK_ERR_ROWS, L - c), q))
+            r0 += L
+        self.rows, self.n_seq, self.blocks = r0, len(lengths), len(ent)
+        self.host = torch.tensor(ent, dtype=torch.int32).reshape(-1, 3).contiguous()
+        self.dev = h2d(self.host, device)
+
+
+def rk_stage_err(f_c, f_n, y, cond_scale: float, weights, err_weights, out, emap: RkErrMap, partials, *, k_prev=(), k_out=None,
+                 row_scale=None, out2=None, out3=None) -> None:
+    """rk_stage for the last stage of a step, plus the embedded error estimate (cvx_rk_stage_err_f32): per block of `emap` the sums of
+    delta^2 and out^2 over its chunk into partials [blocks, 2], delta = sum_j k_prev[j] * err_weights[j] + v * err_weights[m].  A stage
+    may be None only when both of its weights are 0."""
+    rows, dim, m, kp, w = _rk_stage_args(f_c, f_n, y, weights, out, k_prev, k_out, row_scale, out2, out3)
+    _chk_f32(partials)
+    assert len(err_weights) == m + 1 and partials.is_contiguous() and partials.numel() == 2 * emap.blocks and emap.dev.device == y.device
+    we = (C.c_float * (m + 1))(*[float(x) for x in err_weights])
+    _lib.check(_lib.load().cvx_rk_stage_err_f32(f_c.data_ptr(), _p(f_n), y.data_ptr(), cond_scale, _p(row_scale), kp, w, we, m, _p(k_out),
+                                                out.data_ptr(), _p(out2), _p(out3), rows, dim, emap.dev.data_ptr(), emap.host.data_ptr(),
+                                                emap.blocks, partials.data_ptr(), _stream()), "cvx_rk_stage_err_f32")
+
+
+def rk_err_finish(partials, emap: RkErrMap, err) -> None:
+    """err [steps, sequences, 2] = per (step, sequence) the chunk sums of partials [steps, blocks, 2] in chunk order (cvx_rk_err_finish_f32)"""
+    _chk_f32(partials, err)
+    steps = err.shape[0]
+    assert partials.is_contiguous() and err.is_contiguous() and tuple(err.shape) == (steps, emap.n_seq, 2)
+    assert tuple(partials.shape) == (steps, emap.blocks, 2)
+    _lib.check(_lib.load().cvx_rk_err_finish_f32(partials.data_ptr(), emap.dev.data_ptr(), emap.blocks, steps, emap.n_seq, err.data_ptr(),
+                                                 _stream()), "cvx_rk_err_finish_f32")
 
 
 def embed_gather(ids: Optional[torch.Tensor], streams: int, table: torch.Tensor, cond: Optional[torch.Tensor],

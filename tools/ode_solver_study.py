@@ -10,6 +10,13 @@ under each method and what truncation error it leaves.  A synthetic checkpoint s
   error [--frames 1000] [--ref-nfe 512]
         rel-L2 of the final mel of one utterance for every built-in method at 8 ... 64 evaluations, against the named midpoint path
         (the two-call path the parent has) at --ref-nfe evaluations.
+  cost  [--solves 5]
+        ms per solve at the bench shape with and without the embedded error estimate (return_error) for midpoint-32 and rk4-32: the
+        estimate adds one stored stage per step for midpoint, the partial sums and one finishing launch.
+  grids [--frames 1000] [--ref-nfe 512]
+        rel-L2 of the final mel of one utterance for midpoint, heun3 and rk4 at 16, 24 and 32 evaluations on the uniform grid, sway:-1,
+        cosine and the grid fitted from that method's own 64-step error estimate, against midpoint at --ref-nfe evaluations on the
+        uniform grid; the fitted grids are printed.  Synthetic weights: where THIS field is hard, nothing about audio quality.
 
 Every timed process is a fresh child of this one (which never touches the GPU), runs under a time limit, and a failure ends the run."""
 import argparse
@@ -34,14 +41,17 @@ def _model(pkg_root):
 
 
 def worker(pkg_root, settings, solves):
-    """one process: [(method, nfe)] -> ms per solve (host clock around a solve that ends in a device synchronise), after two warm-up solves"""
+    """one process: [(method, nfe[, estimate])] -> ms per solve (host clock around a solve that ends in a device synchronise), after two
+    warm-up solves"""
     torch, syn, model = _model(pkg_root)
     inp = syn.synthetic_inputs("vomix", 8, 1000, 400, seed=3)
     args = [inp["phoneme_ids"].cuda(), inp["cond"].cuda(), inp["mask"].cuda(), 0.7]
     y0 = inp["y0"].cuda()
     out = []
-    for method, nfe in settings:
+    for method, nfe, *flag in settings:
         model.ode_method, model.nfe = method, nfe
+        if flag:                             # (a checkout without the estimate is never asked for it)
+            model.ode_error = bool(flag[0])
         ms = []
         for i in range(2 + solves):
             torch.cuda.synchronize()
@@ -50,14 +60,14 @@ def worker(pkg_root, settings, solves):
             torch.cuda.synchronize()
             if i >= 2:
                 ms.append((time.perf_counter() - t0) * 1e3)
-        out.append(dict(method=method, nfe=nfe, ms=ms))
+        out.append(dict(method=method, nfe=nfe, ms=ms, estimate=bool(flag and flag[0])))
     import covomix_amd
     print("RESULT " + json.dumps(dict(package=os.path.dirname(os.path.abspath(covomix_amd.__file__)), runs=out)), flush=True)
 
 
 def _child(pkg_root, settings, solves):
     cmd = [sys.executable, os.path.abspath(__file__), "_worker", "--root", pkg_root, "--solves", str(solves),
-           "--settings", ",".join(f"{m}:{n}" for m, n in settings)]
+           "--settings", ",".join(":".join(str(x) for x in st) for st in settings)]
     r = subprocess.run(cmd, cwd=pkg_root, capture_output=True, text=True, timeout=600)
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("RESULT ")]
     if r.returncode != 0 or not lines:
@@ -123,9 +133,51 @@ def study_error(frames, ref_nfe):
         print(f"| {nfe} | " + " | ".join(cells) + " |", flush=True)
 
 
+def study_cost(solves):
+    res = _child(ROOT, [("midpoint", 32, 0), ("midpoint", 32, 1), ("rk4", 32, 0), ("rk4", 32, 1)], solves)
+    print(f"bench shape B = 8 x T = 1000, full-size synthetic VoMix, cond_scale 0.7; one process, {solves} solves per setting after 2 warm-up solves")
+    for plain, est in (res[0:2], res[2:4]):
+        (m0, lo0, hi0), (m1, lo1, hi1) = _stats(plain["ms"]), _stats(est["ms"])
+        print(f"{plain['method']:>8s}-{plain['nfe']}: median {m0:.2f} ms (min {lo0:.2f}, max {hi0:.2f}); with the error estimate {m1:.2f} ms "
+              f"(min {lo1:.2f}, max {hi1:.2f}): {m1 - m0:+.2f} ms ({(m1 / m0 - 1) * 100:+.2f} %)")
+
+
+def study_grids(frames, ref_nfe):
+    os.environ["CVX_GRAPH"] = "0"
+    torch, syn, model = _model(ROOT)
+    from covomix_amd.acoustic import TABLEAUS, fit_time_grid
+    inp = syn.synthetic_inputs("vomix", 1, frames, int(0.4 * frames), seed=3)
+    args = [inp["phoneme_ids"].cuda(), inp["cond"].cuda(), inp["mask"].cuda(), 0.7]
+    y0 = inp["y0"].cuda()
+
+    def solve(method, nfe, grid="uniform", estimate=False):
+        model.ode_method, model.nfe, model.ode_grid, model.ode_error = method, nfe, grid, estimate
+        return model.synthesis_sample(*args, y0=y0).double()
+    ref = solve("midpoint", ref_nfe)
+    print(f"one utterance of {frames} frames, full-size synthetic VoMix (precision {model.precision}), cond_scale 0.7; rel-L2 of the final mel against "
+          f"midpoint at {ref_nfe} evaluations on the uniform grid.  'fitted': fit_time_grid on the method's own 64-step uniform estimate.")
+    print("| method | evaluations | uniform | sway:-1 | cosine | fitted |")
+    print("|---|---|---|---|---|---|")
+    fitted = {}
+    for name in ("midpoint", "heun3", "rk4"):
+        n = TABLEAUS[name].stages
+        solve(name, 64 * n, estimate=True)
+        err = model.last_solve_error
+        print(f"# {name}: delta_rms of the 64-step solve, every 8th step: " + " ".join(f"{float(err.delta_rms[k, 0]):.2e}" for k in range(0, 64, 8)), flush=True)
+        for nfe in (16, 24, 32):
+            if nfe % n:
+                print(f"| {name} | {nfe} | - | - | - | - |")
+                continue
+            g = fitted[(name, nfe)] = fit_time_grid(err, nfe // n)
+            cells = [f"{float((solve(name, nfe, grid) - ref).norm() / ref.norm()):.2e}" for grid in ("uniform", "sway:-1", "cosine", g)]
+            print(f"| {name} | {nfe} | " + " | ".join(cells) + " |", flush=True)
+    for (name, nfe), g in fitted.items():
+        print(f"fitted grid {name}-{nfe}: " + " ".join(f"{t:.4f}" for t in g))
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("mode", choices=["time", "error", "_worker"])
+    ap.add_argument("mode", choices=["time", "error", "cost", "grids", "_worker"])
     ap.add_argument("--root", default=None)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--solves", type=int, default=5)
@@ -134,8 +186,12 @@ if __name__ == "__main__":
     ap.add_argument("--ref-nfe", type=int, default=512)
     a = ap.parse_args()
     if a.mode == "_worker":
-        worker(a.root or ROOT, [(m, int(n)) for m, n in (s.split(":") for s in a.settings.split(","))], a.solves)
+        worker(a.root or ROOT, [(st[0], *map(int, st[1:])) for st in (s.split(":") for s in a.settings.split(","))], a.solves)
     elif a.mode == "time":
         study_time(a.root and os.path.abspath(a.root), a.rounds, a.solves)
+    elif a.mode == "cost":
+        study_cost(a.solves)
+    elif a.mode == "grids":
+        study_grids(a.frames, a.ref_nfe)
     else:
         study_error(a.frames, a.ref_nfe)
