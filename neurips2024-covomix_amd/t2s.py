@@ -458,7 +458,7 @@ class TextToSemanticDecoder:
                 setattr(self._layers[i], name, L[name].data_ptr())
         self._graphs: Dict[tuple, torch.cuda.CUDAGraph] = {}
         self._cap = None                                   # capture stream of the decode graphs
-        self._stage = None                                 # staging copies of the state record (two in flight), _decode_chunks
+        self._stage = None                                 # staging copies of the state record (two in flight), _chunks
         self._ensure(8, 8, 0)
 
     @staticmethod
@@ -470,7 +470,7 @@ class TextToSemanticDecoder:
         """Decode buffers for `slots` decode slots (x, q, att, h, logits, slot records, the self-attention caches), `dialogues`
         utterances in flight or queued (context k/v, token rows, dialogue records) and `steps` uniform draws per dialogue.  They only
         grow; growing re-allocates (and drops the captured graphs, which hold the old addresses).  The uniform draws per dialogue
-        are rounded up to whole chunks of CHUNK steps: a lock-step decode (_decode_chunks) runs whole chunks, and its sampling kernel
+        are rounded up to whole chunks of CHUNK steps: a lock-step decode (_chunks) runs whole chunks, and its sampling kernel
         reads the draws of every position it reaches (up to the model's max_length, whatever the call's max_length).
         logprobs: the log-prob buffer [dialogues, streams, max_length] of the scored decode as well - allocated on first use only (only
         scored graphs hold its address, so allocating it leaves the captured graphs alone), and re-allocated with the token rows."""
@@ -578,36 +578,28 @@ class TextToSemanticDecoder:
             dec.queue, dec.dialogues, dec.start = b["queue"].data_ptr(), b["dialogues"].data_ptr(), self.start.data_ptr()
         return dec
 
-    def _launch_steps(self, temperature: float, batch: int, n: int, cfg_scale: float, queue: bool, filt, nd: int, scored: bool,
-                      per: bool = False, mixed: Optional[int] = None) -> None:
-        """n token steps on the current stream.  scored: cvx_t2s_decode_steps_scored (log-probs of every step's token into
+    def _run_steps(self, temperature: float, batch: int, n: int, cfg_scale: float = 1.0, queue: bool = False, filt=None, nd: int = 0,
+                   scored: bool = False, per: bool = False, mixed: Optional[int] = None) -> None:
+        """n token steps on the current stream without a graph.  scored: cvx_t2s_decode_steps_scored (log-probs of every step's token into
         buf["logprobs"], forced dialogues honoured); else cvx_t2s_decode_steps, exactly as before that entry existed.
         per: cvx_t2s_decode_steps_per_dialogue - the settings come from buf["per"], one row per dialogue record; temperature and filt
         are not looked at and cfg_scale only says whether the slots run in guided pairs.
         mixed (with per and queue): cvx_t2s_decode_steps_mixed with that many guided utterances among the nd records - the pair layout
         comes from the records; n = 0 runs its scheduler alone, which arms idle slots."""
-        dec = self._descriptor(temperature, batch, cfg_scale, queue, filt, nd)
-        if per:
-            sc = _lib.T2SScoring(C.sizeof(_lib.T2SScoring), self.max_length, self.buf["logprobs"].data_ptr()) if scored else None
-            pd = _lib.T2SPerDialogue(C.sizeof(_lib.T2SPerDialogue), self.buf["per"].shape[0], self.buf["per"].data_ptr())
-            if mixed is not None:
-                mx = _lib.T2SMixed(C.sizeof(_lib.T2SMixed), int(mixed))
-                _lib.check(_lib.load().cvx_t2s_decode_steps_mixed(C.byref(dec), C.byref(sc) if scored else None, C.byref(pd), C.byref(mx), n,
-                                                                  ops._stream()), "cvx_t2s_decode_steps_mixed")
-                return
-            _lib.check(_lib.load().cvx_t2s_decode_steps_per_dialogue(C.byref(dec), C.byref(sc) if scored else None, C.byref(pd), n, ops._stream()),
-                       "cvx_t2s_decode_steps_per_dialogue")
+        lib, dec = _lib.load(), self._descriptor(temperature, batch, cfg_scale, queue, filt, nd)
+        sc = C.byref(_lib.T2SScoring(C.sizeof(_lib.T2SScoring), self.max_length, self.buf["logprobs"].data_ptr())) if scored else None
+        if not per:
+            if scored:
+                _lib.check(lib.cvx_t2s_decode_steps_scored(C.byref(dec), sc, n, ops._stream()), "cvx_t2s_decode_steps_scored")
+            else:
+                _lib.check(lib.cvx_t2s_decode_steps(C.byref(dec), n, ops._stream()), "cvx_t2s_decode_steps")
             return
-        if not scored:
-            _lib.check(_lib.load().cvx_t2s_decode_steps(C.byref(dec), n, ops._stream()), "cvx_t2s_decode_steps")
+        pd = _lib.T2SPerDialogue(C.sizeof(_lib.T2SPerDialogue), self.buf["per"].shape[0], self.buf["per"].data_ptr())
+        if mixed is not None:
+            mx = _lib.T2SMixed(C.sizeof(_lib.T2SMixed), int(mixed))
+            _lib.check(lib.cvx_t2s_decode_steps_mixed(C.byref(dec), sc, C.byref(pd), C.byref(mx), n, ops._stream()), "cvx_t2s_decode_steps_mixed")
             return
-        sc = _lib.T2SScoring(C.sizeof(_lib.T2SScoring), self.max_length, self.buf["logprobs"].data_ptr())
-        _lib.check(_lib.load().cvx_t2s_decode_steps_scored(C.byref(dec), C.byref(sc), n, ops._stream()), "cvx_t2s_decode_steps_scored")
-
-    def _run_steps(self, temperature: float, batch: int, n: int, cfg_scale: float = 1.0, queue: bool = False, filt=None, nd: int = 0,
-                   scored: bool = False, per: bool = False, mixed: Optional[int] = None) -> None:
-        """n token steps on the current stream without a graph."""
-        self._launch_steps(temperature, batch, n, cfg_scale, queue, filt, nd, scored, per, mixed)
+        _lib.check(lib.cvx_t2s_decode_steps_per_dialogue(C.byref(dec), sc, C.byref(pd), n, ops._stream()), "cvx_t2s_decode_steps_per_dialogue")
 
     def _uniform_view(self, n: int) -> torch.Tensor:
         """[n, steps, streams, vocab] view of the uniform draws of the first n dialogues"""
@@ -656,30 +648,51 @@ class TextToSemanticDecoder:
         self._pin_ev[k].synchronize()
         return self._pin[k][:rows].tolist()
 
-    def _decode_chunks(self, temperature: float, nb: int, max_len: int, cfg_scale: float, watch, ignore_eos: bool = False, filt=None,
-                       scored: bool = False) -> list:
-        """Graph-replayed chunks of CHUNK token steps until every utterance slot in `watch` has sampled its eos (or max_len steps).
-        The host looks at the eos flags ONE CHUNK BEHIND the device: the slot records of chunk i are copied between the replays of
-        chunks i and i + 1 and read while chunk i + 1 runs - the decode chain never waits for a host round trip (nor for a host
+    def _chunks(self, replay, records, rows: int, done, cap: int):
+        """Chunks of CHUNK token steps - one `replay()` each - until `done(rows_list)` says so, at most `cap` of them.
+        The host looks at the device-side records ONE CHUNK BEHIND the device: records[:rows] of chunk i are copied between the replays of
+        chunks i and i + 1 and read (`done`) while chunk i + 1 runs - the decode chain never waits for a host round trip (nor for a host
         thread that is waiting for the interpreter lock while another thread drives the acoustic solve, pipeline.py); the price is
-        at most one chunk decoded past the last eos (masked afterwards like every token behind an eos).  Returns the final records."""
+        at most one chunk decoded past the last end (masked afterwards like every token behind an eos).  A loop that ends at the cap
+        hands the last chunk's records to `done` as well.  -> (chunks run, the last rows read)."""
         self._mirror_setup()
         via_helper = ops.is_partition_stream()
-        steps, i, pending = 0, 0, None
-        while steps < max_len:
-            self._run_chunk(temperature, nb, cfg_scale, False, filt, 0, scored)
-            steps += CHUNK
-            k = i & 1
-            self._mirror_push(k, self.buf["state"][:nb], via_helper)
-            if pending is not None:
-                st = self._mirror_pull(pending, nb)
-                if all(st[r][1] for r in watch) and not ignore_eos:
-                    break
-            pending = k
+        i, pulled, ended = 0, None, False
+        while i < cap and not ended:
+            replay()
+            self._mirror_push(i & 1, records[:rows], via_helper)
+            if i:
+                pulled = self._mirror_pull((i - 1) & 1, rows)
+                ended = done(pulled)
             i += 1
-        if pending is not None:
-            self._pin_ev[pending].synchronize()      # (the helper stream's last copy: the buffers are reused by the next call)
-        return self._read_state(nb)
+        if i and not ended:
+            pulled = self._mirror_pull((i - 1) & 1, rows)
+            done(pulled)
+        if i:
+            self._pin_ev[(i - 1) & 1].synchronize()  # (the last PUSHED buffer, read or not: the helper stream's last copy - the next call reuses the buffers)
+        return i, pulled
+
+    def _capture(self, key: tuple, launch, idle):
+        """The graph stored under `key`, captured on first use: `launch()` (CHUNK steps) runs once outside the capture (module load, kernel
+        attributes) and once inside it, both on the state `idle()` sets up, on which the steps do nothing."""
+        g = self._graphs.get(key)
+        if g is not None:
+            return g
+        idle()
+        launch()                                       # warm-up outside capture
+        cur = torch.cuda.current_stream()
+        if self._cap is None:
+            self._cap = torch.cuda.Stream(device=self.device)
+        ops.saturation_share(cur, self._cap)           # (the capture stream belongs to this call: flag and CU count of `cur`)
+        with ops.CAPTURE_GATE.exclusive():             # (no other entry point of the package syncs / copies meanwhile)
+            cur.synchronize()
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g, stream=self._cap, capture_error_mode="thread_local"):
+                launch()
+        if len(self._graphs) >= 8:
+            self._graphs.clear()
+        self._graphs[key] = g
+        return g
 
     def _graph(self, temperature: float, batch: int, cfg_scale: float = 1.0, queue: bool = False, filt=None, nd: int = 0, scored: bool = False,
                per: bool = False, mixed: Optional[int] = None):
@@ -697,29 +710,12 @@ class TextToSemanticDecoder:
             key = ("per", batch, cfg_scale > 1.0, ops.stream_cus(), queue, self._gen, bool(scored))
         if mixed is not None:
             key = ("mixed", batch, ops.stream_cus(), self._gen, bool(scored))
-        g = self._graphs.get(key)
-        if g is not None:
-            return g
 
-        def launch():
-            self._launch_steps(temperature, batch, CHUNK, cfg_scale, queue, filt, nd, scored, per, mixed)
-        self.buf["state"].copy_(self._slot_records([]))
-        if mixed is not None:                          # (the scheduler of the warm-up steps must find nothing to hand out)
-            self.buf["queue"].zero_()
-        launch()                                       # warm-up outside capture
-        cur = torch.cuda.current_stream()
-        if self._cap is None:
-            self._cap = torch.cuda.Stream(device=self.device)
-        ops.saturation_share(cur, self._cap)           # (the capture stream belongs to this call: flag and CU count of `cur`)
-        with ops.CAPTURE_GATE.exclusive():             # (no other entry point of the package syncs / copies meanwhile)
-            cur.synchronize()
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, stream=self._cap, capture_error_mode="thread_local"):
-                launch()
-        if len(self._graphs) >= 8:
-            self._graphs.clear()
-        self._graphs[key] = g
-        return g
+        def idle():
+            self.buf["state"].copy_(self._slot_records([]))
+            if mixed is not None:                      # (the scheduler of the warm-up steps must find nothing to hand out)
+                self.buf["queue"].zero_()
+        return self._capture(key, lambda: self._run_steps(temperature, batch, CHUNK, cfg_scale, queue, filt, nd, scored, per, mixed), idle)
 
     def _run_chunk(self, temperature: float, batch: int = 1, cfg_scale: float = 1.0, queue: bool = False, filt=None, nd: int = 0,
                    scored: bool = False, per: bool = False, mixed: Optional[int] = None) -> None:
@@ -748,14 +744,28 @@ class TextToSemanticDecoder:
             flat.index_copy_(0, first, L["null"][None, :].expand(n, -1))
         return [t + 1 for t in rg.lengths]
 
-    def _cut(self, j: int, length: int, logits=None, logprobs: bool = False):
-        """(flat tokens, streams[, logits][, logprobs]) of dialogue row j after `length` steps: mask_after_eos (text2semantic.py:73-76)"""
-        eos = self.d["vocab"] - 1
-        streams = self.buf["tokens"][j, :, :length].clone()
-        after = (streams == eos).cumsum(dim=-1) > 0
+    def _guided_contexts(self, sources) -> list:
+        """`_contexts` for guided utterances, a pair of dialogue rows each: the context of utterance u into row 2u, and into row 2u + 1 the
+        null key / value row only = every context key masked out.  -> context rows per dialogue row, [c0, 1, c1, 1, ...]"""
+        n, ctx = len(sources), []
+        for c in self._contexts(sources, range(0, 2 * n, 2)):
+            ctx += [c, 1]
+        for L in self.dec:
+            L["kv_c"][1:2 * n:2, 0].copy_(L["null"][None, :].expand(n, -1))
+        return ctx
+
+    def _mask_after_eos(self, streams: torch.Tensor):
+        """(flat tokens, streams) of the token rows [S, length] of one utterance: a copy of the rows, and their tokens stream after stream
+        without what lies behind a stream's first eos - mask_after_eos (text2semantic.py:73-76)"""
+        streams = streams.clone()
+        after = (streams == self.d["vocab"] - 1).cumsum(dim=-1) > 0
         after = torch.nn.functional.pad(after, (1, -1), value=False)
         flat = streams.masked_fill(after, PAD_ID).reshape(-1)
-        item = (flat[flat != PAD_ID], streams)
+        return flat[flat != PAD_ID], streams
+
+    def _cut(self, j: int, length: int, logits=None, logprobs: bool = False):
+        """(flat tokens, streams[, logits][, logprobs]) of dialogue row j after `length` steps"""
+        item = self._mask_after_eos(self.buf["tokens"][j, :, :length])
         if logits is not None:
             item += (logits[:length],)
         if logprobs:
@@ -782,33 +792,32 @@ class TextToSemanticDecoder:
         return_logprobs: every result gains, as its LAST entry, a float32 [S, length] tensor aligned with `streams`: the log-probability
         the model gave each sampled token - log_softmax of the row the filter sees (the guidance-combined logits under cond_scale > 1),
         before the filter, the temperature and the noise (include/covomix_hip.h).  Off (the default) nothing changes."""
-        d, b = self.d, self.buf
-        S, V = d["streams"], d["vocab"]
+        S, V = self.d["streams"], self.d["vocab"]
         filt = filter_setting(filter_logits_fn, filter_fn_kwargs, V)
-        cfg = float(cond_scale) > 1.0
-        if cfg:
-            if S != 1:
-                raise NotImplementedError("guidance (cond_scale > 1) on a two-output model: the reference feeds the full-width hidden "
-                                          "state to the half-width logit head there (text2semantic.py:783-785) and cannot run")
-            return self._generate_guided(sources, uniforms, max_length, temperature, generator, collect_logits, float(cond_scale),
-                                         ignore_eos, filt, return_logprobs)
-        nb = len(sources)
-        if not 1 <= nb <= MAX_BATCH:
-            raise ValueError(f"1..{MAX_BATCH} utterances per decode batch, got {nb}")
+        guided = float(cond_scale) > 1.0
+        if guided and S != 1:
+            raise NotImplementedError("guidance (cond_scale > 1) on a two-output model: the reference feeds the full-width hidden "
+                                      "state to the half-width logit head there (text2semantic.py:783-785) and cannot run")
+        P = 2 if guided else 1    # decode slots (and dialogue rows) per utterance: utterance u decodes in slot P u, its null context in P u + 1
+        scale = float(cond_scale) if guided else 1.0
+        n = len(sources)
+        if not 1 <= n <= MAX_BATCH // P:
+            raise ValueError(f"1..{MAX_BATCH // P} utterances per {'guided ' if guided else ''}decode batch, got {n}")
+        nb = P * n
         max_len = min(int(max_length or self.max_length), self.max_length)
         us = None
         if uniforms is not None:
             us = [u.to(self.device, torch.float32).reshape(u.shape[0], S, V) for u in uniforms]
             max_len = min([max_len] + [u.shape[0] for u in us])
-        scored = bool(return_logprobs)
+        scored, temperature = bool(return_logprobs), float(temperature)
         self._ensure(nb, nb, max_len, scored)
         b = self.buf
         if not collect_logits and max_len > 0:
-            self._graph(float(temperature), nb, 1.0, False, filt, 0, scored)
-        ctx = self._contexts(sources)
-        uview = self._uniform_view(nb)
+            self._graph(temperature, nb, scale, False, filt, 0, scored)
+        ctx = self._guided_contexts(sources) if guided else self._contexts(sources)
+        uview = self._uniform_view(nb)[0::P]
         if us is None:            # (drawn step-major, as the [steps, batch, streams, vocab] buffer of earlier versions was: same seeds, same tokens)
-            uview[:, :max_len].copy_(torch.rand(max_len, nb, S, V, device=self.device, generator=generator).permute(1, 0, 2, 3))
+            uview[:, :max_len].copy_(torch.rand(max_len, n, S, V, device=self.device, generator=generator).permute(1, 0, 2, 3))
         else:
             for i, u in enumerate(us):
                 uview[i, :max_len].copy_(u[:max_len])
@@ -816,68 +825,107 @@ class TextToSemanticDecoder:
         b["state"].copy_(self._slot_records(ctx))
         logits = []
         st = self._slot_records(ctx).tolist()[:nb]
+        done = lambda st: all(st[r][1] for r in range(0, nb, P)) and not ignore_eos
         if collect_logits:                                              # (tests: one step at a time without a graph)
             for _ in range(max_len):
-                self._run_steps(float(temperature), nb, 1, 1.0, False, filt, 0, scored)
-                logits.append(b["logits"][:nb].clone())
+                self._run_steps(temperature, nb, 1, scale, False, filt, 0, scored)
+                lg = b["logits"][:nb].clone()
+                logits.append(lg[1::2] + (lg[0::2] - lg[1::2]) * scale if guided else lg)
                 st = self._read_state(nb)
-                if all(row[1] for row in st) and not ignore_eos:
+                if done(st):
                     break
         elif max_len > 0:
-            st = self._decode_chunks(float(temperature), nb, max_len, 1.0, range(nb), ignore_eos, filt, scored)
+            self._chunks(lambda: self._run_chunk(temperature, nb, scale, False, filt, 0, scored), b["state"], nb, done, (max_len + CHUNK - 1) // CHUNK)
+            st = self._read_state(nb)
         out = []
-        for i in range(nb):
-            length = min(st[i][2] if st[i][1] and st[i][2] <= max_len and not ignore_eos else max_len, max_len)
-            out.append(self._cut(i, length, torch.stack([lg[i] for lg in logits]) if collect_logits and logits else None, scored))
+        for u in range(n):
+            r = st[P * u]
+            length = min(r[2] if r[1] and r[2] <= max_len and not ignore_eos else max_len, max_len)
+            out.append(self._cut(P * u, length, torch.stack([lg[u] for lg in logits]) if collect_logits and logits else None, scored))
         return out
 
-    def _generate_guided(self, sources, uniforms, max_length, temperature, generator, collect_logits, cond_scale, ignore_eos=False, filt=None,
-                         scored=False):
-        """generate_batch with cond_scale > 1: slots 2u (text context) / 2u + 1 (null context) per utterance u."""
-        V, nu = self.d["vocab"], len(sources)
-        nb = 2 * nu
-        if not 1 <= nu <= MAX_BATCH // 2:
-            raise ValueError(f"1..{MAX_BATCH // 2} utterances per guided decode batch, got {nu}")
+    def _forced_tokens(self, forced, n: int, scored: bool):
+        """`forced` of generate_many: None when no utterance is forced, else the list with every entry given as an int64 [S, L] host tensor
+        (`check_targets`)"""
+        if forced is not None:
+            if not scored or len(forced) != n:
+                raise ValueError("forced: one entry per utterance, with return_logprobs=True")
+            if all(f is None for f in forced):
+                forced = None
+        if forced is not None:
+            forced = list(forced)
+            fi = [j for j in range(n) if forced[j] is not None]
+            for j, t in zip(fi, check_targets([forced[j] for j in fi], self.d["streams"], self.d["vocab"], self.max_length)):
+                forced[j] = t
+        return forced
+
+    def _step_limits(self, n: int, uniforms, max_length, limits, forced):
+        """-> (us, max_len, lim, span, is_forced) of a generate_many window: the caller's draws on the device (None: none given; an entry is
+        None for a forced utterance without draws), the steps of the call (the shortest draws bound it), the step limit of every utterance
+        (a forced one: the length of its tokens) and the steps an utterance can take: the rows of the pinned result buffers"""
+        S, V = self.d["streams"], self.d["vocab"]
         max_len = min(int(max_length or self.max_length), self.max_length)
         us = None
+        is_forced = [forced is not None and forced[j] is not None for j in range(n)]
         if uniforms is not None:
-            us = [u.to(self.device, torch.float32).reshape(u.shape[0], 1, V) for u in uniforms]
-            max_len = min([max_len] + [u.shape[0] for u in us])
-        scored = bool(scored)
-        self._ensure(nb, nb, max_len, scored)
-        b = self.buf
-        if not collect_logits and max_len > 0:
-            self._graph(float(temperature), nb, cond_scale, False, filt, 0, scored)
-        ctx = []
-        for c in self._contexts(sources, range(0, nb, 2)):
-            ctx += [c, 1]                                                # the null slot: row 0 (null k/v) only = every context key masked out
-        for L in self.dec:
-            L["kv_c"][1:nb:2, 0].copy_(L["null"][None, :].expand(nu, -1))
-        uview = self._uniform_view(nb)
-        if us is None:
-            uview[0::2, :max_len].copy_(torch.rand(max_len, nu, 1, V, device=self.device, generator=generator).permute(1, 0, 2, 3))
-        else:
-            for u_, u in enumerate(us):
-                uview[2 * u_, :max_len].copy_(u[:max_len])
-        b["x"][:nb].copy_(self.start[None, :].expand(nb, -1))
-        b["state"].copy_(self._slot_records(ctx))
-        logits = []
-        st = self._slot_records(ctx).tolist()[:nb]
-        if collect_logits:
-            for _ in range(max_len):
-                self._run_steps(float(temperature), nb, 1, cond_scale, False, filt, 0, scored)
-                lg = b["logits"][:nb].clone()
-                logits.append(lg[1::2] + (lg[0::2] - lg[1::2]) * cond_scale)
-                st = self._read_state(nb)
-                if all(st[2 * u_][1] for u_ in range(nu)) and not ignore_eos:
-                    break
-        elif max_len > 0:
-            st = self._decode_chunks(float(temperature), nb, max_len, cond_scale, [2 * u_ for u_ in range(nu)], ignore_eos, filt, scored)
-        out = []
-        for u_ in range(nu):
-            i = 2 * u_
-            length = min(st[i][2] if st[i][1] and st[i][2] <= max_len and not ignore_eos else max_len, max_len)
-            out.append(self._cut(i, length, torch.stack([lg[u_] for lg in logits]) if collect_logits and logits else None, scored))
+            us = [None if (u is None and is_forced[j]) else u.to(self.device, torch.float32).reshape(u.shape[0], S, V) for j, u in enumerate(uniforms)]
+            max_len = min([max_len] + [u.shape[0] for u in us if u is not None])
+        lim = [max_len] * n if limits is None else [max(1, min(int(x), max_len)) for x in limits]
+        if max_len <= 0:
+            raise ValueError("generate_many needs at least one step")
+        span = max_len
+        if forced is not None:
+            lim = [forced[j].shape[1] if is_forced[j] else lim[j] for j in range(n)]
+            span = max(span, max(lim))
+        return us, max_len, lim, span, is_forced
+
+    def _queue_chunks(self, replay, nrec: int, text: list, lim: list, span: int, scored: bool, on_done, last_records) -> list:
+        """The chunks (`_chunks`) of a generate_many window whose state is set up, until the dialogue records show every utterance finished
+        (status >= 2) -> the results.  Utterance j is carried by record text[j]; last_records(records) is what `last_records` keeps of
+        the records read (tests / tools: status, steps and slot of every utterance).
+        Token rows of finished utterances reach the host through the helper stream into pinned memory (a dialogue's rows are final
+        once the host has SEEN it finished: any stream may read them) and are cut on the host - nothing here makes the decode
+        stream wait, so the chunks stay back to back (a device-side boolean index per utterance cost a stream sync each: 64
+        utterances on 64 slots ran 996 ms against 746 ms in lock step)"""
+        n, S, b = len(text), self.d["streams"], self.buf
+        self._mirror_setup()                               # (the helper stream)
+        out: list = [None] * n
+        seen = [False] * n
+        tok_pin = torch.empty(n, S, span, dtype=torch.int64).pin_memory()
+        lp_pin = torch.empty(n, S, span, dtype=torch.float32).pin_memory() if scored else None
+        copies: list = []                                  # (j, steps, event) in flight on the helper stream
+
+        def finish(block: bool):
+            while copies and (block or copies[0][2].query()):
+                j, length, ev = copies.pop(0)
+                ev.synchronize()
+                out[j] = self._mask_after_eos(tok_pin[j, :, :length])
+                if scored:
+                    out[j] += (lp_pin[j, :, :length].clone(),)
+                if on_done is not None:
+                    on_done(j, out[j])
+
+        def collect(records) -> bool:
+            self.last_records = last_records(records)
+            fresh = [j for j in range(n) if not seen[j] and records[text[j]][3] >= 2]
+            if fresh:
+                with torch.cuda.stream(self._helper):
+                    for j in fresh:
+                        seen[j] = True
+                        length = records[text[j]][4]
+                        tok_pin[j, :, :length].copy_(b["tokens"][text[j], :, :length], non_blocking=True)
+                        if scored:
+                            lp_pin[j, :, :length].copy_(b["logprobs"][text[j], :, :length], non_blocking=True)
+                        ev = torch.cuda.Event()
+                        ev.record()
+                        copies.append((j, length, ev))
+            finish(False)
+            return all(seen)
+        cap = (sum(lim) + CHUNK - 1) // CHUNK + 4          # (one slot decoding everything: cannot be reached)
+        i, _ = self._chunks(replay, b["dialogues"], nrec, collect, cap)
+        finish(True)
+        if not all(seen):
+            raise RuntimeError(f"text2semantic continuous decode: {seen.count(False)} of {n} utterances did not finish in {i} chunks")
         return out
 
     @ops.gated
@@ -935,16 +983,7 @@ class TextToSemanticDecoder:
         S, V = d["streams"], d["vocab"]
         n = len(sources)
         scored = bool(return_logprobs)
-        if forced is not None:
-            if not scored or len(forced) != n:
-                raise ValueError("forced: one entry per utterance, with return_logprobs=True")
-            if all(f is None for f in forced):
-                forced = None
-        if forced is not None:
-            forced = list(forced)
-            fi = [j for j in range(n) if forced[j] is not None]
-            for j, t in zip(fi, check_targets([forced[j] for j in fi], S, V, self.max_length)):
-                forced[j] = t
+        forced = self._forced_tokens(forced, n, scored)
         filt = filter_setting(filter_logits_fn, filter_fn_kwargs, V)
         cond_scale = float(cond_scale)
         cfg = cond_scale > 1.0
@@ -975,32 +1014,14 @@ class TextToSemanticDecoder:
         nb = P * max(1, min(int(slots) // P, MAX_BATCH // P, n))
         nb = nb if nb in (1, 2, 4) else min((nb + 7) // 8 * 8, MAX_BATCH)      # whole kernel groups (idle slots cost nothing)
         nrec = P * n
-        max_len = min(int(max_length or self.max_length), self.max_length)
-        us = None
-        is_forced = [forced is not None and forced[j] is not None for j in range(n)]
-        if uniforms is not None:
-            us = [None if (u is None and is_forced[j]) else u.to(self.device, torch.float32).reshape(u.shape[0], S, V) for j, u in enumerate(uniforms)]
-            max_len = min([max_len] + [u.shape[0] for u in us if u is not None])
-        lim = [max_len] * n if limits is None else [max(1, min(int(x), max_len)) for x in limits]
-        if max_len <= 0:
-            raise ValueError("generate_many needs at least one step")
-        span = max_len                # steps an utterance can take: the rows of the pinned result buffers
-        if forced is not None:
-            lim = [forced[j].shape[1] if is_forced[j] else lim[j] for j in range(n)]
-            span = max(span, max(lim))
+        text = list(range(0, nrec, P))                     # the record that carries utterance j
+        us, max_len, lim, span, is_forced = self._step_limits(n, uniforms, max_length, limits, forced)
         pre = check_prefixes([None] * n if prefixes is None else prefixes, n, S, V, lim, forced) if per else [None] * n
         self._ensure(nb, nrec, max_len, scored)
         b = self.buf
         temperature = float(temperature)
         self._graph(temperature, nb, cond_scale, True, filt, nrec, scored, per)
-        if cfg:                   # record 2u: the text context; record 2u + 1: the null key / value row only (every context key masked out)
-            ctx = []
-            for c in self._contexts(sources, range(0, nrec, 2)):
-                ctx += [c, 1]
-            for L in self.dec:
-                L["kv_c"][1:nrec:2, 0].copy_(L["null"][None, :].expand(n, -1))
-        else:
-            ctx = self._contexts(sources)
+        ctx = self._guided_contexts(sources) if cfg else self._contexts(sources)
         uview = self._uniform_view(nrec)[0::P]            # the draws of utterance j live in its first record
         if us is None:
             if not all(is_forced):                         # (a forced dialogue reads no draws: a pure scoring call draws none)
@@ -1013,13 +1034,13 @@ class TextToSemanticDecoder:
         if forced is not None:                             # the token row of a forced dialogue holds its tokens before its first step
             for j in range(n):
                 if is_forced[j]:
-                    b["tokens"][P * j, :, :lim[j]].copy_(ops.h2d(forced[j], self.device))
+                    b["tokens"][text[j], :, :lim[j]].copy_(ops.h2d(forced[j], self.device))
         if per:                                            # one settings row per dialogue record (the odd record of a pair mirrors the even one)
             b["per"][:nrec].copy_(ops.h2d(settings_rows(resolved, [0 if p is None else p.shape[1] for p in pre]).repeat_interleave(P, dim=0),
                                           self.device))
             for j, p in enumerate(pre):                    # the token row of a prefixed dialogue holds the prefix before its first step
                 if p is not None:
-                    b["tokens"][P * j, :, :p.shape[1]].copy_(ops.h2d(p, self.device))
+                    b["tokens"][text[j], :, :p.shape[1]].copy_(ops.h2d(p, self.device))
         first = min(nb, nrec)     # records (= slots) that start at once; whole pairs under guidance (nb and nrec are even)
         rec = torch.tensor([[ctx[r], lim[r // P], flags[r // P], 1 if r < first else 0, 0, r if r < first else 0, 0, 0] for r in range(nrec)],
                            dtype=torch.int32)
@@ -1030,68 +1051,8 @@ class TextToSemanticDecoder:
             slot[r, 5], slot[r, 6] = lim[r // P], flags[r // P]
         b["state"].copy_(slot)
         b["x"][:first].copy_(self.start[None, :].expand(first, -1))
-        self._mirror_setup()
-        via_helper = ops.is_partition_stream()
-        out: list = [None] * n
-        seen = [False] * n
-        # token rows of finished utterances reach the host through the helper stream into pinned memory (a dialogue's rows are final
-        # once the host has SEEN it finished: any stream may read them) and are cut on the host - nothing here makes the decode
-        # stream wait, so the chunks stay back to back (a device-side boolean index per utterance cost a stream sync each: 64
-        # utterances on 64 slots ran 996 ms against 746 ms in lock step)
-        tok_pin = torch.empty(n, S, span, dtype=torch.int64).pin_memory()
-        lp_pin = torch.empty(n, S, span, dtype=torch.float32).pin_memory() if scored else None
-        copies: list = []                                  # (j, steps, event) in flight on the helper stream
-        eos = V - 1
-
-        def finish(block: bool):
-            while copies and (block or copies[0][2].query()):
-                j, length, ev = copies.pop(0)
-                ev.synchronize()
-                streams = tok_pin[j, :, :length].clone()
-                after = (streams == eos).cumsum(dim=-1) > 0          # mask_after_eos (text2semantic.py:73-76)
-                after = torch.nn.functional.pad(after, (1, -1), value=False)
-                flat = streams.masked_fill(after, PAD_ID).reshape(-1)
-                out[j] = (flat[flat != PAD_ID], streams)
-                if scored:
-                    out[j] += (lp_pin[j, :, :length].clone(),)
-                if on_done is not None:
-                    on_done(j, out[j])
-
-        def collect(records):
-            records = records[0::P]
-            self.last_records = records          # (tests / tools: status, steps and slot of every utterance)
-            fresh = [j for j in range(n) if not seen[j] and records[j][3] >= 2]
-            if fresh:
-                with torch.cuda.stream(self._helper):
-                    for j in fresh:
-                        seen[j] = True
-                        length = records[j][4]
-                        tok_pin[j, :, :length].copy_(b["tokens"][P * j, :, :length], non_blocking=True)
-                        if scored:
-                            lp_pin[j, :, :length].copy_(b["logprobs"][P * j, :, :length], non_blocking=True)
-                        ev = torch.cuda.Event()
-                        ev.record()
-                        copies.append((j, length, ev))
-            finish(False)
-
-        i, pending = 0, None
-        cap = (sum(lim) + CHUNK - 1) // CHUNK + 4          # (one slot decoding everything: cannot be reached)
-        while not all(seen) and i < cap:
-            self._run_chunk(temperature, nb, cond_scale, True, filt, nrec, scored, per)
-            k = i & 1
-            self._mirror_push(k, b["dialogues"][:nrec], via_helper)
-            if pending is not None:
-                collect(self._mirror_pull(pending, nrec))
-            pending = k
-            i += 1
-        if not all(seen) and pending is not None:
-            collect(self._mirror_pull(pending, nrec))
-        if pending is not None:
-            self._pin_ev[pending].synchronize()
-        finish(True)
-        if not all(seen):
-            raise RuntimeError(f"text2semantic continuous decode: {seen.count(False)} of {n} utterances did not finish in {i} chunks")
-        return out
+        return self._queue_chunks(lambda: self._run_chunk(temperature, nb, cond_scale, True, filt, nrec, scored, per), nrec, text, lim, span, scored,
+                                  on_done, lambda records: records[0::P])
 
     def _generate_many_mixed(self, sources, uniforms, max_length, temperature, generator, slots, ignore_eos, limits, on_done, cond_scale,
                              filter_logits_fn, filter_fn_kwargs, return_logprobs, forced, settings, prefixes):
@@ -1103,16 +1064,7 @@ class TextToSemanticDecoder:
         S, V = d["streams"], d["vocab"]
         n = len(sources)
         scored = bool(return_logprobs)
-        if forced is not None:
-            if not scored or len(forced) != n:
-                raise ValueError("forced: one entry per utterance, with return_logprobs=True")
-            if all(f is None for f in forced):
-                forced = None
-        if forced is not None:
-            forced = list(forced)
-            fi = [j for j in range(n) if forced[j] is not None]
-            for j, t in zip(fi, check_targets([forced[j] for j in fi], S, V, self.max_length)):
-                forced[j] = t
+        forced = self._forced_tokens(forced, n, scored)
         filter_setting(filter_logits_fn, filter_fn_kwargs, V)
         resolved = check_settings([None] * n if settings is None else settings, n, V, S, temperature, filter_logits_fn, filter_fn_kwargs,
                                   float(cond_scale), mixed=True)
@@ -1140,19 +1092,7 @@ class TextToSemanticDecoder:
         text = first[:-1]                                      # the record that carries utterance j
         nulls = [text[j] + 1 for j in range(n) if kinds[j]]
         nb = max(1, min(int(slots), MAX_BATCH, nrec))
-        max_len = min(int(max_length or self.max_length), self.max_length)
-        us = None
-        is_forced = [forced is not None and forced[j] is not None for j in range(n)]
-        if uniforms is not None:
-            us = [None if (u is None and is_forced[j]) else u.to(self.device, torch.float32).reshape(u.shape[0], S, V) for j, u in enumerate(uniforms)]
-            max_len = min([max_len] + [u.shape[0] for u in us if u is not None])
-        lim = [max_len] * n if limits is None else [max(1, min(int(x), max_len)) for x in limits]
-        if max_len <= 0:
-            raise ValueError("generate_many needs at least one step")
-        span = max_len
-        if forced is not None:
-            lim = [forced[j].shape[1] if is_forced[j] else lim[j] for j in range(n)]
-            span = max(span, max(lim))
+        us, max_len, lim, span, is_forced = self._step_limits(n, uniforms, max_length, limits, forced)
         pre = check_prefixes([None] * n if prefixes is None else prefixes, n, S, V, lim, forced)
         self._ensure(nb, nrec, max_len, scored)
         b = self.buf
@@ -1189,63 +1129,8 @@ class TextToSemanticDecoder:
         b["queue"].copy_(torch.tensor([0, nrec], dtype=torch.int32))
         b["state"].copy_(self._slot_records([]))
         self._run_steps(1.0, nb, 0, 1.0, True, None, nrec, scored, True, ng)         # the scheduler alone: arms the first slots
-        self._mirror_setup()
-        via_helper = ops.is_partition_stream()
-        out: list = [None] * n
-        seen = [False] * n
-        tok_pin = torch.empty(n, S, span, dtype=torch.int64).pin_memory()
-        lp_pin = torch.empty(n, S, span, dtype=torch.float32).pin_memory() if scored else None
-        copies: list = []                                  # (j, steps, event) in flight on the helper stream
-        eos = V - 1
-
-        def finish(block: bool):
-            while copies and (block or copies[0][2].query()):
-                j, length, ev = copies.pop(0)
-                ev.synchronize()
-                streams = tok_pin[j, :, :length].clone()
-                after = (streams == eos).cumsum(dim=-1) > 0          # mask_after_eos (text2semantic.py:73-76)
-                after = torch.nn.functional.pad(after, (1, -1), value=False)
-                flat = streams.masked_fill(after, PAD_ID).reshape(-1)
-                out[j] = (flat[flat != PAD_ID], streams)
-                if scored:
-                    out[j] += (lp_pin[j, :, :length].clone(),)
-                if on_done is not None:
-                    on_done(j, out[j])
-
-        def collect(records):
-            self.last_records = [list(records[text[j]]) + [records[text[j] + 1][5] if kinds[j] else None] for j in range(n)]
-            fresh = [j for j in range(n) if not seen[j] and records[text[j]][3] >= 2]
-            if fresh:
-                with torch.cuda.stream(self._helper):
-                    for j in fresh:
-                        seen[j] = True
-                        length = records[text[j]][4]
-                        tok_pin[j, :, :length].copy_(b["tokens"][text[j], :, :length], non_blocking=True)
-                        if scored:
-                            lp_pin[j, :, :length].copy_(b["logprobs"][text[j], :, :length], non_blocking=True)
-                        ev = torch.cuda.Event()
-                        ev.record()
-                        copies.append((j, length, ev))
-            finish(False)
-
-        i, pending = 0, None
-        cap = (sum(lim) + CHUNK - 1) // CHUNK + 4          # (one slot decoding everything: cannot be reached)
-        while not all(seen) and i < cap:
-            self._run_chunk(1.0, nb, 1.0, True, None, nrec, scored, True, ng)
-            k = i & 1
-            self._mirror_push(k, b["dialogues"][:nrec], via_helper)
-            if pending is not None:
-                collect(self._mirror_pull(pending, nrec))
-            pending = k
-            i += 1
-        if not all(seen) and pending is not None:
-            collect(self._mirror_pull(pending, nrec))
-        if pending is not None:
-            self._pin_ev[pending].synchronize()
-        finish(True)
-        if not all(seen):
-            raise RuntimeError(f"text2semantic continuous decode: {seen.count(False)} of {n} utterances did not finish in {i} chunks")
-        return out
+        return self._queue_chunks(lambda: self._run_chunk(1.0, nb, 1.0, True, None, nrec, scored, True, ng), nrec, text, lim, span, scored, on_done,
+                                  lambda records: [list(records[text[j]]) + [records[text[j] + 1][5] if kinds[j] else None] for j in range(n)])
 
     # ------------------------------------------------------------------ beam search
     def _beam_scale(self, cond_scale) -> float:
@@ -1289,34 +1174,42 @@ class TextToSemanticDecoder:
         self._ensure_beam()["groups"].copy_(g)
 
     def _beam_graph(self, batch: int, beam_size: int, scale: float = 1.0):
-        """The captured graph of CHUNK beam steps for this (batch, beam size, stream CU count); `_graph`'s procedure, a key of its own shape.
+        """The captured graph of CHUNK beam steps for this (batch, beam size, stream CU count), through `_capture` as `_graph`'s, under a key of its own shape.
         The guided chain (scale > 1) has graphs of its own kind, "beamg", whose key carries the scale (a kernel argument)."""
         self._ensure_beam()
         key = ("beamg", beam_size, batch, float(scale), ops.stream_cus(), self._gen) if scale > 1.0 else \
             ("beam", beam_size, batch, ops.stream_cus(), self._gen)
-        g = self._graphs.get(key)
-        if g is not None:
-            return g
-        self._beam_idle()
-        self._launch_beam(batch, beam_size, CHUNK, scale=scale)       # warm-up outside capture
-        cur = torch.cuda.current_stream()
-        if self._cap is None:
-            self._cap = torch.cuda.Stream(device=self.device)
-        ops.saturation_share(cur, self._cap)
-        with ops.CAPTURE_GATE.exclusive():
-            cur.synchronize()
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, stream=self._cap, capture_error_mode="thread_local"):
-                self._launch_beam(batch, beam_size, CHUNK, scale=scale)
-        if len(self._graphs) >= 8:
-            self._graphs.clear()
-        self._graphs[key] = g
-        return g
+        return self._capture(key, lambda: self._launch_beam(batch, beam_size, CHUNK, scale=scale), self._beam_idle)
+
+    def _beam_slot_records(self, ctx, B: int, nb: int, guided: bool) -> torch.Tensor:
+        """slot records [slots, SR] (CPU) of nb beam slots at position 0, the others idle (`_slot_records`); ctx: context rows per dialogue
+        row.  Unguided: the B hypotheses of utterance u are slots [u B, (u + 1) B) on dialogue row u; guided: 2 B slots, even ones on row
+        2u (the text context), odd ones on row 2u + 1 (the null context) - the rows of `_guided_contexts`."""
+        rec = self._slot_records([])
+        rows = [2 * (i // (2 * B)) + (i & 1) if guided else i // B for i in range(nb)]
+        rec[:nb] = torch.tensor([[0, 0, 0, ctx[r], r, 0, 0, 0] for r in rows], dtype=torch.int32)
+        return rec
+
+    def _beam_results(self, B: int, length_penalty: float, scores, lengths, tokens, logprobs, parents, h_tok, h_lp, steps, status=None) -> list:
+        """Per utterance the list of its B hypotheses (flat tokens, streams, logprobs, score), best first (`beam_rank`), and its record in
+        `last_beam`.  Per hypothesis u B + i (host): scores [n B], lengths (a list), tokens and logprobs [n B, S, L]; the search's history
+        per utterance (device; the first steps[u] rows are copied): parents [n, L, B], h_tok and h_lp [n, L, B, S]; status: optional
+        (status, group) per utterance."""
+        S, out = self.d["streams"], []
+        for u, T in enumerate(steps):
+            ln, sc = lengths[u * B:(u + 1) * B], scores[u * B:(u + 1) * B]
+            order = beam_rank(sc, ln, S, length_penalty)
+            out.append([self._mask_after_eos(tokens[u * B + i, :, :ln[i]]) + (logprobs[u * B + i, :, :ln[i]].clone(), float(sc[i])) for i in order])
+            self.last_beam.append(dict(steps=T, order=order, lengths=ln, scores=sc.clone(), parents=parents[u, :T].cpu(),
+                                       tokens=h_tok[u, :T].cpu(), logprobs=h_lp[u, :T].cpu()))
+            if status is not None:
+                self.last_beam[-1].update(status=status[u][0], group=status[u][1])
+        return out
 
     def _beam_wave(self, sources, B: int, max_len: int, length_penalty: float, scale: float = 1.0) -> list:
         """One lock-step wave: utterance u in slots [u B, (u + 1) B).  -> per utterance the list of its B hypotheses, best first.
         scale > 1 (guided): hypothesis h is the slot pair (2h, 2h + 1) - text context / null context - and utterance u owns the kv_c rows
-        2u (its context) and 2u + 1 (the null key / value alone), as in _generate_guided; everything kept per hypothesis (scores, history,
+        2u (its context) and 2u + 1 (the null key / value alone), as in a guided generate_batch; everything kept per hypothesis (scores, history,
         back-tracked rows) has nh = n B rows, everything per slot nb = 2 nh."""
         d = self.d
         S, n = d["streams"], len(sources)
@@ -1325,20 +1218,9 @@ class TextToSemanticDecoder:
         nb = 2 * nh if guided else nh
         self._ensure(nb, nb, 0)
         bm = self._ensure_beam()
-        use_graph = os.environ.get("CVX_GRAPH", "1") == "1"
-        if use_graph:
-            self._beam_graph(nb, B, scale)
-        if guided:
-            ctx = self._contexts(sources, range(0, 2 * n, 2))
-            for L in self.dec:
-                L["kv_c"][1:2 * n:2, 0].copy_(L["null"][None, :].expand(n, -1))
-            idle = [self.max_length, 1, 0, 1, 0, 0, 0, 0]
-            rows = [([0, 0, 0, 1, 2 * (i // (2 * B)) + 1, 0, 0, 0] if i & 1 else [0, 0, 0, ctx[i // (2 * B)], 2 * (i // (2 * B)), 0, 0, 0])
-                    if i < nb else idle for i in range(self._slots)]
-        else:
-            ctx = self._contexts(sources)
-            rows = [[0, 0, 0, ctx[i // B], i // B, 0, 0, 0] if i < nb else [self.max_length, 1, 0, 1, 0, 0, 0, 0] for i in range(self._slots)]
-        self.buf["state"].copy_(torch.tensor(rows, dtype=torch.int32))
+        graph = self._beam_graph(nb, B, scale) if os.environ.get("CVX_GRAPH", "1") == "1" else None
+        ctx = self._guided_contexts(sources) if guided else self._contexts(sources)
+        self.buf["state"].copy_(self._beam_slot_records(ctx, B, nb, guided))
         self.buf["x"][:nb].copy_(self.start[None, :].expand(nb, -1))
         sc = torch.full((self._slots,), -math.inf)
         sc[0:nh:B] = 0.0                                   # before step 0 only hypothesis 0 of an utterance is live
@@ -1349,47 +1231,15 @@ class TextToSemanticDecoder:
         g[:, 1] = 1
         g[:n, 1], g[:n, 2] = 0, max_len
         bm["groups"].copy_(g)
-        # chunks of CHUNK steps; the host reads the slot records one chunk behind the device (_decode_chunks)
-        self._mirror_setup()
-        via_helper = ops.is_partition_stream()
-        steps, i, pending = 0, 0, None
-        while steps < max_len:
-            if use_graph:
-                self._beam_graph(nb, B, scale).replay()
-            else:
-                self._launch_beam(nb, B, CHUNK, scale=scale)
-            steps += CHUNK
-            k = i & 1
-            self._mirror_push(k, self.buf["state"][:nb], via_helper)
-            if pending is not None and all(r[1] for r in self._mirror_pull(pending, nb)):
-                break
-            pending = k
-            i += 1
-        if pending is not None:
-            self._pin_ev[pending].synchronize()
+        self._chunks(graph.replay if graph is not None else lambda: self._launch_beam(nb, B, CHUNK, scale=scale), self.buf["state"], nb,
+                     lambda st: all(r[1] for r in st), (max_len + CHUNK - 1) // CHUNK)
         self._launch_beam(nb, B, 0, backtrack=True, scale=scale)
         st = self._read_state(nb)[::2 if guided else 1]    # (per hypothesis: the text half's record)
-        nb = nh                                            # from here on rows are hypotheses
-        scores, groups = bm["scores"][:nb].cpu(), bm["groups"][:n].tolist()
-        tokens, logprobs = self.buf["tokens"][:nb].cpu(), bm["logprobs"][:nb].cpu()
-        eos = d["vocab"] - 1
-        out = []
-        for u in range(n):
-            T = groups[u][0]
-            lengths = [st[u * B + i][2] for i in range(B)]
-            order = beam_rank(scores[u * B:(u + 1) * B], lengths, S, length_penalty)
-            hyps = []
-            for i in order:
-                streams = tokens[u * B + i, :, :lengths[i]].clone()
-                after = (streams == eos).cumsum(dim=-1) > 0          # mask_after_eos (text2semantic.py:73-76)
-                after = torch.nn.functional.pad(after, (1, -1), value=False)
-                flat = streams.masked_fill(after, PAD_ID).reshape(-1)
-                hyps.append((flat[flat != PAD_ID], streams, logprobs[u * B + i, :, :lengths[i]].clone(), float(scores[u * B + i])))
-            out.append(hyps)
-            rec = lambda name, *tail: bm[name][:T * nb * math.prod(tail)].view(T, nb, *tail)[:, u * B:(u + 1) * B].cpu()
-            self.last_beam.append(dict(steps=T, order=order, lengths=lengths, scores=scores[u * B:(u + 1) * B].clone(),
-                                       parents=rec("parents"), tokens=rec("hist_tokens", S), logprobs=rec("hist_logprobs", S)))
-        return out
+        L = self.max_length                                # the history is kept per hypothesis: [steps, nh, ...]
+        hist = lambda name, *tail: bm[name][:L * nh * math.prod(tail)].view(L, n, B, *tail).transpose(0, 1)
+        scores, steps = bm["scores"][:nh].cpu(), [row[0] for row in bm["groups"][:n].tolist()]
+        return self._beam_results(B, length_penalty, scores, [r[2] for r in st], self.buf["tokens"][:nh].cpu(), bm["logprobs"][:nh].cpu(),
+                                  hist("parents"), hist("hist_tokens", S), hist("hist_logprobs", S), steps)
 
     @ops.gated
     @torch.no_grad()
@@ -1465,28 +1315,11 @@ class TextToSemanticDecoder:
         _lib.check(_lib.load().cvx_t2s_beam_queue_steps(C.byref(dec), C.byref(bs), C.byref(qs), n, ops._stream()), "cvx_t2s_beam_queue_steps")
 
     def _beam_queue_graph(self, batch: int, beam_size: int, scale: float = 1.0):
-        """The captured graph of CHUNK steps of the refilled beam chain; `_beam_graph`'s procedure.  (The number of utterances sizes the
+        """The captured graph of CHUNK steps of the refilled beam chain (`_capture`).  (The number of utterances sizes the
         back-track launch only, which is not part of the graph: the steps read the device-side queue.)  Guided: kind "beamqg", with the scale."""
         key = ("beamqg", beam_size, batch, float(scale), ops.stream_cus(), self._gen) if scale > 1.0 else \
             ("beamq", beam_size, batch, ops.stream_cus(), self._gen)
-        g = self._graphs.get(key)
-        if g is not None:
-            return g
-        self._beam_idle()
-        self._launch_beam_queue(batch, beam_size, 1, CHUNK, scale=scale)       # warm-up outside capture
-        cur = torch.cuda.current_stream()
-        if self._cap is None:
-            self._cap = torch.cuda.Stream(device=self.device)
-        ops.saturation_share(cur, self._cap)
-        with ops.CAPTURE_GATE.exclusive():
-            cur.synchronize()
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, stream=self._cap, capture_error_mode="thread_local"):
-                self._launch_beam_queue(batch, beam_size, 1, CHUNK, scale=scale)
-        if len(self._graphs) >= 8:
-            self._graphs.clear()
-        self._graphs[key] = g
-        return g
+        return self._capture(key, lambda: self._launch_beam_queue(batch, beam_size, 1, CHUNK, scale=scale), self._beam_idle)
 
     def _beam_queue_window(self, sources, B: int, lim: list, length_penalty: float, slots: int, scale: float = 1.0) -> list:
         """One window of generate_beam_many: its utterances' contexts resident, the groups refilled on the device until all have ended.
@@ -1499,19 +1332,9 @@ class TextToSemanticDecoder:
         nb = G * B * P                                     # (the buffers hold whole 8-slot kernel groups: _ensure)
         self._ensure(nb, n * P, 0)
         bm, bq = self._ensure_beam(), self._ensure_beam_queue(max(n * B, WINDOW))
-        use_graph = os.environ.get("CVX_GRAPH", "1") == "1"
-        if use_graph:
-            self._beam_queue_graph(nb, B, scale)
-        if guided:
-            ctx = self._contexts(sources, range(0, 2 * n, 2))
-            for Ld in self.dec:
-                Ld["kv_c"][1:2 * n:2, 0].copy_(Ld["null"][None, :].expand(n, -1))
-            rows = [([0, 0, 0, 1, 2 * (i // (2 * B)) + 1, 0, 0, 0] if i & 1 else [0, 0, 0, ctx[i // (2 * B)], 2 * (i // (2 * B)), 0, 0, 0])
-                    if i < nb else [L, 1, 0, 1, 0, 0, 0, 0] for i in range(self._slots)]
-        else:
-            ctx = self._contexts(sources)
-            rows = [[0, 0, 0, ctx[i // B], i // B, 0, 0, 0] if i < nb else [L, 1, 0, 1, 0, 0, 0, 0] for i in range(self._slots)]
-        self.buf["state"].copy_(torch.tensor(rows, dtype=torch.int32))
+        graph = self._beam_queue_graph(nb, B, scale) if os.environ.get("CVX_GRAPH", "1") == "1" else None
+        ctx = self._guided_contexts(sources) if guided else self._contexts(sources)
+        self.buf["state"].copy_(self._beam_slot_records(ctx, B, nb, guided))
         self.buf["x"][:nb].copy_(self.start[None, :].expand(nb, -1))
         sc = torch.full((self._slots,), -math.inf)
         sc[0:G * B:B] = 0.0                                # before step 0 only hypothesis 0 of an utterance is live
@@ -1523,56 +1346,19 @@ class TextToSemanticDecoder:
             g[u] = torch.tensor([0, 0, lim[u], u], dtype=torch.int32)
         bm["groups"].copy_(g)
         bq["owner"].view(2, self._slots, L)[0, :nb, 0].copy_(bq["slot_ids"][:nb])     # (position 0 of a starting slot: the slot itself)
-        bq["utterances"][:n].copy_(torch.tensor([[ctx[j], lim[j], 0, 1 if j < G else 0, 0, j if j < G else 0, 0, 0] for j in range(n)],
+        bq["utterances"][:n].copy_(torch.tensor([[ctx[P * j], lim[j], 0, 1 if j < G else 0, 0, j if j < G else 0, 0, 0] for j in range(n)],
                                                 dtype=torch.int32))
         bq["queue"].copy_(torch.tensor([G, n], dtype=torch.int32))
-        # chunks of CHUNK steps; the host reads the utterance records one chunk behind the device (generate_many)
-        self._mirror_setup()
-        via_helper = ops.is_partition_stream()
-        i, pending, rec = 0, None, None
-        done = lambda r: r is not None and all(row[3] >= 2 for row in r)
+        done = lambda r: all(row[3] >= 2 for row in r)
         cap = (sum(lim) + CHUNK - 1) // CHUNK + 4          # (one group decoding everything: cannot be reached)
-        while not done(rec) and i < cap:
-            if use_graph:
-                self._beam_queue_graph(nb, B, scale).replay()
-            else:
-                self._launch_beam_queue(nb, B, n, CHUNK, scale=scale)
-            k = i & 1
-            self._mirror_push(k, bq["utterances"][:n], via_helper)
-            if pending is not None:
-                rec = self._mirror_pull(pending, n)
-            pending = k
-            i += 1
-        if not done(rec) and pending is not None:
-            rec = self._mirror_pull(pending, n)
-        if pending is not None:
-            self._pin_ev[pending].synchronize()
+        i, rec = self._chunks(graph.replay if graph is not None else lambda: self._launch_beam_queue(nb, B, n, CHUNK, scale=scale), bq["utterances"], n, done, cap)
         if not done(rec):
-            left = n if rec is None else sum(1 for row in rec if row[3] < 2)
-            raise RuntimeError(f"text2semantic refilled beam decode: {left} of {n} utterances did not finish in {i} chunks")
+            raise RuntimeError(f"text2semantic refilled beam decode: {sum(1 for row in rec if row[3] < 2)} of {n} utterances did not finish in {i} chunks")
         self._launch_beam_queue(nb, B, n, 0, backtrack=True, scale=scale)
-        scores, lengths_all = bq["final_scores"][:n * B].cpu(), bq["final_steps"][:n * B].tolist()
-        tokens, logprobs = bq["tokens"][:n * B].cpu(), bq["logprobs"][:n * B].cpu()
         hist = lambda name, *tail: bq[name][:n * L * B * math.prod(tail)].view(n, L, B, *tail)
-        parents, h_tok, h_lp = hist("parents"), hist("hist_tokens", S), hist("hist_logprobs", S)
-        eos = d["vocab"] - 1
-        out = []
-        for u in range(n):
-            T = rec[u][4]
-            lengths = lengths_all[u * B:(u + 1) * B]
-            order = beam_rank(scores[u * B:(u + 1) * B], lengths, S, length_penalty)
-            hyps = []
-            for i in order:
-                streams = tokens[u * B + i, :, :lengths[i]].clone()
-                after = (streams == eos).cumsum(dim=-1) > 0          # mask_after_eos (text2semantic.py:73-76)
-                after = torch.nn.functional.pad(after, (1, -1), value=False)
-                flat = streams.masked_fill(after, PAD_ID).reshape(-1)
-                hyps.append((flat[flat != PAD_ID], streams, logprobs[u * B + i, :, :lengths[i]].clone(), float(scores[u * B + i])))
-            out.append(hyps)
-            self.last_beam.append(dict(steps=T, order=order, lengths=lengths, scores=scores[u * B:(u + 1) * B].clone(),
-                                       parents=parents[u, :T].cpu(), tokens=h_tok[u, :T].cpu(), logprobs=h_lp[u, :T].cpu(),
-                                       status=rec[u][3], group=rec[u][5]))
-        return out
+        return self._beam_results(B, length_penalty, bq["final_scores"][:n * B].cpu(), bq["final_steps"][:n * B].tolist(), bq["tokens"][:n * B].cpu(),
+                                  bq["logprobs"][:n * B].cpu(), hist("parents"), hist("hist_tokens", S), hist("hist_logprobs", S),
+                                  [row[4] for row in rec], [(row[3], row[5]) for row in rec])
 
     @ops.gated
     @torch.no_grad()
