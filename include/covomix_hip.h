@@ -75,7 +75,9 @@ typedef const cvx_ctx* cvx_stream_t;
  * per lane (same values, same addresses); CVX_GEMM_FLAG_VT_PIECES keeps the earlier store code selectable.  Still 113 (a symbol and a
  * struct added): cvx_t2s_decode_steps_mixed with cvx_t2s_mixed - guided and unguided dialogues in one slot pool; slot record [7], so
  * far reserved, carries a slot's role there.  Still 113 (two symbols added, no struct changed): cvx_t2s_beam_guided_steps and
- * cvx_t2s_beam_guided_queue_steps - beam search under classifier-free guidance, on the structs of the unguided entry points. */
+ * cvx_t2s_beam_guided_queue_steps - beam search under classifier-free guidance, on the structs of the unguided entry points.  Still 113
+ * (two symbols and a struct added): cvx_t2s_decode_steps_rules with cvx_t2s_rules, cvx_t2s_rules_f32 - repetition penalty, no-repeat
+ * n-gram and minimum length per dialogue; cvx_t2s_per_dialogue and its rows are untouched. */
 #define CVX_ABI_VERSION 113
 int         cvx_version(void);
 const char* cvx_last_error_string(void);
@@ -860,6 +862,43 @@ typedef struct cvx_t2s_mixed {
 
 int cvx_t2s_decode_steps_mixed(const cvx_t2s_decoder* dec, const cvx_t2s_scoring* scoring, const cvx_t2s_per_dialogue* per,
                                const cvx_t2s_mixed* mixed, int32_t n_steps, cvx_stream_t stream);
+
+/* History rules: the chain of cvx_t2s_decode_steps_per_dialogue (mixed == NULL) or of cvx_t2s_decode_steps_mixed (mixed != NULL), ending
+ * in sampling kernels that first change the row the filter sees by what the stream has ALREADY EMITTED.  Still ABI 113: symbols and a struct
+ * added; cvx_t2s_per_dialogue, its 8-word rows and every other entry point are untouched.
+ *   rules->table [n_records][4] 32-bit words, one row per dialogue record, indexed like the settings table (a null half mirrors its text half):
+ *     [0] float theta   repetition penalty, > 0; 1 is off        [1] int32 window W >= 0; 0 = the whole history
+ *     [2] int32 ngram   n in 0..8; 0 is off                      [3] int32 min_len m >= 0
+ *   Per output stream s of a dialogue at position pos, h = tokens[dialogue][s][0, pos) - the stream's own token row, a forced prefix
+ *   included; a refilled slot names a new dialogue and so starts with an empty history.  On the row the filter would see (the
+ *   guidance-combined row for a pair), in this order, before the filter, the temperature and the noise:
+ *     1. every id that occurs in h[max(0, pos - W), pos) is penalised ONCE: l = l > 0 ? l / theta : l * theta (an IEEE fp32 division);
+ *     2. for every j in [0, pos - n] with h[j, j + n - 1) == h[pos - n + 1, pos) the id h[j + n - 1] becomes -inf (n = 1: every id of h);
+ *     3. while pos < m the eos (vocab - 1) becomes -inf.
+ *   If no entry is finite after 3, the bans of 2 are void for this step; 1 and 3 stay.  The eos is an id like any other for 1 and 2.
+ *   Given steps (a prefix, a forced dialogue) select nothing: the rules do not act there.  Log-probabilities stay the model's: with
+ *   scoring they are the log-softmax of the row BEFORE the rules, so they equal, bit for bit, the teacher-forced log-probs of the same tokens.
+ *   A neutral row (theta = 1, n = 0, m = 0) gives the tokens and log-probs of the chain without rules, bit for bit.
+ *   Clamps: the device takes n into [0, 8], W and m into [0, max_len], theta <= 0 or NaN as 1, a record number outside the table onto its
+ *   first / last row, and an id outside [0, vocab) in the history marks nothing.
+ * No host synchronisation; graph-capturable; the launches of the chain it stands for.  CVX_EINVAL, nothing launched: struct_size !=
+ * sizeof(cvx_t2s_rules), rules or table NULL, n_records < 1 or below what `per` must hold (dec->n_dialogues; without a queue dec->batch),
+ * and everything cvx_t2s_decode_steps_per_dialogue (mixed == NULL) or cvx_t2s_decode_steps_mixed refuses. */
+typedef struct cvx_t2s_rules {
+    uint32_t struct_size;
+    int32_t n_records;
+    const void* table;
+} cvx_t2s_rules;
+
+int cvx_t2s_decode_steps_rules(const cvx_t2s_decoder* dec, const cvx_t2s_scoring* scoring, const cvx_t2s_per_dialogue* per,
+                               const cvx_t2s_mixed* mixed, const cvx_t2s_rules* rules, int32_t n_steps, cvx_stream_t stream);
+
+/* The history rules alone, through the device code of the decode: out[r] = the row the filter would see for logits[r] [V <= 1024] after
+ * the rules of table[r] (4 words, above; W and m only clamped at 0), with h = history[r][0, hist_len[r]) (int64 [rows, hist_ld]; hist_len
+ * clamped into [0, hist_ld]; history may be NULL when hist_ld == 0) and pos = hist_len[r].  The inputs are not written.  CVX_EINVAL: a NULL
+ * pointer, rows < 0, V outside [1, 1024], hist_ld < 0. */
+int cvx_t2s_rules_f32(const float* logits, const int64_t* history, const int32_t* hist_len, const void* table, int64_t rows, int32_t V,
+                      int32_t hist_ld, int32_t eos_id, float* out, cvx_stream_t stream);
 
 /* Beam search on the decode slots - the deterministic decode behind the reference's beam_search_decode flag, which its generate accepts
  * and never implements (text2semantic.py:673-677): the algorithm below is this library's definition.

@@ -173,6 +173,16 @@ class T2SMixed(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("n_guided", C.c_int32)]
 
 
+class T2SRules(C.Structure):
+    """cvx_t2s_rules: struct_size = sizeof(this); table [n_records, 4] 32-bit words on the device, one row per dialogue record:
+    [0] float theta (repetition penalty) [1] int32 window [2] int32 no-repeat n-gram size [3] int32 minimum length"""
+    _fields_ = [("struct_size", C.c_uint32), ("n_records", C.c_int32), ("table", C.c_void_p)]
+
+
+T2S_RULES_WORDS = 4                              # 32-bit words per row of that table
+T2S_RULES_MAX_NGRAM = 8
+
+
 class T2SBeam(C.Structure):
     """cvx_t2s_beam: struct_size = sizeof(this); device state of the beam chain (include/covomix_hip.h)"""
     _fields_ = [("struct_size", C.c_uint32), ("beam_size", C.c_int32), ("hist_len", C.c_int32), ("backtrack", C.c_int32)] + \
@@ -236,6 +246,10 @@ SIGNATURES = {
                                                     C.c_void_p]),
     "cvx_t2s_decode_steps_mixed": (C.c_int, [C.POINTER(T2SDecoder), C.POINTER(T2SScoring), C.POINTER(T2SPerDialogue), C.POINTER(T2SMixed),
                                              C.c_int32, C.c_void_p]),
+    "cvx_t2s_decode_steps_rules": (C.c_int, [C.POINTER(T2SDecoder), C.POINTER(T2SScoring), C.POINTER(T2SPerDialogue), C.POINTER(T2SMixed),
+                                             C.POINTER(T2SRules), C.c_int32, C.c_void_p]),
+    "cvx_t2s_rules_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
+                                    C.c_void_p]),
     "cvx_t2s_beam_steps": (C.c_int, [C.POINTER(T2SDecoder), C.POINTER(T2SBeam), C.c_int32, C.c_void_p]),
     "cvx_t2s_beam_queue_steps": (C.c_int, [C.POINTER(T2SDecoder), C.POINTER(T2SBeam), C.POINTER(T2SBeamQueue), C.c_int32, C.c_void_p]),
     "cvx_t2s_beam_guided_steps": (C.c_int, [C.POINTER(T2SDecoder), C.POINTER(T2SBeam), C.c_int32, C.c_void_p]),

@@ -245,7 +245,7 @@ class CoVoMixModel:
                                        prompt_mel=None, uniforms=None, generator=None, max_length=None, slots=64,
                                        filter_logits_fn="top_k", filter_fn_kwargs=None, return_logprobs=False, best_of=1,
                                        beam_size=10, length_penalty=1.0, prefix=None, best_of_temperatures=None, mixed_guidance=False,
-                                       guided_beam=False):
+                                       guided_beam=False, repetition_penalty=1.0, repetition_window=0, no_repeat_ngram_size=0, min_length=0):
         """reference conditional_model.py:313-321 -> TextToSemanticWrapper.sample (text2semantic.py:1237-1251): the
         sampled semantic tokens as one flat int64 tensor (two-output models: stream 1 then stream 2) on the input's
         device.  (`temprature` is the reference's spelling.)  `uniforms` / `generator` (optional) fix the U(0,1) draws
@@ -278,13 +278,19 @@ class CoVoMixModel:
         the result starts with them (t2s.generate_many(prefixes=...)).
         best_of_temperatures (extension): a sequence of N temperatures - best_of = N with candidate c of every utterance decoded at
         temperature c, all in the one generate_many call of best_of; a best_of other than 1 or N is a ValueError.
+        repetition_penalty / repetition_window / no_repeat_ngram_size / min_length (extension; t2s.generate_batch, t2s.check_rules): the
+        history rules of the decode - a penalty on every id a stream has emitted in its last `repetition_window` tokens (0: all), no
+        n-gram twice in a stream, no eos below min_length.  Scalars, or - with a list of texts - lists of the same length (per-utterance
+        settings, as above).  All off by default: the call is then what it was.  Log-probs stay those of the model's unmodified rows.
         None of these combines with beam search (ValueError)."""
         if not self.is_text2semantic:
             raise TypeError("this checkpoint is an acoustic model: use synthesis_sample")
         ids = grapheme_token_ids
         many = isinstance(ids, (list, tuple))
         lists = {k: list(v) for k, v in (("temperature", temprature), ("cond_scale", cond_scale), ("filter_logits_fn", filter_logits_fn),
-                                         ("filter_fn_kwargs", filter_fn_kwargs)) if isinstance(v, (list, tuple))}
+                                         ("filter_fn_kwargs", filter_fn_kwargs), ("repetition_penalty", repetition_penalty),
+                                         ("repetition_window", repetition_window), ("no_repeat_ngram_size", no_repeat_ngram_size),
+                                         ("min_length", min_length)) if isinstance(v, (list, tuple))}
         for k, v in lists.items():
             if not many or len(v) != len(ids):
                 raise ValueError(f"a list of {k} values goes with a list of texts of the same length ({len(v)} values, "
@@ -304,9 +310,21 @@ class CoVoMixModel:
             filter_logits_fn = lists.pop("filter_logits_fn")[0]
         if lists.get("filter_fn_kwargs") and all(x == lists["filter_fn_kwargs"][0] for x in lists["filter_fn_kwargs"]):
             filter_fn_kwargs = lists.pop("filter_fn_kwargs")[0]
+        # the history rules: a list whose entries are all equal is its scalar; a scalar that is off is not passed on (the call as it was)
+        rule_kw = dict(repetition_penalty=repetition_penalty, repetition_window=repetition_window, no_repeat_ngram_size=no_repeat_ngram_size,
+                       min_length=min_length)
+        for k in list(rule_kw):
+            if lists.get(k) and all(x == lists[k][0] for x in lists[k]):
+                rule_kw[k] = lists.pop(k)[0]
+        from .t2s import RULE_FIELDS, RULES_OFF, best_candidate, check_beam_size, check_best_of, check_rules, sequence_logprob
+        rule_kw = {k: v for k, v in rule_kw.items() if k not in lists}
+        check_rules(None, 1, 1 << 30, **rule_kw)
+        rule_kw = {k: v for k, v in rule_kw.items() if v != RULES_OFF[RULE_FIELDS.index(k)]}
         per = bool(lists) or prefix is not None or best_of_temperatures is not None
-        from .t2s import best_candidate, check_beam_size, check_best_of, sequence_logprob
         if beam_search_decode:
+            if rule_kw or any(k in lists for k in RULE_FIELDS):
+                raise ValueError("beam search does not run the history rules (repetition_penalty, repetition_window, no_repeat_ngram_size, "
+                                 "min_length): leave them off, or sample")
             if per:
                 raise ValueError("beam search takes no per-utterance settings, no prefix and no best_of_temperatures")
             if uniforms is not None or generator is not None:
@@ -361,7 +379,7 @@ class CoVoMixModel:
                                           filter_logits_fn="top_k" if "filter_logits_fn" in lists else filter_logits_fn,
                                           filter_fn_kwargs=None if "filter_logits_fn" in lists or "filter_fn_kwargs" in lists else filter_fn_kwargs,
                                           return_logprobs=bool(return_logprobs) or N > 1, settings=sets, prefixes=pres,
-                                          **({"mixed_guidance": True} if mixed_guidance else {}))
+                                          **({"mixed_guidance": True} if mixed_guidance else {}), **rule_kw)
             eos = self._t2s.d["vocab"] - 1
             out = []
             for j, i in enumerate(ids_l):
@@ -377,7 +395,7 @@ class CoVoMixModel:
                 us = [u[c] for u in (list(uniforms) if many else [uniforms]) for c in range(N)]
             res = self._t2s.generate_many([i for i in ids_l for _ in range(N)], us, max_length, float(temprature), generator, slots=slots,
                                           cond_scale=float(cond_scale), filter_logits_fn=filter_logits_fn, filter_fn_kwargs=filter_fn_kwargs,
-                                          return_logprobs=True)
+                                          return_logprobs=True, **rule_kw)
             eos = self._t2s.d["vocab"] - 1
             out = []
             for j, i in enumerate(ids_l):
@@ -390,18 +408,18 @@ class CoVoMixModel:
             # any number of utterances through 64 continuously refilled decode slots (guidance: 32 slot pairs)
             if return_logprobs:
                 res = self._t2s.generate_many(ids, uniforms, max_length, float(temprature), generator, slots=slots, cond_scale=float(cond_scale),
-                                              filter_logits_fn=filter_logits_fn, filter_fn_kwargs=filter_fn_kwargs, return_logprobs=True)
+                                              filter_logits_fn=filter_logits_fn, filter_fn_kwargs=filter_fn_kwargs, return_logprobs=True, **rule_kw)
                 return [tuple(t.to(i.device) for t in r) for r, i in zip(res, ids)]
             res = self._t2s.generate_many(ids, uniforms, max_length, float(temprature), generator, slots=slots, cond_scale=float(cond_scale),
-                                          filter_logits_fn=filter_logits_fn, filter_fn_kwargs=filter_fn_kwargs)
+                                          filter_logits_fn=filter_logits_fn, filter_fn_kwargs=filter_fn_kwargs, **rule_kw)
             return [r[0].to(i.device) for r, i in zip(res, ids)]
         if return_logprobs:
             res = self._t2s.generate(ids, uniforms=uniforms, max_length=max_length, temperature=float(temprature), generator=generator,
                                      cond_scale=float(cond_scale), filter_logits_fn=filter_logits_fn, filter_fn_kwargs=filter_fn_kwargs,
-                                     return_logprobs=True)
+                                     return_logprobs=True, **rule_kw)
             return tuple(t.to(ids.device) for t in res)
         out = self._t2s.generate(ids, uniforms=uniforms, max_length=max_length, temperature=float(temprature), generator=generator,
-                                 cond_scale=float(cond_scale), filter_logits_fn=filter_logits_fn, filter_fn_kwargs=filter_fn_kwargs)
+                                 cond_scale=float(cond_scale), filter_logits_fn=filter_logits_fn, filter_fn_kwargs=filter_fn_kwargs, **rule_kw)
         return out.to(ids.device) if ids.device != out.device else out
 
     @ops.gated

@@ -27,6 +27,10 @@
 //   sample_mixed_kernel, mixed_schedule_kernel   guided and unguided dialogues in one slot pool (cvx_t2s_decode_steps_mixed): a slot's
 //                       role (single / text half / null half) comes from its record, and a one-block launch after the sampling
 //                       kernel hands the idle slots the next records - a guided record takes two slots, wherever they are.
+//   sample_rules_kernel, sample_mixed_rules_kernel   those two under the HISTORY RULES of the dialogue (cvx_t2s_decode_steps_rules): repetition
+//                       penalty, no-repeat n-gram and minimum length from the stream's own token row - per-id marks in LDS (rules_marks), the
+//                       ruled row staged in place of the plain one (rules_stage), then the same filter and argmax; rules_rows_kernel: the
+//                       rules alone (cvx_t2s_rules_f32).
 // BEAM SEARCH (cvx_t2s_beam_steps; the algorithm: include/covomix_hip.h): the B hypotheses of an utterance sit in B neighbouring slots and
 // continue from each other's KV caches through an ancestry table - no cache row is ever copied:
 //   attn_owner_kernel      attn_kernel's body with key / value j read from the cache of slot owner[j] (the row staged in LDS);
@@ -45,7 +49,7 @@
 //                          records, the next input (one embedding row into both x rows) and the ancestry rows (text row from the parent's text
 //                          row, null row from its null row) for both halves; the queue form re-arms both halves of a refilled group.
 //                          The back-track kernels are shared: their rows are hypotheses either way.
-// ONE BODY PER STEP: the three sampling kernels instantiate sample_step, the four merge kernels beam_merge_step, the two back-track kernels
+// ONE BODY PER STEP: the five sampling kernels instantiate sample_step, the four merge kernels beam_merge_step, the two back-track kernels
 // beam_backtrack_step.  What such sharing does to a kernel is read from the compiler (tools/kernel_text_diff.py against the parent's
 // assembly), not assumed: the default chain's kernels keep their instruction text (tests/test_t2s_code_objects.py holds their resources).
 // The reference rotates ALL cached keys again every step with rotary_embedding_torch's interleaved pairs
@@ -733,6 +737,87 @@ __device__ __forceinline__ float row_logprob(const float* lg, int V, int tok, fl
     return threadIdx.x < 64 ? (lg[tok] - m) - logf(sum) : 0.f;
 }
 
+// ---- history rules (cvx_t2s_decode_steps_rules, cvx_t2s_rules_f32; the definition: include/covomix_hip.h): what an output stream has
+// emitted so far - its own token row at positions [0, pos), a forced prefix included - changes the row the filter sees, in this order:
+// repetition penalty, no-repeat n-gram, minimum length.  Part of the SELECTION, like the filter: log-probs stay those of the unmodified row.
+struct RulesArgs {
+    const int* table;        // [n_records][RULES_WORDS] 32-bit words: [0] float theta [1] int window [2] int ngram [3] int min_len
+    int n_records;
+};
+constexpr int RULES_WORDS = 4;
+constexpr int RULES_MAX_NGRAM = 8;
+struct Rules { float theta; int W, n, m; };
+
+// a table row with stray values clamped (they index nothing either way): n into [0, 8], W and m into [0, cap], theta <= 0 or NaN -> 1 (off)
+__device__ __forceinline__ Rules rules_row(const int* row, int cap)
+{
+    Rules r;
+    r.theta = __int_as_float(row[0]);
+    if (!(r.theta > 0.f)) r.theta = 1.f;
+    r.W = min(max(row[1], 0), cap);
+    r.n = min(max(row[2], 0), RULES_MAX_NGRAM);
+    r.m = min(max(row[3], 0), cap);
+    return r;
+}
+
+// Per-id marks of the history h[0, pos) in LDS (pen, ban: 1024 bytes each; two arrays of bytes, every store writes a 1: no read-modify-write):
+//   pen[t]  t occurs in h[max(0, pos - W), pos)  (W = 0: in all of h)
+//   ban[t]  t = h[e] for a position e in [n - 1, pos) whose n - 1 predecessors equal the last n - 1 tokens of h (n = 1: every id of h)
+// tid strides over the positions; an id outside [0, V) marks nothing.  The history was written by earlier launches on the stream (or by
+// the host): plain loads.  Synchronises before it returns.
+template <int NT>
+__device__ __forceinline__ void rules_marks(const int64_t* h, int pos, int V, const Rules& r, uint8_t* pen, uint8_t* ban)
+{
+    const int tid = threadIdx.x;
+    for (int i = tid; i < 1024; i += NT) { pen[i] = 0; ban[i] = 0; }
+    __syncthreads();
+    const int lo = r.W > 0 ? max(0, pos - r.W) : 0;
+    const int n1 = r.n - 1;
+    for (int e = tid; e < pos; e += NT) {
+        const int64_t t = h[e];
+        if (t < 0 || t >= V) continue;
+        if (e >= lo) pen[t] = 1;
+        if (r.n >= 1 && e >= n1) {
+            bool same = true;
+            for (int i = 0; i < n1; ++i) same = same && h[e - n1 + i] == h[pos - n1 + i];
+            if (same) ban[t] = 1;
+        }
+    }
+    __syncthreads();
+}
+
+// entry i of the row the filter sees under the rules: stage_row's value, the penalty (an IEEE division), the eos below the minimum length, the ban
+__device__ __forceinline__ float rules_value(const float* lrow, const float* nrow, float cfg_scale, int i, float theta, bool pen, bool no_eos, bool ban)
+{
+    float l = aload(lrow + i);
+    if (nrow) {
+        const float n = aload(nrow + i);
+        l = n + (l - n) * cfg_scale;
+    }
+    if (pen) l = l > 0.f ? __fdiv_rn(l, theta) : l * theta;
+    return (no_eos || ban) ? -INFINITY : l;
+}
+
+// stage_row under the rules: lg[0, V) from the marks.  When no entry is finite afterwards the n-gram bans of this step are void: the banned
+// entries are staged again without the ban (the penalty and the eos suppression stay).  lg: 1024 floats of LDS; synchronises before it returns.
+template <int NT>
+__device__ __forceinline__ void rules_stage(const float* lrow, const float* nrow, float cfg_scale, int V, int pos, int eos_id, const Rules& r,
+                                            const uint8_t* pen, const uint8_t* ban, float* lg)
+{
+    const int tid = threadIdx.x;
+    int finite = 0;
+    for (int i = tid; i < V; i += NT) {
+        const float l = rules_value(lrow, nrow, cfg_scale, i, r.theta, pen[i] != 0, i == eos_id && pos < r.m, ban[i] != 0);
+        lg[i] = l;
+        finite |= (l - l == 0.f) ? 1 : 0;               // (neither an infinity nor a NaN)
+    }
+    if (!__syncthreads_or(finite)) {                    // (block-uniform)
+        for (int i = tid; i < V; i += NT)
+            if (ban[i]) lg[i] = rules_value(lrow, nrow, cfg_scale, i, r.theta, pen[i] != 0, i == eos_id && pos < r.m, false);
+    }
+    __syncthreads();
+}
+
 // per-dialogue settings (cvx_t2s_decode_steps_per_dialogue, cvx_t2s_decode_steps_mixed)
 struct PerArgs {
     const int* table;        // [n_records][PER_WORDS] 32-bit words: [0] float inv_temp [1] int filter mode [2] int top_k [3] float top_p
@@ -768,10 +853,15 @@ template <bool MIXED> __device__ __forceinline__ int null_slot(int b, int pb)
 //               records is the business of mixed_schedule_kernel, the launch that follows: a guided head needs TWO idle slots, which no
 //               single block can know.  That launch clears the null half's role too, not this one: the null half's own block may be reading
 //               it now, and with the role unchanged every word a block decides by is its own slot's or constant during the launch (no fences).
-// lg, ex: 1024 floats (ex: FILT_TOP_P, PER or LOGP only), bv / bi: 16 entries, chosen: one int of LDS.
-template <int NT, int FILT, bool LOGP, bool PER, bool MIXED>
-__device__ __forceinline__ void sample_step(const SampleArgs& a, const PerArgs& p, int b, float* lg, float* ex, float* bv, int* bi, int* chosen)
+//   RULES       (with PER) the HISTORY RULES of the dialogue's row of the rules table, on sampled steps only: the marks of the stream's own
+//               token row below pos, the ruled row staged into lg, then sample_select as it is, reading that row from lg (every thread
+//               copies its own entries onto themselves).  LOGP: the unmodified row is staged again before the epilogue - the given-step path.
+// lg, ex: 1024 floats (ex: FILT_TOP_P, PER or LOGP only), bv / bi: 16 entries, chosen: one int of LDS; pen, ban: 1024 bytes each (RULES only).
+template <int NT, int FILT, bool LOGP, bool PER, bool MIXED, bool RULES = false>
+__device__ __forceinline__ void sample_step(const SampleArgs& a, const PerArgs& p, int b, float* lg, float* ex, float* bv, int* bi, int* chosen,
+                                            const RulesArgs* ru = nullptr, uint8_t* pen = nullptr, uint8_t* ban = nullptr)
 {
+    static_assert(!RULES || PER, "the rules chain reads its settings per dialogue");
     const int tid = threadIdx.x;
     const bool cfg = !MIXED && a.cfg_scale > 1.0f;
     if (cfg && (b & 1)) return;                     // the null-context slot follows its partner (block-uniform)
@@ -809,6 +899,14 @@ __device__ __forceinline__ void sample_step(const SampleArgs& a, const PerArgs& 
             tok = (int)min((int64_t)(a.V - 1), max((int64_t)0, a.tokens[(dlg * a.streams + s) * a.max_len + pos]));
         } else {
             const float* const urow = a.uniforms + ((dlg * a.uniform_steps + pos) * a.streams + s) * a.V;
+            if constexpr (RULES) {
+                const Rules r = rules_row(ru->table + (int64_t)RULES_WORDS * min((int64_t)(ru->n_records - 1), max((int64_t)0, dlg)), a.max_len);
+                rules_marks<NT>(a.tokens + (dlg * a.streams + s) * a.max_len, pos, a.V, r, pen, ban);
+                rules_stage<NT>(lrow, nrow, scale, a.V, pos, a.eos_id, r, pen, ban, lg);
+                if (nucleus) tok = sample_select<NT, FILT_TOP_P, false>(lg, nullptr, 1.f, urow, a.V, top_k, top_p, inv_temp, nullptr, lg, ex, bv, bi, chosen);
+                else tok = sample_select<NT, FILT_TOP_K, false>(lg, nullptr, 1.f, urow, a.V, top_k, top_p, inv_temp, nullptr, lg, ex, bv, bi, chosen);
+                if (LOGP) stage_row<NT>(lrow, nrow, scale, a.V, lg);
+            } else
             if constexpr (!PER) tok = sample_select<NT, FILT, false>(lrow, nrow, scale, urow, a.V, top_k, top_p, inv_temp, nullptr, lg, ex, bv, bi, chosen);
             else if (nucleus) tok = sample_select<NT, FILT_TOP_P, false>(lrow, nrow, scale, urow, a.V, top_k, top_p, inv_temp, nullptr, lg, ex, bv, bi, chosen);
             else tok = sample_select<NT, FILT_TOP_K, false>(lrow, nrow, scale, urow, a.V, top_k, top_p, inv_temp, nullptr, lg, ex, bv, bi, chosen);
@@ -937,6 +1035,53 @@ __global__ __launch_bounds__(1024) void sample_mixed_kernel(const SampleArgs a, 
     __shared__ int bi[16];
     __shared__ int chosen;
     sample_step<1024, FILT_TOP_K, LOGP, true, true>(a, p, blockIdx.x, lg, ex, bv, bi, &chosen);
+}
+
+// the per-dialogue and the mixed chain under the history rules (cvx_t2s_decode_steps_rules)
+template <bool LOGP>
+__global__ __launch_bounds__(1024) void sample_rules_kernel(const SampleArgs a, const PerArgs p, const RulesArgs ru)
+{
+    __shared__ __attribute__((aligned(16))) float lg[1024];
+    __shared__ __attribute__((aligned(16))) float ex[1024];
+    __shared__ float bv[16];
+    __shared__ int bi[16];
+    __shared__ int chosen;
+    __shared__ uint8_t pen[1024], ban[1024];
+    sample_step<1024, FILT_TOP_K, LOGP, true, false, true>(a, p, blockIdx.x, lg, ex, bv, bi, &chosen, &ru, pen, ban);
+}
+
+template <bool LOGP>
+__global__ __launch_bounds__(1024) void sample_mixed_rules_kernel(const SampleArgs a, const PerArgs p, const RulesArgs ru)
+{
+    __shared__ __attribute__((aligned(16))) float lg[1024];
+    __shared__ __attribute__((aligned(16))) float ex[1024];
+    __shared__ float bv[16];
+    __shared__ int bi[16];
+    __shared__ int chosen;
+    __shared__ uint8_t pen[1024], ban[1024];
+    sample_step<1024, FILT_TOP_K, LOGP, true, true, true>(a, p, blockIdx.x, lg, ex, bv, bi, &chosen, &ru, pen, ban);
+}
+
+// the history rules alone: one block per row, no slot state (cvx_t2s_rules_f32)
+struct RulesRowsArgs {
+    const float* logits;     // [rows, V]
+    const int64_t* history;  // [rows, hist_ld]
+    const int* hist_len;     // [rows]: pos, clamped into [0, hist_ld]
+    const int* table;        // [rows][RULES_WORDS]
+    float* out;              // [rows, V]
+    int V, hist_ld, eos_id;
+};
+
+__global__ __launch_bounds__(1024) void rules_rows_kernel(const RulesRowsArgs a)
+{
+    __shared__ __attribute__((aligned(16))) float lg[1024];
+    __shared__ uint8_t pen[1024], ban[1024];
+    const int64_t r = blockIdx.x;
+    const int pos = min(max(a.hist_len[r], 0), a.hist_ld);
+    const Rules ru = rules_row(a.table + RULES_WORDS * r, 0x7fffffff);
+    rules_marks<1024>(a.history + r * a.hist_ld, pos, a.V, ru, pen, ban);
+    rules_stage<1024>(a.logits + r * a.V, nullptr, 1.f, a.V, pos, a.eos_id, ru, pen, ban, lg);
+    for (int i = threadIdx.x; i < a.V; i += 1024) a.out[r * a.V + i] = lg[i];
 }
 
 // The scheduler of the mixed pool: ONE block, launched after sample_mixed_kernel (the kernel boundary makes every record write of that
@@ -1599,6 +1744,7 @@ struct T2sSelect {
     } kind;
     float* logprobs;         // SAMPLE / PER / MIXED: non-NULL picks the scoring instantiation
     PerArgs per;             // PER / MIXED
+    RulesArgs rules;         // PER / MIXED: a table (cvx_t2s_decode_steps_rules) picks the kernels that apply the history rules
     const cvx_t2s_beam* bm;  // BEAM / BEAM_QUEUE
     BeamQueueArgs bq;        // BEAM_QUEUE
     bool guided;             // BEAM / BEAM_QUEUE: cvx_t2s_beam_guided_steps / _queue_steps - a hypothesis is a slot pair, the shortlist reads the
@@ -1676,7 +1822,14 @@ static int t2s_decode_run(const cvx_t2s_decoder* d, int32_t n_steps, const T2sSe
         }
         const SampleArgs sa = sample_args(d, sel.logprobs);
         const bool top_p = d->filter_mode == CVX_T2S_FILTER_TOP_P;
-        if (sel.kind == T2sSelect::MIXED) {
+        if (sel.rules.table) {
+            if (sel.kind == T2sSelect::MIXED) {
+                if (sel.logprobs) hipLaunchKernelGGL(sample_mixed_rules_kernel<true>, slots, block, 0, st, sa, sel.per, sel.rules);
+                else hipLaunchKernelGGL(sample_mixed_rules_kernel<false>, slots, block, 0, st, sa, sel.per, sel.rules);
+                hipLaunchKernelGGL(mixed_schedule_kernel, dim3(1), block, 0, st, sa);
+            } else if (sel.logprobs) hipLaunchKernelGGL(sample_rules_kernel<true>, slots, block, 0, st, sa, sel.per, sel.rules);
+            else hipLaunchKernelGGL(sample_rules_kernel<false>, slots, block, 0, st, sa, sel.per, sel.rules);
+        } else if (sel.kind == T2sSelect::MIXED) {
             if (sel.logprobs) hipLaunchKernelGGL(sample_mixed_kernel<true>, slots, block, 0, st, sa, sel.per);
             else hipLaunchKernelGGL(sample_mixed_kernel<false>, slots, block, 0, st, sa, sel.per);
             hipLaunchKernelGGL(mixed_schedule_kernel, dim3(1), block, 0, st, sa);
@@ -1784,23 +1937,63 @@ extern "C" int cvx_t2s_decode_steps_per_dialogue(const cvx_t2s_decoder* d, const
     return t2s_decode_run(d, n_steps, sel, s);
 }
 
+// cvx_t2s_mixed, with the settings table and the optional scoring block of the mixed chain
+static int t2s_mixed_block(const char* who, const cvx_t2s_decoder* d, const cvx_t2s_scoring* sc, const cvx_t2s_per_dialogue* per,
+                           const cvx_t2s_mixed* mx, T2sSelect& sel)
+{
+    T2S_TRY(t2s_struct_size(who, "cvx_t2s_mixed", mx));
+    CVX_REQUIRE(d->queue, "%s: the scheduler hands out records from the dialogue queue (queue must not be NULL)", who);
+    CVX_REQUIRE(!(d->cfg_scale > 1.f), "%s: cfg_scale = %g > 1 asks for the launch-wide pair layout; here the layout is per "
+                "record (flag bit 2) and the scale comes from the table", who, (double)d->cfg_scale);
+    T2S_TRY(t2s_per_dialogue_block(who, d, per, sel));
+    T2S_TRY(t2s_scoring_block(who, d, sc, true, sel));
+    CVX_REQUIRE(mx->n_guided >= 0 && 2 * (int64_t)mx->n_guided <= d->n_dialogues,
+                "%s: n_guided = %d guided utterances take two records each of the %d", who, mx->n_guided, d->n_dialogues);
+    CVX_REQUIRE(mx->n_guided == 0 || (d->streams == 1 && d->batch >= 2),
+                "%s: guided records need a one-output model and two slots (streams = %d, batch = %d)", who, d->streams, d->batch);
+    return CVX_OK;
+}
+
 extern "C" int cvx_t2s_decode_steps_mixed(const cvx_t2s_decoder* d, const cvx_t2s_scoring* sc, const cvx_t2s_per_dialogue* per,
                                           const cvx_t2s_mixed* mx, int32_t n_steps, cvx_stream_t s)
 {
     const char* const who = "t2s_decode_mixed";
     T2sSelect sel{T2sSelect::MIXED};
     T2S_TRY(t2s_validate(d, n_steps, true));
-    T2S_TRY(t2s_struct_size(who, "cvx_t2s_mixed", mx));
-    CVX_REQUIRE(d->queue, "t2s_decode_mixed: the scheduler hands out records from the dialogue queue (queue must not be NULL)");
-    CVX_REQUIRE(!(d->cfg_scale > 1.f), "t2s_decode_mixed: cfg_scale = %g > 1 asks for the launch-wide pair layout; here the layout is per "
-                "record (flag bit 2) and the scale comes from the table", (double)d->cfg_scale);
-    T2S_TRY(t2s_per_dialogue_block(who, d, per, sel));
-    T2S_TRY(t2s_scoring_block(who, d, sc, true, sel));
-    CVX_REQUIRE(mx->n_guided >= 0 && 2 * (int64_t)mx->n_guided <= d->n_dialogues,
-                "t2s_decode_mixed: n_guided = %d guided utterances take two records each of the %d", mx->n_guided, d->n_dialogues);
-    CVX_REQUIRE(mx->n_guided == 0 || (d->streams == 1 && d->batch >= 2),
-                "t2s_decode_mixed: guided records need a one-output model and two slots (streams = %d, batch = %d)", d->streams, d->batch);
+    T2S_TRY(t2s_mixed_block(who, d, sc, per, mx, sel));
     return t2s_decode_run(d, n_steps, sel, s);
+}
+
+// the per-dialogue chain (mx == NULL) or the mixed chain under the history rules: one rules row per row of the settings table
+extern "C" int cvx_t2s_decode_steps_rules(const cvx_t2s_decoder* d, const cvx_t2s_scoring* sc, const cvx_t2s_per_dialogue* per,
+                                          const cvx_t2s_mixed* mx, const cvx_t2s_rules* ru, int32_t n_steps, cvx_stream_t s)
+{
+    const char* const who = "t2s_decode_rules";
+    T2sSelect sel{mx ? T2sSelect::MIXED : T2sSelect::PER};
+    T2S_TRY(t2s_validate(d, n_steps, true));
+    if (mx) T2S_TRY(t2s_mixed_block(who, d, sc, per, mx, sel));
+    else {
+        T2S_TRY(t2s_per_dialogue_block(who, d, per, sel));
+        T2S_TRY(t2s_scoring_block(who, d, sc, true, sel));
+    }
+    T2S_TRY(t2s_struct_size(who, "cvx_t2s_rules", ru));
+    CVX_REQUIRE(ru->table && ru->n_records >= 1, "%s: null rules table or n_records = %d < 1", who, ru->n_records);
+    CVX_REQUIRE(ru->n_records >= d->n_dialogues && (d->queue || ru->n_records >= d->batch),
+                "%s: rules n_records = %d rows for %d dialogue records / %d slots", who, ru->n_records, d->n_dialogues, d->batch);
+    sel.rules = RulesArgs{static_cast<const int*>(ru->table), ru->n_records};
+    return t2s_decode_run(d, n_steps, sel, s);
+}
+
+extern "C" int cvx_t2s_rules_f32(const float* logits, const int64_t* history, const int32_t* hist_len, const void* table, int64_t rows,
+                                 int32_t V, int32_t hist_ld, int32_t eos_id, float* out, cvx_stream_t s)
+{
+    CVX_REQUIRE(logits && hist_len && table && out && rows >= 0 && rows <= 0x7fffffff && V >= 1 && V <= 1024 && hist_ld >= 0 &&
+                (history || hist_ld == 0), "t2s_rules: bad arguments (rows=%lld V=%d hist_ld=%d)", (long long)rows, V, hist_ld);
+    if (rows == 0) return CVX_OK;
+    const RulesRowsArgs a{logits, history, hist_len, static_cast<const int*>(table), out, V, hist_ld, eos_id};
+    hipLaunchKernelGGL(rules_rows_kernel, dim3((unsigned)rows), dim3(1024), 0, cvx_hip_stream(s), a);
+    CVX_CHECK_LAUNCH("cvx_t2s_rules_f32");
+    return CVX_OK;
 }
 
 // cvx_t2s_beam_steps and cvx_t2s_beam_guided_steps: the checks, the steps, the back-track (one thread per hypothesis)

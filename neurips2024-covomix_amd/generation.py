@@ -90,6 +90,15 @@ def build_parser() -> ArgumentParser:
     p.add_argument("--t2s_filter_thres", type=float, default=None, help="extension: the filter's thres (top_k: k = ceil(thres * vocab), "
                    "reference default 0.1; top_p: the nucleus mass, reference default 0.9, inside (0, 1))")
     p.add_argument("--t2s_top_k", type=int, default=None, help="extension: an explicit k for --t2s_filter top_k (overrides the thres)")
+    p.add_argument("--t2s_repetition_penalty", type=float, default=None, help="extension: history rule of the text2semantic decode - every "
+                   "token id a stream has already emitted (inside --t2s_repetition_window) is penalised once before the filter: "
+                   "l > 0 ? l / penalty : l * penalty; > 0, 1 is off")
+    p.add_argument("--t2s_repetition_window", type=int, default=None, help="extension: the last W tokens of a stream the repetition penalty "
+                   "looks at (0, the default: all of them)")
+    p.add_argument("--t2s_no_repeat_ngram", type=int, default=None, help="extension: history rule - no n-gram of this size occurs twice in a "
+                   "stream (0..8; 0 is off)")
+    p.add_argument("--t2s_min_length", type=int, default=None, help="extension: history rule - the eos cannot be selected below this many "
+                   "steps")
     p.add_argument("--t2s_best_of", type=int, default=1, help="extension: decode this many candidates per turn through the continuously "
                    "refilled slots and keep the one the model finds most likely (largest mean token log-probability; 1 = off: today's files)")
     p.add_argument("--t2s_best_of_temperatures", type=str, default=None, help="extension: T1,T2,... - --t2s_best_of with one temperature per "
@@ -239,7 +248,18 @@ def t2s_sampling_kwargs(args) -> dict:
             kw["guided_beam"] = True
     if getattr(args, "t2s_mixed_guidance", False):
         kw["mixed_guidance"] = True
+    for flag, key, conv in T2S_RULE_FLAGS:
+        if getattr(args, "t2s_" + flag, None) is not None:
+            if beam:
+                raise ValueError(f"--t2s_beam_size does not combine with the history rules (--t2s_{flag})")
+            kw[key] = conv(getattr(args, "t2s_" + flag))
     return kw
+
+
+# the history rules: (flag without --t2s_ = key of <name>.t2s.json, facade keyword, conversion)
+T2S_RULE_FLAGS = (("repetition_penalty", "repetition_penalty", float), ("repetition_window", "repetition_window", int),
+                  ("no_repeat_ngram", "no_repeat_ngram_size", int), ("min_length", "min_length", int))
+T2S_RULE_KEYWORDS = tuple(key for _, key, _ in T2S_RULE_FLAGS)
 
 
 def _candidate_salt(c: int) -> int:
@@ -248,13 +268,13 @@ def _candidate_salt(c: int) -> int:
     return 1 if c == 0 else 0x100 + int(c)
 
 
-T2S_SIDE_FIELDS = ("temperature", "filter", "filter_thres", "top_k", "cond_scale")
+T2S_SIDE_FIELDS = ("temperature", "filter", "filter_thres", "top_k", "cond_scale") + tuple(flag for flag, _, _ in T2S_RULE_FLAGS)
 
 
 def _turn_side_files(text_dir, name: str, k: int, src):
     """The optional side files of one text turn -> (settings dict or None, prefix tokens or None).
-    `<stem>.t2s.json`: any of temperature, filter ("top_k" / "top_p"), filter_thres, top_k, cond_scale for this turn - they override the
-    --t2s_* flags.  `<stem>.prefix.semantic.npy`: tokens the turn's decode continues from, in the layout of `<name>.semantic.npy` (flat:
+    `<stem>.t2s.json`: any of temperature, filter ("top_k" / "top_p"), filter_thres, top_k, cond_scale, repetition_penalty,
+    repetition_window, no_repeat_ngram, min_length for this turn - they override the --t2s_* flags.  `<stem>.prefix.semantic.npy`: tokens the turn's decode continues from, in the layout of `<name>.semantic.npy` (flat:
     stream 1 then stream 2 on a two-output model, equally long).  <stem> is the turn's own file stem - `<name>.turn<k>` for a turn file,
     `<name>` for a whole-utterance file; the turns of a `<name>.txt` look for `<name>.turn<k>.*` and then take the utterance's
     `<name>.t2s.json` (the prefix `<name>.prefix.semantic.npy` goes to turn 0 only)."""
@@ -281,8 +301,11 @@ def _turn_side_files(text_dir, name: str, k: int, src):
 def _turn_sampling(sampling: dict, side) -> dict:
     """The facade keywords of ONE turn: the --t2s_* flags (t2s_sampling_kwargs) overridden by the turn's `.t2s.json`.  A filter named in
     the side file drops the flags' thres / k of ANOTHER filter."""
-    kw = {k: sampling[k] for k in ("temprature", "cond_scale", "filter_logits_fn", "filter_fn_kwargs") if k in sampling}
+    kw = {k: sampling[k] for k in ("temprature", "cond_scale", "filter_logits_fn", "filter_fn_kwargs") + T2S_RULE_KEYWORDS if k in sampling}
     side = side or {}
+    for flag, key, conv in T2S_RULE_FLAGS:
+        if flag in side:
+            kw[key] = conv(side[flag])
     if "temperature" in side:
         kw["temprature"] = float(side["temperature"])
     if "cond_scale" in side:
@@ -359,7 +382,9 @@ def _predict_turns(work, t2s, device, seed: int, slots: int = 64, sampling=None,
             # turns with side files: every turn's own keywords as lists; guided and unguided turns do not share a launch - two calls -
             # unless --t2s_mixed_guidance puts them into one slot pool (one call, the same tokens)
             per = [_turn_sampling(sampling or {}, side.get((name, k), (None, None))[0]) for name, k, _ in part]
-            rest = {k_: v for k_, v in (sampling or {}).items() if k_ not in ("temprature", "cond_scale", "filter_logits_fn", "filter_fn_kwargs")}
+            rest = {k_: v for k_, v in (sampling or {}).items()
+                    if k_ not in ("temprature", "cond_scale", "filter_logits_fn", "filter_fn_kwargs") + T2S_RULE_KEYWORDS}
+            rule_off = dict(repetition_penalty=1.0, repetition_window=0, no_repeat_ngram_size=0, min_length=0)
             one_call = bool((sampling or {}).get("mixed_guidance"))
             for guided in ((None,) if one_call else (False, True)):
                 sel = [i for i, kw_ in enumerate(per) if one_call or (kw_.get("cond_scale", 1.0) > 1.0) == guided]
@@ -376,7 +401,9 @@ def _predict_turns(work, t2s, device, seed: int, slots: int = 64, sampling=None,
                                                           cond_scale=[per[i].get("cond_scale", 1.0) for i in sel],
                                                           filter_logits_fn=[per[i].get("filter_logits_fn", "top_k") for i in sel],
                                                           filter_fn_kwargs=[per[i]["filter_fn_kwargs"] for i in sel],
-                                                          prefix=pres if any(p_ is not None for p_ in pres) else None, **rest)
+                                                          prefix=pres if any(p_ is not None for p_ in pres) else None, **rest,
+                                                          **{key: [per[i].get(key, rule_off[key]) for i in sel] for key in T2S_RULE_KEYWORDS
+                                                             if any(key in per[i] for i in sel)})
                 for i, t in zip(sel, toks):
                     out[(part[i][0], part[i][1])] = t.cpu().numpy().astype(np.int64)
     return out

@@ -830,6 +830,28 @@ def t2s_logprob(logits: torch.Tensor, tokens: torch.Tensor) -> torch.Tensor:
     return out
 
 
+def t2s_rules(logits: torch.Tensor, history: torch.Tensor, hist_len: torch.Tensor, table: torch.Tensor, eos_id: int,
+              out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The history rules of the text2semantic decode alone (cvx_t2s_rules_f32; the definition: include/covomix_hip.h,
+    cvx_t2s_decode_steps_rules), through the decode's device code: logits [rows, V] fp32, history int64 [rows, hist_ld] (row r holds
+    hist_len[r] tokens, int32 [rows]), table int32 [rows, 4] (`t2s.rules_rows`) -> the rows the filter would see, fp32 [rows, V]
+    (into `out` when given: contiguous [rows, V]).  The inputs are not written."""
+    _chk_f32(logits)
+    assert logits.ndim == 2 and logits.is_contiguous()
+    rows, V = logits.shape
+    assert history.is_cuda and history.dtype == torch.int64 and history.ndim == 2 and history.shape[0] == rows and history.is_contiguous()
+    assert hist_len.is_cuda and hist_len.dtype == torch.int32 and hist_len.shape == (rows,) and hist_len.is_contiguous()
+    assert table.is_cuda and table.dtype == torch.int32 and table.shape == (rows, _lib.T2S_RULES_WORDS) and table.is_contiguous()
+    if out is None:
+        out = torch.empty(rows, V, dtype=torch.float32, device=logits.device)
+    _chk_f32(out)
+    assert out.shape == (rows, V) and out.is_contiguous()
+    _lib.check(_lib.load().cvx_t2s_rules_f32(logits.data_ptr(), history.data_ptr() if history.shape[1] else None, hist_len.data_ptr(),
+                                             table.data_ptr(), rows, V, history.shape[1], int(eos_id), out.data_ptr(), _stream()),
+               "cvx_t2s_rules_f32")
+    return out
+
+
 def t2s_beam_select(logits: torch.Tensor, scores: torch.Tensor, finished: torch.Tensor, beam_size: int):
     """One selection step of the beam search (cvx_t2s_beam_select_f32; the algorithm: include/covomix_hip.h): logits [G * B, S, V] fp32, scores
     fp32 [G * B], finished uint8 / bool [G * B] -> (parents int32 [G * B] - the index inside the group -, tokens int64 [G * B, S], token

@@ -8,7 +8,9 @@ filter_fn_kwargs, text2semantic.py:118-132, :796) - in every decode schedule bel
 reference's generate accepts without a body, text2semantic.py:673-677 - the algorithm is defined in include/covomix_hip.h; `generate_beam_many`:
 any number of utterances through continuously refilled groups of beam_size slots); no speculative
 decoding, no padded text batches.  Beside the tokens: the log-probability of every sampled token (return_logprobs), teacher-forced scoring of given tokens
-through the same decode slots (score_many) and the mean token log-probability best-of-N selects by (sequence_logprob).
+through the same decode slots (score_many) and the mean token log-probability best-of-N selects by (sequence_logprob).  And what looks at
+the tokens an utterance has ALREADY emitted: the history rules - repetition penalty, no-repeat n-gram, minimum length (check_rules;
+cvx_t2s_decode_steps_rules) - per utterance and per output stream, in every sampled schedule; off by default.
 
   encoder  (source transformer, once per utterance): the full-sequence kernels of the acoustic path - fp32 GEMM with
            the RoPE epilogue, flash attention, RMSNorm - plus a GEGLU kernel;
@@ -188,9 +190,26 @@ class UtteranceSettings(NamedTuple):
     filter_logits_fn: Optional[object] = None
     filter_fn_kwargs: Optional[dict] = None
     cond_scale: Optional[float] = None
+    repetition_penalty: Optional[float] = None
+    repetition_window: Optional[int] = None
+    no_repeat_ngram_size: Optional[int] = None
+    min_length: Optional[int] = None
 
 
 SETTING_FIELDS = UtteranceSettings._fields
+RULE_FIELDS = ("repetition_penalty", "repetition_window", "no_repeat_ngram_size", "min_length")      # the history rules (check_rules)
+RULES_OFF = (1.0, 0, 0, 0)
+
+
+def _setting_entry(e) -> dict:
+    """one entry of `settings` (None, a mapping, a record) as a dict"""
+    if e is None:
+        return {}
+    if isinstance(e, Mapping):
+        return dict(e)
+    if hasattr(e, "_asdict"):
+        return e._asdict()
+    return {f: getattr(e, f) for f in SETTING_FIELDS if hasattr(e, f)}
 
 
 def check_settings(settings, n: int, vocab: int, streams: int = 1, temperature: float = 1.0, filter_logits_fn="top_k", filter_fn_kwargs=None,
@@ -213,14 +232,7 @@ def check_settings(settings, n: int, vocab: int, streams: int = 1, temperature: 
         raise NotImplementedError("guidance (cond_scale > 1) on a two-output model: the reference cannot run it (generate_batch)")
     out = []
     for j, e in enumerate(settings):
-        if e is None:
-            e = {}
-        elif isinstance(e, Mapping):
-            e = dict(e)
-        elif hasattr(e, "_asdict"):
-            e = e._asdict()
-        else:
-            e = {f: getattr(e, f) for f in SETTING_FIELDS if hasattr(e, f)}
+        e = _setting_entry(e)
         unknown = sorted(set(e) - set(SETTING_FIELDS))
         if unknown:
             raise ValueError(f"settings[{j}]: unknown fields {unknown}; known: {list(SETTING_FIELDS)}")
@@ -272,6 +284,66 @@ def settings_rows(resolved, prefix_lens=None) -> torch.Tensor:
     rows[:, 4] = f([r[2] for r in resolved]).view(torch.int32)
     if prefix_lens is not None:
         rows[:, 5] = torch.tensor([int(x) for x in prefix_lens], dtype=torch.int32)
+    return rows
+
+
+def check_rules(settings, n: int, max_length: int, repetition_penalty: float = 1.0, repetition_window: int = 0,
+                no_repeat_ngram_size: int = 0, min_length: int = 0) -> list:
+    """The history rules of n utterances resolved against the call's scalars: -> n tuples (theta, W, ngram, min_len) - the repetition
+    penalty theta > 0 (1: off) over the last W >= 0 tokens of a stream (0: all of them), the no-repeat n-gram size in 0..8 (0: off) and
+    the minimum length (the eos is not selectable below it); the definition: include/covomix_hip.h, cvx_t2s_decode_steps_rules.
+    settings: None (the scalars for everyone) or n entries as `check_settings` takes them; a field an entry leaves out or None takes the
+    scalar, other fields are not looked at.  ValueError: another length, a penalty that is not a finite number > 0, W < 0, an n-gram size
+    outside 0..8, a minimum length < 0 or > max_length, a non-integer W / size / length.  Pure host code."""
+    entries = [None] * n if settings is None else list(settings)
+    if len(entries) != n:
+        raise ValueError(f"settings: {len(entries)} entries for {n} utterances")
+    scalars = dict(zip(RULE_FIELDS, (repetition_penalty, repetition_window, no_repeat_ngram_size, min_length)))
+
+    def whole(name, v, where):
+        if isinstance(v, bool) or (not isinstance(v, int) and not (isinstance(v, float) and v == int(v))):
+            raise ValueError(f"{where}{name} = {v!r} must be an integer")
+        return int(v)
+    out = []
+    for j, e in enumerate([None] + entries):               # (the scalars themselves first: a bad scalar is refused whatever the entries say)
+        e = _setting_entry(e)
+        where = "" if j == 0 else f"settings[{j - 1}]: "
+        get = lambda f: scalars[f] if e.get(f) is None else e[f]
+        try:
+            theta = float(get("repetition_penalty"))
+        except (TypeError, ValueError):
+            raise ValueError(f"{where}repetition_penalty = {get('repetition_penalty')!r} must be a number") from None
+        if not (theta > 0.0 and math.isfinite(theta)):
+            raise ValueError(f"{where}repetition_penalty = {theta} must be a finite number > 0 (1 is off)")
+        W = whole("repetition_window", get("repetition_window"), where)
+        if W < 0:
+            raise ValueError(f"{where}repetition_window = {W} must be >= 0 (0: the whole history)")
+        ng = whole("no_repeat_ngram_size", get("no_repeat_ngram_size"), where)
+        if not 0 <= ng <= _lib.T2S_RULES_MAX_NGRAM:
+            raise ValueError(f"{where}no_repeat_ngram_size = {ng} outside 0..{_lib.T2S_RULES_MAX_NGRAM} (0 is off)")
+        m = whole("min_length", get("min_length"), where)
+        if not 0 <= m <= int(max_length):
+            raise ValueError(f"{where}min_length = {m} outside [0, max_length = {int(max_length)}]")
+        if j:
+            out.append((theta, W, ng, m))
+    return out
+
+
+def rules_active(resolved) -> bool:
+    """does any tuple of check_rules switch a rule on?  (A penalty of 1 with any window, n-gram size 0 and minimum length 0 change nothing.)"""
+    return any(r[0] != 1.0 or r[2] != 0 or r[3] != 0 for r in resolved)
+
+
+def rules_rows(resolved) -> torch.Tensor:
+    """The rows of the device's rules table (cvx_t2s_rules; include/covomix_hip.h) for the tuples of check_rules: int32 [n, 4] holding
+    [0] theta (fp32 bits) [1] window [2] n-gram size [3] minimum length."""
+    n = len(resolved)
+    rows = torch.zeros(n, _lib.T2S_RULES_WORDS, dtype=torch.int32)
+    if n == 0:
+        return rows
+    rows[:, 0] = torch.tensor([r[0] for r in resolved], dtype=torch.float64).to(torch.float32).view(torch.int32)
+    for c in (1, 2, 3):
+        rows[:, c] = torch.tensor([int(r[c]) for r in resolved], dtype=torch.int32)
     return rows
 
 
@@ -494,7 +566,8 @@ class TextToSemanticDecoder:
             self.buf.update(tokens=torch.zeros(dialogues, S, self.max_length, dtype=torch.int64, device=dev),
                             dialogues=torch.zeros(dialogues, SR, dtype=torch.int32, device=dev),
                             queue=torch.zeros(2, dtype=torch.int32, device=dev),
-                            per=torch.zeros(dialogues, _lib.T2S_PER_WORDS, dtype=torch.int32, device=dev))
+                            per=torch.zeros(dialogues, _lib.T2S_PER_WORDS, dtype=torch.int32, device=dev),
+                            rules=torch.zeros(dialogues, _lib.T2S_RULES_WORDS, dtype=torch.int32, device=dev))
             self.buf.pop("logprobs", None)
             self._dialogues, grown = dialogues, True
         if logprobs and "logprobs" not in self.buf:
@@ -579,13 +652,15 @@ class TextToSemanticDecoder:
         return dec
 
     def _run_steps(self, temperature: float, batch: int, n: int, cfg_scale: float = 1.0, queue: bool = False, filt=None, nd: int = 0,
-                   scored: bool = False, per: bool = False, mixed: Optional[int] = None) -> None:
+                   scored: bool = False, per: bool = False, mixed: Optional[int] = None, rules: bool = False) -> None:
         """n token steps on the current stream without a graph.  scored: cvx_t2s_decode_steps_scored (log-probs of every step's token into
         buf["logprobs"], forced dialogues honoured); else cvx_t2s_decode_steps, exactly as before that entry existed.
         per: cvx_t2s_decode_steps_per_dialogue - the settings come from buf["per"], one row per dialogue record; temperature and filt
         are not looked at and cfg_scale only says whether the slots run in guided pairs.
         mixed (with per and queue): cvx_t2s_decode_steps_mixed with that many guided utterances among the nd records - the pair layout
-        comes from the records; n = 0 runs its scheduler alone, which arms idle slots."""
+        comes from the records; n = 0 runs its scheduler alone, which arms idle slots.
+        rules (with per): cvx_t2s_decode_steps_rules - that chain, or the mixed one, under the history rules of buf["rules"], one row per
+        dialogue record."""
         lib, dec = _lib.load(), self._descriptor(temperature, batch, cfg_scale, queue, filt, nd)
         sc = C.byref(_lib.T2SScoring(C.sizeof(_lib.T2SScoring), self.max_length, self.buf["logprobs"].data_ptr())) if scored else None
         if not per:
@@ -595,6 +670,11 @@ class TextToSemanticDecoder:
                 _lib.check(lib.cvx_t2s_decode_steps(C.byref(dec), n, ops._stream()), "cvx_t2s_decode_steps")
             return
         pd = _lib.T2SPerDialogue(C.sizeof(_lib.T2SPerDialogue), self.buf["per"].shape[0], self.buf["per"].data_ptr())
+        if rules:
+            mx = None if mixed is None else C.byref(_lib.T2SMixed(C.sizeof(_lib.T2SMixed), int(mixed)))
+            ru = _lib.T2SRules(C.sizeof(_lib.T2SRules), self.buf["rules"].shape[0], self.buf["rules"].data_ptr())
+            _lib.check(lib.cvx_t2s_decode_steps_rules(C.byref(dec), sc, C.byref(pd), mx, C.byref(ru), n, ops._stream()), "cvx_t2s_decode_steps_rules")
+            return
         if mixed is not None:
             mx = _lib.T2SMixed(C.sizeof(_lib.T2SMixed), int(mixed))
             _lib.check(lib.cvx_t2s_decode_steps_mixed(C.byref(dec), sc, C.byref(pd), C.byref(mx), n, ops._stream()), "cvx_t2s_decode_steps_mixed")
@@ -695,7 +775,7 @@ class TextToSemanticDecoder:
         return g
 
     def _graph(self, temperature: float, batch: int, cfg_scale: float = 1.0, queue: bool = False, filt=None, nd: int = 0, scored: bool = False,
-               per: bool = False, mixed: Optional[int] = None):
+               per: bool = False, mixed: Optional[int] = None, rules: bool = False):
         """The captured graph of CHUNK token steps for this (batch, stream CU count, mode, filter, scoring); captured on first use.  (nd, the
         number of dialogue records, is only validated by the C call: it is not part of the key.)  Capturing runs the
         steps once outside the capture (module load, kernel attributes): callers get their graph BEFORE they set up the decode state -
@@ -703,28 +783,32 @@ class TextToSemanticDecoder:
         per: the per-dialogue chain, whose settings live in a device table - its key carries a "per" marker INSTEAD of (temperature, scale,
         filter), so one graph per (batch, CUs, guided?, queue, scored) serves every mix of settings.
         mixed: the mixed chain (cvx_t2s_decode_steps_mixed) - its key is ("mixed", batch, CUs, scored): the launches depend on neither the
-        settings nor on how many utterances are guided."""
+        settings nor on how many utterances are guided.
+        rules: the per-dialogue or mixed chain under the history rules (cvx_t2s_decode_steps_rules) - the key gains a "rules" marker, not
+        the values: they live in a device table too, and one graph serves every mix of rules."""
         filt = filt or self._default_filter
         key = (temperature, batch, cfg_scale, ops.stream_cus(), queue, self._gen, filt, bool(scored))   # (the kernels' shape follows the CUs the stream owns)
         if per:
             key = ("per", batch, cfg_scale > 1.0, ops.stream_cus(), queue, self._gen, bool(scored))
         if mixed is not None:
             key = ("mixed", batch, ops.stream_cus(), self._gen, bool(scored))
+        if rules:
+            key += ("rules",)
 
         def idle():
             self.buf["state"].copy_(self._slot_records([]))
             if mixed is not None:                      # (the scheduler of the warm-up steps must find nothing to hand out)
                 self.buf["queue"].zero_()
-        return self._capture(key, lambda: self._run_steps(temperature, batch, CHUNK, cfg_scale, queue, filt, nd, scored, per, mixed), idle)
+        return self._capture(key, lambda: self._run_steps(temperature, batch, CHUNK, cfg_scale, queue, filt, nd, scored, per, mixed, rules), idle)
 
     def _run_chunk(self, temperature: float, batch: int = 1, cfg_scale: float = 1.0, queue: bool = False, filt=None, nd: int = 0,
-                   scored: bool = False, per: bool = False, mixed: Optional[int] = None) -> None:
+                   scored: bool = False, per: bool = False, mixed: Optional[int] = None, rules: bool = False) -> None:
         """CHUNK token steps on the current stream: a graph replay of the per-launch path (the graph must exist - `_graph` - unless
         CVX_GRAPH=0 asks for plain launches)."""
         if os.environ.get("CVX_GRAPH", "1") != "1":
-            self._run_steps(temperature, batch, CHUNK, cfg_scale, queue, filt, nd, scored, per, mixed)
+            self._run_steps(temperature, batch, CHUNK, cfg_scale, queue, filt, nd, scored, per, mixed, rules)
             return
-        self._graph(temperature, batch, cfg_scale, queue, filt, nd, scored, per, mixed).replay()
+        self._graph(temperature, batch, cfg_scale, queue, filt, nd, scored, per, mixed, rules).replay()
 
     def _contexts(self, sources, rows=None) -> list:
         """encoder + the cross-attention k/v of the utterances into dialogue rows `rows` (default 0, 1, ...): [null | to_kv(enc)]
@@ -777,7 +861,8 @@ class TextToSemanticDecoder:
                               #  e.g. the generator's graph-safe state, would become inference tensors)
     def generate_batch(self, sources, uniforms=None, max_length: Optional[int] = None, temperature: float = 1.0,
                        generator: Optional[torch.Generator] = None, collect_logits: bool = False, cond_scale: float = 1.0,
-                       ignore_eos: bool = False, filter_logits_fn="top_k", filter_fn_kwargs=None, return_logprobs: bool = False):
+                       ignore_eos: bool = False, filter_logits_fn="top_k", filter_fn_kwargs=None, return_logprobs: bool = False,
+                       repetition_penalty: float = 1.0, repetition_window: int = 0, no_repeat_ngram_size: int = 0, min_length: int = 0):
         """Decode up to MAX_BATCH utterances together IN LOCK STEP (all start at position 0; the batch runs until the last one has
         sampled its eos).  sources: list of [n] / [1, n] id tensors; uniforms: optional list of [steps, streams, vocab] tensors (one
         per utterance).  Returns a list of (flat tokens, streams[, logits]) tuples, each exactly what `generate` returns for that
@@ -791,9 +876,19 @@ class TextToSemanticDecoder:
         the reference's top_k with k = ceil(0.1 * vocab).
         return_logprobs: every result gains, as its LAST entry, a float32 [S, length] tensor aligned with `streams`: the log-probability
         the model gave each sampled token - log_softmax of the row the filter sees (the guidance-combined logits under cond_scale > 1),
-        before the filter, the temperature and the noise (include/covomix_hip.h).  Off (the default) nothing changes."""
+        before the filter, the temperature and the noise (include/covomix_hip.h).  Off (the default) nothing changes.
+        repetition_penalty / repetition_window / no_repeat_ngram_size / min_length: the HISTORY RULES (`check_rules`; the definition:
+        include/covomix_hip.h, cvx_t2s_decode_steps_rules) - per output stream, from the tokens the stream has emitted so far: every id
+        seen in its last `repetition_window` tokens (0: all) is penalised once (l > 0 ? l / penalty : l * penalty), an id that would
+        complete an n-gram the stream already holds is not selectable, and neither is the eos below min_length.  They act on the row
+        the filter sees, before the filter; logits under collect_logits and log-probs under return_logprobs stay those of the row
+        BEFORE the rules (so the log-probs still equal score_many of the tokens).  All off (the defaults): the call as it was, graph for
+        graph; any on: the per-dialogue chain under a rules table with equal rows (cvx_t2s_decode_steps_rules)."""
         S, V = self.d["streams"], self.d["vocab"]
         filt = filter_setting(filter_logits_fn, filter_fn_kwargs, V)
+        rules = check_rules(None, len(sources), self._rule_bound(max_length), repetition_penalty, repetition_window, no_repeat_ngram_size,
+                            min_length)
+        ruled = rules_active(rules)
         guided = float(cond_scale) > 1.0
         if guided and S != 1:
             raise NotImplementedError("guidance (cond_scale > 1) on a two-output model: the reference feeds the full-width hidden "
@@ -813,7 +908,11 @@ class TextToSemanticDecoder:
         self._ensure(nb, nb, max_len, scored)
         b = self.buf
         if not collect_logits and max_len > 0:
-            self._graph(temperature, nb, scale, False, filt, 0, scored)
+            self._graph(temperature, nb, scale, False, filt, 0, scored, ruled, None, ruled)
+        if ruled:                 # the settings and the rules as table rows, one per slot (slot b decodes dialogue b; a null half mirrors its text half)
+            resolved = check_settings([None] * n, n, V, S, temperature, filter_logits_fn, filter_fn_kwargs, scale)
+            b["per"][:nb].copy_(ops.h2d(settings_rows(resolved).repeat_interleave(P, dim=0), self.device))
+            b["rules"][:nb].copy_(ops.h2d(rules_rows(rules).repeat_interleave(P, dim=0), self.device))
         ctx = self._guided_contexts(sources) if guided else self._contexts(sources)
         uview = self._uniform_view(nb)[0::P]
         if us is None:            # (drawn step-major, as the [steps, batch, streams, vocab] buffer of earlier versions was: same seeds, same tokens)
@@ -828,14 +927,15 @@ class TextToSemanticDecoder:
         done = lambda st: all(st[r][1] for r in range(0, nb, P)) and not ignore_eos
         if collect_logits:                                              # (tests: one step at a time without a graph)
             for _ in range(max_len):
-                self._run_steps(temperature, nb, 1, scale, False, filt, 0, scored)
+                self._run_steps(temperature, nb, 1, scale, False, filt, 0, scored, ruled, None, ruled)
                 lg = b["logits"][:nb].clone()
                 logits.append(lg[1::2] + (lg[0::2] - lg[1::2]) * scale if guided else lg)
                 st = self._read_state(nb)
                 if done(st):
                     break
         elif max_len > 0:
-            self._chunks(lambda: self._run_chunk(temperature, nb, scale, False, filt, 0, scored), b["state"], nb, done, (max_len + CHUNK - 1) // CHUNK)
+            self._chunks(lambda: self._run_chunk(temperature, nb, scale, False, filt, 0, scored, ruled, None, ruled), b["state"], nb, done,
+                         (max_len + CHUNK - 1) // CHUNK)
             st = self._read_state(nb)
         out = []
         for u in range(n):
@@ -933,7 +1033,8 @@ class TextToSemanticDecoder:
     def generate_many(self, sources, uniforms=None, max_length: Optional[int] = None, temperature: float = 1.0,
                       generator: Optional[torch.Generator] = None, slots: int = 32, ignore_eos: bool = False, limits=None, on_done=None,
                       cond_scale: float = 1.0, filter_logits_fn="top_k", filter_fn_kwargs=None, return_logprobs: bool = False, forced=None,
-                      settings=None, prefixes=None, mixed_guidance: bool = False):
+                      settings=None, prefixes=None, mixed_guidance: bool = False, repetition_penalty: float = 1.0, repetition_window: int = 0,
+                      no_repeat_ngram_size: int = 0, min_length: int = 0):
         """Decode ANY number of utterances through `slots` decode slots with continuous batching: every utterance runs the
         reference's loop (text2semantic.py:749-848) from position 0 to its first eos (:803-818) or its step limit, and the slot it
         ran in takes the next pending utterance in the sampling kernel of that very step (cvx_t2s_decoder.queue) - utterances end
@@ -975,10 +1076,18 @@ class TextToSemanticDecoder:
         >= 2 when any utterance is guided; WINDOW counts records, and windows are cut on utterance boundaries (`mixed_windows`).
         last_records stays one record per utterance (that of the text half) and gains, as a ninth entry, the slot of the null half of a
         guided utterance (None for an unguided one).  Every other argument keeps its meaning, and every utterance gets, bit for bit, what
-        it gets alone."""
+        it gets alone.
+        repetition_penalty / repetition_window / no_repeat_ngram_size / min_length (generate_batch): the history rules, as scalars for
+        the call; the entries of `settings` may name them per utterance (`check_rules`).  With every rule off the call is what it was,
+        graph for graph.  With any on, the call runs the per-dialogue (or mixed) chain under a rules table
+        (cvx_t2s_decode_steps_rules) and ONE graph serves every mix; an utterance's history is its own token row, so a refilled slot
+        inherits nothing and every utterance still gets, bit for bit, what it gets alone with its rules.  A prefix counts as history;
+        given steps (prefix, forced) are not subject to the rules."""
+        rule_kw = dict(repetition_penalty=repetition_penalty, repetition_window=repetition_window, no_repeat_ngram_size=no_repeat_ngram_size,
+                       min_length=min_length)
         if mixed_guidance:
             return self._generate_many_mixed(sources, uniforms, max_length, temperature, generator, slots, ignore_eos, limits, on_done,
-                                             cond_scale, filter_logits_fn, filter_fn_kwargs, return_logprobs, forced, settings, prefixes)
+                                             cond_scale, filter_logits_fn, filter_fn_kwargs, return_logprobs, forced, settings, prefixes, rule_kw)
         d = self.d
         S, V = d["streams"], d["vocab"]
         n = len(sources)
@@ -990,7 +1099,9 @@ class TextToSemanticDecoder:
         if cfg and S != 1:
             raise NotImplementedError("guidance (cond_scale > 1) on a two-output model: the reference cannot run it (generate_batch)")
         P = 2 if cfg else 1       # dialogue records (and decode slots) per utterance
-        per = settings is not None or prefixes is not None
+        rules = check_rules(settings, n, self._rule_bound(max_length), **rule_kw)
+        ruled = rules_active(rules)
+        per = settings is not None or prefixes is not None or ruled
         resolved = None
         if per:                   # (validated for the whole call before any window runs)
             resolved = check_settings([None] * n if settings is None else settings, n, V, S, temperature, filter_logits_fn, filter_fn_kwargs,
@@ -1009,7 +1120,7 @@ class TextToSemanticDecoder:
                                           cond_scale, filter_logits_fn, filter_fn_kwargs, return_logprobs,
                                           None if forced is None else forced[w:w + win],
                                           None if settings is None else list(settings)[w:w + win],
-                                          None if prefixes is None else list(prefixes)[w:w + win])
+                                          None if prefixes is None else list(prefixes)[w:w + win], **rule_kw)
             return out
         nb = P * max(1, min(int(slots) // P, MAX_BATCH // P, n))
         nb = nb if nb in (1, 2, 4) else min((nb + 7) // 8 * 8, MAX_BATCH)      # whole kernel groups (idle slots cost nothing)
@@ -1020,7 +1131,7 @@ class TextToSemanticDecoder:
         self._ensure(nb, nrec, max_len, scored)
         b = self.buf
         temperature = float(temperature)
-        self._graph(temperature, nb, cond_scale, True, filt, nrec, scored, per)
+        self._graph(temperature, nb, cond_scale, True, filt, nrec, scored, per, None, ruled)
         ctx = self._guided_contexts(sources) if cfg else self._contexts(sources)
         uview = self._uniform_view(nrec)[0::P]            # the draws of utterance j live in its first record
         if us is None:
@@ -1041,6 +1152,8 @@ class TextToSemanticDecoder:
             for j, p in enumerate(pre):                    # the token row of a prefixed dialogue holds the prefix before its first step
                 if p is not None:
                     b["tokens"][text[j], :, :p.shape[1]].copy_(ops.h2d(p, self.device))
+        if ruled:
+            b["rules"][:nrec].copy_(ops.h2d(rules_rows(rules).repeat_interleave(P, dim=0), self.device))
         first = min(nb, nrec)     # records (= slots) that start at once; whole pairs under guidance (nb and nrec are even)
         rec = torch.tensor([[ctx[r], lim[r // P], flags[r // P], 1 if r < first else 0, 0, r if r < first else 0, 0, 0] for r in range(nrec)],
                            dtype=torch.int32)
@@ -1051,11 +1164,11 @@ class TextToSemanticDecoder:
             slot[r, 5], slot[r, 6] = lim[r // P], flags[r // P]
         b["state"].copy_(slot)
         b["x"][:first].copy_(self.start[None, :].expand(first, -1))
-        return self._queue_chunks(lambda: self._run_chunk(temperature, nb, cond_scale, True, filt, nrec, scored, per), nrec, text, lim, span, scored,
-                                  on_done, lambda records: records[0::P])
+        return self._queue_chunks(lambda: self._run_chunk(temperature, nb, cond_scale, True, filt, nrec, scored, per, None, ruled), nrec, text, lim,
+                                  span, scored, on_done, lambda records: records[0::P])
 
     def _generate_many_mixed(self, sources, uniforms, max_length, temperature, generator, slots, ignore_eos, limits, on_done, cond_scale,
-                             filter_logits_fn, filter_fn_kwargs, return_logprobs, forced, settings, prefixes):
+                             filter_logits_fn, filter_fn_kwargs, return_logprobs, forced, settings, prefixes, rule_kw=None):
         """generate_many(mixed_guidance=True): the records are laid out by prefix sum (`mixed_records`: one per unguided utterance; text
         half and null half per guided one), everything that belongs to an utterance - uniforms, tokens, log-probs, prefix, forced tokens -
         lives in its text record, the settings row is mirrored onto the null record, and the slots are armed by the device's scheduler (a
@@ -1068,6 +1181,8 @@ class TextToSemanticDecoder:
         filter_setting(filter_logits_fn, filter_fn_kwargs, V)
         resolved = check_settings([None] * n if settings is None else settings, n, V, S, temperature, filter_logits_fn, filter_fn_kwargs,
                                   float(cond_scale), mixed=True)
+        rules = check_rules(settings, n, self._rule_bound(max_length), **(rule_kw or {}))
+        ruled = rules_active(rules)
         if prefixes is not None and len(list(prefixes)) != n:
             raise ValueError(f"prefixes: {len(list(prefixes))} entries for {n} utterances")
         kinds = [r[2] > 1.0 for r in resolved]
@@ -1083,7 +1198,7 @@ class TextToSemanticDecoder:
                 out += self._generate_many_mixed(sources[w0:w1], cut(uniforms, w0, w1), max_length, temperature, generator, slots, ignore_eos,
                                                  cut(limits, w0, w1), None if on_done is None else (lambda j, r, w0=w0: on_done(w0 + j, r)),
                                                  cond_scale, filter_logits_fn, filter_fn_kwargs, return_logprobs, cut(forced, w0, w1),
-                                                 cut(settings, w0, w1), cut(prefixes, w0, w1))
+                                                 cut(settings, w0, w1), cut(prefixes, w0, w1), rule_kw)
                 recs += self.last_records
             self.last_records = recs
             return out
@@ -1096,7 +1211,7 @@ class TextToSemanticDecoder:
         pre = check_prefixes([None] * n if prefixes is None else prefixes, n, S, V, lim, forced)
         self._ensure(nb, nrec, max_len, scored)
         b = self.buf
-        self._graph(1.0, nb, 1.0, True, None, nrec, scored, True, ng)
+        self._graph(1.0, nb, 1.0, True, None, nrec, scored, True, ng, ruled)
         ctx_text = self._contexts(sources, text)
         ctx = [1] * nrec
         for j in range(n):
@@ -1124,12 +1239,14 @@ class TextToSemanticDecoder:
         owner = [j for j in range(n) for _ in range(2 if kinds[j] else 1)]           # record -> utterance
         rows = settings_rows(resolved, [0 if p_ is None else p_.shape[1] for p_ in pre])
         b["per"][:nrec].copy_(ops.h2d(rows[torch.tensor(owner, dtype=torch.int64)].contiguous(), self.device))
+        if ruled:
+            b["rules"][:nrec].copy_(ops.h2d(rules_rows(rules)[torch.tensor(owner, dtype=torch.int64)].contiguous(), self.device))
         rec = torch.tensor([[ctx[r], lim[owner[r]], flags[owner[r]], 0, 0, 0, 0, 0] for r in range(nrec)], dtype=torch.int32)
         b["dialogues"][:nrec].copy_(rec)
         b["queue"].copy_(torch.tensor([0, nrec], dtype=torch.int32))
         b["state"].copy_(self._slot_records([]))
-        self._run_steps(1.0, nb, 0, 1.0, True, None, nrec, scored, True, ng)         # the scheduler alone: arms the first slots
-        return self._queue_chunks(lambda: self._run_chunk(1.0, nb, 1.0, True, None, nrec, scored, True, ng), nrec, text, lim, span, scored, on_done,
+        self._run_steps(1.0, nb, 0, 1.0, True, None, nrec, scored, True, ng, ruled)  # the scheduler alone: arms the first slots
+        return self._queue_chunks(lambda: self._run_chunk(1.0, nb, 1.0, True, None, nrec, scored, True, ng, ruled), nrec, text, lim, span, scored, on_done,
                                   lambda records: [list(records[text[j]]) + [records[text[j] + 1][5] if kinds[j] else None] for j in range(n)])
 
     # ------------------------------------------------------------------ beam search
@@ -1139,6 +1256,17 @@ class TextToSemanticDecoder:
         if scale > 1.0 and self.d["streams"] != 1:
             raise NotImplementedError("guidance (cond_scale > 1) on a two-output model: the reference cannot run it (generate_batch)")
         return scale
+
+    def _rule_bound(self, max_length) -> int:
+        """the bound of min_length (check_rules): the steps the call may take; a call without steps is refused by its own check, not here"""
+        return max(0, min(int(max_length or self.max_length), self.max_length))
+
+    def _beam_rules(self, max_length, *rule_scalars) -> None:
+        """Beam search takes no history rules yet: a hypothesis' history runs through the ancestry table, not through one token row, and
+        blocking along it is a later change.  The scalars are validated (`check_rules`), and any rule switched on is a ValueError."""
+        if rules_active(check_rules(None, 1, self._rule_bound(max_length), *rule_scalars)):
+            raise ValueError("beam search does not run the history rules (repetition_penalty, no_repeat_ngram_size, min_length): a hypothesis' "
+                             "history lives in the ancestry table - sample instead, or leave them off")
 
     def _ensure_beam(self) -> dict:
         """Device state of the beam chain (cvx_t2s_beam), for the decode buffers' current slot capacity: allocated on first use, and again
@@ -1244,7 +1372,8 @@ class TextToSemanticDecoder:
     @ops.gated
     @torch.no_grad()
     def generate_beam(self, sources, beam_size: int = 10, max_length: Optional[int] = None, length_penalty: float = 1.0,
-                      return_beams: bool = False, cond_scale: float = 1.0):
+                      return_beams: bool = False, cond_scale: float = 1.0, repetition_penalty: float = 1.0, repetition_window: int = 0,
+                      no_repeat_ngram_size: int = 0, min_length: int = 0):
         """Beam search (the algorithm: include/covomix_hip.h, cvx_t2s_beam_steps): deterministic, no draws - temperature, logit filter and
         uniforms play no part.  Every step keeps the beam_size hypotheses with the largest cumulative log-probability (fp32); a hypothesis
         that takes an eos in any stream is finished and competes with its score unchanged; the utterance ends when all are finished or after
@@ -1261,7 +1390,9 @@ class TextToSemanticDecoder:
         cond_scale > 1 (one-output models): beam search under classifier-free guidance (cvx_t2s_beam_guided_steps) - every hypothesis is a
         slot pair (text context, null context), the search ranks by the log-softmax of null + (cond - null) * cond_scale, and logprobs
         equal, bit for bit, score_many(..., cond_scale=cond_scale); waves hold MAX_BATCH // (2 * beam_size) utterances.  Return values and
-        `last_beam` have the same shape.  ValueError for cond_scale < 1, NotImplementedError for a two-output model."""
+        `last_beam` have the same shape.  ValueError for cond_scale < 1, NotImplementedError for a two-output model.
+        The history rules (generate_batch) do not run under beam search: any of them switched on is a ValueError (`_beam_rules`)."""
+        self._beam_rules(max_length, repetition_penalty, repetition_window, no_repeat_ngram_size, min_length)
         B = check_beam_size(beam_size)
         scale = self._beam_scale(cond_scale)
         one = torch.is_tensor(sources)
@@ -1363,7 +1494,8 @@ class TextToSemanticDecoder:
     @ops.gated
     @torch.no_grad()
     def generate_beam_many(self, sources, beam_size: int = 10, max_length: Optional[int] = None, length_penalty: float = 1.0,
-                           return_beams: bool = False, slots: int = 64, limits=None, cond_scale: float = 1.0):
+                           return_beams: bool = False, slots: int = 64, limits=None, cond_scale: float = 1.0, repetition_penalty: float = 1.0,
+                           repetition_window: int = 0, no_repeat_ngram_size: int = 0, min_length: int = 0):
         """generate_beam for ANY number of utterances through continuously refilled slot GROUPS (cvx_t2s_beam_queue_steps): slots // beam_size
         groups (at most MAX_BATCH // beam_size) of beam_size neighbouring slots; a group whose utterance has ended - all hypotheses finished,
         or its step limit - takes the next pending utterance inside the selection kernel of that very step, as generate_many's slots do.
@@ -1374,7 +1506,9 @@ class TextToSemanticDecoder:
         cond_scale > 1 (one-output models): the guided search of generate_beam(cond_scale=...) through slots // (2 * beam_size) groups of
         slot pairs (cvx_t2s_beam_guided_queue_steps); every utterance again equals generate_beam(cond_scale=...) alone, bit for bit.
         ValueError (before any device work): beam_size outside 1..16, slots that hold no group (slots < beam_size, or < 2 * beam_size under
-        guidance), cond_scale < 1, limits of another length than sources.  NotImplementedError: guidance on a two-output model."""
+        guidance), cond_scale < 1, limits of another length than sources, any history rule switched on (`_beam_rules`).
+        NotImplementedError: guidance on a two-output model."""
+        self._beam_rules(max_length, repetition_penalty, repetition_window, no_repeat_ngram_size, min_length)
         B = check_beam_size(beam_size)
         scale = self._beam_scale(cond_scale)
         srcs = list(sources)
@@ -1431,17 +1565,20 @@ class TextToSemanticDecoder:
     def generate(self, source_ids: torch.Tensor, uniforms: Optional[torch.Tensor] = None, max_length: Optional[int] = None,
                  temperature: float = 1.0, generator: Optional[torch.Generator] = None, return_streams: bool = False,
                  collect_logits: bool = False, cond_scale: float = 1.0, filter_logits_fn="top_k", filter_fn_kwargs=None,
-                 return_logprobs: bool = False):
+                 return_logprobs: bool = False, repetition_penalty: float = 1.0, repetition_window: int = 0, no_repeat_ngram_size: int = 0,
+                 min_length: int = 0):
         """== TextToSemanticWrapper.sample(grapheme_token_ids): flat int64 tensor, stream 1 then stream 2 (two-output
         models), each cut after its eos.  uniforms [steps, streams, vocab] (or [steps, streams, 1, vocab]) replaces
         the random draws of gumbel_noise (text2semantic.py:108-110); default: torch.rand from `generator`.
         collect_logits (tests): step one token at a time without a graph and also return the pre-filter logits
         [steps, streams, vocab].  cond_scale / filter_logits_fn / filter_fn_kwargs: see generate_batch.  return_logprobs: returns
-        (flat tokens, streams[, logits], logprobs) - logprobs float32 [S, length] aligned with streams (generate_batch)."""
+        (flat tokens, streams[, logits], logprobs) - logprobs float32 [S, length] aligned with streams (generate_batch).
+        repetition_penalty / repetition_window / no_repeat_ngram_size / min_length: the history rules (generate_batch)."""
         if source_ids.ndim == 2 and source_ids.shape[0] != 1:
             raise NotImplementedError("one utterance per call (the generation scripts run batch 1); see generate_batch")
         res = self.generate_batch([source_ids], None if uniforms is None else [uniforms], max_length, temperature, generator,
-                                  collect_logits, cond_scale, False, filter_logits_fn, filter_fn_kwargs, return_logprobs)[0]
+                                  collect_logits, cond_scale, False, filter_logits_fn, filter_fn_kwargs, return_logprobs, repetition_penalty,
+                                  repetition_window, no_repeat_ngram_size, min_length)[0]
         if collect_logits or return_logprobs:
             return res
         return res if return_streams else res[0]

@@ -21,7 +21,15 @@ wall time of the call / STEPS (the encoder pass, the arming copies and the back-
 interleaved REPEATS times in one process; (c) generate_beam_many(cond_scale=1.5) against generate_beam(cond_scale=1.5) in lock-step waves of
 3 utterances (each wave to its longest limit) on 24 utterances with step limits 100..608.  PARTS=a runs on a commit without guided beams
 too: fresh processes of two commits, alternating, compare them.
-    BEAM=1 PARTS=a,b,c STEPS=256 REPEATS=5 OUT=profile.txt python tools/bench_t2s.py"""
+    BEAM=1 PARTS=a,b,c STEPS=256 REPEATS=5 OUT=profile.txt python tools/bench_t2s.py
+RULES=1: the history rules (cvx_t2s_decode_steps_rules) on the full-size CoMix and CoSingle models at 8 and 64 slots, slot b decoding
+dialogue b without a queue.  Every run decodes WARM (256) untimed steps - the histories the rules scan - and then STEPS (256) timed ones, so a
+timed step sees a history of WARM .. WARM + STEPS tokens per stream.  SIDES (D,A,B): D = the default chain (cvx_t2s_decode_steps), A = the
+per-dialogue chain with one (default) setting in every row, B = the rules chain on the same settings with an active rule set in every row
+(penalty 1.3 over the last 64 tokens, no 3-gram twice, minimum length beyond the run); interleaved REPEATS times -> us per step, min / median
+/ max, and the effective shader clock.  SIDES=D,A uses nothing a commit without the rules lacks: fresh processes of two commits, alternating,
+compare them (OUT is appended to).
+    RULES=1 SIDES=D,A,B STEPS=256 WARM=256 REPEATS=5 OUT=profile.txt python tools/bench_t2s.py"""
 import os, sys, time, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import covomix_amd.synthetic as syn
@@ -254,6 +262,76 @@ def beam_ab():
             f.write("\n".join(lines) + "\n")
 
 
+def rules_ab():
+    """D / A / B of RULES=1 (see the module docstring)"""
+    import statistics
+    from covomix_amd.t2s import check_settings, settings_rows
+    med = statistics.median
+    steps, warm, reps = int(os.environ.get("STEPS", "256")), int(os.environ.get("WARM", "256")), int(os.environ.get("REPEATS", "5"))
+    sides = [x.strip() for x in os.environ.get("SIDES", "D,A,B").split(",")]
+    names = {"D": "D default chain", "A": "A per-dialogue chain", "B": "B rules chain (1.3 / 64, 3-gram, min length)"}
+    lines = [f"text2semantic history rules, device: {torch.cuda.get_device_name(0)}; sides {' '.join(sides)}; slot b decodes dialogue b, no queue; "
+             f"{warm} untimed steps, then {steps} timed = {steps // CHUNK} graph replays of {CHUNK} steps between two synchronisations; "
+             f"{reps} rounds {' '.join(sides)} ..."]
+    for model, kw in (("CoMix", dict(two_output=True, dim=512, dim_target=1024)), ("CoSingle", dict(two_output=False, dim=512, dim_target=512))):
+        sd = {k: torch.from_numpy(v) for k, v in syn.t2s_state_dict(syn.t2s_param_shapes(**kw), seed=0).items()}
+        m = TextToSemanticDecoder(sd, dev, max_length=2048)
+        V, S = m.d["vocab"], m.d["streams"]
+        g = torch.Generator().manual_seed(3)
+        for nb in (8, 64):
+            srcs = [torch.randint(1, 30000, (1, 48), generator=g) for _ in range(nb)]
+            m._ensure(nb, nb, warm + steps)
+            chunk = {"D": lambda: m._run_chunk(1.0, nb), "A": lambda: m._run_chunk(1.0, nb, per=True),
+                     "B": lambda: m._run_chunk(1.0, nb, per=True, rules=True)}
+            for k in sides:                                  # graphs of the timed shapes (captured on idle slots)
+                m._graph(1.0, nb, **({} if k == "D" else {"per": True} if k == "A" else {"per": True, "rules": True}))
+            rec = m._slot_records(m._contexts(srcs)).to(dev)
+            m.buf["uniforms"].uniform_(1e-6, 1 - 1e-6)
+            m.buf["per"][:nb].copy_(settings_rows(check_settings([None] * nb, nb, V, S)).to(dev))
+            if "B" in sides:
+                from covomix_amd.t2s import check_rules, rules_rows
+                m.buf["rules"][:nb].copy_(rules_rows(check_rules(None, nb, m.max_length, 1.3, 64, 3, warm + steps)).to(dev))
+            start = m.start[None, :].expand(nb, -1)
+
+            def run(k):
+                m.buf["x"][:nb].copy_(start)
+                m.buf["state"].copy_(rec)
+                for _ in range(warm // CHUNK):
+                    chunk[k]()
+                torch.cuda.synchronize(); t0 = time.perf_counter()
+                for _ in range(steps // CHUNK):
+                    chunk[k]()
+                torch.cuda.synchronize()
+                return (time.perf_counter() - t0) / steps * 1e6, m.buf["tokens"][:nb, :, :warm + steps].clone()
+            tok = {k: run(k)[1] for k in sides}              # warm-up of every timed shape; and what must agree does
+            if "D" in tok and "A" in tok:
+                assert torch.equal(tok["D"], tok["A"]), "the per-dialogue chain decodes other tokens than the default chain"
+            c0 = ops.clock_stamps()
+            t = {k: [] for k in sides}
+            for _ in range(reps):
+                for k in sides:
+                    t[k].append(run(k)[0])
+            clk = ops.clock_from_stamps(c0, ops.clock_stamps())
+            lines.append(f"{model}, {nb} slots; effective shader clock over the timed rounds ({clk.get('cus', 0)} CUs): "
+                         + (f"{clk['mhz']:.0f} MHz" if clk else "not reported"))
+            for k in sides:
+                v = sorted(t[k])
+                lines.append(f"  {names[k]:45s} us/step  min {v[0]:8.1f}  median {med(v):8.1f}  max {v[-1]:8.1f}   all {[round(x, 1) for x in t[k]]}")
+            if "A" in t and "B" in t:
+                rep_ = 0 if "B" not in tok else sum(1 for b in range(nb) for s_ in range(S)
+                                                    if len({tuple(tok["B"][b, s_, i:i + 3].tolist()) for i in range(warm + steps - 2)}) < warm + steps - 2)
+                lines.append(f"  B median - A median = {med(t['B']) - med(t['A']):+.1f} us per step (A's own spread {max(t['A']) - min(t['A']):.1f}); "
+                             f"streams of B with a repeated 3-gram: {rep_} of {nb * S}")
+        del m
+    print("\n".join(lines), flush=True)
+    if os.environ.get("OUT"):
+        with open(os.environ["OUT"], "a") as f:
+            f.write("\n".join(lines) + "\n")
+
+
+if os.environ.get("RULES", "0") == "1":
+    rules_ab()
+    sys.exit(0)
 if os.environ.get("PER", "0") == "1":
     per_dialogue_ab()
     sys.exit(0)
