@@ -21,7 +21,7 @@ Restates, in plain torch CPU ops (fp32 by default, fp64 on request):
 """
 from __future__ import annotations
 
-from typing import Dict, Optional
+from typing import Dict, Optional, Sequence
 
 import numpy as np
 import torch
@@ -53,8 +53,9 @@ def pos_conv_weight(sd, dtype=torch.float32) -> torch.Tensor:
     return (v * (g / v.pow(2).sum(dim=(0, 1), keepdim=True).sqrt())).to(dtype)
 
 
-def encoder(sd, x: torch.Tensor, n_layers: int, heads: int = 12, groups: int = 16, dtype=torch.float32) -> torch.Tensor:
-    """x [B, T, D] -> output of encoder layer n_layers (1-based), wav2vec2.py:1078-1163."""
+def encoder(sd, x: torch.Tensor, n_layers: int, heads: int = 12, groups: int = 16, dtype=torch.float32, taps: Optional[dict] = None) -> torch.Tensor:
+    """x [B, T, D] -> output of encoder layer n_layers (1-based), wav2vec2.py:1078-1163.  `taps`: a dict whose integer keys name
+    layers (0 = the encoder's input LayerNorm); each receives that layer's output on the way, so one pass serves several layers."""
     B, T, D = x.shape
     w = pos_conv_weight(sd, dtype)
     k = w.shape[-1]
@@ -63,6 +64,8 @@ def encoder(sd, x: torch.Tensor, n_layers: int, heads: int = 12, groups: int = 1
         pc = pc[:, :, :-1]                                                      # SamePad
     x = x + F.gelu(pc).transpose(1, 2)
     x = F.layer_norm(x, (D,), _t(sd, "encoder.layer_norm.weight", dtype), _t(sd, "encoder.layer_norm.bias", dtype), 1e-5)
+    if taps is not None and 0 in taps:
+        taps[0] = x
     dh = D // heads
     for i in range(n_layers):
         p = f"encoder.layers.{i}."
@@ -77,26 +80,41 @@ def encoder(sd, x: torch.Tensor, n_layers: int, heads: int = 12, groups: int = 1
         h = F.gelu(lin(x, "fc1"))
         x = x + lin(h, "fc2")
         x = F.layer_norm(x, (D,), _t(sd, p + "final_layer_norm.weight", dtype), _t(sd, p + "final_layer_norm.bias", dtype), 1e-5)
+        if taps is not None and i + 1 in taps:
+            taps[i + 1] = x
     return x
 
 
-def extract_features(sd, wav: torch.Tensor, output_layer: int = 12, dtype=torch.float32) -> torch.Tensor:
-    """HubertModel.extract_features(source, mask=False, output_layer) -> [B, T, 768]  (hubert.py:433-480, 533-549)."""
+def extract_features(sd, wav: torch.Tensor, output_layer: int = 12, dtype=torch.float32, taps: Optional[dict] = None) -> torch.Tensor:
+    """HubertModel.extract_features(source, mask=False, output_layer) -> [B, T, 768]  (hubert.py:433-480, 533-549).
+    `taps` as in encoder(); the key "conv" receives the conv features [B, T, 512]."""
     f = conv_features(sd, wav, dtype)
+    if taps is not None and "conv" in taps:
+        taps["conv"] = f
     f = F.layer_norm(f, (f.shape[-1],), _t(sd, "layer_norm.weight", dtype), _t(sd, "layer_norm.bias", dtype), 1e-5)
     x = F.linear(f, _t(sd, "post_extract_proj.weight", dtype), _t(sd, "post_extract_proj.bias", dtype))
-    return encoder(sd, x, output_layer, dtype=dtype)
+    return encoder(sd, x, output_layer, dtype=dtype, taps=taps)
 
 
 def get_feats(sd, wav: np.ndarray, layer: int = 12, normalize: bool = False, max_chunk: int = 1600000,
-              dtype=torch.float32) -> torch.Tensor:
-    """hubert_feature_reader.py:58-78 on an already loaded mono waveform -> [T, 768]."""
+              dtype=torch.float32, layers: Optional[Sequence[int]] = None, conv: bool = False):
+    """hubert_feature_reader.py:58-78 on an already loaded mono waveform -> [T, 768].
+    With `layers` (and / or conv=True): ONE pass up to the deepest layer named, returning {layer: [T, 768]} for every layer in
+    `layers` (0 = the encoder's input LayerNorm) plus {"conv": [T, 512]} - the same tensors the single-layer calls give."""
     x = torch.from_numpy(np.asarray(wav)).float()
     if normalize:
         x = F.layer_norm(x, x.shape)
     x = x.view(1, -1)
-    out = [extract_features(sd, x[:, s: s + max_chunk], layer, dtype) for s in range(0, x.shape[1], max_chunk)]
-    return torch.cat(out, 1).squeeze(0)
+    if layers is None and not conv:
+        out = [extract_features(sd, x[:, s: s + max_chunk], layer, dtype) for s in range(0, x.shape[1], max_chunk)]
+        return torch.cat(out, 1).squeeze(0)
+    keys = [int(l) for l in (layers or ())] + (["conv"] if conv else [])
+    chunks = []
+    for s in range(0, x.shape[1], max_chunk):
+        taps = dict.fromkeys(keys)
+        extract_features(sd, x[:, s: s + max_chunk], max([k for k in keys if k != "conv"], default=0), dtype, taps=taps)
+        chunks.append(taps)
+    return {k: torch.cat([c[k] for c in chunks], 1).squeeze(0) for k in keys}
 
 
 def apply_kmeans(centers: np.ndarray, feats: torch.Tensor) -> np.ndarray:

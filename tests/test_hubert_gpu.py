@@ -78,6 +78,29 @@ def test_layernorm_kernel(rows, D):
     assert torch.equal(xin, got)
 
 
+@pytest.mark.parametrize("rows", [1, 5])
+@pytest.mark.parametrize("D", [4, 260, 516, 772, 1020])
+def test_layernorm_kernel_partial_vector_rounds(rows, D):
+    """D one float4 past a template instance's previous round (260, 516, 772), one short of a full last round (1020) and a single
+    lane (4): the last vector round of layernorm_kernel<NV> is partial.  One wave per row, four rows per block: 1 and 5 rows leave
+    three waves of the last block without a row.  Also a constant row (variance 0: the output is beta) and the in-place form."""
+    from covomix_amd import ops
+    g = torch.Generator().manual_seed(100 * rows + D)
+    x = torch.randn(rows, D, generator=g) * 3 + 1.5
+    x[rows - 1] = 2.75                                                   # a constant row
+    w, b = torch.randn(D, generator=g), torch.randn(D, generator=g)
+    want = torch.nn.functional.layer_norm(x.double(), (D,), w.double(), b.double(), 1e-5)
+    guard = torch.full((rows + 1, D), float("nan")).cuda()               # the row after the last must stay untouched
+    got = ops.layernorm(x.cuda(), w.cuda(), b.cuda(), out=guard[:rows])
+    assert rel(got, want) < 5e-7
+    assert torch.equal(got[rows - 1].cpu(), b) and bool(torch.isnan(guard[rows]).all())
+    if rows > 1:
+        assert rel(got[:rows - 1], want[:rows - 1]) < 5e-7
+    xin = x.cuda()
+    ops.layernorm(xin, w.cuda(), b.cuda(), out=xin)                      # in place
+    assert torch.equal(xin, got)
+
+
 @pytest.mark.parametrize("n", [400, 8000, 5215, 40003])
 def test_conv0_groupnorm_gelu(sd, n):
     from covomix_amd import ops
@@ -90,6 +113,31 @@ def test_conv0_groupnorm_gelu(sd, n):
     got = ops.hubert_conv0_gn_gelu(wav.cuda(), w.reshape(512, 10).contiguous().cuda(), gw.cuda(), gb.cuda(), 5)
     assert got.shape == y.shape == ((n - 10) // 5 + 1, 512)
     assert rel(got, y) < 2e-6
+
+
+@pytest.mark.parametrize("L", [1, 16, 17, 128, 129])
+@pytest.mark.parametrize("C,k,stride", [(4, 1, 1), (260, 32, 8), (512, 10, 5)])
+def test_conv0_groupnorm_gelu_geometry_edges(C, k, stride, L):
+    """The geometry cvx_hubert_conv0_gn_gelu_f32 accepts beyond HuBERT-Base's (512, 10, 5): a channel count below one block and one
+    past it, the longest kernel and stride; L output frames at the 16-frame block edge of conv0_kernel, the 128-row chunk edge of the
+    statistics, and L = 1 (variance 0: every output is gelu(beta)).  The sample count leaves a remainder the stride does not use."""
+    from covomix_amd import ops
+    n = (L - 1) * stride + k + (stride - 1)
+    g = torch.Generator().manual_seed(1000 * C + L)
+    wav = torch.randn(n, generator=g) * 0.1 + 0.03
+    w = torch.randn(C, 1, k, generator=g) / k ** 0.5
+    gw, gb = torch.randn(C, generator=g), torch.randn(C, generator=g)
+    y = torch.nn.functional.conv1d(wav.double().view(1, 1, -1), w.double(), stride=stride)
+    if L > 1:
+        y = torch.nn.functional.group_norm(y, C, gw.double(), gb.double(), 1e-5)
+    else:                                                                # (torch refuses one value per channel) y - mean = 0
+        y = (y - y) * gw.double()[None, :, None] + gb.double()[None, :, None]
+    y = torch.nn.functional.gelu(y)[0].T
+    got = ops.hubert_conv0_gn_gelu(wav.cuda(), w.reshape(C, k).contiguous().cuda(), gw.cuda(), gb.cuda(), stride)
+    assert got.shape == y.shape == (L, C)
+    assert rel(got, y) < 2e-6
+    if L == 1:
+        assert rel(got[0], torch.nn.functional.gelu(gb.double())) < 2e-6
 
 
 def test_positional_conv_groups(sd, enc):
@@ -157,6 +205,48 @@ def test_kmeans_argmin_kernel_vs_oracle_with_ties():
     assert float(margin.min()) >= 0
     assert km(x).tolist() == want.tolist()                                # numpy in -> numpy out, like the reference
     assert km(np.zeros((0, 768), np.float32)).shape == (0,)
+
+
+@pytest.mark.parametrize("D", [4, 100])
+@pytest.mark.parametrize("K", [1, 63, 64, 65])
+def test_kmeans_argmin_kernel_geometry_edges(K, D):
+    """kmeans_argmin_kernel away from K = 500, D = 768: fewer centres than lanes, exactly 64, one past (lane 0 holds centres 0 and 64),
+    and a single centre (no runner-up: the margin is +inf).  Small-integer features and centres make every fp32 distance exact, so
+    labels AND margins must equal the fp64 ones exactly.  Ties: between centres j and j + 64 (the same lane), across lanes, and
+    three-fold - the lowest index wins and the margin is 0."""
+    from covomix_amd import ops
+    rs = np.random.RandomState(10 * K + D)
+    C = rs.randint(-3, 4, size=(K, D)).astype(np.float32)
+    x = rs.randint(-3, 4, size=(23, D)).astype(np.float32)               # 23 rows: the last block has one idle wave
+    if K >= 2:
+        x[0] = C[K - 1]                                                  # an exact hit on the last centre ...
+        x[4] = C[1]
+    if K >= 63:
+        C[40] = C[7]; x[1] = C[7]                                        # ... a tie across lanes: 7 wins over 40
+        C[62] = C[20]; C[33] = C[20]; x[2] = C[20]                       # a three-fold tie: 20
+    if K == 65:
+        C[64] = C[0]; x[3] = C[0]                                        # a tie inside lane 0: centre 0 wins over 64
+        x[0] = C[64]                                                     # (the last centre again, now equal to the first)
+    xd, Cd = torch.from_numpy(x).double(), torch.from_numpy(C).double()
+    dots = xd @ Cd.T
+    dist = (xd.pow(2).sum(1, keepdim=True) - 2 * dots) + Cd.pow(2).sum(1)[None]
+    want = dist.argmin(1)
+    if K > 1:
+        two = dist.topk(2, dim=1, largest=False).values
+        want_margin = two[:, 1] - two[:, 0]
+    else:
+        want_margin = torch.full((23,), float("inf"), dtype=torch.float64)
+    assert float(dist.abs().max()) < 2 ** 20                             # every term an integer far below 2^24: exact in fp32
+    labels, margin = ops.kmeans_argmin(torch.from_numpy(x).cuda(), dots.float().cuda().contiguous(), Cd.pow(2).sum(1).float().cuda(),
+                                       with_margin=True)
+    assert labels.dtype == torch.int64
+    np.testing.assert_array_equal(labels.cpu().numpy(), want.numpy())
+    np.testing.assert_array_equal(margin.cpu().double().numpy(), want_margin.numpy())
+    if K >= 63:
+        assert labels[1].item() == 7 and labels[2].item() == 20 and margin[1].item() == 0.0 and margin[2].item() == 0.0
+    if K == 65:
+        assert labels[3].item() == 0 and labels[0].item() == 0 and margin[3].item() == 0.0
+    assert torch.equal(ops.kmeans_argmin(torch.from_numpy(x).cuda(), dots.float().cuda().contiguous(), Cd.pow(2).sum(1).float().cuda()), labels)
 
 
 def test_other_lengths_vs_fp64_oracle(sd, enc):

@@ -74,6 +74,23 @@ def test_oracle_normalized_waveform_and_chunking(gold, sd):
     assert parts.shape == want.shape and torch.equal(parts, want)
 
 
+def test_oracle_several_layers_in_one_pass(gold, sd):
+    """get_feats(layers=..., conv=True) taps one pass: the same tensors, bit for bit, as one call per layer - chunked too."""
+    wav = gold["b_wav"]
+    with torch.no_grad():
+        for dtype in (torch.float32, torch.float64):
+            taps = ho.get_feats(sd, wav, layers=(0, 1, 3), conv=True, dtype=dtype)
+            assert set(taps) == {0, 1, 3, "conv"}
+            for layer in (0, 1, 3):
+                assert torch.equal(taps[layer], ho.get_feats(sd, wav, layer=layer, dtype=dtype))
+            assert torch.equal(taps["conv"], ho.conv_features(sd, torch.from_numpy(wav).view(1, -1), dtype)[0])
+        parts = ho.get_feats(sd, wav, layers=(2,), max_chunk=3000)
+        assert torch.equal(parts[2], ho.get_feats(sd, wav, layer=2, max_chunk=3000))
+        only_conv = ho.get_feats(sd, wav, conv=True)
+        assert set(only_conv) == {"conv"}
+        assert torch.equal(only_conv["conv"], ho.conv_features(sd, torch.from_numpy(wav).view(1, -1))[0])
+
+
 @pytest.mark.parametrize("orig,new", [(8000, 16000), (44100, 16000), (16000, 8000)])
 def test_resampler_restatement_properties(orig, new):
     """torchaudio is absent (parity unpinned): check what the windowed-sinc bank must satisfy, and scipy's polyphase
