@@ -19,7 +19,7 @@ Python here only sequences kernel launches on torch's current stream and owns de
 from __future__ import annotations
 
 from dataclasses import dataclass, field
-from typing import Dict, List, Optional, Sequence, Tuple, Union
+from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple, Union
 
 import math
 import os
@@ -47,6 +47,57 @@ def _dims_from_state(sd: Dict[str, torch.Tensor]) -> dict:
                 time_hidden=sd["sinu_pos_emb.1.weight"].shape[0])
 
 
+# ---------------------------------------------------------------------- which kernels a solve runs: a function of its row count
+SPLIT_IO_ABOVE_ROWS = 64         # up to here the fp32 kernels; above, activations that only feed GEMMs live as split pairs
+FUSE_NORM_BELOW_ROWS = 2048      # below: every norm rides in the GEMM that produces its input (the split-K path normalises inside its reduction)
+LARGE_KERNEL_MIN_ROWS = 2048     # the deferred-norm forms exist in the large-problem GEMM only, which takes no fewer rows
+GRAPH_MAX_ROWS = 8192            # default of CVX_GRAPH_MAX_ROWS: larger batches are GPU-bound and stay eager
+
+
+@dataclass(frozen=True)
+class Route:
+    """What route() decided for one network evaluation of M rows; every consumer reads this record."""
+    split_io: bool                   # the split pipe: (fp16 hi, lo) activations, f16x3 / f16 kernels on every consumer GEMM
+    interleaved: bool                # GEMM A operands as ops.SplitIL (needs interleaved weights: f16x3, dim % 32 == 0)
+    fuse_norm: bool                  # to_out / ff2 / combiner calls carry norm=
+    splitk_scratch: bool             # ops.gemm hands its split-K scratch over (its own rule: SPLITK_SCRATCH_MAX_ROWS)
+    deferred: bool                   # pair-only residual stream, norms deferred into the GEMMs (_layers_pair_stream)
+    graph: bool                      # the solve is captured once per shape and replayed
+    ragged_capacity: Optional[int]   # rows of a ragged batch's workspace (None: equal-length batch)
+
+
+def route(M: int, dim: int, precision: str, ragged_rows: Optional[int] = None) -> Route:
+    """The route of an evaluation of M rows (B T, doubled under guidance; ragged_rows = M for a packed ragged batch).  Pure: no tensor,
+    no device; the environment and VectorField.DEFER_MIN_ROWS are read now."""
+    env = os.environ.get
+    # split activations need K % 32 == 0 on every consumer GEMM; the single-term kernel of 'f16' consumes 64 k per stage
+    split_io = precision != "fp32" and M > SPLIT_IO_ABOVE_ROWS and dim % (64 if precision == "f16" else 32) == 0
+    interleaved = split_io and precision == "f16x3" and M >= ops.il_min_rows() and dim >= 512
+    deferred = (interleaved and M >= max(VectorField.DEFER_MIN_ROWS, LARGE_KERNEL_MIN_ROWS) and dim % 64 == 0 and dim <= 4096
+                and env("CVX_DEFER_NORM", "1") == "1")
+    graph = ragged_rows is None and env("CVX_GRAPH", "1") != "0" and M <= int(env("CVX_GRAPH_MAX_ROWS", GRAPH_MAX_ROWS))
+    q = VectorField.RAGGED_ROW_QUANTUM
+    return Route(split_io, interleaved, split_io and M < FUSE_NORM_BELOW_ROWS, split_io and M <= ops.SPLITK_SCRATCH_MAX_ROWS, deferred,
+                 graph, None if ragged_rows is None else (ragged_rows + q - 1) // q * q)
+
+
+class _Linear(NamedTuple):
+    """One linear of the network: fp32 weight, bias (or None), its load-time (hi, lo, 1/scale) split and the interleaved copy of that."""
+    w: torch.Tensor
+    bias: Optional[torch.Tensor]
+    split: Optional[tuple]
+    il: Optional[tuple]
+    plain: Optional[tuple]           # the w_split of a call without split I/O: none under 'f16' (VectorField.__init__)
+
+
+class _Layer(NamedTuple):
+    comb: Optional[_Linear]          # the skip combiner of the later layers (None: this layer pushes a skip)
+    qkv: _Linear
+    out: _Linear
+    ff1: _Linear
+    ff2: _Linear
+
+
 class VectorField:
     """Device-resident weights of one CoVoMix network + the launch sequence of one evaluation."""
 
@@ -69,52 +120,49 @@ class VectorField:
             raise ValueError("only conv_pos_embed_kernel_size == 31 is supported (reference default)")
         self.sd = sd
         # adaptive-norm projection weights packed [2*n_norms*dim, time_hidden]: (gamma, beta) per norm
-        ws, bs = [], []
-        for i in range(d["depth"]):
-            for n in (1, 3):
-                p = f"transformer.layers.{i}.{n}"
-                ws += [sd[p + ".to_gamma.weight"], sd[p + ".to_beta.weight"]]
-                bs += [sd[p + ".to_gamma.bias"], sd[p + ".to_beta.bias"]]
-        self.ada_w = torch.cat(ws, dim=0).contiguous()
-        self.ada_b = torch.cat(bs, dim=0).contiguous()
-        for i in range(d["depth"]):          # the unpacked copies are never read again
-            for n in (1, 3):
-                for nm in ("to_gamma", "to_beta"):
-                    for s in ("weight", "bias"):
-                        del sd[f"transformer.layers.{i}.{n}.{nm}.{s}"]
+        names = [f"transformer.layers.{i}.{n}.{nm}" for i in range(d["depth"]) for n in (1, 3) for nm in ("to_gamma", "to_beta")]
+        self.ada_w = torch.cat([sd[k + ".weight"] for k in names], dim=0).contiguous()
+        self.ada_b = torch.cat([sd[k + ".bias"] for k in names], dim=0).contiguous()
+        for k in names:                      # the unpacked copies are never read again
+            del sd[k + ".weight"], sd[k + ".bias"]
         self.dw_w = sd["conv_embed.dw_conv1d.0.weight"].reshape(d["dim"], 31).contiguous()
         inv_freq = sd.get("transformer.rotary_emb.inv_freq")
         if inv_freq is None:
             inv_freq = 1.0 / (10000 ** (torch.arange(0, 64, 2, device=device).float() / 64))
         self.inv_freq = inv_freq
         self._ws: Dict[tuple, dict] = {}
-        # split (fp16 hi, fp16 lo, 1/scale) copies of the big GEMM weights - load-time packing
-        self.split: Dict[str, tuple] = {}
-        if precision in ("f16x3", "f16"):
-            for k, v in sd.items():
-                if k.endswith(".weight") and v.ndim == 2 and v.shape[1] % 32 == 0 and (
-                        ".2.to_qkv" in k or ".2.to_out" in k or ".4.0." in k or ".4.2." in k
-                        or (k.startswith("transformer.layers.") and k.endswith(".0.weight")) or k == "to_pred.weight"):
-                    self.split[k] = ops.split_f16(v, with_lo=(precision == "f16x3"))
-            # the step-invariant columns of to_embed (phoneme embeddings | conditioning mel: one [2BT, 2208] x [2208, 1024] product
-            # per solve) - 0.74 ms on the fp32 pipe at the bench shape
-            # the adaptive-norm table GEMM - [n evaluation times, dim] x the packed [4 depth dim, dim] matrix: pure weight
-            # streaming at 32 rows - 1.35 ms per solve on the fp32 kernel inside the model (cold weights), 0.76 ms here
-            # (rocprofv3).  Neither is close to the 134 MB / HBM rate = 30 us: DESIGN 4.4
-            # (solves of more than 32 evaluation times build self.split["ada"] on demand: _time_tables)
-            w_rest = sd["to_embed.weight"][:, d["dim_out"]:]
-            if precision == "f16x3" and w_rest.shape[1] % 32 == 0:
-                self.w_rest = w_rest.contiguous()
-                self.split["to_embed.rest"] = ops.split_f16(self.w_rest)
-        self._init_gain_model()
-        # interleaved copies ([hi 32 | lo 32] per K-step: whole cache lines for the DMA) for the large-problem kernel
-        self.split_il: Dict[str, tuple] = {}
         self._dn_bufs: Dict[tuple, dict] = {}          # deferred norm: W diag(gamma(t)) pairs per (n, depth, solver grid)
         self._time_cache: Dict[tuple, dict] = {}       # solver grid (nfe, method) -> everything that depends on the evaluation times only
-        if precision == "f16x3":
-            for k, v in self.split.items():
-                if v[0].shape[0] >= 512 or k == "to_pred.weight":
-                    self.split_il[k] = ops.split_f16_interleaved(v)
+        def linear(name: str) -> Optional[_Linear]:
+            """The record of one linear (None: the checkpoint has none of that name): load-time packing of the big GEMM weights as
+            split (fp16 hi, fp16 lo, 1/scale) copies, and for the medium- and large-problem kernels an interleaved copy of those
+            ([hi 32 | lo 32] per K-step: whole cache lines for the DMA)."""
+            w, bias = sd.get(name + ".weight"), sd.get(name + ".bias")
+            if w is None:
+                return None
+            sp = ops.split_f16(w, with_lo=(precision == "f16x3")) if precision != "fp32" and w.shape[1] % 32 == 0 else None
+            il = ops.split_f16_interleaved(sp) if precision == "f16x3" and sp is not None and (w.shape[0] >= 512 or name == "to_pred") else None
+            # a call without split I/O passes no w_split under 'f16': the single-term kernel needs a pre-split A, and ops.gemm would
+            # otherwise take the f16x3 branch above SPLIT_IO_ABOVE_ROWS rows - the fp32 kernels run instead
+            return _Linear(w, bias, sp, il, None if precision == "f16" else sp)
+        self.layers = [_Layer(*(linear(f"transformer.layers.{i}.{n}") for n in ("0", "2.to_qkv", "2.to_out", "4.0", "4.2")))
+                       for i in range(d["depth"])]
+        self.to_pred = linear("to_pred")
+        self.final_gamma = sd["transformer.final_norm.gamma"]
+        self.embed_x = sd["to_embed.weight"][:, : d["dim_out"]]          # the x columns of to_embed: every evaluation
+        # the step-invariant columns of to_embed (phoneme embeddings | conditioning mel: one [2BT, 2208] x [2208, 1024] product
+        # per solve) - 0.74 ms on the fp32 pipe at the bench shape
+        # the adaptive-norm table GEMM - [n evaluation times, dim] x the packed [4 depth dim, dim] matrix: pure weight
+        # streaming at 32 rows - 1.35 ms per solve on the fp32 kernel inside the model (cold weights), 0.76 ms here
+        # (rocprofv3).  Neither is close to the 134 MB / HBM rate = 30 us: DESIGN 4.4
+        # (solves of more than 32 evaluation times build self.ada_split on demand: _time_tables)
+        self.ada_split = None
+        w_rest = sd["to_embed.weight"][:, d["dim_out"]:]
+        pack = precision == "f16x3" and w_rest.shape[1] % 32 == 0
+        w_rest = w_rest.contiguous() if pack else w_rest
+        sp = ops.split_f16(w_rest) if pack else None
+        self.embed_rest = _Linear(w_rest, sd["to_embed.bias"], sp, None, sp)
+        self._init_gain_model()
 
     # ------------------------------------------------------------------ activation pre-scales (scale-free split pairs)
     # An (fp16 hi, fp16 lo) pair has full (22-bit) precision only while |x| is inside [2^-3, 2^16): below, `lo` falls into
@@ -138,14 +186,12 @@ class VectorField:
             w = w if rows is None else w[rows[0]:rows[1]]
             return float(w.double().square().sum().sqrt() / (w.shape[0] ** 0.5))
         g = dict(qk=[], v=[], o=[], f1=[], b1=[], f2=[], comb=[])
-        for i in range(d["depth"]):
-            p = f"transformer.layers.{i}"
-            wq = sd[p + ".2.to_qkv.weight"]
-            g["qk"].append(fro(wq, (0, 2 * inner))); g["v"].append(fro(wq, (2 * inner, 3 * inner)))
-            g["o"].append(fro(sd[p + ".2.to_out.weight"]))
-            g["f1"].append(fro(sd[p + ".4.0.weight"])); g["b1"].append(float(sd[p + ".4.0.bias"].double().square().mean()))
-            g["f2"].append(fro(sd[p + ".4.2.weight"]))
-            g["comb"].append(fro(sd[p + ".0.weight"]) if (p + ".0.weight") in sd else 0.0)
+        for ly in self.layers:
+            g["qk"].append(fro(ly.qkv.w, (0, 2 * inner))); g["v"].append(fro(ly.qkv.w, (2 * inner, 3 * inner)))
+            g["o"].append(fro(ly.out.w))
+            g["f1"].append(fro(ly.ff1.w)); g["b1"].append(float(ly.ff1.bias.double().square().mean()))
+            g["f2"].append(fro(ly.ff2.w))
+            g["comb"].append(fro(ly.comb.w) if ly.comb is not None else 0.0)
         dev = self.device
         self.gain = {k: torch.tensor(v, dtype=torch.float32, device=dev) for k, v in g.items()}
         # embedding output: x columns (x ~ N(0,1) at t = 0, O(1) later), phoneme-embedding columns (RMS of the table), cond
@@ -156,13 +202,11 @@ class VectorField:
         ms = lambda w: float(w.square().sum() / w.shape[0])
         self.embed_ms = (ms(we[:, :n_x]) + emb_ms * ms(we[:, n_x:n_x + n_e]) + 16.0 * ms(we[:, n_x + n_e:])
                          + float(sd["to_embed.bias"].double().square().mean()))
-        self.has_comb = [c > 0.0 for c in g["comb"]]
-        gf = float(sd["transformer.final_norm.gamma"].double().square().mean().sqrt())
+        gf = float(self.final_gamma.double().square().mean().sqrt())
         self.pred_scale = torch.tensor([self._pow2(self.TARGET_RMS / max(gf, 1e-30))], dtype=torch.float32, device=dev)
 
     @staticmethod
     def _pow2(x: float) -> float:
-        import math
         return 2.0 ** max(-40, min(40, round(math.log2(x)))) if x > 0 and math.isfinite(x) else 1.0
 
     def _activation_scales(self, table: torch.Tensor) -> tuple:
@@ -189,7 +233,7 @@ class VectorField:
         stages = []                          # mean squares of the stream per layer: at its input, behind its skip combiner, behind to_out, behind ff2
         for i in range(L):
             h_in = h2
-            if self.has_comb[i]:
+            if self.layers[i].comb is not None:
                 h2 = (h2 + skips.pop()) * gn["comb"][i].square()
             else:
                 skips.append(h2)
@@ -208,18 +252,17 @@ class VectorField:
     RAGGED_ROW_QUANTUM = 1024       # ragged batches: workspaces are sized in steps of this many rows and shared by every
                                     # batch composition that fits (a directory never repeats a composition)
 
-    def _workspace(self, Bt: int, T: int, ragged_rows: int = 0) -> dict:
+    def route(self, M: int, ragged_rows: Optional[int] = None) -> Route:
+        return route(M, self.d["dim"], self.precision, ragged_rows)
+
+    def _workspace(self, Bt: int, T: int, ragged_rows: int = 0, r: Optional[Route] = None) -> dict:
         """Buffers of one batch shape.  Equal-length batch: Bt sequences of T frames.  Ragged batch (ragged_rows = M > 0):
         capacity rounded up to RAGGED_ROW_QUANTUM rows, ONE V^T row set per head over all packed rows, no RoPE table (it
         depends on the composition: prepare() builds it per call); callers use a row-cut view (_ws_cut)."""
         d, dev = self.d, self.device
-        if ragged_rows:
-            q = self.RAGGED_ROW_QUANTUM
-            M = (ragged_rows + q - 1) // q * q
-            key = ("ragged", M, ragged_rows >= ops.il_min_rows())  # (the interleaved-pair choice below depends on the real row count)
-        else:
-            M = Bt * T
-            key = (Bt, T)
+        r = r or self.route(ragged_rows or Bt * T, ragged_rows or None)        # (prepare() passes the route it made for the batch)
+        M = r.ragged_capacity or Bt * T
+        key = ("ragged", M, ragged_rows >= ops.il_min_rows()) if ragged_rows else (Bt, T)  # (the pair layout depends on the real row count)
         ws = self._ws.pop(key, None)
         if ws is not None:
             self._ws[key] = ws                                   # most recently used last
@@ -236,11 +279,9 @@ class VectorField:
             lo_too = self.precision == "f16x3"          # 'f16': (hi, None)
             h16 = lambda *s: (torch.empty(*s, dtype=torch.float16, device=dev),
                               torch.empty(*s, dtype=torch.float16, device=dev) if lo_too else None)
-            # GEMM A operands: for the large-problem kernel (M >= 2048, interleaved weights available) as INTERLEAVED pairs
-            # ([hi 32 | lo 32] per K-step: whole cache lines for the DMA), otherwise as two separate fp16 tensors
-            a16 = h16
-            if lo_too and (ragged_rows or M) >= ops.il_min_rows() and self.split_il and d["dim"] >= 512:
-                a16 = lambda rows, cols: ops.SplitIL(rows, cols, dev)
+            # GEMM A operands: for the medium- and large-problem kernels (from ops.il_min_rows() rows, interleaved weights available)
+            # as INTERLEAVED pairs ([hi 32 | lo 32] per K-step: whole cache lines for the DMA), otherwise as two separate fp16 tensors
+            a16 = (lambda rows, cols: ops.SplitIL(rows, cols, dev)) if r.interleaved else h16
             ws["normed16"], ws["att16"], ws["ff16"] = a16(M, d["dim"]), a16(M, d["heads"] * 64), a16(M, 4 * d["dim"])
             # final norm -> to_pred (N = 80): the medium-problem kernel takes it (interleaved pair; K slices below 2048 rows)
             ws["pred16"] = a16(M, d["dim"]) if (a16 is not h16 and d["dim_out"] % 16 == 0) else h16(M, d["dim"])
@@ -287,20 +328,20 @@ class VectorField:
         if lengths is not None:
             B, T, M1 = len(lengths), None, int(sum(lengths))
             assert cond.ndim == 2 and cond.shape[0] == M1 and phoneme_ids.shape[0] == M1
-            Bt = 2 * B if use_null else B
             rg = ops.Ragged(lengths, self.device, repeat=2 if use_null else 1)
-            full = self._workspace(0, 0, ragged_rows=rg.M)
-            ws = self._ws_cut(full, 0, rg.M, vt=None)            # row views of the capacity-sized buffers; V^T stays whole
+        else:
+            B, T, _ = cond.shape
+            M1 = B * T
+        Bt, M = (2 * B, 2 * M1) if use_null else (B, M1)
+        r = self.route(M, ragged_rows=None if rg is None else M)   # from the real row count: read here, by _workspace and by evaluate()
+        if rg is not None:
+            full = self._workspace(0, 0, M, r)
+            ws = self._ws_cut(full, 0, M, vt=None)               # row views of the capacity-sized buffers; V^T stays whole
             ws["whole"] = full
             ws["rope"] = self._rope_tables(rg.positions())       # per-ROW tables: the to_qkv epilogue then runs with rope_T = M
         else:
-            B, T, _ = cond.shape
-            Bt = 2 * B if use_null else B
-            M1 = B * T
-            ws = self._workspace(Bt, T)
-        n = times.numel()
+            ws = self._workspace(Bt, T, r=r)
         tt = self._time_tables(times, times_key)
-        table = tt["table"]
         # step-invariant to_embed columns: rows [0, M1) conditional, rows [M1, 2*M1) null branch
         g = ws["gathered"]
         ids = phoneme_ids.to(torch.int64).contiguous()
@@ -309,20 +350,18 @@ class VectorField:
         if use_null:
             ops.embed_gather(None, d["streams"], sd["to_phoneme_emb.weight"], None, sd["null_cond"], d["dim_cond"],
                              d["null_id"], g[M1:], M1)
-        if "to_embed.rest" in self.split:
-            ops.gemm(g, self.w_rest, ws["base"], bias=sd["to_embed.bias"], w_split=self.split["to_embed.rest"])
-        else:
-            ops.gemm(g, sd["to_embed.weight"][:, d["dim_out"]:], ws["base"], bias=sd["to_embed.bias"])
-        ctx = dict(ws=ws, table=table, B=B, T=T, Bt=Bt, M1=M1, use_null=use_null, M=(2 * M1 if use_null else M1), ragged=rg)
+        rest = self.embed_rest
+        ops.gemm(g, rest.w, ws["base"], bias=rest.bias, w_split=rest.split)
+        ctx = dict(ws=ws, table=tt["table"], B=B, T=T, Bt=Bt, M1=M1, use_null=use_null, M=M, ragged=rg, route=r)
         if "S" in tt:
             ctx["scales"], ctx["h_scale"] = tt["S"], tt["H"]                   # keep the tensors alive as long as the pointers
             ctx["sp"], ctx["hp"] = tt["sp"], tt["H"].data_ptr()
-            if self._defers(ctx["M"], ws):
+            if r.deferred:
                 if tt["dn"] is None:
                     # built by split-pair kernels (split_f16_colscale_il): cached only when the build itself stayed inside the window
                     # (_tables_clean) - a clamped table must not outlive the call that is flagged for it
                     clean0 = self._flag_clear()
-                    dn = self._deferred_norm_tables(table, tt["HS"], times_key)
+                    dn = self._deferred_norm_tables(tt["table"], tt["HS"], times_key)
                     if tt.get("cached") and clean0 and self._flag_clear():
                         tt["dn"], tt["dn_ready"] = dn, self._ready_event()
                     ctx["dn"] = dn
@@ -388,10 +427,9 @@ class VectorField:
         table = torch.empty(n, self.ada_w.shape[0], dtype=torch.float32, device=self.device)
         if skinny(self.ada_w):
             ops.gemm_skinny(temb, self.ada_w, table, bias=self.ada_b)
-        elif "ada" in self.split or (self.precision == "f16x3" and self.ada_w.shape[1] % 32 == 0):
-            if "ada" not in self.split:
-                self.split["ada"] = ops.split_f16(self.ada_w)
-            ops.gemm(temb, self.ada_w, table, bias=self.ada_b, w_split=self.split["ada"], a_split=ops.split_act_f16(temb))
+        elif self.precision == "f16x3" and self.ada_w.shape[1] % 32 == 0:
+            self.ada_split = self.ada_split or ops.split_f16(self.ada_w)
+            ops.gemm(temb, self.ada_w, table, bias=self.ada_b, w_split=self.ada_split, a_split=ops.split_act_f16(temb))
         else:
             ops.gemm(temb, self.ada_w, table, bias=self.ada_b)
         ent = dict(table=table, dn=None)
@@ -411,35 +449,17 @@ class VectorField:
         return ent
 
     # ------------------------------------------------------------------ deferred AdaptiveRMSNorm (large batches)
-    DEFER_MIN_ROWS = int(os.environ.get("CVX_DEFER_NORM_ROWS", "8192"))
-    DEFER_RULE = False       # (round 4 kept batches whose 256-row rounds came out part-empty - 18,000 / 20,480 rows - off this path; with the
-                             #  large-problem kernel's 192-row tiles, round 5, the path wins at every size from 8192 rows: tools/archive/defer_rows_bench.py,
-                             #  20,480 rows 448.7 vs 470.1 ms, 18,000 rows 404.2 vs 417.5, 9,300 rows 232.8 vs 242.1)
-
-    def _defers(self, M: int, ws: dict) -> bool:
-        """Large batches run WITHOUT the norm kernel and with the residual stream as split pairs only.  An AdaptiveRMSNorm is one
-        gamma / beta row per evaluation for every frame (acoustic.py:198-204), so for the product that follows it (:306-318)
-            norm(x) W^T = (sqrt(D) / ||x_row||) * (x (W diag(gamma))^T) + beta W^T :
-        * the producing GEMM (to_out, ff2, skip combiner) writes its output ONLY as the split pair the skip combiners already
-          needed (no fp32 store: it moves the bytes the fp32 form moved), reads its residual from that pair, and leaves the rows'
-          sums of squares per 64 columns (cvx_gemm_split_io.R_hi / c_rowsq); cvx_rownorm_scale_f32 makes one factor per row;
-        * the consuming GEMM (to_qkv, ff1) multiplies its accumulator rows by that factor, carries beta W^T in its bias and runs on
-          W diag(gamma(t)) - split copies of the weights for every evaluation time of the solver grid, built ONCE per (model, grid)
-          (_time_tables; cvx_split_f16_colscale_il: 7 GB for 32 evaluation times - capacity HBM3E has - written in ~2 ms).
-        The norm kernel (131 MB of traffic per launch at the bench shape, 16 of 17 launches per evaluation) does not run and ff2 no
-        longer writes its output twice.  Only the first layer's attention norm (input from the embedding, fp32) and the final norm
-        stay.  Large-problem kernel only: batches of DEFER_MIN_ROWS rows and more (CVX_DEFER_NORM=0: off)."""
-        if not (self.precision == "f16x3" and M >= self.DEFER_MIN_ROWS and isinstance(ws.get("normed16"), ops.SplitIL)
-                and self.d["dim"] % 64 == 0 and 512 <= self.d["dim"] <= 4096 and os.environ.get("CVX_DEFER_NORM", "1") == "1"):
-            return False
-        return True
+    DEFER_MIN_ROWS = int(os.environ.get("CVX_DEFER_NORM_ROWS", "8192"))      # (route() floors it at LARGE_KERNEL_MIN_ROWS)
+    # The row count is the whole rule: round 4 kept batches whose 256-row rounds came out part-empty - 18,000 / 20,480 rows - off this path;
+    # with the large-problem kernel's 192-row tiles, round 5, the path wins at every size from 8192 rows: tools/archive/defer_rows_bench.py,
+    # 20,480 rows 448.7 vs 470.1 ms, 18,000 rows 404.2 vs 417.5, 9,300 rows 232.8 vs 242.1
 
     def _deferred_norm_tables(self, table: torch.Tensor, HS: torch.Tensor, times_key) -> dict:
         """Per (evaluation time, layer): W diag(gamma) for to_qkv (layers 1..) and ff1 as interleaved split pairs, beta W^T as their
         bias (ff1: b1 + beta_ff W1^T), and the power of two that keeps |gamma| <= 1 inside the weight pair (divided out on the
         accumulators through the consumer's a_scale).  A function of the weights and the evaluation times: built once per solver
         grid (_time_tables)."""
-        d, sd = self.d, self.sd
+        d = self.d
         n, L, dim = table.shape[0], d["depth"], d["dim"]
         tab = table.view(n, L, 4, dim)
         tiny = torch.finfo(torch.float32).tiny
@@ -461,95 +481,21 @@ class VectorField:
             bufs = dict(wq=[None if i == 0 else mk(3 * d["heads"] * 64) for i in range(L)], w1=[mk(4 * dim) for _ in range(L)])
             self._dn_bufs[key] = bufs
         b1p, bq, wq, w1 = [], [], [], []
-        for i in range(L):
-            p = f"transformer.layers.{i}"
-            nq, n1 = p + ".2.to_qkv.weight", p + ".4.0.weight"
-            b1p.append(beta_w(tab[:, i, 3, :], sd[n1], sd[p + ".4.0.bias"]))
-            inv1 = self.split_il[n1][1]
-            ops.split_f16_colscale_il(sd[n1], tab[:, i, 2, :], gs[:, i, 1], 1.0 / inv1, bufs["w1"][i])
+        for i, ly in enumerate(self.layers):
+            b1p.append(beta_w(tab[:, i, 3, :], ly.ff1.w, ly.ff1.bias))
+            inv1 = ly.ff1.il[1]
+            ops.split_f16_colscale_il(ly.ff1.w, tab[:, i, 2, :], gs[:, i, 1], 1.0 / inv1, bufs["w1"][i])
             w1.append([(bufs["w1"][i][e], inv1) for e in range(n)])
             if i == 0:
                 bq.append(None); wq.append(None)
                 continue
-            bq.append(beta_w(tab[:, i, 1, :], sd[nq], None))
-            invq = self.split_il[nq][1]
-            ops.split_f16_colscale_il(sd[nq], tab[:, i, 0, :], gs[:, i, 0], 1.0 / invq, bufs["wq"][i])
+            bq.append(beta_w(tab[:, i, 1, :], ly.qkv.w, None))
+            invq = ly.qkv.il[1]
+            ops.split_f16_colscale_il(ly.qkv.w, tab[:, i, 0, :], gs[:, i, 0], 1.0 / invq, bufs["wq"][i])
             wq.append([(bufs["wq"][i][e], invq) for e in range(n)])
         a0, h0 = AS.data_ptr(), HS.data_ptr()
         return dict(b1p=b1p, bq=bq, wq=wq, w1=w1, gs=gs, AS=AS, HS=HS, hsp=[[h0 + 4 * (4 * i + k) for k in range(4)] for i in range(L)],
                          asp=[[(a0 + 4 * ((e * L + i) * 2), a0 + 4 * ((e * L + i) * 2 + 1)) for i in range(L)] for e in range(n)])
-
-    def _layers_pair_stream(self, ctx: dict, step: int, ws: dict, h: torch.Tensor, twin: dict, free: list, Bt: int, T: int, M: int, rg):
-        """The transformer layers of one evaluation with the residual stream as split pairs and every AdaptiveRMSNorm deferred into
-        the GEMMs on either side of it (see _defers).  h: the embedding output (fp32, its pair already in twin[id(h)])."""
-        d, sd, dn = self.d, self.sd, ctx["dn"]
-        dim, L = d["dim"], d["depth"]
-        tab = ctx["table"][step]
-        sp, il = self.split.get, self.split_il.get
-        sp_step, pp, hsp = ctx["sp"][step], self.pred_scale.data_ptr(), dn["hsp"]
-        cur = hsp[0][0]                      # device pointer of the pre-scale the current h's pair carries (one per stage, _activation_scales)
-        take = free.pop
-        parts64, rt_dim = dim // 64, float(dim) ** 0.5
-        n16, a16, f16 = ws["normed16"], ws["att16"], ws["ff16"]
-        rowsq = ws["rowsq"]
-        rs = ws["rs"]
-        def factor():                        # sqrt(D) / ||row|| from the producer's partial sums (computing it in the consumer's epilogue instead
-            ops.rownorm_scale(rowsq, M, parts64, rs, rt_dim)       # was built and measured: + 5 ms per step against these 480 launches of 5 us)
-        fkw = dict(a_row_scale=rs)
-        skips: List[tuple] = []
-        have_rs = False                      # rowsq holds the sums of squares of the current h's rows (per 64 columns)
-        for i in range(L):
-            p = f"transformer.layers.{i}"
-            s_na, s_qk, s_v, s_at, s_nf, s_ff = sp_step[i]
-            as_a, as_f = dn["asp"][step][i]
-            last = i + 1 == L
-            if self.has_comb[i]:
-                s, s_scale = skips.pop()
-                comb = take()
-                ops.gemm(h, sd[p + ".0.weight"], comb, bias=sd[p + ".0.bias"], a2=s, w_split=sp(p + ".0.weight"), w_il=il(p + ".0.weight"),
-                         a_split=twin[id(h)], a2_split=twin[id(s)], a_scale=cur, a2_scale=s_scale, out_split=twin[id(comb)], c_scale=hsp[i][1],
-                         c_rowsq=rowsq, write_f32=False)
-                cur = hsp[i][1]
-                factor()
-                have_rs = True
-                free += [h, s]
-                h, keep_input = comb, False
-            else:
-                skips.append((h, cur))
-                keep_input = True
-            nq = p + ".2.to_qkv.weight"
-            if have_rs:
-                ops.gemm(ws["normed"], sd[nq], ws["qkv"], rope=ws["rope"], rope_cols=2 * d["heads"] * 64, w_split=sp(nq), w_il=dn["wq"][i][step],
-                         a_split=twin[id(h)], out_split=ws["qk16"], vt_split=ws["vt16"], write_f32=False, a_scale=as_a, c_scale=s_qk, vt_scale=s_v,
-                         bias=dn["bq"][i][step], **fkw)
-            else:                            # first layer: the embedding output exists in fp32
-                ops.adarmsnorm(h, tab[(4 * i) * dim:(4 * i + 1) * dim], tab[(4 * i + 1) * dim:(4 * i + 2) * dim], None, out_split=n16, split_scale=s_na)
-                ops.gemm(ws["normed"], sd[nq], ws["qkv"], rope=ws["rope"], rope_cols=2 * d["heads"] * 64, w_split=sp(nq), w_il=il(nq),
-                         a_split=n16, out_split=ws["qk16"], vt_split=ws["vt16"], write_f32=False, a_scale=s_na, c_scale=s_qk, vt_scale=s_v)
-            ops.attention_f16x3(ws["qk16"], ws["vt16"], None, Bt, T, d["heads"], 64 ** -0.5, out_split=a16,
-                                qk_scale=s_qk, v_scale=s_v, out_scale=s_at, ragged=rg)
-            h_att = take() if keep_input else h
-            no = p + ".2.to_out.weight"
-            ops.gemm(ws["att"], sd[no], h_att, w_split=sp(no), w_il=il(no), a_split=a16, a_scale=s_at, res_split=twin[id(h)], res_scale=cur,
-                     out_split=twin[id(h_att)], c_scale=hsp[i][2], c_rowsq=rowsq, write_f32=False)
-            cur = hsp[i][2]
-            factor()
-            h = h_att
-            n1, n2 = p + ".4.0.weight", p + ".4.2.weight"
-            ops.gemm(ws["normed"], sd[n1], ws["ff"], bias=dn["b1p"][i][step], act=ops.ACT_GELU, w_split=sp(n1), w_il=dn["w1"][i][step],
-                     a_split=twin[id(h)], out_split=f16, write_f32=False, a_scale=as_f, c_scale=s_ff, **fkw)
-            next_defers = (not last) and not self.has_comb[i + 1]          # the next layer's attention norm reads THIS output's rows
-            ops.gemm(ws["ff"], sd[n2], h, bias=sd[p + ".4.2.bias"], w_split=sp(n2), w_il=il(n2), a_split=f16, a_scale=s_ff,
-                     res_split=twin[id(h)], res_scale=cur, out_split=twin[id(h)], c_scale=hsp[i][3], c_rowsq=rowsq if next_defers else None,
-                     write_f32=last)                                      # (the final norm reads fp32)
-            cur = hsp[i][3]
-            if next_defers:
-                factor()
-            have_rs = next_defers
-        ops.adarmsnorm(h, sd["transformer.final_norm.gamma"], None, None, out_split=ws["pred16"], split_scale=pp)
-        ops.gemm(ws["normed"], sd["to_pred.weight"], ws["pred"], w_split=sp("to_pred.weight"), a_split=ws["pred16"], a_scale=pp,
-                 w_il=il("to_pred.weight") if isinstance(ws["pred16"], ops.SplitIL) else None)
-        return ws["pred"]
 
     # ------------------------------------------------------------------ one evaluation (both CFG branches)
     @staticmethod
@@ -577,127 +523,179 @@ class VectorField:
 
     def evaluate(self, ctx: dict, step: int) -> torch.Tensor:
         """Run the network on ws['xin'] (rows: cond branch then null branch) at evaluation time #step.
-        Returns ws['pred'] [Bt*T, dim_out]."""
-        d, sd, ws = self.d, self.sd, ctx["ws"]
-        Bt, T, M, rg = ctx["Bt"], ctx["T"], ctx["M"], ctx.get("ragged")
-        dim = d["dim"]
-        tab = ctx["table"][step]
+        Returns ws['pred'] [Bt*T, dim_out].  The front runs here; the layers on the walker ctx['route'] names, then _head."""
+        ws, r = ctx["ws"], ctx["route"]
         free: List[torch.Tensor] = list(ws["h"])
-        take = free.pop
-        # split activations need the f16x3 kernel on every consumer GEMM (K % 32 == 0 and more than 64 rows; the
-        # single-term mode consumes 64 k per stage).  'f16' without split I/O falls back to the fp32 kernels.
-        il = self.split_il.get
-        if self.precision == "f16":
-            split_io = M > 64 and dim % 64 == 0
-            sp = self.split.get if split_io else (lambda k: None)
-        else:
-            split_io = self.precision == "f16x3" and M > 64 and dim % 32 == 0
-            sp = self.split.get
-
-        h = take()
-        h0 = take()
-        ops.gemm(ws["xin"], sd["to_embed.weight"][:, : d["dim_out"]], h0, residual=ws["base"])
-        ops.dwconv31_gelu_res(h0, self.dw_w, sd["conv_embed.dw_conv1d.0.bias"], h, Bt, T, ragged=rg)
+        h, h0 = free.pop(), free.pop()
+        ops.gemm(ws["xin"], self.embed_x, h0, residual=ws["base"])
+        ops.dwconv31_gelu_res(h0, self.dw_w, self.sd["conv_embed.dw_conv1d.0.bias"], h, ctx["Bt"], ctx["T"], ragged=ctx["ragged"])
         free.append(h0)
+        if not r.split_io:
+            return self._head(ctx, self._layers_fp32(ctx, step, h, free), False)
         # residual-stream tensors that later feed a skip combiner (as x or as the popped skip) also get a split
         # twin, so that GEMM takes both operands pre-split (all-DMA kernel) instead of splitting on the fly
-        twin = {id(b): pr for b, pr in zip(ws["h"], ws["h16"])} if split_io else None
-        sp_step = ctx["sp"][step] if (split_io and "sp" in ctx) else None
-        hp = ctx["hp"] if sp_step is not None else None
-        pp = self.pred_scale.data_ptr() if sp_step is not None else None
-        use_dn = split_io and M >= 2048 and ctx.get("dn") is not None
-        if split_io:
-            tw = twin[id(h)]
-            h0s = ctx["dn"]["hsp"][0][0] if use_dn else hp      # (deferred-norm path: one pre-scale per stage of the stream)
-            ops.split_act_f16(h, tw, scale=h0s) if isinstance(tw, ops.SplitIL) else ops.split_act_f16(h, *tw, scale=h0s)
+        twin = {id(b): pr for b, pr in zip(ws["h"], ws["h16"])}
+        tw = twin[id(h)]
+        h0s = ctx["dn"]["hsp"][0][0] if r.deferred else ctx["hp"]      # (deferred-norm path: one pre-scale per stage of the stream)
+        ops.split_act_f16(h, tw, scale=h0s) if isinstance(tw, ops.SplitIL) else ops.split_act_f16(h, *tw, scale=h0s)
+        if r.deferred:
+            return self._head(ctx, self._layers_pair_stream(ctx, step, h, twin, free), False)
+        return self._head(ctx, *self._layers_split(ctx, step, h, twin, free, r.fuse_norm))
 
-        # every to_out / ff2 / skip-combiner product is followed by a norm of its output: one call (ops.gemm(norm=...)), so that
-        # problems on the split-K path (one utterance) normalise inside the reduction
-        # (2048 rows and more never split K: the call would run the same two kernels, so it stays two calls there)
-        fuse_norm = split_io and M < 2048
-        normed_ahead = False                 # the attention norm of the layer about to start was produced by the previous GEMM
-        if use_dn:                           # (decided per call in prepare())
-            return self._layers_pair_stream(ctx, step, ws, h, twin, free, Bt, T, M, rg)
-        def tab_rows(i_, k_):
-            return tab[(4 * i_ + k_) * dim:(4 * i_ + k_ + 1) * dim]
+    def _head(self, ctx: dict, h: torch.Tensor, normed_ahead: bool) -> torch.Tensor:
+        """The final RMSNorm and to_pred.  normed_ahead: the last ff2 wrote the normed pair already (fuse_norm)."""
+        ws = ctx["ws"]
+        if not ctx["route"].split_io:
+            ops.adarmsnorm(h, self.final_gamma, None, ws["normed"])
+            return ops.gemm(ws["normed"], self.to_pred.w, ws["pred"], w_split=self.to_pred.plain)
+        pp = self.pred_scale.data_ptr()
+        if not normed_ahead:
+            ops.adarmsnorm(h, self.final_gamma, None, None, out_split=ws["pred16"], split_scale=pp)
+        lin = self.to_pred                   # (ops.gemm reads w_il only where pred16 is an interleaved pair)
+        return ops.gemm(ws["normed"], lin.w, ws["pred"], w_split=lin.split, w_il=lin.il, a_split=ws["pred16"], a_scale=pp)
+
+    def _layers_fp32(self, ctx: dict, step: int, h: torch.Tensor, free: list) -> torch.Tensor:
+        """The layers on the fp32 residual stream with fp32 activations (no split I/O: up to SPLIT_IO_ABOVE_ROWS rows, 'fp32', odd widths)."""
+        d, ws, Bt, T, rg = self.d, ctx["ws"], ctx["Bt"], ctx["T"], ctx["ragged"]
+        tab = ctx["table"][step].view(d["depth"], 4, d["dim"])
         skips: List[torch.Tensor] = []
-        for i in range(d["depth"]):
-            p = f"transformer.layers.{i}"
-            g_attn = tab[(4 * i + 0) * dim:(4 * i + 1) * dim]
-            b_attn = tab[(4 * i + 1) * dim:(4 * i + 2) * dim]
-            g_ff = tab[(4 * i + 2) * dim:(4 * i + 3) * dim]
-            b_ff = tab[(4 * i + 3) * dim:(4 * i + 4) * dim]
-            if (p + ".0.weight") in sd:
-                s = skips.pop()
-                comb = take()
-                if split_io:
-                    nm = dict(gamma=g_attn, beta=b_attn, out_split=ws["normed16"],
-                              scale=sp_step[i][0] if sp_step is not None else None) if fuse_norm else None
-                    ops.gemm(h, sd[p + ".0.weight"], comb, bias=sd[p + ".0.bias"], a2=s, w_split=sp(p + ".0.weight"), w_il=il(p + ".0.weight"),
-                             a_split=twin[id(h)], a2_split=twin[id(s)], a_scale=hp, norm=nm)
-                    normed_ahead = nm is not None
-                else:
-                    ops.gemm(h, sd[p + ".0.weight"], comb, bias=sd[p + ".0.bias"], a2=s, w_split=sp(p + ".0.weight"))
-                free += [h, s]
-                h, keep_input = comb, False
-            else:
+        for i, (cb, qkv, out, ff1, ff2) in enumerate(self.layers):
+            g_attn, b_attn, g_ff, b_ff = tab[i].unbind(0)
+            keep_input = cb is None              # this layer's input stays alive as a skip
+            if keep_input:
                 skips.append(h)
-                keep_input = True
-            if split_io:
-                n16, a16, f16 = ws["normed16"], ws["att16"], ws["ff16"]
-                # device pointers of this (evaluation, layer)'s activation pre-scales: normed, q|k, v, attention out, normed, ff
-                s_na, s_qk, s_v, s_at, s_nf, s_ff = sp_step[i] if sp_step is not None else (None,) * 6
-                if not normed_ahead:
-                    ops.adarmsnorm(h, g_attn, b_attn, None, out_split=n16, split_scale=s_na)
-                # q | k split row-major, v split + transposed, straight into the f16x3 attention (any T: sequences whose
-                # length is not a multiple of 4 store their v columns 2 bytes at a time)
-                ops.gemm(ws["normed"], sd[p + ".2.to_qkv.weight"], ws["qkv"], rope=ws["rope"], rope_cols=2 * d["heads"] * 64,
-                         w_split=sp(p + ".2.to_qkv.weight"), w_il=il(p + ".2.to_qkv.weight"), a_split=n16, out_split=ws["qk16"], vt_split=ws["vt16"],
-                         write_f32=False, a_scale=s_na, c_scale=s_qk, vt_scale=s_v)
-                normed_ahead = False
-                ops.attention_f16x3(ws["qk16"], ws["vt16"], None, Bt, T, d["heads"], 64 ** -0.5, out_split=a16,
-                                    qk_scale=s_qk, v_scale=s_v, out_scale=s_at, ragged=rg)
-                h_att = take() if keep_input else h
-                ops.gemm(ws["att"], sd[p + ".2.to_out.weight"], h_att, residual=h, w_split=sp(p + ".2.to_out.weight"), w_il=il(p + ".2.to_out.weight"),
-                         a_split=a16, a_scale=s_at, norm=dict(gamma=g_ff, beta=b_ff, out_split=n16, scale=s_nf) if fuse_norm else None)
-                h = h_att
-                if not fuse_norm:
-                    ops.adarmsnorm(h, g_ff, b_ff, None, out_split=n16, split_scale=s_nf)
-                ops.gemm(ws["normed"], sd[p + ".4.0.weight"], ws["ff"], bias=sd[p + ".4.0.bias"], act=ops.ACT_GELU,
-                         w_split=sp(p + ".4.0.weight"), w_il=il(p + ".4.0.weight"), a_split=n16, out_split=f16, write_f32=False,
-                         a_scale=s_nf, c_scale=s_ff)
-                last = i + 1 == d["depth"]
-                nm = None
-                if fuse_norm and last:                   # the final RMSNorm in front of to_pred
-                    nm = dict(gamma=sd["transformer.final_norm.gamma"], beta=None, out_split=ws["pred16"], scale=pp)
-                elif fuse_norm and (f"transformer.layers.{i + 1}.0.weight") not in sd:      # next layer starts with its attention norm
-                    nm = dict(gamma=tab_rows(i + 1, 0), beta=tab_rows(i + 1, 1), out_split=n16,
-                              scale=sp_step[i + 1][0] if sp_step is not None else None)
-                ops.gemm(ws["ff"], sd[p + ".4.2.weight"], h, bias=sd[p + ".4.2.bias"], residual=h,
-                         w_split=sp(p + ".4.2.weight"), w_il=il(p + ".4.2.weight"), a_split=f16,
-                         out_split=None if last else twin[id(h)], a_scale=s_ff, c_scale=None if last else hp, norm=nm)
-                normed_ahead = nm is not None
-                continue
+            else:
+                s, comb = skips.pop(), free.pop()
+                ops.gemm(h, cb.w, comb, bias=cb.bias, w_split=cb.plain, a2=s)
+                free += [h, s]
+                h = comb
             ops.adarmsnorm(h, g_attn, b_attn, ws["normed"])
-            ops.gemm(ws["normed"], sd[p + ".2.to_qkv.weight"], ws["qkv"], rope=ws["rope"], rope_cols=2 * d["heads"] * 64,
-                     w_split=sp(p + ".2.to_qkv.weight"))
+            ops.gemm(ws["normed"], qkv.w, ws["qkv"], w_split=qkv.plain, rope=ws["rope"], rope_cols=2 * d["heads"] * 64)
             ops.attention(ws["qkv"], ws["att"], Bt, T, d["heads"], 64 ** -0.5, ragged=rg)
-            h_att = take() if keep_input else h
-            ops.gemm(ws["att"], sd[p + ".2.to_out.weight"], h_att, residual=h, w_split=sp(p + ".2.to_out.weight"))
-            h = h_att
+            h_in, h = h, (free.pop() if keep_input else h)
+            ops.gemm(ws["att"], out.w, h, w_split=out.plain, residual=h_in)
             ops.adarmsnorm(h, g_ff, b_ff, ws["normed"])
-            ops.gemm(ws["normed"], sd[p + ".4.0.weight"], ws["ff"], bias=sd[p + ".4.0.bias"], act=ops.ACT_GELU,
-                     w_split=sp(p + ".4.0.weight"))
-            ops.gemm(ws["ff"], sd[p + ".4.2.weight"], h, bias=sd[p + ".4.2.bias"], residual=h, w_split=sp(p + ".4.2.weight"))
-        if split_io:
+            ops.gemm(ws["normed"], ff1.w, ws["ff"], bias=ff1.bias, w_split=ff1.plain, act=ops.ACT_GELU)
+            ops.gemm(ws["ff"], ff2.w, h, bias=ff2.bias, w_split=ff2.plain, residual=h)
+        return h
+
+    def _layers_split(self, ctx: dict, step: int, h: torch.Tensor, twin: dict, free: list, fuse_norm: bool) -> tuple:
+        """The layers on the fp32 residual stream with split-pair activations; returns (h, the final norm is done already).
+        fuse_norm: every to_out / ff2 / skip-combiner product is followed by a norm of its output: one call (ops.gemm(norm=...)), so
+        that problems on the split-K path (one utterance) normalise inside the reduction (FUSE_NORM_BELOW_ROWS rows and more never
+        split K: the call would run the same two kernels, so it stays two calls there)."""
+        d, ws, Bt, T, rg = self.d, ctx["ws"], ctx["Bt"], ctx["T"], ctx["ragged"]
+        tab = ctx["table"][step].view(d["depth"], 4, d["dim"])
+        sp_step, hp, pp = ctx["sp"][step], ctx["hp"], self.pred_scale.data_ptr()
+        n16, a16, f16 = ws["normed16"], ws["att16"], ws["ff16"]
+        normed_ahead = False                 # the attention norm of the layer about to start was produced by the previous GEMM
+        skips: List[torch.Tensor] = []
+        for i, (cb, qkv, out, ff1, ff2) in enumerate(self.layers):
+            g_attn, b_attn, g_ff, b_ff = tab[i].unbind(0)
+            # device pointers of this (evaluation, layer)'s activation pre-scales: normed, q|k, v, attention out, normed, ff
+            s_na, s_qk, s_v, s_at, s_nf, s_ff = sp_step[i]
+            keep_input = cb is None              # this layer's input stays alive as a skip
+            if keep_input:
+                skips.append(h)
+            else:
+                s, comb = skips.pop(), free.pop()
+                ops.gemm(h, cb.w, comb, bias=cb.bias, w_split=cb.split, w_il=cb.il, a2=s, a_split=twin[id(h)], a2_split=twin[id(s)], a_scale=hp,
+                         norm=dict(gamma=g_attn, beta=b_attn, out_split=n16, scale=s_na) if fuse_norm else None)
+                normed_ahead = fuse_norm
+                free += [h, s]
+                h = comb
             if not normed_ahead:
-                ops.adarmsnorm(h, sd["transformer.final_norm.gamma"], None, None, out_split=ws["pred16"], split_scale=pp)
-            ops.gemm(ws["normed"], sd["to_pred.weight"], ws["pred"], w_split=sp("to_pred.weight"), a_split=ws["pred16"], a_scale=pp,
-                     w_il=il("to_pred.weight") if isinstance(ws["pred16"], ops.SplitIL) else None)
-        else:
-            ops.adarmsnorm(h, sd["transformer.final_norm.gamma"], None, ws["normed"])
-            ops.gemm(ws["normed"], sd["to_pred.weight"], ws["pred"], w_split=sp("to_pred.weight"))
-        return ws["pred"]
+                ops.adarmsnorm(h, g_attn, b_attn, None, out_split=n16, split_scale=s_na)
+            # q | k split row-major, v split + transposed, straight into the f16x3 attention (any T: sequences whose
+            # length is not a multiple of 4 store their v columns 2 bytes at a time)
+            ops.gemm(ws["normed"], qkv.w, ws["qkv"], w_split=qkv.split, w_il=qkv.il, rope=ws["rope"], rope_cols=2 * d["heads"] * 64, a_split=n16,
+                     out_split=ws["qk16"], vt_split=ws["vt16"], write_f32=False, a_scale=s_na, c_scale=s_qk, vt_scale=s_v)
+            ops.attention_f16x3(ws["qk16"], ws["vt16"], None, Bt, T, d["heads"], 64 ** -0.5, out_split=a16,
+                                qk_scale=s_qk, v_scale=s_v, out_scale=s_at, ragged=rg)
+            h_in, h = h, (free.pop() if keep_input else h)
+            ops.gemm(ws["att"], out.w, h, w_split=out.split, w_il=out.il, residual=h_in, a_split=a16, a_scale=s_at,
+                     norm=dict(gamma=g_ff, beta=b_ff, out_split=n16, scale=s_nf) if fuse_norm else None)
+            if not fuse_norm:
+                ops.adarmsnorm(h, g_ff, b_ff, None, out_split=n16, split_scale=s_nf)
+            ops.gemm(ws["normed"], ff1.w, ws["ff"], bias=ff1.bias, w_split=ff1.split, w_il=ff1.il, act=ops.ACT_GELU, a_split=n16, out_split=f16,
+                     write_f32=False, a_scale=s_nf, c_scale=s_ff)
+            last = i + 1 == d["depth"]
+            nm = None
+            if fuse_norm and last:                   # the final RMSNorm in front of to_pred
+                nm = dict(gamma=self.final_gamma, beta=None, out_split=ws["pred16"], scale=pp)
+            elif fuse_norm and self.layers[i + 1].comb is None:      # next layer starts with its attention norm
+                nm = dict(gamma=tab[i + 1, 0], beta=tab[i + 1, 1], out_split=n16, scale=sp_step[i + 1][0])
+            ops.gemm(ws["ff"], ff2.w, h, bias=ff2.bias, w_split=ff2.split, w_il=ff2.il, residual=h, a_split=f16,
+                     out_split=None if last else twin[id(h)], a_scale=s_ff, c_scale=None if last else hp, norm=nm)
+            normed_ahead = nm is not None
+        return h, normed_ahead
+
+    def _layers_pair_stream(self, ctx: dict, step: int, h: torch.Tensor, twin: dict, free: list) -> torch.Tensor:
+        """The layers with the residual stream as split pairs only and WITHOUT the norm kernel (route.deferred).  h: the embedding
+        output (fp32, its pair already in twin[id(h)]).  An AdaptiveRMSNorm is one gamma / beta row per evaluation for every frame
+        (acoustic.py:198-204), so for the product that follows it (:306-318)
+            norm(x) W^T = (sqrt(D) / ||x_row||) * (x (W diag(gamma))^T) + beta W^T :
+        * the producing GEMM (to_out, ff2, skip combiner) writes its output ONLY as the split pair the skip combiners already
+          needed (no fp32 store: it moves the bytes the fp32 form moved), reads its residual from that pair, and leaves the rows'
+          sums of squares per 64 columns (cvx_gemm_split_io.R_hi / c_rowsq); cvx_rownorm_scale_f32 makes one factor per row;
+        * the consuming GEMM (to_qkv, ff1) multiplies its accumulator rows by that factor, carries beta W^T in its bias and runs on
+          W diag(gamma(t)) - split copies of the weights for every evaluation time of the solver grid, built ONCE per (model, grid)
+          (_time_tables; cvx_split_f16_colscale_il: 7 GB for 32 evaluation times - capacity HBM3E has - written in ~2 ms).
+        The norm kernel (131 MB of traffic per launch at the bench shape, 16 of 17 launches per evaluation) does not run and ff2 no
+        longer writes its output twice.  Only the first layer's attention norm (input from the embedding, fp32) and the final norm
+        stay.  Large-problem kernel only: batches of DEFER_MIN_ROWS rows and more (CVX_DEFER_NORM=0: off)."""
+        d, ws, dn, Bt, T, M, rg = self.d, ctx["ws"], ctx["dn"], ctx["Bt"], ctx["T"], ctx["M"], ctx["ragged"]
+        dim, L = d["dim"], d["depth"]
+        tab = ctx["table"][step].view(L, 4, dim)
+        sp_step, hsp = ctx["sp"][step], dn["hsp"]
+        cur = hsp[0][0]                      # device pointer of the pre-scale the current h's pair carries (one per stage, _activation_scales)
+        parts64, rt_dim, rowsq, rs = dim // 64, float(dim) ** 0.5, ws["rowsq"], ws["rs"]
+        n16, a16, f16 = ws["normed16"], ws["att16"], ws["ff16"]
+        def factor():                        # sqrt(D) / ||row|| from the producer's partial sums (computing it in the consumer's epilogue instead
+            ops.rownorm_scale(rowsq, M, parts64, rs, rt_dim)       # was built and measured: + 5 ms per step against these 480 launches of 5 us)
+        qkv_kw = dict(rope=ws["rope"], rope_cols=2 * d["heads"] * 64, out_split=ws["qk16"], vt_split=ws["vt16"], write_f32=False)
+        skips: List[tuple] = []
+        have_rs = False                      # rowsq holds the sums of squares of the current h's rows (per 64 columns)
+        for i, (cb, qkv, out, ff1, ff2) in enumerate(self.layers):
+            s_na, s_qk, s_v, s_at, s_nf, s_ff = sp_step[i]
+            as_a, as_f = dn["asp"][step][i]
+            last = i + 1 == L
+            keep_input = cb is None              # this layer's input stays alive as a skip
+            if keep_input:
+                skips.append((h, cur))
+            else:
+                (s, s_scale), comb = skips.pop(), free.pop()
+                ops.gemm(h, cb.w, comb, bias=cb.bias, w_split=cb.split, w_il=cb.il, a2=s, a_split=twin[id(h)], a2_split=twin[id(s)], a_scale=cur,
+                         a2_scale=s_scale, out_split=twin[id(comb)], c_scale=hsp[i][1], c_rowsq=rowsq, write_f32=False)
+                cur = hsp[i][1]
+                factor()
+                have_rs = True
+                free += [h, s]
+                h = comb
+            if have_rs:
+                ops.gemm(ws["normed"], qkv.w, ws["qkv"], w_split=qkv.split, w_il=dn["wq"][i][step], bias=dn["bq"][i][step], a_split=twin[id(h)],
+                         a_scale=as_a, a_row_scale=rs, c_scale=s_qk, vt_scale=s_v, **qkv_kw)
+            else:                            # first layer: the embedding output exists in fp32
+                ops.adarmsnorm(h, tab[i, 0], tab[i, 1], None, out_split=n16, split_scale=s_na)
+                ops.gemm(ws["normed"], qkv.w, ws["qkv"], w_split=qkv.split, w_il=qkv.il, a_split=n16, a_scale=s_na, c_scale=s_qk, vt_scale=s_v, **qkv_kw)
+            ops.attention_f16x3(ws["qk16"], ws["vt16"], None, Bt, T, d["heads"], 64 ** -0.5, out_split=a16,
+                                qk_scale=s_qk, v_scale=s_v, out_scale=s_at, ragged=rg)
+            h_in, h = h, (free.pop() if keep_input else h)
+            ops.gemm(ws["att"], out.w, h, w_split=out.split, w_il=out.il, a_split=a16, a_scale=s_at, res_split=twin[id(h_in)], res_scale=cur,
+                     out_split=twin[id(h)], c_scale=hsp[i][2], c_rowsq=rowsq, write_f32=False)
+            cur = hsp[i][2]
+            factor()
+            ops.gemm(ws["normed"], ff1.w, ws["ff"], w_split=ff1.split, w_il=dn["w1"][i][step], bias=dn["b1p"][i][step], act=ops.ACT_GELU,
+                     a_split=twin[id(h)], out_split=f16, write_f32=False, a_scale=as_f, a_row_scale=rs, c_scale=s_ff)
+            feeds_norm = (not last) and self.layers[i + 1].comb is None   # the next layer's attention norm reads THIS output's rows
+            ops.gemm(ws["ff"], ff2.w, h, bias=ff2.bias, w_split=ff2.split, w_il=ff2.il, a_split=f16, a_scale=s_ff, res_split=twin[id(h)],
+                     res_scale=cur, out_split=twin[id(h)], c_scale=hsp[i][3], c_rowsq=rowsq if feeds_norm else None,
+                     write_f32=last)                                      # (the final norm reads fp32)
+            cur = hsp[i][3]
+            if feeds_norm:
+                factor()
+            have_rs = feeds_norm
+        return h
 
 
 @dataclass(frozen=True)
@@ -1076,7 +1074,6 @@ class FlowMatchingSampler:
     def sample(self, *, phoneme_ids: torch.Tensor, cond: torch.Tensor, mask: Optional[torch.Tensor] = None,
                cond_scale: Union[float, Sequence[float]] = 1.0, y0: Optional[torch.Tensor] = None, return_error: bool = False):
         """return_error: also measure the embedded error estimate - the result is (y, SolveError), y with the bits of the plain call."""
-        import os
         f, d = self.field, self.field.d
         dev = f.device
         if cond.ndim != 3 or cond.shape[-1] != d["dim_cond"]:
@@ -1097,8 +1094,7 @@ class FlowMatchingSampler:
         # per-utterance scales: one float per row, read by the stage kernel (a row at 1.0 takes its conditional branch there)
         row_scale = None if per is None else ops.h2d(torch.tensor(per, dtype=torch.float32).repeat_interleave(T), dev)
         times, dts = evaluation_times(self.nfe, self.method, self.grid)
-        rows = (2 * B if use_null else B) * T
-        if os.environ.get("CVX_GRAPH", "1") == "0" or rows > int(os.environ.get("CVX_GRAPH_MAX_ROWS", "8192")):
+        if not f.route((2 * B if use_null else B) * T).graph:
             err = self._error_state([T] * B, return_error)
             self._integrate(phoneme_ids, cond, y, ops.h2d(times, dev), dts, s, use_null, row_scale=row_scale, err=err)
             return (y, self._solve_error(err, [T] * B)) if return_error else y

@@ -109,6 +109,7 @@ def gemm_flags(extra: int):
         _TL.flags = old
 
 _SPLITK_WS: dict = {}
+SPLITK_SCRATCH_MAX_ROWS = 2048   # gemm hands the split-K scratch over up to this many rows (acoustic.route names the rule next to its neighbours)
 
 
 def il_min_rows() -> int:
@@ -289,7 +290,7 @@ def gemm(a: torch.Tensor, w: torch.Tensor, out: torch.Tensor, *, bias=None, act=
         io = GemmSplitIO()
         io.write_f32 = 1 if write_f32 else 0
         io.a_scale_dev, io.c_scale_dev, io.vt_scale_dev = _sp(a_scale), _sp(c_scale), _sp(vt_scale)
-        if a_split is not None and M <= 2048 and rope is None:          # small problems may split K (see the header)
+        if a_split is not None and M <= SPLITK_SCRATCH_MAX_ROWS and rope is None:         # small problems may split K (see the header)
             ws = _splitk_workspace(a.device)
             io.workspace, io.workspace_floats = ws.data_ptr(), ws.numel()
         if a_split is not None:

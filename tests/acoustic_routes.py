@@ -1,40 +1,44 @@
 """Shared by tests/test_acoustic_routes.py (CPU) and tests/test_acoustic_routes_gpu.py: which kernels one evaluation of the acoustic
 network launches, as a function of its row count M (B T without guidance, 2 B T with the null branch, the sum of the lengths - doubled
-under guidance - for a ragged batch).  Restated from the rules of acoustic.VectorField (evaluate, _workspace, _defers), ops.gemm and
-FlowMatchingSampler.sample as written, with no import of their logic: only the constants the package publishes are read from it.
+under guidance - for a ragged batch).  Restated from the rules of acoustic.route and ops.gemm, with no import of their logic: only the
+constants the package publishes are read from it, and tests/test_acoustic_routes.py holds this function to acoustic.route field for field.
 
   M <= 64            fp32 GEMM, ops.attention, adarmsnorm into fp32 (split_io false)
   65 ... 127         split pipe on separate (hi, lo) tensors, norms fused into their producers (fuse_norm), split-K scratch handed over
   128 ... 2047       interleaved pairs (SplitIL) if dim >= 512 and the precision keeps lo halves; otherwise as above
-  2048               fuse_norm off (evaluate: M < 2048), scratch still handed over (ops.gemm: M <= 2048)
+  2048               fuse_norm off (FUSE_NORM_BELOW_ROWS: M < 2048), scratch still handed over (ops.SPLITK_SCRATCH_MAX_ROWS: M <= 2048)
   2049 ... 8191      no scratch, stand-alone norms
-  >= DEFER_MIN_ROWS  deferred norms on the pair-only residual stream (f16x3, interleaved pairs, 512 <= dim <= 4096)
+  >= DEFER_MIN_ROWS  deferred norms on the pair-only residual stream (f16x3, interleaved pairs, 512 <= dim <= 4096, dim % 64 == 0); the
+                     large-problem kernel they need starts at 2048 rows, so a DEFER_MIN_ROWS below that acts as 2048
   > 8192             no captured graph (CVX_GRAPH_MAX_ROWS); a ragged batch never has one"""
 import os
 from collections import namedtuple
 
-SPLIT_IO_ABOVE_ROWS = 64          # acoustic.py, evaluate: split_io = ... M > 64 ...        (inline there: restated)
-FUSE_NORM_BELOW_ROWS = 2048       # acoustic.py, evaluate: fuse_norm = split_io and M < 2048  (inline there: restated)
-SCRATCH_UP_TO_ROWS = 2048         # ops.py, gemm: a_split is not None and M <= 2048 and rope is None  (inline there: restated)
-GRAPH_MAX_ROWS_DEFAULT = 8192     # acoustic.py, sample: rows > int(os.environ.get("CVX_GRAPH_MAX_ROWS", "8192")) stays eager
+SPLIT_IO_ABOVE_ROWS = 64          # restates acoustic.SPLIT_IO_ABOVE_ROWS: the split pipe runs for M > 64
+FUSE_NORM_BELOW_ROWS = 2048       # restates acoustic.FUSE_NORM_BELOW_ROWS: norms ride in their producers for M < 2048
+SCRATCH_UP_TO_ROWS = 2048         # restates ops.SPLITK_SCRATCH_MAX_ROWS: ops.gemm hands the split-K scratch over for M <= 2048 without RoPE
+GRAPH_MAX_ROWS_DEFAULT = 8192     # restates acoustic.GRAPH_MAX_ROWS: rows > CVX_GRAPH_MAX_ROWS (this by default) stay eager
+DEFER_FLOOR_ROWS = 2048           # restates acoustic.LARGE_KERNEL_MIN_ROWS: the deferred forms need the large-problem kernel
 MI355X_CUS = 256                  # what cvx_ctx_cus gives for a stream without a CU mask
 
 Route = namedtuple("Route", "split_io interleaved fuse_norm splitk_scratch deferred graph ragged_capacity")
 
 
 def published():
-    """(il_min_rows, DEFER_MIN_ROWS, RAGGED_ROW_QUANTUM, graph row limit): the constants the package publishes (host code only)"""
-    from covomix_amd import ops
-    from covomix_amd.acoustic import VectorField
-    return (ops.il_min_rows(), VectorField.DEFER_MIN_ROWS, VectorField.RAGGED_ROW_QUANTUM,
-            int(os.environ.get("CVX_GRAPH_MAX_ROWS", str(GRAPH_MAX_ROWS_DEFAULT))))
+    """(il_min_rows, DEFER_MIN_ROWS, RAGGED_ROW_QUANTUM, graph row limit) and the five named thresholds (SPLIT_IO_ABOVE_ROWS,
+    FUSE_NORM_BELOW_ROWS, SPLITK_SCRATCH_MAX_ROWS, GRAPH_MAX_ROWS, LARGE_KERNEL_MIN_ROWS): the constants the package publishes (host
+    code only).  route() below reads the first four; the others are compared with its own literals by the CPU test."""
+    from covomix_amd import acoustic as ac, ops
+    return (ops.il_min_rows(), ac.VectorField.DEFER_MIN_ROWS, ac.VectorField.RAGGED_ROW_QUANTUM,
+            int(os.environ.get("CVX_GRAPH_MAX_ROWS", str(GRAPH_MAX_ROWS_DEFAULT))),
+            ac.SPLIT_IO_ABOVE_ROWS, ac.FUSE_NORM_BELOW_ROWS, ops.SPLITK_SCRATCH_MAX_ROWS, ac.GRAPH_MAX_ROWS, ac.LARGE_KERNEL_MIN_ROWS)
 
 
-def route(M, dim, precision, ragged_rows=None):
+def route(M, dim, precision, ragged_rows=None, consts=None):
     """The route of one evaluation of M rows.  ragged_rows: the row count of a packed ragged batch (then equal to M), None for an
-    equal-length batch."""
+    equal-length batch.  consts: published(), read once by a caller that asks for many routes under the same settings."""
     assert precision in ("f16x3", "fp32", "f16") and (ragged_rows is None or ragged_rows == M)
-    il_rows, defer_rows, quantum, graph_rows = published()
+    il_rows, defer_rows, quantum, graph_rows = (consts or published())[:4]
     if precision == "f16x3":
         split_io = M > SPLIT_IO_ABOVE_ROWS and dim % 32 == 0
     elif precision == "f16":
@@ -45,7 +49,7 @@ def route(M, dim, precision, ragged_rows=None):
     interleaved = split_io and precision == "f16x3" and M >= il_rows and dim >= 512
     fuse_norm = split_io and M < FUSE_NORM_BELOW_ROWS
     splitk_scratch = split_io and M <= SCRATCH_UP_TO_ROWS
-    deferred = interleaved and M >= defer_rows and dim % 64 == 0 and 512 <= dim <= 4096 and os.environ.get("CVX_DEFER_NORM", "1") == "1"
+    deferred = interleaved and M >= max(defer_rows, DEFER_FLOOR_ROWS) and dim % 64 == 0 and 512 <= dim <= 4096 and os.environ.get("CVX_DEFER_NORM", "1") == "1"
     graph = ragged_rows is None and M <= graph_rows and os.environ.get("CVX_GRAPH", "1") != "0"
     capacity = None if ragged_rows is None else -(-ragged_rows // quantum) * quantum
     return Route(split_io, interleaved, fuse_norm, splitk_scratch, deferred, graph, capacity)

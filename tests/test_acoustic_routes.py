@@ -1,8 +1,9 @@
-"""CPU: the route table of tests/acoustic_routes.py against the package's published constants, the text of the three inline rules it
-restates, and the library's own host arithmetic for the split-K scratch (cvx_gemm_f16x3_workspace_floats).
+"""CPU: the route table of tests/acoustic_routes.py against the package's published constants and against acoustic.route itself, field for
+field, and the library's own host arithmetic for the split-K scratch (cvx_gemm_f16x3_workspace_floats).
 
-The finding this file writes down: at exactly M = 2048 rows two rules meet that are not the same rule.  evaluate() fuses the norms into
-their producers for M < 2048; ops.gemm hands the split-K scratch over for M <= 2048; cvx_gemm_f16x3_workspace_floats counts the
+The finding this file writes down: at exactly M = 2048 rows two rules meet that are not the same rule.  The walkers fuse the norms into
+their producers for M < acoustic.FUSE_NORM_BELOW_ROWS = 2048; ops.gemm hands the split-K scratch over for M <=
+ops.SPLITK_SCRATCH_MAX_ROWS = 2048; cvx_gemm_f16x3_workspace_floats counts the
 medium-problem kernel's slices for M < 2048 only; and the launch code asks splitk_factor_p8m whenever the round rule picked the
 medium-problem kernel and a scratch came with the call, without looking at M.  On 256 CUs the round rule gives every GEMM of a
 dim = 512 or dim = 1024 layer to the medium-problem kernel at 2048 rows, so that one row count runs K slices on separate blocks, the
@@ -10,11 +11,12 @@ plain reduction kernel and a STAND-ALONE adarmsnorm: the launch code follows ops
 written past the scratch (the launch code compares the slices' floats with the size the caller passed, and ops.gemm passes 4 x 2048 x
 4096 floats whatever the shape) and no norm is left undone (norm= is never passed at 2048 rows); a caller that sized its scratch by
 workspace_floats would merely get one slice where ops.gemm's callers get two or four."""
-import inspect
+import dataclasses
+import operator
 
 import pytest
-from acoustic_routes import (FUSE_NORM_BELOW_ROWS, GRAPH_MAX_ROWS_DEFAULT, SCRATCH_UP_TO_ROWS, SPLIT_IO_ABOVE_ROWS, Route, expected_record,
-                             gemm_kernel, layer_gemms, published, route)
+from acoustic_routes import (DEFER_FLOOR_ROWS, FUSE_NORM_BELOW_ROWS, GRAPH_MAX_ROWS_DEFAULT, SCRATCH_UP_TO_ROWS, SPLIT_IO_ABOVE_ROWS, Route,
+                             expected_record, gemm_kernel, layer_gemms, published, route)
 from gemm_guarded import WORKSPACE_FLOATS, splitk_factor_p8m
 from hubert_routes import splitk_factor
 
@@ -25,20 +27,48 @@ def lib():
     return _lib.load()
 
 
-def test_published_constants_and_inline_rules():
-    """The constants the table reads, and the text of the three rules it restates: a change of either must come with a change of
-    tests/acoustic_routes.py (and of the cases of the GPU file, which sit either side of these numbers)."""
-    from covomix_amd import acoustic, ops
-    assert published() == (128, 8192, 1024, 8192)
-    ev = inspect.getsource(acoustic.VectorField.evaluate)
-    assert f'split_io = self.precision == "f16x3" and M > {SPLIT_IO_ABOVE_ROWS} and dim % 32 == 0' in ev
-    assert f"split_io = M > {SPLIT_IO_ABOVE_ROWS} and dim % 64 == 0" in ev
-    assert f"fuse_norm = split_io and M < {FUSE_NORM_BELOW_ROWS}" in ev
-    assert f"a_split is not None and M <= {SCRATCH_UP_TO_ROWS} and rope is None" in inspect.getsource(ops.gemm)
-    assert f'int(os.environ.get("CVX_GRAPH_MAX_ROWS", "{GRAPH_MAX_ROWS_DEFAULT}"))' in inspect.getsource(acoustic.FlowMatchingSampler.sample)
-    ws = inspect.getsource(acoustic.VectorField._workspace)
-    assert "(ragged_rows or M) >= ops.il_min_rows() and self.split_il and d[\"dim\"] >= 512" in ws
-    assert 'key = ("ragged", M, ragged_rows >= ops.il_min_rows())' in ws
+SWEEP_ROWS = tuple(range(1, 8201)) + (9216, 16000, 16384, 20480)
+SWEEP_DIMS = (96, 128, 512, 520, 1024, 4096, 8192)          # 96 and 520: the % 32 (f16x3) and % 64 (f16, deferred) conditions
+
+
+def _sweep(what):
+    """acoustic.route == the restated route, field for field, over every row count, width, precision and batch kind"""
+    from covomix_amd import acoustic as ac
+    fields, consts = operator.attrgetter(*Route._fields), published()
+    assert type(ac.route(1, 512, "f16x3")) is ac.Route and tuple(f.name for f in dataclasses.fields(ac.Route)) == Route._fields
+    for p in ("f16x3", "fp32", "f16"):
+        for dim in SWEEP_DIMS:
+            for M in SWEEP_ROWS:
+                for rr in (None, M):
+                    got, want = ac.route(M, dim, p, rr), route(M, dim, p, rr, consts)
+                    assert fields(got) == want, (what, M, dim, p, rr, got, want)
+
+
+def test_published_constants_and_inline_rules(monkeypatch):
+    """The constants the table reads, its restated literals against the library's named thresholds, and the library's route function
+    against the restated one in the default environment: a change of either must come with a change of tests/acoustic_routes.py (and
+    of the cases of the GPU file, which sit either side of these numbers)."""
+    for k in ("CVX_DEFER_NORM", "CVX_GRAPH", "CVX_GRAPH_MAX_ROWS"):
+        monkeypatch.delenv(k, raising=False)
+    assert published() == (128, 8192, 1024, 8192, SPLIT_IO_ABOVE_ROWS, FUSE_NORM_BELOW_ROWS, SCRATCH_UP_TO_ROWS, GRAPH_MAX_ROWS_DEFAULT,
+                           DEFER_FLOOR_ROWS)
+    _sweep("defaults")
+
+
+@pytest.mark.parametrize("name,value", [("CVX_DEFER_NORM", "0"), ("CVX_GRAPH", "0"), ("CVX_GRAPH_MAX_ROWS", "4096"), ("DEFER_MIN_ROWS", 2048),
+                                        ("DEFER_MIN_ROWS", 1024)])
+def test_route_function_under_a_setting(name, value, monkeypatch):
+    """The same sweep with one switch moved.  DEFER_MIN_ROWS = 1024 pins the floor the deferred forms have at 2048 rows (the
+    large-problem kernel takes no fewer): the setting acts as 2048."""
+    from covomix_amd import acoustic as ac
+    for k in ("CVX_DEFER_NORM", "CVX_GRAPH", "CVX_GRAPH_MAX_ROWS"):
+        monkeypatch.delenv(k, raising=False)
+    if name == "DEFER_MIN_ROWS":
+        monkeypatch.setattr(ac.VectorField, name, value)
+        assert [ac.route(M, 512, "f16x3").deferred for M in (value - 1, value, 2047, 2048)] == [False, value == 2048, False, True]
+    else:
+        monkeypatch.setenv(name, value)
+    _sweep(f"{name}={value}")
 
 
 def test_route_table_at_every_crossing():

@@ -23,6 +23,7 @@ with interleaved weights and the deferred path) where the routes really differ, 
 Model: the synthetic state of test_parity_at_size_gpu._state at dim = 512, dim_emb = 64, depth = 4 (skip combiners in layers 2-3),
 heads = 8; for the 2048-row crossing also dim = 1024, depth = 2, heads = 16 (dim_emb = 64), whose fused norms ride in
 splitk_reduce_norm_kernel<4> instead of <2>.  nfe = 2: one midpoint step.  Cases alternate VoMix and VoSingle."""
+import dataclasses
 import warnings
 
 import pytest
@@ -212,6 +213,7 @@ def test_equal_length_route_and_accuracy(width, kind, case, precision, monkeypat
     want = expected_record(r, dims["depth"], _comb_layers(_sd(width, kind)[0]), NFE)
     inp = _inputs(kind, B, T)
     model = _model(width, kind, precision)
+    assert dataclasses.astuple(model._get_field().route(M)) == r          # the library's own record, field for field
     rec = _Recorder(monkeypatch)
     out = _quiet(_solve, model, inp, s)
     # 1. the route: a graphed shape makes the eager warm-up pass and the capture pass, an eager one a single pass - all on the same route
@@ -259,6 +261,7 @@ def test_ragged_route_accuracy_and_rows_behind_the_cut(kind, lengths, s, monkeyp
     utts = [_utt(kind, T) for T in lengths]
     model = _model("main", kind, "f16x3")
     field = model._get_field()
+    assert dataclasses.astuple(field.route(M, ragged_rows=M)) == r        # the library's own record, field for field
     # 6. the capacity-sized workspace, made ahead of the solve (prepare() finds it under the same key): everything the kernels read or
     # write through the row views gets a recognisable value behind the cut
     full = field._workspace(0, 0, ragged_rows=M)

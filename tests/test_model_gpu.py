@@ -315,7 +315,6 @@ def test_time_tables_are_cached_per_model_and_grid_not_across_checkpoints(monkey
     import covomix_amd.ops as ops
     import covomix_amd.synthetic as syn
     monkeypatch.setattr(ac.VectorField, "DEFER_MIN_ROWS", 2048)          # the deferred-norm tables too (2 x 2 x 600 = 2400 rows)
-    monkeypatch.setattr(ac.VectorField, "DEFER_RULE", False)
     monkeypatch.setenv("CVX_GRAPH", "0")
     sd = _state("vomix")
     model = CoVoMixModel.from_state_dict(sd, nfe=4).eval().to("cuda:0")
