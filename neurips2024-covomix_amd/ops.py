@@ -1095,13 +1095,20 @@ def hifigan_cl_rows(L: int) -> int:
     return HIFI_HALO_L + (L + 255) // 256 * 256 + 64
 
 
+HIFI_NARROW_NP = 64     # stages up to this tile width run one fused kernel per conv pair (intermediate in LDS): no split pairs in HBM
+
+
+def hifigan_tile(c: int) -> int:
+    """Tile width Np of the split-pipe vocoder kernels for c <= 256 channels; a stage's channels-last buffers are that wide."""
+    assert 1 <= c <= 256, "the split-pipe vocoder kernels support up to 256 channels"
+    return 32 if c <= 32 else 64 if c <= 64 else 128 if c <= 128 else 256
+
+
 def hifigan_pack_weight_f16x3(w: torch.Tensor):
     """Conv1d weight [Cout, Cin, k] (fp32, on the GPU) -> (w_hi, w_lo, 1/scale, Np, Cp_in): pre-scaled split pair
     packed [Cp_in/32][k][Np][32] for cvx_hifigan_conv1d_f16x3.  Load-time plumbing."""
     cout, cin, k = w.shape
-    tile = lambda c: 32 if c <= 32 else 64 if c <= 64 else 128 if c <= 128 else 256
-    assert cout <= 256 and cin <= 256, "conv1d_f16x3 supports up to 256 channels"
-    np_, cp = tile(cout), tile(cin)          # a stage's buffers are as wide as its output tile, for inputs too
+    np_, cp = hifigan_tile(cout), hifigan_tile(cin)          # a stage's buffers are as wide as its output tile, for inputs too
     full = torch.zeros(np_, cp, k, dtype=torch.float32, device=w.device)
     full[:cout, :cin] = w
     packed = full.reshape(np_, cp // 32, 32, k).permute(1, 3, 0, 2).contiguous()      # [chunk][tap][co][ci]
@@ -1117,9 +1124,8 @@ def hifigan_pack_conv_transpose1d_f16x3(w: torch.Tensor, bias: torch.Tensor, str
     the taps a tile runs but a phase does not see - zero weights, wasted MFMAs - are fewest.  Load-time plumbing."""
     cin, cout, K = w.shape
     s = int(stride)
-    tile = lambda c: 32 if c <= 32 else 64 if c <= 64 else 128 if c <= 128 else 256
-    assert cout <= 256 and 1 <= s <= 8
-    np_out, cp = tile(cout), cp_in or (cin + 31) // 32 * 32          # cp_in: channel count of the input buffers (>= cin, x32)
+    assert 1 <= s <= 8
+    np_out, cp = hifigan_tile(cout), cp_in or (cin + 31) // 32 * 32  # cp_in: channel count of the input buffers (>= cin, x32)
     assert cp >= cin and cp % 32 == 0
     ph = []                                               # per phase: (c, a, J) - J taps, input offsets a - J + 1 .. a
     for r in range(s):
@@ -1265,7 +1271,7 @@ def hifigan_conv1d_form(np_: int, L: int, B: int, n_problems: int = 1, cus: Opti
 
 
 def _fill_resblock16(a, x_cl, z, block, B: int, L: int, scratch: dict, accum, out, out_scale: float, z_scale, items) -> None:
-    narrow = x_cl.shape[2] <= 64              # fused pair kernel: no split pairs in HBM (z / t / rz0 / rz1 unused)
+    narrow = x_cl.shape[2] <= HIFI_NARROW_NP  # fused pair kernel: z / t / rz0 / rz1 unused
     zh, zl = z if z is not None else (None, None)
     assert narrow or z is not None
     a.x, a.z_hi, a.z_lo = x_cl.data_ptr(), _p(zh), _p(zl)

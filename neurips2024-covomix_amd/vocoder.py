@@ -14,22 +14,24 @@ fuses the preceding leaky_relu, bias, the ResBlock residual add and the running
 `xs += resblock(x)` / `xs / num_kernels` of Generator.forward (models.py:104-110).
 
 precision (constructor argument or env CVX_VOCODER_PRECISION):
-  'f16x3' (default)  the 72 ResBlock convolutions (97 % of the FLOPs) run on the fp16 matrix pipe with split-precision
-                     operands (cvx_hifigan_conv1d_f16x3, channels-last activations with zero halos); conv_pre, the four
-                     ConvTranspose1d upsamplers and conv_post stay on the fp32 kernels, with a layout converter on
-                     either side of every ResBlock stage;
+  'f16x3' (default)  the ResBlock convolutions (97 % of the FLOPs) and, where the whole configuration fits, the ConvTranspose1d
+                     upsamplers run on the fp16 matrix pipe with split-precision operands on channels-last activations with zero
+                     halos; conv_pre and conv_post stay on the fp32 kernels.  `plan()` says which kernels a configuration gets;
   'fp32'             everything on v_mfma_f32_32x32x2_f32 (cvx_hifigan_conv1d_f32).
 """
 from __future__ import annotations
 
 import os
-from typing import Dict, List, Optional
+from dataclasses import dataclass
+from types import SimpleNamespace
+from typing import Dict, Optional, Tuple
 
 import torch
 
 from . import ops
 
 LRELU_SLOPE = 0.1   # models.py:8
+PRESCALE_TARGET = 1024.0    # a split stage's pairs hold leaky_relu(x) * zs, zs the power of two that brings the measured max|x| to 2^10
 
 
 class AttrDict(dict):
@@ -38,9 +40,6 @@ class AttrDict(dict):
     def __init__(self, *args, **kwargs):
         super().__init__(*args, **kwargs)
         self.__dict__ = self
-
-
-GROUP_STAGE = True      # wide stages: the ResBlocks of a stage share launches (tests flip it to compare against block after block)
 
 
 def get_padding(kernel_size: int, dilation: int = 1) -> int:
@@ -62,21 +61,141 @@ def fold_weight_norm(sd: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
     return out
 
 
-class _Conv:
-    __slots__ = ("wp", "bias", "cout", "cin", "k", "dil", "pad", "up", "lout_fn", "w16", "bias16", "wp_poly", "padding", "w16t")
+# ---- which kernels a generator runs ---------------------------------------------------------
+@dataclass(frozen=True)
+class Stage:
+    """One upsampling rate: ConvTranspose1d, then the ResBlocks summed into xs (models.py:102-110)."""
+    channels: int
+    rate: int
+    ksize: int
+    upsampler: str                  # 'split' | 'polyphase' | 'stuffed'
+    resblocks: str                  # 'grouped' | 'blocks' | 'fp32'
+    blocks: Tuple[str, ...]         # per ResBlock 'call' | 'pairs' | 'convs' ('grouped': the calls that share launches; 'fp32': empty)
+    np: Optional[int]               # width of the stage's channels-last buffers = the kernels' tile width; None on an fp32 stage
+    wide: bool                      # the stage keeps split pairs in HBM (np > ops.HIFI_NARROW_NP)
+    mul: int                        # an item of T mel frames has mul * T + add positions behind this stage's upsampler
+    add: int
+
+
+@dataclass(frozen=True)
+class Plan:
+    pipeline: str                   # 'channels_last' | 'channel_major'
+    stages: Tuple[Stage, ...]
+    cp_in: Optional[int]            # channels-last pipeline: channel width of the first upsampler's input pair
+
+
+def plan(h, precision: str, group_stages: bool = True) -> Plan:
+    """Every choice of kernels a generator of configuration h makes, decided once (host arithmetic: no GPU, no library, no tensors).
+
+      configuration property                                                          what it decides
+      precision 'fp32'                                                                channel-major flow, every stage 'fp32'
+      stage channels <= 256, every (k - 1) * dilation of the ResBlocks even, <= 50    the stage's ResBlocks on the split pipe
+      ... of EVERY stage; last stage <= 64 channels; rates <= 8; 3 dilations a block  channels-last pipeline, 'split' upsamplers
+      otherwise                                                                       channel-major flow: 'polyphase' upsamplers
+                                                                                      (rate 1: 'stuffed'), converters around a split stage
+      stage tile width np > 64                                                        wide: split pairs in HBM
+      wide, 2 or 3 ResBlocks of 3 dilations, group_stages                             'grouped': one call for the stage
+      otherwise, per ResBlock: 3 dilations / other counts, narrow / wide              'call' / 'pairs' / 'convs'
+    """
+    split_pipe = precision == "f16x3"
+    rates, ksizes = list(h["upsample_rates"]), list(h["upsample_kernel_sizes"])
+    dils = [list(d) for _, d in zip(h["resblock_kernel_sizes"], h["resblock_dilation_sizes"])]
+    chans = [h["upsample_initial_channel"] // 2 ** (i + 1) for i in range(len(rates))]
+    # cvx_hifigan_conv1d_f16x3 (include/covomix_hip.h) takes its 'same' padding of (k - 1) * dil / 2 zeros a side from the buffers' zero
+    # halos: (k - 1) * dil even, and <= 50 - the activation tile it stages has 64 rows beyond its positions.  convs2 has dilation 1.
+    reaches = [(k - 1) * d for k, ds in zip(h["resblock_kernel_sizes"], dils) for d in ds + [1]]
+    taps_fit = all(r <= 50 and r % 2 == 0 for r in reaches)
+    split_res = [split_pipe and taps_fit and c <= 256 for c in chans]           # 256: the widest tile (ops.hifigan_tile)
+    # the stride-1 form computes `rate` phases per input row over L_in + 1 rows at most (1 <= k - 2 pad <= 2 rate), in up to 8 column
+    # tiles of a whole number of phases (rate <= 8), 256 columns a phase at most
+    split_up = [split_pipe and c <= 256 and u <= 8 and 1 <= k - 2 * ((k - u) // 2) <= 2 * u for c, u, k in zip(chans, rates, ksizes)]
+    # channels-last from conv_pre to the waveform needs every upsampler and ResBlock on the split pipe, a last stage conv_post's
+    # channels-last kernel can read (one tile of <= 64 channels), and the three-dilation blocks it was built and measured with
+    cl = all(split_up) and all(split_res) and chans[-1] <= ops.HIFI_NARROW_NP and all(len(d) == 3 for d in dils)
+    stages, mul, add = [], 1, 0                 # conv_pre (7 taps, padding 3) keeps the length
+    for c, u, k, split in zip(chans, rates, ksizes, split_res):
+        mul, add = mul * u, (add - 1) * u + k - 2 * ((k - u) // 2)             # ConvTranspose1d(stride u, padding (k - u) // 2), models.py:85-88
+        upsampler = "split" if cl else "polyphase" if u > 1 else "stuffed"      # polyphase: 1 / rate of the zero-stuffed form's work
+        if not split:
+            stages.append(Stage(c, u, k, upsampler, "fp32", (), None, False, mul, add))
+            continue
+        np_ = ops.hifigan_tile(c)
+        wide = np_ > ops.HIFI_NARROW_NP
+        # one C call runs a ResBlock of three conv pairs (narrow: three fused kernels; wide: six convolutions); other dilation
+        # counts go pair by pair through the fused kernel, or convolution by convolution where the stage is too wide for it
+        blocks = tuple("call" if len(d) == 3 else "convs" if wide else "pairs" for d in dils)
+        # the ResBlocks of a wide stage are independent until xs sums them: 2 or 3 of them share launches (cvx_hifigan_resblock_stage_
+        # f16x3 takes up to 3 three-pair blocks; a narrow block is three launches already), bit-identical to block after block
+        grouped = group_stages and wide and 2 <= len(blocks) <= 3 and all(b == "call" for b in blocks)
+        stages.append(Stage(c, u, k, upsampler, "grouped" if grouped else "blocks", blocks, np_, wide, mul, add))
+    c0 = h["upsample_initial_channel"]
+    cp_in = (ops.hifigan_tile(c0) if c0 <= 256 else (c0 + 31) // 32 * 32) if cl else None    # (only the first upsampler reads > 256 channels)
+    return Plan("channels_last" if cl else "channel_major", tuple(stages), cp_in)
+
+
+# ---- buffers of one call shape ------------------------------------------------------------------
+@dataclass
+class StageBuffers:
+    """Channels-last buffers [B, ops.hifigan_cl_rows(L), np] of one split stage; None where a stage has no such buffer."""
+    L: int
+    x0: torch.Tensor                # fp32 stage input (the upsampler's output)
+    xs: torch.Tensor                # fp32 sum of the ResBlocks / num_kernels
+    zs: torch.Tensor                # fp32[1]: pre-scale of the stage's pairs
+    amax: torch.Tensor              # int32[1]: bit pattern of a measured max|x|; zero between its producer and consumer pairs
+    scratch: tuple                  # dict(r0, r1, t, rz0, rz1) as ops.hifigan_resblock_f16x3 takes it (narrow: the pairs t, rz0, rz1 are None)
+    z0: Optional[tuple]             # wide: split(leaky_relu(x0) * zs)
+    zn: Optional[tuple]             # channels-last pipeline, not the last stage: the next upsampler's input pair
+    zs_next: Optional[torch.Tensor]
+
+
+@dataclass
+class Workspace:
+    stages: Tuple[Optional[StageBuffers], ...]      # None: an fp32 stage
+    zin: Optional[tuple]            # channels-last pipeline: the first upsampler's input pair split(leaky_relu(conv_pre(mel)) * zs_in)
+    zs_in: Optional[torch.Tensor]
+    amax_in: Optional[torch.Tensor]
+
+
+def workspace(p: Plan, B: int, T_in: int, device) -> Workspace:
+    """All buffers of a call of B mels of T_in frames, zero-initialised ONCE: the kernels only ever write valid rows (zeros behind
+    a shorter item's end, zeros into the padded channels), so halos and padding stay zero from call to call."""
+    f32 = lambda shape: torch.zeros(shape, dtype=torch.float32, device=device)
+    pair = lambda shape: (torch.zeros(shape, dtype=torch.float16, device=device), torch.zeros(shape, dtype=torch.float16, device=device))
+    scale = lambda: torch.ones(1, dtype=torch.float32, device=device)
+    amax = lambda: torch.zeros(1, dtype=torch.int32, device=device)
+    cl = p.pipeline == "channels_last"
+    stages = []
+    for i, st in enumerate(p.stages):
+        L = st.mul * T_in + st.add
+        if st.resblocks == "fp32":
+            stages.append(None)
+            continue
+        shape = (B, ops.hifigan_cl_rows(L), st.np)
+        pairs = lambda: {k: pair(shape) if st.wide else None for k in ("t", "rz0", "rz1")}
+        # blocks that share launches need scratch of their OWN; block after block, one set serves all
+        scratch = tuple(dict(r0=f32(shape), r1=f32(shape), **pairs()) for _ in range(len(st.blocks) if st.resblocks == "grouped" else 1))
+        feeds_next = cl and i + 1 < len(p.stages)
+        zn = None if not feeds_next else scratch[0]["t"] if st.wide else pair(shape)     # (t is free once xs is complete)
+        stages.append(StageBuffers(L, f32(shape), f32(shape), scale(), amax(), scratch, pair(shape) if st.wide else None,
+                                   zn, scale() if feeds_next else None))
+    if not cl:
+        return Workspace(tuple(stages), None, None, None)
+    return Workspace(tuple(stages), pair((B, ops.hifigan_cl_rows(T_in), p.cp_in)), scale(), amax())
+
+
+WORKSPACE_SHAPES = 3    # call shapes (B, T) whose buffers a generator keeps; one more clears them
 
 
 class Generator:
-    def __init__(self, h, precision: Optional[str] = None):
+    def __init__(self, h, precision: Optional[str] = None, group_stages: bool = True):
         if str(h["resblock"]) != "1":
             raise NotImplementedError("only ResBlock1 (resblock == '1') is supported, as in config_covomix.json")
         self.precision = precision or os.environ.get("CVX_VOCODER_PRECISION", "f16x3")
         if self.precision not in ("f16x3", "fp32"):
             raise ValueError(f"vocoder precision must be 'f16x3' or 'fp32', got {self.precision!r}")
-        self._cl: Dict[tuple, dict] = {}
-        self.act_scales = True               # measured per-stage power-of-two pre-scales of the split pairs
-        # channels-last pipeline (round 3): the upsamplers on the split pipe too, no layout converters between the stages
-        self.cl_pipeline = True
+        self.group_stages = group_stages     # False: the ResBlocks of a wide stage block after block (same bits; tests compare)
+        self.plan: Optional[Plan] = None
+        self._ws: Dict[tuple, Workspace] = {}
         self.h = h
         self.num_kernels = len(h["resblock_kernel_sizes"])
         self.num_upsamples = len(h["upsample_rates"])
@@ -90,8 +209,7 @@ class Generator:
     def load_state_dict(self, sd: Dict[str, torch.Tensor], strict: bool = True):
         self._sd = {k: v.detach().to("cpu") for k, v in sd.items()}
         self._has_weight_norm = any(k.endswith(".weight_g") for k in self._sd)
-        self._packed = None
-        self._fp32_twin = None
+        self._packed = self._fp32_twin = None
         return self
 
     def state_dict(self):
@@ -104,8 +222,8 @@ class Generator:
         device = torch.device(device)
         if device != self.device:
             self.device = device
-            self._packed = None
-            self._fp32_twin = None
+            self._packed = self._fp32_twin = None
+            self._ws.clear()
         return self
 
     def remove_weight_norm(self):
@@ -113,33 +231,24 @@ class Generator:
         if self._has_weight_norm:
             self._sd = fold_weight_norm(self._sd)
             self._has_weight_norm = False
-            self._packed = None
-            self._fp32_twin = None
+            self._packed = self._fp32_twin = None
         return self
 
     # ---- weight packing -----------------------------------------------------------------
-    def _conv(self, name: str, dil: int = 1, pad: int = 0, transposed: bool = False, up: int = 1) -> _Conv:
-        sd = self._sd
-        w = sd[name + ".weight"].float()
-        c = _Conv()
-        if transposed:
-            c.cin, c.cout, c.k = w.shape
-            c.pad = c.k - 1 - pad            # stride-1 conv over the zero-stuffed input, flipped kernel
-        else:
-            c.cout, c.cin, c.k = w.shape
-            c.pad = pad
-        c.dil, c.up = dil, up
-        c.wp = ops.hifigan_pack_weight(w, transposed).to(self.device)
-        c.wp_poly, c.padding = None, pad
-        if transposed and up > 1:                 # polyphase form: 1/stride of the zero-stuffed form's matrix work
+    def _conv(self, name: str, form: str, dil: int = 1, pad: int = 0, up: int = 1, cp_in: Optional[int] = None) -> SimpleNamespace:
+        """Pack one convolution the way the plan names: 'fp32' / 'f16x3' (Conv1d), 'split' / 'polyphase' / 'stuffed' (ConvTranspose1d)."""
+        w = self._sd[name + ".weight"].float()
+        transposed = form in ("split", "polyphase", "stuffed")
+        c = SimpleNamespace(cout=w.shape[1 if transposed else 0], k=w.shape[2], dil=dil, up=up, padding=pad)
+        c.pad = c.k - 1 - pad if transposed else pad        # transposed: stride-1 conv over the zero-stuffed input, flipped kernel
+        c.bias = self._sd[name + ".bias"].float().to(self.device).contiguous()
+        if form in ("fp32", "stuffed"):
+            c.wp = ops.hifigan_pack_weight(w, transposed).to(self.device)
+        elif form == "polyphase":
             c.wp_poly = ops.hifigan_pack_conv_transpose1d(w, up, pad).to(self.device)
-        c.bias = sd[name + ".bias"].float().to(self.device).contiguous()
-        c.w16 = c.bias16 = c.w16t = None
-        if self.precision == "f16x3" and transposed and 1 <= c.k - 2 * pad <= 2 * up and c.cout <= 256 and up <= 8:
-            cp_in = (32 if c.cin <= 32 else 64 if c.cin <= 64 else 128 if c.cin <= 128 else 256) if c.cin <= 256 else (c.cin + 31) // 32 * 32
-            c.w16t = ops.hifigan_pack_conv_transpose1d_f16x3(w.to(self.device), c.bias, up, pad, cp_in)   # (input = a stage's Np-wide buffers)
-        if (self.precision == "f16x3" and not transposed and up == 1 and name.startswith("resblocks.") and c.cout <= 256
-                and (c.k - 1) * dil <= 50 and (c.k - 1) * dil % 2 == 0):
+        elif form == "split":                # (input = the Np-wide buffers of the stage before)
+            c.w16t = ops.hifigan_pack_conv_transpose1d_f16x3(w.to(self.device), c.bias, up, pad, cp_in)
+        else:
             c.w16 = ops.hifigan_pack_weight_f16x3(w.to(self.device))
             c.bias16 = torch.zeros(c.w16[3], dtype=torch.float32, device=self.device)
             c.bias16[: c.cout] = c.bias
@@ -162,22 +271,27 @@ class Generator:
         if self.device.type != "cuda":
             raise ops._lib.CovomixHipError("Generator must be moved to a GPU (`.to('cuda')`): covomix_amd has no CPU path")
         h = self.h
-        pk = dict(pre=self._conv("conv_pre", pad=3), ups=[], res=[])
-        for i, (u, k) in enumerate(zip(h["upsample_rates"], h["upsample_kernel_sizes"])):
-            pk["ups"].append(self._conv(f"ups.{i}", pad=(k - u) // 2, transposed=True, up=u))
+        self.plan = plan(h, self.precision, self.group_stages)
+        pk = dict(pre=self._conv("conv_pre", "fp32", pad=3), ups=[], res=[])
+        cp_in = self.plan.cp_in
+        for i, st in enumerate(self.plan.stages):
+            pk["ups"].append(self._conv(f"ups.{i}", st.upsampler, pad=(st.ksize - st.rate) // 2, up=st.rate, cp_in=cp_in))
+            form, cp_in = "fp32" if st.resblocks == "fp32" else "f16x3", st.np
             blocks = []
             for j, (rk, dils) in enumerate(zip(h["resblock_kernel_sizes"], h["resblock_dilation_sizes"])):
                 p = f"resblocks.{i * self.num_kernels + j}"
-                blocks.append([(self._conv(f"{p}.convs1.{m}", dil=d, pad=get_padding(rk, d)),
-                                self._conv(f"{p}.convs2.{m}", dil=1, pad=get_padding(rk, 1)))
+                blocks.append([(self._conv(f"{p}.convs1.{m}", form, dil=d, pad=get_padding(rk, d)),
+                                self._conv(f"{p}.convs2.{m}", form, dil=1, pad=get_padding(rk, 1)))
                                for m, d in enumerate(dils)])
             pk["res"].append(blocks)
         pk["post_w"] = self._sd["conv_post.weight"].float().reshape(-1, 7).contiguous().to(self.device)
         pk["post_b"] = float(self._sd["conv_post.bias"].float().reshape(-1)[0])
+        if pk["pre"].k != 7 or [(c.cout, c.k) for c in pk["ups"]] != [(st.channels, st.ksize) for st in self.plan.stages]:
+            raise ValueError("Generator: the weights' channel counts or kernel sizes are not the configuration's (the plan's buffer sizes)")
         self._packed = pk
 
     # ---- forward ------------------------------------------------------------------------
-    def _run(self, c: _Conv, x: torch.Tensor, out: Optional[torch.Tensor] = None, *, in_slope=1.0, res=None,
+    def _run(self, c, x: torch.Tensor, out: Optional[torch.Tensor] = None, *, in_slope=1.0, res=None,
              accum=None, out_scale=1.0, items=None) -> torch.Tensor:
         B, _, lin = x.shape
         lout = (lin - 1) * c.up + 1 + 2 * c.pad - (c.k - 1) * c.dil
@@ -186,20 +300,10 @@ class Generator:
         return ops.hifigan_conv1d(x, c.wp, c.bias, out, cout=c.cout, ksize=c.k, dil=c.dil, pad=c.pad, up=c.up,
                                   in_slope=in_slope, res=res, accum=accum, out_scale=out_scale, items=items)
 
-    @staticmethod
-    def _affine(c: _Conv, mul: int, add: int) -> tuple:
-        """Output length of convolution c as a function of the item's mel frames T, given its input length mul * T + add."""
-        # lout = (lin - 1) * up + 1 + 2 * pad - (k - 1) * dil
-        return mul * c.up, (add - 1) * c.up + 1 + 2 * c.pad - (c.k - 1) * c.dil
-
     def output_length(self, frames: int) -> int:
         """Samples the generator returns for a mel of `frames` frames."""
-        if self._packed is None:
-            self._pack()
-        mul, add = 1, 0
-        for c in [self._packed["pre"]] + self._packed["ups"]:
-            mul, add = self._affine(c, mul, add)
-        return mul * frames + add
+        last = self.pack().plan.stages[-1]
+        return last.mul * frames + last.add
 
     @ops.gated
     @torch.no_grad()
@@ -247,191 +351,121 @@ class Generator:
         return [y[b, :, : self.output_length(T[b])] for b in range(len(mels))]
 
     def _forward(self, mel: torch.Tensor, lengths=None) -> torch.Tensor:
-        if self._packed is None:
-            self._pack()
-        pk = self._packed
+        pk = self.pack()._packed
         unbatched = mel.ndim == 2
         x = mel.to(device=self.device, dtype=torch.float32)
         if unbatched:
             x = x.unsqueeze(0)
         x = x.contiguous()
-        lens, mul, add = None, 1, 0               # ragged batch: item b is valid on mul * lens[b] + add positions of x
+        B, _, T = x.shape
+        lens = None
         if lengths is not None:
-            if len(lengths) != x.shape[0] or min(lengths) < 1 or max(lengths) > x.shape[2]:
-                raise ValueError(f"lengths must hold one frame count in [1, {x.shape[2]}] per batch item")
+            if len(lengths) != B or min(lengths) < 1 or max(lengths) > T:
+                raise ValueError(f"lengths must hold one frame count in [1, {T}] per batch item")
             lens = ops.h2d(torch.tensor([int(t) for t in lengths], dtype=torch.int32), self.device)
-        it = lambda: None if lens is None else (lens, mul, add)
-        mul, add = self._affine(pk["pre"], mul, add)
-        x = self._run(pk["pre"], x, items=it())
-        if (self.cl_pipeline and self.precision == "f16x3" and all(u.w16t is not None for u in pk["ups"]) and pk["ups"][-1].cout <= 64
-                and all(c.w16 is not None and len(block) == 3 for blocks in pk["res"] for block in blocks for pair in block for c in pair)):
-            y = self._forward_channels_last(pk, x, lens, mul, add)
-            return y.squeeze(0) if unbatched else y
-        for i in range(self.num_upsamples):
-            up = pk["ups"][i]
-            mul, add = self._affine(up, mul, add)
-            split = all(c.w16 is not None for block in pk["res"][i] for pair in block for c in pair)
-            if up.wp_poly is not None:                                      # leaky_relu + ConvTranspose1d (polyphase)
-                B, _, lin = x.shape
-                lout = (lin - 1) * up.up + 1 + 2 * up.pad - (up.k - 1)
-                buf = self._cl_buffers(B, up.cout, lout) if split and self.act_scales else None
-                y = torch.empty(B, up.cout, lout, dtype=torch.float32, device=x.device)
-                x = ops.hifigan_conv_transpose1d(x, up.wp_poly, up.bias, y, cout=up.cout, ksize=up.k, stride=up.up, padding=up.padding,
-                                                 in_slope=LRELU_SLOPE, amax_bits=buf["zs_scratch"] if buf is not None else None, items=it())
-                if split:
-                    x = self._resblocks_f16x3(pk["res"][i], x, measured=buf is not None, items=it())
-                    continue
-            else:
-                x = self._run(up, x, in_slope=LRELU_SLOPE, items=it())
-                if split:
-                    x = self._resblocks_f16x3(pk["res"][i], x, items=it())
-                    continue
-            t = torch.empty_like(x)
-            r = torch.empty_like(x)
-            xs = torch.empty_like(x)
-            nblk = len(pk["res"][i])
-            for j, block in enumerate(pk["res"][i]):
-                cur = x
-                for m, (c1, c2) in enumerate(block):
-                    self._run(c1, cur, t, in_slope=LRELU_SLOPE, items=it())
-                    if m + 1 < len(block):
-                        self._run(c2, t, r, in_slope=LRELU_SLOPE, res=cur, items=it())
-                        cur = r
-                    else:                                                    # last pair: fold into xs
-                        self._run(c2, t, xs, in_slope=LRELU_SLOPE, res=cur, accum=xs if j > 0 else None,
-                                  out_scale=(1.0 / self.num_kernels) if j == nblk - 1 else 1.0, items=it())
-            x = xs
-        B, _, L = x.shape
-        y = torch.empty(B, 1, L, dtype=torch.float32, device=x.device)
-        ops.hifigan_post(x, pk["post_w"], pk["post_b"], y, slope=0.01)       # F.leaky_relu default slope (:112)
+        items = lambda mul, add: None if lens is None else (lens, mul, add)      # item b is valid on mul * lengths[b] + add positions
+        ws = self._ws.get((B, T))
+        if ws is None:
+            if len(self._ws) >= WORKSPACE_SHAPES:
+                self._ws.clear()
+            ws = self._ws[(B, T)] = workspace(self.plan, B, T, self.device)
+        x = self._run(pk["pre"], x, items=items(1, 0))
+        run = self._channels_last if self.plan.pipeline == "channels_last" else self._channel_major
+        y = run(pk, ws, x, [items(st.mul, st.add) for st in self.plan.stages])
         return y.squeeze(0) if unbatched else y
 
     forward = __call__
 
-    # ---- ResBlock stage on the split-precision kernel ---------------------------------------
-    def _cl_buffers(self, B: int, C: int, L: int) -> dict:
-        """Channels-last buffers of one stage, zero-initialised ONCE (the kernels only ever write valid rows, and
-        write zeros into the padded channels), cached per shape."""
-        key = (B, C, L)
-        buf = self._cl.get(key)
-        if buf is None:
-            Lp, Cp = ops.hifigan_cl_rows(L), (C + 31) // 32 * 32
-            np_ = 32 if C <= 32 else 64 if C <= 64 else 128 if C <= 128 else 256
-            assert np_ == Cp or Cp < np_          # Cp (input padding, x32) <= Np (output tile); use Np for both
-            Cp = np_
-            f32 = lambda: torch.zeros(B, Lp, Cp, dtype=torch.float32, device=self.device)
-            f16 = lambda: (torch.zeros(B, Lp, Cp, dtype=torch.float16, device=self.device),
-                           torch.zeros(B, Lp, Cp, dtype=torch.float16, device=self.device))
-            buf = dict(x0=f32(), r0=f32(), r1=f32(), xs=f32())
-            buf["zs"] = torch.ones(1, dtype=torch.float32, device=self.device)
-            buf["zs_scratch"] = torch.zeros(1, dtype=torch.int32, device=self.device)
-            if Cp > 64:                           # (the narrow stages run one kernel per conv pair: no split pairs in HBM)
-                buf.update(z0=f16(), t=f16(), rz0=f16(), rz1=f16())
-                # the ResBlocks of a wide stage share launches (cvx_hifigan_resblock_stage_f16x3): every block needs its OWN scratch
-                buf["blk"] = [dict(t=buf["t"], rz0=buf["rz0"], rz1=buf["rz1"], r0=buf["r0"], r1=buf["r1"])] + \
-                             [dict(t=f16(), rz0=f16(), rz1=f16(), r0=f32(), r1=f32()) for _ in range(self.num_kernels - 1)]
-            if len(self._cl) >= 12:
-                self._cl.clear()
-            self._cl[key] = buf
-        return buf
-
-    def _resblocks_f16x3(self, blocks, x: torch.Tensor, measured: bool = False, items=None) -> torch.Tensor:
-        """xs = sum_j ResBlock1_j(x) / num_kernels  (models.py:104-110, :35-42) for one upsampling stage."""
-        B, C, L = x.shape
-        buf = self._cl_buffers(B, C, L)
-        # activation pre-scale of this stage's split pairs: the power of two that brings max|x| of the stage input to 2^10
-        # (measured on the device; the intermediates of a ResBlock stay within a few binades of its input)
-        # (measured: the ConvTranspose1d that produced x left max|x| in zs_scratch)
-        if not self.act_scales:
-            zs = None
-        elif measured:
-            zs = ops.pow2_scale_from_amax(buf["zs_scratch"], 1024.0, buf["zs"])
-        else:
-            zs = ops.amax_pow2_scale(x, 1024.0, buf["zs"], buf["zs_scratch"])
-        ops.hifigan_to_channels_last(x, buf["x0"], buf.get("z0"), LRELU_SLOPE, z_scale=zs)
-        self._resblocks_cl(blocks, buf, B, L, zs, items)
-        out = torch.empty_like(x)
-        return ops.hifigan_from_channels_last(buf["xs"], out)
-
-    def _resblocks_cl(self, blocks, buf: dict, B: int, L: int, zs, items=None) -> None:
-        """buf["xs"] = sum_j ResBlock1_j(x) / num_kernels from buf["x0"] (fp32) and, on the wide stages, buf["z0"] =
-        split(leaky_relu(x0) * zs): all channels-last."""
-        narrow = "z0" not in buf
-        nblk = len(blocks)
-        if not narrow and 1 < nblk <= 3 and nblk <= len(buf.get("blk", ())) and all(len(b) == 3 for b in blocks) and GROUP_STAGE:
-            # wide stage: the blocks' independent convolutions share launches (18 -> 8 per stage), same bits as block after block
-            ops.hifigan_resblock_stage_f16x3(buf["x0"], buf["z0"], blocks, B, L, buf["blk"][:nblk], buf["xs"],
-                                             out_scale=1.0 / self.num_kernels, z_scale=zs, items=items)
-            return
-        for j, block in enumerate(blocks):
-            if len(block) == 3:                   # one C call per ResBlock: cvx_hifigan_resblock_f16x3 (6 launches, or 3 fused pairs)
-                ops.hifigan_resblock_f16x3(buf["x0"], buf.get("z0"), block, B, L, buf, accum=buf["xs"] if j > 0 else None, out=buf["xs"],
-                                           out_scale=(1.0 / self.num_kernels) if j == nblk - 1 else 1.0, z_scale=zs, items=items)
+    def _channel_major(self, pk, ws: Workspace, x: torch.Tensor, items) -> torch.Tensor:
+        """Upsamplers on the fp32 kernels, channel-major; a split stage sits between two layout converters, an fp32 stage stays
+        channel-major throughout."""
+        B, _, T = x.shape
+        for i, (st, sb) in enumerate(zip(self.plan.stages, ws.stages)):
+            up, split = pk["ups"][i], st.resblocks != "fp32"
+            if st.upsampler == "polyphase":                                 # leaky_relu + ConvTranspose1d; leaves max|out| for a split stage
+                y = torch.empty(B, st.channels, st.mul * T + st.add, dtype=torch.float32, device=x.device)
+                x = ops.hifigan_conv_transpose1d(x, up.wp_poly, up.bias, y, cout=up.cout, ksize=up.k, stride=up.up, padding=up.padding,
+                                                 in_slope=LRELU_SLOPE, amax_bits=sb.amax if split else None, items=items[i])
+            else:
+                x = self._run(up, x, in_slope=LRELU_SLOPE, items=items[i])
+            if not split:
+                x = self._resblocks_fp32(pk["res"][i], x, items[i])
                 continue
-            if narrow:                            # other dilation counts: pair by pair
-                cur = buf["x0"]
-                for m, (c1, c2) in enumerate(block):
-                    if m + 1 < len(block):
-                        nxt = buf["r0"] if m % 2 == 0 else buf["r1"]
-                        ops.hifigan_resblock_pair_f16x3(cur, c1, c2, B, L, nxt, z_scale=zs, items=items)
-                        cur = nxt
-                    else:
-                        ops.hifigan_resblock_pair_f16x3(cur, c1, c2, B, L, buf["xs"], accum=buf["xs"] if j > 0 else None,
-                                                        out_scale=(1.0 / self.num_kernels) if j == nblk - 1 else 1.0, z_scale=zs, items=items)
-                continue
-            cur_x, cur_z = buf["x0"], buf["z0"]   # other dilation counts: convolution by convolution
-            for m, (c1, c2) in enumerate(block):
-                ops.hifigan_conv1d_f16x3(cur_z, c1.w16, c1.bias16, B, L, ksize=c1.k, dil=c1.dil, out_z=buf["t"], z_slope=LRELU_SLOPE, z_scale=zs, items=items)
-                if m + 1 < len(block):
-                    ox, oz = (buf["r0"], buf["rz0"]) if m % 2 == 0 else (buf["r1"], buf["rz1"])
-                    ops.hifigan_conv1d_f16x3(buf["t"], c2.w16, c2.bias16, B, L, ksize=c2.k, dil=c2.dil, res=cur_x, out_x=ox,
-                                             out_z=oz, z_slope=LRELU_SLOPE, z_scale=zs, items=items)
-                    cur_x, cur_z = ox, oz
-                else:
-                    ops.hifigan_conv1d_f16x3(buf["t"], c2.w16, c2.bias16, B, L, ksize=c2.k, dil=c2.dil, res=cur_x,
-                                             accum=buf["xs"] if j > 0 else None, out_x=buf["xs"],
-                                             out_scale=(1.0 / self.num_kernels) if j == nblk - 1 else 1.0, z_scale=zs, items=items)
+            if st.upsampler == "polyphase":
+                zs = ops.pow2_scale_from_amax(sb.amax, PRESCALE_TARGET, sb.zs)
+            else:
+                zs = ops.amax_pow2_scale(x, PRESCALE_TARGET, sb.zs, sb.amax)
+            ops.hifigan_to_channels_last(x, sb.x0, sb.z0, LRELU_SLOPE, z_scale=zs)
+            self._resblocks(st, pk["res"][i], sb, B, zs, items[i])
+            x = ops.hifigan_from_channels_last(sb.xs, torch.empty_like(x))
+        y = torch.empty(B, 1, x.shape[2], dtype=torch.float32, device=x.device)
+        return ops.hifigan_post(x, pk["post_w"], pk["post_b"], y, slope=0.01)       # F.leaky_relu default slope (:112)
 
-    def _forward_channels_last(self, pk, x: torch.Tensor, lens, mul: int, add: int) -> torch.Tensor:
+    def _channels_last(self, pk, ws: Workspace, x: torch.Tensor, items) -> torch.Tensor:
         """Everything behind conv_pre on channels-last buffers: per stage
             ConvTranspose1d on the split pipe (stride-1 form; leaves max|out| on the device) -> fp32 x0
             -> [wide stages] z0 = split(leaky_relu(x0) * zs)  -> the ResBlocks -> xs
             -> max|xs| -> the next upsampler's input pair split(leaky_relu(xs) * zs'),
-        then conv_post + tanh straight from the last xs.  No channel-major tensor exists between conv_pre and the waveform
-        (round 2 converted twice per stage and ran the upsamplers on the fp32 pipe: 1.9 of 11.4 ms)."""
-        B, C, L = x.shape
-        it = lambda: None if lens is None else (lens, mul, add)
-        up0 = pk["ups"][0].w16t
-        key = ("in", B, up0["cp_in"], L)
-        zin = self._cl.get(key)
-        if zin is None:
-            shape = (B, ops.hifigan_cl_rows(L), up0["cp_in"])
-            zin = dict(z=(torch.zeros(shape, dtype=torch.float16, device=self.device), torch.zeros(shape, dtype=torch.float16, device=self.device)),
-                       zs=torch.ones(1, dtype=torch.float32, device=self.device), scr=torch.zeros(1, dtype=torch.int32, device=self.device))
-            self._cl[key] = zin
-        cur_zs = ops.amax_pow2_scale(x, 1024.0, zin["zs"], zin["scr"]) if self.act_scales else None
-        ops.hifigan_to_channels_last(x, None, zin["z"], LRELU_SLOPE, z_scale=cur_zs)
-        cur_z, lin = zin["z"], L
-        for i in range(self.num_upsamples):
-            up = pk["ups"][i]
-            mul, add = self._affine(up, mul, add)
-            lout = (lin - 1) * up.up + up.k - 2 * up.padding
-            buf = self._cl_buffers(B, up.cout, lout)
-            ops.hifigan_conv_transpose1d_f16x3(cur_z, up.w16t, B, lin, buf["x0"], lout, z_scale=cur_zs,
-                                               amax_bits=buf["zs_scratch"] if self.act_scales else None, items=it())
-            zs = ops.pow2_scale_from_amax(buf["zs_scratch"], 1024.0, buf["zs"]) if self.act_scales else None
-            if "z0" in buf:
-                ops.hifigan_split_channels_last(buf["x0"], buf["z0"], LRELU_SLOPE, z_scale=zs)
-            self._resblocks_cl(pk["res"][i], buf, B, lout, zs, it())
-            if i + 1 < self.num_upsamples:
-                if "zn" not in buf:                   # the next upsampler's input pair (the wide stages lend their t pair)
-                    buf["zn"] = buf["t"] if "t" in buf else (torch.zeros_like(buf["xs"], dtype=torch.float16), torch.zeros_like(buf["xs"], dtype=torch.float16))
-                    buf["zs_out"] = torch.ones(1, dtype=torch.float32, device=self.device)
-                cur_zs = ops.amax_pow2_scale(buf["xs"], 1024.0, buf["zs_out"], buf["zs_scratch"]) if self.act_scales else None
-                ops.hifigan_split_channels_last(buf["xs"], buf["zn"], LRELU_SLOPE, z_scale=cur_zs)
-                cur_z, lin = buf["zn"], lout
-        y = torch.empty(B, 1, lout, dtype=torch.float32, device=x.device)
-        return ops.hifigan_post_channels_last(buf["xs"], pk["ups"][-1].cout, lout, pk["post_w"], pk["post_b"], y, slope=0.01)
+        then conv_post + tanh straight from the last xs.  No channel-major tensor exists between conv_pre and the waveform."""
+        B, _, lin = x.shape
+        cur_z, cur_zs = ws.zin, ops.amax_pow2_scale(x, PRESCALE_TARGET, ws.zs_in, ws.amax_in)
+        ops.hifigan_to_channels_last(x, None, cur_z, LRELU_SLOPE, z_scale=cur_zs)
+        for i, (st, sb) in enumerate(zip(self.plan.stages, ws.stages)):
+            ops.hifigan_conv_transpose1d_f16x3(cur_z, pk["ups"][i].w16t, B, lin, sb.x0, sb.L, z_scale=cur_zs, amax_bits=sb.amax, items=items[i])
+            zs = ops.pow2_scale_from_amax(sb.amax, PRESCALE_TARGET, sb.zs)
+            if st.wide:
+                ops.hifigan_split_channels_last(sb.x0, sb.z0, LRELU_SLOPE, z_scale=zs)
+            self._resblocks(st, pk["res"][i], sb, B, zs, items[i])
+            if sb.zn is not None:
+                cur_zs = ops.amax_pow2_scale(sb.xs, PRESCALE_TARGET, sb.zs_next, sb.amax)
+                ops.hifigan_split_channels_last(sb.xs, sb.zn, LRELU_SLOPE, z_scale=cur_zs)
+                cur_z, lin = sb.zn, sb.L
+        y = torch.empty(B, 1, sb.L, dtype=torch.float32, device=x.device)
+        return ops.hifigan_post_channels_last(sb.xs, st.channels, sb.L, pk["post_w"], pk["post_b"], y, slope=0.01)
+
+    # ---- the ResBlocks of one stage: xs = sum_j ResBlock1_j(x) / num_kernels  (models.py:104-110, :35-42) ------------------
+    def _fold(self, j: int, n: int, xs: torch.Tensor, last: bool = True) -> tuple:
+        """(accum, out_scale) of a convolution of block j of n: the LAST one of a block adds to xs (from the second block on) and the
+        last block's divides by num_kernels; the others write a block's intermediate."""
+        return (xs if last and j > 0 else None), (1.0 / self.num_kernels if last and j == n - 1 else 1.0)
+
+    def _resblocks_fp32(self, blocks, x: torch.Tensor, items) -> torch.Tensor:
+        t, r, xs = torch.empty_like(x), torch.empty_like(x), torch.empty_like(x)
+        for j, block in enumerate(blocks):
+            cur = x
+            for m, (c1, c2) in enumerate(block):
+                last = m + 1 == len(block)
+                accum, out_scale = self._fold(j, len(blocks), xs, last)
+                self._run(c1, cur, t, in_slope=LRELU_SLOPE, items=items)
+                cur = self._run(c2, t, xs if last else r, in_slope=LRELU_SLOPE, res=cur, accum=accum, out_scale=out_scale, items=items)
+        return xs
+
+    def _resblocks(self, st: Stage, blocks, sb: StageBuffers, B: int, zs, items) -> None:
+        """sb.xs from sb.x0 (fp32) and, on a wide stage, sb.z0 = split(leaky_relu(x0) * zs): all channels-last."""
+        n, L = len(blocks), sb.L
+        if st.resblocks == "grouped":           # 18 -> 8 launches per stage
+            ops.hifigan_resblock_stage_f16x3(sb.x0, sb.z0, blocks, B, L, sb.scratch, sb.xs, out_scale=self._fold(n - 1, n, sb.xs)[1],
+                                             z_scale=zs, items=items)
+            return
+        s = sb.scratch[0]
+        for j, (form, block) in enumerate(zip(st.blocks, blocks)):
+            if form == "call":                  # cvx_hifigan_resblock_f16x3: 6 launches, or 3 fused pairs
+                accum, out_scale = self._fold(j, n, sb.xs)
+                ops.hifigan_resblock_f16x3(sb.x0, sb.z0, block, B, L, s, accum=accum, out=sb.xs, out_scale=out_scale, z_scale=zs, items=items)
+                continue
+            cur_x, cur_z = sb.x0, sb.z0
+            for m, (c1, c2) in enumerate(block):
+                last = m + 1 == len(block)
+                accum, out_scale = self._fold(j, n, sb.xs, last)
+                out_x, out_z = (sb.xs, None) if last else (s["r0"], s["rz0"]) if m % 2 == 0 else (s["r1"], s["rz1"])
+                if form == "pairs":
+                    ops.hifigan_resblock_pair_f16x3(cur_x, c1, c2, B, L, out_x, accum=accum, out_scale=out_scale, z_scale=zs, items=items)
+                else:
+                    ops.hifigan_conv1d_f16x3(cur_z, c1.w16, c1.bias16, B, L, ksize=c1.k, dil=c1.dil, out_z=s["t"], z_slope=LRELU_SLOPE,
+                                             z_scale=zs, items=items)
+                    ops.hifigan_conv1d_f16x3(s["t"], c2.w16, c2.bias16, B, L, ksize=c2.k, dil=c2.dil, res=cur_x, accum=accum, out_x=out_x,
+                                             out_scale=out_scale, out_z=out_z, z_slope=LRELU_SLOPE, z_scale=zs, items=items)
+                cur_x, cur_z = out_x, out_z
 
 
 def mel_decode_to_wav(generator: Generator, mel: torch.Tensor):

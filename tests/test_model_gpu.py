@@ -263,23 +263,19 @@ def test_vocoder_grouped_resblock_stages_are_bit_identical_to_block_after_block(
     18 -> 8 launches per stage).  Same arithmetic per output element, same accumulation order into xs: the waveform must equal, bit for
     bit, the one the block-after-block schedule gives (and both the ragged and the unragged call)."""
     import covomix_amd.synthetic as syn
-    from covomix_amd import vocoder
     from covomix_amd.vocoder import AttrDict, Generator
     h = AttrDict(syn.HIFIGAN_COVOMIX_CONFIG)
     vsd = {k: torch.from_numpy(v) for k, v in syn.synth_state_dict(syn.hifigan_param_shapes(h), seed=0).items()}
-    gen = Generator(h).to("cuda:0")
-    gen.load_state_dict(vsd); gen.eval(); gen.remove_weight_norm()
+    gen, gen_plain = Generator(h).to("cuda:0"), Generator(h, group_stages=False).to("cuda:0")
+    for g in (gen, gen_plain):
+        g.load_state_dict(vsd); g.eval(); g.remove_weight_norm()
     mel = (torch.randn(B, 80, T, generator=torch.Generator().manual_seed(9)) * 2 - 6).clamp(-11.52, 2.0).cuda()
     lens = [T - 37 * i for i in range(B)]
-    assert vocoder.GROUP_STAGE
     grouped = gen(mel).clone()
     grouped_r = gen(mel, lengths=lens).clone() if B > 1 else None
-    vocoder.GROUP_STAGE = False
-    try:
-        plain = gen(mel).clone()
-        plain_r = gen(mel, lengths=lens).clone() if B > 1 else None
-    finally:
-        vocoder.GROUP_STAGE = True
+    plain = gen_plain(mel).clone()
+    plain_r = gen_plain(mel, lengths=lens).clone() if B > 1 else None
+    assert [st.resblocks for st in gen.plan.stages[:2]] == ["grouped"] * 2 and all(st.resblocks == "blocks" for st in gen_plain.plan.stages)
     assert torch.equal(grouped, plain)
     if B > 1:
         assert torch.equal(grouped_r, plain_r)
