@@ -1171,6 +1171,64 @@ int64_t cvx_hubert_workspace_bytes(const cvx_hubert_model* m, int64_t n_samples)
 int cvx_hubert_extract_features(const cvx_hubert_model* m, const float* wav, int64_t n_samples, int32_t output_layer,
                                 float* out, void* workspace, int64_t workspace_bytes, cvx_stream_t s);
 
+/* MANY UTTERANCES IN ONE CALL (ragged batch; opt-in - the one-utterance entry points above are unchanged).
+ * The utterances are PACKED into one waveform: item b starts at sample S_b, a multiple of the conv stack's total hop (the product of
+ * conv_stride[], 320 for HuBERT-Base), the slack in between is ZERO.  Row j of conv layer i of item b is then global row
+ * S_b / (stride_0 ... stride_i) + j of ONE strided GEMM over the whole buffer; a valid row reads only valid rows of its own item, rows
+ * that straddle two items are computed and never read.  The valid frames are then gathered into compact [M = sum T_b, C] rows and the
+ * encoder runs on M rows: GroupNorm statistics per item, zero halos of the positional convolution per item, attention keys restricted
+ * to the own item (cvx_attention_varlen_f32).  An item's features do not depend on its neighbours' samples.
+ *
+ * ITEM TABLE: int32 words, filled on the HOST by cvx_hubert_items_fill (cvx_hubert_items_words of them); the caller uploads a copy and
+ * passes both.  n = n_items, nc = n_conv, halo = pos_k / 2:
+ *   header[16]        magic, n, nc, hop, halo, M = sum T_b, Mh = M + n * 2 * halo, max T_b, packed samples (S_last + n_last), 0 ...
+ *   slot[n]           S_b / hop
+ *   samples[n]        n_b
+ *   start[nc][n]      first global row of item b after conv layer i
+ *   rows[nc][n]       its row count there (rows[nc - 1][b] = T_b = cvx_hubert_frames(m, n_b); 0 is legal)
+ *   c0[n][3]          (start[0][b], rows[0][b], first GroupNorm statistics chunk of item b)
+ *   cu[n + 1]         cu_seqlens over compact rows
+ *   cuh[n + 1]        the same over haloed rows, cuh[b] = cu[b] + b * 2 * halo
+ *   gather[M]         compact row -> global row of the last conv layer
+ *   pack_src[Mh]      haloed row -> compact row, -1 in a halo
+ *   unpack[M]         compact row -> haloed row where its positional-convolution output lands (cuh[b] + t)
+ * cvx_hubert_items_fill: offsets == NULL packs the items tightly (every start rounded up to the hop); with offsets the caller chooses
+ * S_b.  CVX_EINVAL (nothing is launched, here and in every call that takes a table) when n_items <= 0, an offset is no multiple of the
+ * hop, items overlap or are out of order, or the total frame count reaches 2^24.  cvx_hubert_items_words returns -1 then.
+ * cvx_hubert_extract_features_many: wav = the packed waveform of header[8] samples (slack zeroed by the caller); out = [M, dim];
+ * workspace as for the one-utterance call, cvx_hubert_workspace_bytes_many bytes (-1 for an illegal table).  The host table is
+ * re-derived from its slot[] / samples[] and compared word by word before anything is launched.  The positional convolution's GEMMs
+ * run over all Mh - pos_k haloed rows, pos_k rows per item more than the frames. */
+int64_t cvx_hubert_items_words(const cvx_hubert_model* m, const int64_t* n_samples, int32_t n_items);
+int cvx_hubert_items_fill(const cvx_hubert_model* m, const int64_t* n_samples, const int64_t* offsets, int32_t n_items,
+                          int32_t* table, int64_t table_words);
+int64_t cvx_hubert_workspace_bytes_many(const cvx_hubert_model* m, const int32_t* items_host, int32_t n_items);
+int cvx_hubert_extract_features_many(const cvx_hubert_model* m, const float* wav, const int32_t* items_host, const int32_t* items_dev,
+                                     int32_t n_items, int32_t output_layer, float* out, void* workspace, int64_t workspace_bytes,
+                                     cvx_stream_t s);
+/* The stepping stones of the call above, each on its own.
+ * cvx_hubert_conv0_gn_gelu_many_f32: the first conv layer over the whole packed waveform with GroupNorm statistics PER ITEM.
+ * rows3 = n_items triples (first row, rows, first statistics chunk = sum over the items before of ceil(rows / 128)), the same words
+ * in host and in device memory (the table's c0[]); items in row order, not overlapping; an item of 0 rows may start behind the last row
+ * (a trailing item shorter than one stride).  out = [L, C], L = (n_samples - k) / stride + 1:
+ * an item's rows normalised with its own mean / rstd (fixed-order partial sums, no atomics), every other row ZERO.
+ * workspace: cvx_hubert_conv0_many_workspace_floats floats. */
+int64_t cvx_hubert_conv0_many_workspace_floats(const int32_t* rows3_host, int32_t n_items, int32_t C);
+int cvx_hubert_conv0_gn_gelu_many_f32(const float* wav, int64_t n_samples, const float* w, int32_t C, int32_t k, int32_t stride,
+                                      const float* gn_gamma, const float* gn_beta, float eps,
+                                      const int32_t* rows3_host, const int32_t* rows3_dev, int32_t n_items,
+                                      float* out, float* workspace, int64_t workspace_floats, cvx_stream_t s);
+/* out[r, :] = x[map[r], :] (map[r] < 0: zeros); map = `rows` int32 in device memory, C % 4 == 0. */
+int cvx_row_gather_f32(const float* x, float* out, const int32_t* map_dev, int64_t rows, int32_t C, cvx_stream_t s);
+/* Ragged cvx_hubert_group_pack_f32: out[g][j][c] = x[pack_src[j]][g*D/groups + c], 0 where pack_src[j] < 0 (halo rows are WRITTEN,
+ * every call); out = [groups, rows, D/groups], rows = Mh, (D/groups) % 4 == 0.  Output frame t of item b of group g reads the
+ * contiguous run out[g][cuh[b] + t .. + pos_k - 1][:]. */
+int cvx_hubert_group_pack_many_f32(const float* x, float* out, const int32_t* pack_src_dev, int64_t rows, int32_t D, int32_t groups,
+                                   cvx_stream_t s);
+/* The inverse mapping with the residual: x[r, :] = h[r, :] + conv[unpack[r], :] for r < rows (= M); conv = [>= Mh - pos_k, D]. */
+int cvx_hubert_group_unpack_add_f32(const float* h, const float* conv, const int32_t* unpack_dev, float* x, int64_t rows, int32_t D,
+                                    cvx_stream_t s);
+
 /* Sample-rate conversion in front of the tokeniser (hubert_feature_reader.py:38-41: torchaudio.transforms.Resample,
  * third-party; its published polyphase windowed-sinc algorithm): out[i*up + j] = sum_k kern[j][k] * x[i*down + k - width]
  * with x = 0 outside [0, n), kern = [up][2*width + down] computed by the host (covomix_amd.hubert.sinc_resample_kernel),

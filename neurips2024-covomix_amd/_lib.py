@@ -273,6 +273,18 @@ SIGNATURES = {
     "cvx_hubert_workspace_bytes": (C.c_int64, [C.POINTER(HubertModel), C.c_int64]),
     "cvx_hubert_extract_features": (C.c_int, [C.POINTER(HubertModel), C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p,
                                               C.c_int64, C.c_void_p]),
+    "cvx_hubert_items_words": (C.c_int64, [C.POINTER(HubertModel), C.c_void_p, C.c_int32]),
+    "cvx_hubert_items_fill": (C.c_int, [C.POINTER(HubertModel), C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64]),
+    "cvx_hubert_workspace_bytes_many": (C.c_int64, [C.POINTER(HubertModel), C.c_void_p, C.c_int32]),
+    "cvx_hubert_extract_features_many": (C.c_int, [C.POINTER(HubertModel), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                                                   C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "cvx_hubert_conv0_many_workspace_floats": (C.c_int64, [C.c_void_p, C.c_int32, C.c_int32]),
+    "cvx_hubert_conv0_gn_gelu_many_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
+                                                    C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                                                    C.c_int64, C.c_void_p]),
+    "cvx_row_gather_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]),
+    "cvx_hubert_group_pack_many_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p]),
+    "cvx_hubert_group_unpack_add_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]),
     "cvx_rope_attention_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
                                          C.c_float, C.c_void_p, C.c_void_p]),
     "cvx_hifigan_convt_f32": (C.c_int, [C.POINTER(ConvArgs), C.c_void_p]),

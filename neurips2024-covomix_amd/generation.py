@@ -15,7 +15,8 @@ Upstream stages:
       log-mel of `<prompt_dir>/<name>.wav` (8 kHz) computed on the GPU
   * prompt tokens (N4, built: hubert.py): `<prompt_dir>/<name>.hubert_code.npy` if present (what
       fairseq-hubert/get_fisher_semantic_tokens.py wrote offline), else, with --hubert_ckpt and --km_path, the HuBERT
-      layer-12 + k-means codes of `<prompt_dir>/<name>.wav` computed on the GPU (resampled to the checkpoint's rate);
+      layer-12 + k-means codes of `<prompt_dir>/<name>.wav` computed on the GPU (resampled to the checkpoint's rate;
+      --hubert_batch N > 1: all such prompts of the run up front, N per ragged call, instead of one call per prompt);
       dialogue mode uses `<name>_1.*` and `<name>_2.*` (dialogue_generation.py:285-286)
 Dialogue covosingle / covosinx decode the text turn by turn (split at "[spkchange]") with alternating prompts / streams
 exactly as dialogue_generation.py:145-193, :205-272 do; pre-tokenised turns are `<name>.turn<k>.semantic.npy` /
@@ -70,6 +71,8 @@ def build_parser() -> ArgumentParser:
     p.add_argument("--hubert_ckpt", type=str, default=None, help="HuBERT checkpoint (fairseq layout): tokenise <name>.wav prompts "
                    "that have no <name>.hubert_code.npy (fairseq-hubert/get_fisher_semantic_tokens.py:23-24)")
     p.add_argument("--km_path", type=str, default=None, help="k-means model (joblib) for --hubert_ckpt")
+    p.add_argument("--hubert_batch", type=int, default=1, help="with --hubert_ckpt: N > 1 tokenises the run's wav prompts up front, N per "
+                   "ragged call (HubertTokenizer.wav2code_many; 16 is the measured recommendation); 1 = one call per prompt as it is needed")
     p.add_argument("--nfe", type=int, default=32, help="extension: CFG-combined field evaluations of the midpoint solver (32 = the "
                    "reference's ode_step_size 0.0625, acoustic.py:586-591; 64 = BASELINE config 5's 64-step setting)")
     p.add_argument("--ode_method", type=str, default="midpoint", help="extension: the fixed-grid solver (the reference's "
@@ -117,13 +120,16 @@ def build_parser() -> ArgumentParser:
 
 HEAD_START = 16     # utterances read before the first launch of a large directory (generation.run, --pipeline off)
 _HUBERT = None      # HubertTokenizer, built by main() when --hubert_ckpt / --km_path are given
+_HUBERT_CODES: dict = {}   # (prompt_dir, prompt name) -> code string, filled by the --hubert_batch pre-pass
 
 
 def _load_prompt(prompt_dir: str, name: str):
     code = os.path.join(prompt_dir, name + ".hubert_code.npy")
     if os.path.isfile(code) or _HUBERT is None:
         tok = torch.from_numpy(np.load(code).astype(np.int64))
-    else:                                                  # encoder.wav2code(file, 1) (get_fisher_semantic_tokens.py:35-37, row N4)
+    elif (prompt_dir, name) in _HUBERT_CODES:              # tokenised by the --hubert_batch pre-pass
+        tok = torch.tensor([int(c) for c in _HUBERT_CODES[(prompt_dir, name)].split(" ")], dtype=torch.int64)
+    else:                                                # encoder.wav2code(file, 1) (get_fisher_semantic_tokens.py:35-37, row N4)
         tok = torch.tensor([int(c) for c in _HUBERT.wav2code(os.path.join(prompt_dir, name + ".wav"), 1).split(" ")], dtype=torch.int64)
     npy = os.path.join(prompt_dir, name + ".mel.npy")
     if os.path.isfile(npy):
@@ -132,6 +138,22 @@ def _load_prompt(prompt_dir: str, name: str):
         from .mel import extract_mel
         mel = extract_mel(os.path.join(prompt_dir, name + ".wav"))
     return assembly.truncate_prompt(tok, mel)            # -> tokens [Tp], mel [Tp, 80]
+
+
+def prompt_names(names, dialogue: bool):
+    """The prompt files `_build_items` will ask `_load_prompt` for: <name> for a monologue, <name>_1 and <name>_2 for a dialogue."""
+    return [n + suffix for n in names for suffix in (("_1", "_2") if dialogue else ("",))]
+
+
+def pretokenise_prompts(prompt_dir: str, names, batch: int) -> int:
+    """--hubert_batch N > 1: tokenise every prompt of the run that has no <name>.hubert_code.npy in groups of N
+    (HubertTokenizer.wav2code_many) and keep the codes for `_load_prompt`.  -> number of prompts tokenised."""
+    todo = [n for n in dict.fromkeys(names) if not os.path.isfile(os.path.join(prompt_dir, n + ".hubert_code.npy"))]
+    for i in range(0, len(todo), batch):
+        group = todo[i:i + batch]
+        for n, code in zip(group, _HUBERT.wav2code_many([os.path.join(prompt_dir, n + ".wav") for n in group], 1)):
+            _HUBERT_CODES[(prompt_dir, n)] = code
+    return len(todo)
 
 
 def remove_punctuation(text: str) -> str:
@@ -544,6 +566,12 @@ def run(dialogue: bool, argv=None) -> int:
 
     names, sources, plan = utterance_plan(args.text_dir, dialogue, args.mode, t2s is not None, world)
     mine = plan[rank]
+    _HUBERT_CODES.clear()
+    prepass_s = 0.0                                               # (added to `seconds` below, and reported on its own in last_stats)
+    if _HUBERT is not None and args.hubert_batch > 1:
+        t_pre = time.perf_counter()
+        pretokenise_prompts(args.prompt_dir, prompt_names(mine, dialogue), int(args.hubert_batch))
+        prepass_s = time.perf_counter() - t_pre
     work = [(n, k, s) for n in mine for k, s in enumerate(sources[n])]
     to_decode = sum(1 for _, _, (kind, _) in work if kind != "sem")
     mode = args.pipeline
@@ -727,7 +755,7 @@ def run(dialogue: bool, argv=None) -> int:
         frames = sum(nfr)
     drain()
     torch.cuda.synchronize()
-    elapsed = time.perf_counter() - t0
+    elapsed = time.perf_counter() - t0 + prepass_s                # (--hubert_batch 1 tokenises inside the loop: both forms are counted)
     for n in mine:
         if not segments[n]:
             continue
@@ -740,7 +768,8 @@ def run(dialogue: bool, argv=None) -> int:
         with open(args.ode_error_json + (f".rank{rank}" if rank else ""), "w") as f:
             json.dump({n: [segs[k] for k in sorted(segs)] for n, segs in sorted(solve_errors.items())}, f, indent=1)
     print(f"rank {rank}: {done} utterances, {frames} generated frames in {elapsed:.3f} s ({frames / max(elapsed, 1e-9):.1f} frames/s, "
-          f"{'text2semantic + ' if mode != 'off' else ''}sampling + vocoder, excluding model load; --pipeline {mode})")
+          f"{'text2semantic + ' if mode != 'off' else ''}sampling + vocoder, excluding model load; --pipeline {mode}"
+          + (f"; of that {prepass_s:.3f} s in the --hubert_batch pre-pass" if prepass_s else "") + ")")
     run.last_stats = dict(utterances=done, frames=frames, seconds=elapsed, pipeline=mode, load_seconds=load_s, batches=batch_log,
-                          max_frames=max_frames, head_start=bool(head_start))
+                          max_frames=max_frames, head_start=bool(head_start), hubert_prepass_seconds=prepass_s)
     return done

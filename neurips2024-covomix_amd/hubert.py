@@ -15,6 +15,9 @@ runs entirely through the C ABI of libcovomix_hip.so, activations channels-last 
   12 post-LN layers                    GEMM (q|k|v fused), cvx_attention_f32, GEMM(+residual), LayerNorm, GEMM(+GELU),
                                        GEMM(+residual), LayerNorm
   k-means                              GEMM against cluster_centers_, cvx_kmeans_argmin_f32
+Many prompts of different lengths in ONE call (opt-in; the reference has no counterpart, it runs one file at a time):
+HubertEncoder.extract_features_many -> HubertFeatureReader.get_feats_many -> HubertTokenizer.wav2code_many ->
+tokenize_directory(batch=N), through cvx_hubert_extract_features_many (packed waveform + item table, include/covomix_hip.h).
 torch is used for device memory and one-time weight re-layouts only.  There is no CPU path: `use_cuda=False` raises.
 """
 from __future__ import annotations
@@ -28,6 +31,7 @@ import torch
 from . import ops
 
 DEFAULT_CONV_LAYERS = "[(512,10,5)] + [(512,3,2)] * 4 + [(512,2,2)] * 2"       # hubert.py:136-137
+DEFAULT_MAX_BATCH_SAMPLES = 2_560_000       # packed samples of one ragged call: sixteen 10-s prompts at 16 kHz (get_feats_many)
 
 
 def parse_conv_layers(spec: str) -> List[Tuple[int, int, int]]:
@@ -85,6 +89,76 @@ def resample(wav: torch.Tensor, orig_freq: int, new_freq: int) -> torch.Tensor:
     _lib.check(_lib.load().cvx_resample_fir_f32(wav.data_ptr(), n, k.data_ptr(), new, orig, width, out.data_ptr(), n_out,
                                                 ops._stream()), "cvx_resample_fir_f32")
     return out
+
+
+class ItemTable:
+    """The item table of a ragged tokeniser call (include/covomix_hip.h, "MANY UTTERANCES IN ONE CALL"): int32 words filled by
+    cvx_hubert_items_fill on the host, with named views.  Host arithmetic only - no GPU needed."""
+
+    HEADER = 16
+
+    def __init__(self, words: np.ndarray):
+        self.words = words
+        _magic, self.n, self.n_conv, self.hop, self.halo, self.M, self.Mh, self.max_T, self.samples_total = (int(v) for v in words[:9])
+        n, nc, o = self.n, self.n_conv, self.HEADER
+        def take(count, shape=None):
+            nonlocal o
+            v = words[o:o + count]
+            o += count
+            return v if shape is None else v.reshape(shape)
+        self.slot, self.samples = take(n), take(n)
+        self.start, self.rows, self.c0 = take(nc * n, (nc, n)), take(nc * n, (nc, n)), take(3 * n, (n, 3))
+        self.cu, self.cuh = take(n + 1), take(n + 1)
+        self.gather, self.pack_src, self.unpack = take(self.M), take(self.Mh), take(self.M)
+        assert o == words.size
+        self.offsets = self.slot.astype(np.int64) * self.hop              # S_b, in samples
+        self.frames = self.rows[nc - 1]                                   # T_b
+
+
+def _geometry_model(conv_layers, pos_k: int):
+    """A cvx_hubert_model with the conv geometry and pos_k only: all the host-side table arithmetic reads."""
+    from . import _lib
+    m = _lib.HubertModel()
+    m.n_conv = len(conv_layers)
+    for i, (c, k, s) in enumerate(conv_layers):
+        m.conv_c[i], m.conv_k[i], m.conv_stride[i] = c, k, s
+    m.pos_k = pos_k
+    return m
+
+
+def item_table(lengths: Sequence[int], conv_layers=None, pos_k: int = 128, offsets: Optional[Sequence[int]] = None) -> ItemTable:
+    """Item table for waveforms of `lengths` samples: packed tightly, every start rounded up to the conv stack's hop (offsets=None), or
+    at the caller's `offsets`.  Raises CovomixHipError for an illegal batch (no items, unaligned or overlapping offsets, 2^24 frames)."""
+    import ctypes as C
+    from . import _lib
+    lib = _lib.load()
+    m = _geometry_model(conv_layers or parse_conv_layers(DEFAULT_CONV_LAYERS), pos_k)
+    n = len(lengths)
+    ns = np.ascontiguousarray(lengths, dtype=np.int64)
+    words = int(lib.cvx_hubert_items_words(C.byref(m), ns.ctypes.data, n)) if n else -1     # depends on the lengths only
+    if words < 0:
+        _lib.check(-22, "cvx_hubert_items_words")
+    table = np.zeros(words, dtype=np.int32)
+    offs = None if offsets is None else np.ascontiguousarray(offsets, dtype=np.int64)
+    _lib.check(lib.cvx_hubert_items_fill(C.byref(m), ns.ctypes.data, None if offs is None else offs.ctypes.data, n, table.ctypes.data, words),
+               "cvx_hubert_items_fill")
+    return ItemTable(table)
+
+
+def split_batches(lengths: Sequence[int], max_batch_samples: int, hop: int = 320) -> List[List[int]]:
+    """Indices of `lengths` in order, cut into consecutive groups whose PACKED size (every item rounded up to the hop) stays within
+    max_batch_samples; an item larger than the budget forms a group of its own."""
+    groups, cur, used = [], [], 0
+    for i, n in enumerate(lengths):
+        size = -(-int(n) // hop) * hop
+        if cur and used + size > max_batch_samples:
+            groups.append(cur)
+            cur, used = [], 0
+        cur.append(i)
+        used += size
+    if cur:
+        groups.append(cur)
+    return groups
 
 
 class HubertEncoder:
@@ -276,6 +350,54 @@ class HubertEncoder:
                    "cvx_hubert_extract_features")
         return out
 
+    @ops.gated
+    def extract_features_many(self, waves: Sequence[Union[np.ndarray, torch.Tensor]], output_layer: Optional[int] = None,
+                              out: Optional[torch.Tensor] = None) -> List[torch.Tensor]:
+        """extract_features of every 1-D waveform in `waves` from ONE C call (cvx_hubert_extract_features_many): the waveforms are
+        packed into one buffer (each start rounded up to the hop, slack zeroed), the item table is uploaded once, and the [sum T_b, D]
+        result is sliced.  -> list of [T_b, D] tensors in input order, an empty [0, D] tensor for an item shorter than the receptive
+        field (views of `out` [sum T_b, D], which the caller may provide).  An item's features do not depend on the other items.  Defined for the default precision="f16x3" one-call path only:
+        precision="fp32" and stepped=True raise NotImplementedError (there is no batched fp32 or stepped twin)."""
+        if self.stepped or self.precision != "f16x3":
+            raise NotImplementedError("extract_features_many exists for precision='f16x3', stepped=False only")
+        import ctypes as C
+        from . import _lib
+        lib = _lib.load()
+        waves = [w if isinstance(w, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(w, dtype=np.float32)) for w in waves]
+        waves = [w.reshape(-1) for w in waves]
+        if not waves:
+            return []
+        n_layers = len(self.layers) if output_layer is None else int(output_layer)
+        assert 0 <= n_layers <= len(self.layers), f"output_layer {output_layer} out of range"
+        tab = item_table([w.numel() for w in waves], self.conv_layers, self.pos_k)
+        if out is None:
+            out = torch.empty(tab.M, self.dim, dtype=torch.float32, device=self.device)
+        assert out.shape == (tab.M, self.dim) and out.dtype == torch.float32 and out.is_cuda and out.is_contiguous()
+        if tab.M:
+            if all(w.device.type == "cpu" for w in waves):               # pack on the host, one upload
+                host = torch.zeros(tab.samples_total, dtype=torch.float32)
+                for w, s0 in zip(waves, tab.offsets):
+                    host[int(s0):int(s0) + w.numel()] = w.float()
+                packed = ops.h2d(host, self.device)
+            else:
+                packed = torch.zeros(tab.samples_total, dtype=torch.float32, device=self.device)
+                for w, s0 in zip(waves, tab.offsets):
+                    packed[int(s0):int(s0) + w.numel()] = w.to(device=self.device, dtype=torch.float32)
+            words = torch.from_numpy(tab.words)
+            words_dev = ops.h2d(words, self.device)
+            m = self._c_model()
+            ops.ensure_saturation_bound()
+            need = int(lib.cvx_hubert_workspace_bytes_many(C.byref(m), words.data_ptr(), tab.n))
+            if need < 0:
+                _lib.check(-22, "cvx_hubert_workspace_bytes_many")
+            if self._ws is None or self._ws.numel() < need:
+                self._ws = None                                        # release before growing
+                self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+            _lib.check(lib.cvx_hubert_extract_features_many(C.byref(m), packed.data_ptr(), words.data_ptr(), words_dev.data_ptr(), tab.n,
+                                                            n_layers, out.data_ptr(), self._ws.data_ptr(), self._ws.numel(), ops._stream()),
+                       "cvx_hubert_extract_features_many")
+        return [out[int(tab.cu[b]):int(tab.cu[b + 1])] for b in range(tab.n)]
+
     def _c_model(self):
         """cvx_hubert_model over this object's device tensors (built once; the tensors stay referenced by self)."""
         if self._cmodel is not None:
@@ -371,6 +493,39 @@ class HubertFeatureReader:
                 feat.append(self.model.extract_features(x[:, start: start + self.max_chunk], output_layer=self.layer))
         return torch.cat(feat, 0)
 
+    @ops.gated
+    def get_feats_many(self, paths_or_arrays, channel_ids=None, max_batch_samples: int = DEFAULT_MAX_BATCH_SAMPLES):
+        """get_feats of every entry (a path, or a waveform array) through HubertEncoder.extract_features_many -> list of [T, D]
+        tensors in input order.  `normalize` is applied per whole file as in get_feats; a file longer than max_chunk contributes its
+        chunks as separate ITEMS (the reference runs each chunk alone and concatenates, :68-76).  channel_ids: one id for all entries,
+        or one per entry.  A list whose packed size exceeds max_batch_samples is cut into several calls (split_batches).  The default,
+        2 560 000 samples = sixteen 10-s prompts, makes cvx_hubert_workspace_bytes_many 3.57e9 bytes for HuBERT-Base (2.23e8 per 10 s
+        of audio; cvx_hubert_workspace_bytes is 2.45e8 for one 10-s prompt)."""
+        n = len(paths_or_arrays)
+        if channel_ids is None or isinstance(channel_ids, int):
+            channel_ids = [channel_ids] * n
+        assert len(channel_ids) == n
+        items, owner = [], []
+        with torch.no_grad():
+            for i, (src, ch) in enumerate(zip(paths_or_arrays, channel_ids)):
+                x = self.read_audio(src, None, ch) if isinstance(src, str) else np.asarray(src, dtype=np.float32)
+                x = torch.from_numpy(np.ascontiguousarray(x)).float()
+                if self.normalize:                                 # over the whole file, on the GPU as in get_feats
+                    x = _waveform_layer_norm(x.cuda())
+                for start in range(0, x.numel(), self.max_chunk):
+                    items.append(x[start: start + self.max_chunk])
+                    owner.append(i)
+            feats = [None] * len(items)
+            hop = int(np.prod([s for _c, _k, s in self.model.conv_layers]))
+            for group in split_batches([w.numel() for w in items], max_batch_samples, hop):
+                for j, f in zip(group, self.model.extract_features_many([items[j] for j in group], output_layer=self.layer)):
+                    feats[j] = f
+        out = []
+        for i in range(n):
+            mine = [f for f, o in zip(feats, owner) if o == i]
+            out.append(torch.cat(mine, 0) if mine else torch.empty(0, self.model.dim, dtype=torch.float32, device=self.model.device))
+        return out
+
 
 def _waveform_layer_norm(x: torch.Tensor) -> torch.Tensor:
     """F.layer_norm over the whole 1-D waveform (no affine, eps 1e-5).  A length-n reduction of a vector that is read
@@ -425,9 +580,19 @@ class HubertTokenizer:
     def wav2codes(self, path):
         return [self.wav2code(path, channel_id=1), self.wav2code(path, channel_id=2)]
 
+    def wav2code_many(self, paths, channel_id=1):
+        """wav2code of every path from one ragged feature call and one k-means call over the packed frames -> list of code strings."""
+        feats = self.feature_extractor.get_feats_many(list(paths), channel_ids=channel_id)
+        if not feats:
+            return []
+        code = self.quantizer(torch.cat(feats, 0))
+        cuts = np.cumsum([f.shape[0] for f in feats])[:-1]
+        return [' '.join(map(str, c)) for c in np.split(code, cuts)]
 
-def tokenize_directory(process_dir: str, target_dir: str, hubert_path: str, km_path: str, hubert_layer: int = 12) -> int:
-    """fairseq-hubert/get_fisher_semantic_tokens.py:30-40: every *.wav -> <name>.hubert_code.npy (array of str codes)."""
+
+def tokenize_directory(process_dir: str, target_dir: str, hubert_path: str, km_path: str, hubert_layer: int = 12, batch: int = 1) -> int:
+    """fairseq-hubert/get_fisher_semantic_tokens.py:30-40: every *.wav -> <name>.hubert_code.npy (array of str codes).
+    batch > 1 tokenises the files in groups of `batch` through HubertTokenizer.wav2code_many; batch = 1 is the reference's loop."""
     import glob
     import os
     rank, world, local = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("LOCAL_RANK", "0"))
@@ -436,6 +601,13 @@ def tokenize_directory(process_dir: str, target_dir: str, hubert_path: str, km_p
     encoder = HubertTokenizer(hubert_path=hubert_path, hubert_layer=hubert_layer, km_path=km_path)
     files = sorted(glob.glob(os.path.join(process_dir, "*.wav")))[rank::world]
     os.makedirs(target_dir, exist_ok=True)
+    if batch > 1:
+        for i in range(0, len(files), batch):
+            group = files[i:i + batch]
+            for process_file, code in zip(group, encoder.wav2code_many(group, 1)):
+                file_name = process_file.split("/")[-1].split(".")[0]
+                np.save(os.path.join(target_dir, file_name + '.hubert_code'), np.array(code.split(" ")))
+        return len(files)
     for process_file in files:
         codes = encoder.wav2code(process_file, 1).split(" ")
         file_name = process_file.split("/")[-1].split(".")[0]

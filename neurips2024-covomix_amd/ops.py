@@ -1420,6 +1420,79 @@ def hubert_group_pack(x: torch.Tensor, groups: int, halo: int) -> torch.Tensor:
     return out
 
 
+def _i32_pair(a, device):
+    """A host int32 array and its copy on the device (the ragged HuBERT calls take both: the host words size and validate the
+    launch, the kernels read the device words)."""
+    host = torch.as_tensor(a, dtype=torch.int32).reshape(-1).contiguous()
+    assert host.device.type == "cpu"
+    return host, h2d(host, device)
+
+
+def hubert_conv0_gn_gelu_many(wav: torch.Tensor, w: torch.Tensor, gn_gamma: torch.Tensor, gn_beta: torch.Tensor, stride: int,
+                              starts: Sequence[int], rows: Sequence[int], eps: float = 1e-5) -> torch.Tensor:
+    """hubert_conv0_gn_gelu over a PACKED waveform with GroupNorm statistics per item: item b owns rows [starts[b], starts[b] +
+    rows[b]) of the [L, C] output (in row order, not overlapping); every row of no item comes back zero."""
+    _chk_f32(wav, w, gn_gamma, gn_beta)
+    assert wav.dim() == 1 and wav.is_contiguous() and w.is_contiguous() and w.dim() == 2 and len(starts) == len(rows) > 0
+    C, k = w.shape
+    n = wav.numel()
+    L = (n - k) // stride + 1
+    rows3, chunk = [], 0
+    for s0, r in zip(starts, rows):
+        rows3 += [int(s0), int(r), chunk]
+        chunk += -(-int(r) // 128)
+    host, dev = _i32_pair(rows3, wav.device)
+    lib = _lib.load()
+    out = torch.empty(max(L, 0), C, dtype=torch.float32, device=wav.device)
+    need = int(lib.cvx_hubert_conv0_many_workspace_floats(host.data_ptr(), len(starts), C))
+    ws = torch.empty(max(need, 1), dtype=torch.float32, device=wav.device)
+    _lib.check(lib.cvx_hubert_conv0_gn_gelu_many_f32(wav.data_ptr(), n, w.data_ptr(), C, k, stride, gn_gamma.data_ptr(), gn_beta.data_ptr(),
+                                                     eps, host.data_ptr(), dev.data_ptr(), len(starts), out.data_ptr(), ws.data_ptr(),
+                                                     ws.numel(), _stream()), "cvx_hubert_conv0_gn_gelu_many_f32")
+    return out
+
+
+def row_gather(x: torch.Tensor, row_map: Sequence[int], out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out[r] = x[row_map[r]] (zeros where row_map[r] < 0); x [R, C] fp32, C % 4 == 0."""
+    _chk_f32(x, out)
+    assert x.dim() == 2 and x.is_contiguous()
+    host, dev = _i32_pair(row_map, x.device)
+    assert host.numel() == 0 or int(host.max()) < x.shape[0]
+    out = torch.empty(host.numel(), x.shape[1], dtype=torch.float32, device=x.device) if out is None else out
+    assert out.is_contiguous() and out.shape == (host.numel(), x.shape[1])
+    _lib.check(_lib.load().cvx_row_gather_f32(x.data_ptr(), out.data_ptr(), dev.data_ptr(), host.numel(), x.shape[1], _stream()),
+               "cvx_row_gather_f32")
+    return out
+
+
+def hubert_group_pack_many(x: torch.Tensor, groups: int, pack_src: Sequence[int], out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Ragged hubert_group_pack: x [M, D] -> [groups, len(pack_src), D/groups], row j of every group = x[pack_src[j]]'s slice, zero
+    where pack_src[j] < 0 (the items' halos, written on every call)."""
+    _chk_f32(x, out)
+    assert x.dim() == 2 and x.is_contiguous()
+    host, dev = _i32_pair(pack_src, x.device)
+    M, D = x.shape
+    assert host.numel() > 0 and int(host.max()) < M
+    out = torch.empty(groups, host.numel(), D // groups, dtype=torch.float32, device=x.device) if out is None else out
+    assert out.is_contiguous() and out.shape == (groups, host.numel(), D // groups)
+    _lib.check(_lib.load().cvx_hubert_group_pack_many_f32(x.data_ptr(), out.data_ptr(), dev.data_ptr(), host.numel(), D, groups, _stream()),
+               "cvx_hubert_group_pack_many_f32")
+    return out
+
+
+def hubert_group_unpack_add(h: torch.Tensor, conv: torch.Tensor, unpack: Sequence[int], out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out[r] = h[r] + conv[unpack[r]]: the positional convolution's output rows (haloed numbering) back on compact rows."""
+    _chk_f32(h, conv, out)
+    assert h.dim() == 2 and h.is_contiguous() and conv.is_contiguous() and conv.shape[1] == h.shape[1]
+    host, dev = _i32_pair(unpack, h.device)
+    assert host.numel() == h.shape[0] and (host.numel() == 0 or (int(host.min()) >= 0 and int(host.max()) < conv.shape[0]))
+    out = torch.empty_like(h) if out is None else out
+    assert out.is_contiguous() and out.shape == h.shape
+    _lib.check(_lib.load().cvx_hubert_group_unpack_add_f32(h.data_ptr(), conv.data_ptr(), dev.data_ptr(), out.data_ptr(), h.shape[0],
+                                                           h.shape[1], _stream()), "cvx_hubert_group_unpack_add_f32")
+    return out
+
+
 def kmeans_argmin(x: torch.Tensor, dots: torch.Tensor, cnorm: torch.Tensor, with_margin: bool = False):
     """labels[t] = argmin_j (|x_t|^2 - 2 dots[t, j]) + cnorm[j]  (int64); optionally also the runner-up margin."""
     _chk_f32(x, dots, cnorm)
