@@ -77,7 +77,8 @@ typedef const cvx_ctx* cvx_stream_t;
  * far reserved, carries a slot's role there.  Still 113 (two symbols added, no struct changed): cvx_t2s_beam_guided_steps and
  * cvx_t2s_beam_guided_queue_steps - beam search under classifier-free guidance, on the structs of the unguided entry points.  Still 113
  * (two symbols and a struct added): cvx_t2s_decode_steps_rules with cvx_t2s_rules, cvx_t2s_rules_f32 - repetition penalty, no-repeat
- * n-gram and minimum length per dialogue; cvx_t2s_per_dialogue and its rows are untouched. */
+ * n-gram and minimum length per dialogue; cvx_t2s_per_dialogue and its rows are untouched.  Still 113 (two symbols added, no struct
+ * changed): cvx_t2s_beam_rules_steps and cvx_t2s_beam_select_rules_f32 - no-repeat n-gram and minimum length under beam search. */
 #define CVX_ABI_VERSION 113
 int         cvx_version(void);
 const char* cvx_last_error_string(void);
@@ -1048,6 +1049,47 @@ int cvx_t2s_beam_guided_queue_steps(const cvx_t2s_decoder* dec, const cvx_t2s_be
 int cvx_t2s_beam_select_f32(const float* logits, const float* scores_in, const uint8_t* finished_in, int32_t groups, int32_t beam_size,
                             int32_t streams, int32_t V, int32_t* parents, int64_t* tokens, float* token_lp, float* scores_out,
                             uint8_t* finished_out, cvx_stream_t stream);
+
+/* Beam search UNDER THE HISTORY RULES no-repeat n-gram and minimum length: cvx_t2s_beam_steps (bq == NULL, dec->cfg_scale <= 1),
+ * cvx_t2s_beam_guided_steps (bq == NULL, dec->cfg_scale > 1), cvx_t2s_beam_queue_steps or cvx_t2s_beam_guided_queue_steps (bq != NULL, by
+ * dec->cfg_scale) - their structs, layouts, launches and results - with shortlist and merge kernels that first REMOVE candidates.  Still ABI
+ * 113: two symbols added, no struct changed.  A hypothesis' score stays the sum of the model's log-probabilities: nothing is renormalised,
+ * nothing is penalised.
+ *   1. History.  For a live hypothesis at position pos and output stream s, h_s holds the pos tokens its ANCESTRY took in stream s, oldest
+ *      first.  A live hypothesis has taken no eos, so h_s holds ids in [0, V - 1) only.  A re-armed group (queue forms) starts a new
+ *      utterance with an empty history.  The device reads it along the ancestry table: owner[pos & 1][slot][j + 1] names the slot the
+ *      ancestor sat in after step j, whose hist_tokens entry of step j is h_s[j] (the text half's row and slot / 2 in the guided chain).
+ *   2. Order.  lp[s][j] is computed exactly as in cvx_t2s_beam_steps / cvx_t2s_beam_guided_steps: the log_softmax of the raw row, or of the
+ *      guidance-combined row, the same function and the same bits.  The bans are applied AFTER it, as -inf on lp.
+ *   3. The two bans.  No-repeat n-gram, n in 1..8: for every j in [0, pos - n] with h_s[j, j + n - 1) == h_s[pos - n + 1, pos) the id
+ *      h_s[j + n - 1] is banned (n = 1: every id of h_s) - point 2 of cvx_t2s_rules, word for word.  Minimum length m: while pos < m the eos
+ *      (V - 1) is banned in every stream.
+ *   4. Void bans.  If the bans leave no un-banned entry in stream s's row, the n-gram bans of that stream are void for this step and the eos
+ *      ban stays (as in the sampled chain).
+ *   5. Shortlist and merge.  The shortlist ranks the banned lp with the order of cvx_t2s_beam_steps (lp descending, index ascending).  A
+ *      shortlist entry whose lp is -inf gives no candidate; a live hypothesis with no candidate left contributes none; a new slot for which
+ *      no candidate is left becomes a dead hypothesis exactly as cvx_t2s_beam_steps defines it.
+ *   6. What stays the model's.  hist_logprobs, the back-tracked logprobs, scores and final_scores are the model's log-probs and their fp32
+ *      sums in the association of cvx_t2s_beam_steps: every returned hypothesis' log-probs equal, bit for bit, the teacher-forced log-probs
+ *      of its tokens (under dec->cfg_scale in the guided chain), and its score is the fp32 sum the selection kept.
+ *   7. The table.  rules->table [n_records][4] words as in cvx_t2s_rules, one row per UTTERANCE: row = group index in the lock-step forms,
+ *      row = utterance number (groups record [3]) in the queue forms.  The device reads [2] (n, clamped into [0, 8]) and [3] (m, clamped into
+ *      [0, max_len]) and ignores [0] and [1]: beam search has no repetition penalty (it would make the search score something other than the
+ *      model's log-probability).  A row with n = 0 and m = 0 gives the chain without rules, bit for bit.
+ * Per step: the launches of the chain it stands for, no more.  No host synchronisation, graph-capturable.  CVX_EINVAL, nothing launched:
+ * rules->struct_size != sizeof(cvx_t2s_rules), rules or table NULL, n_records below the groups of the launch (lock-step: dec->batch /
+ * beam_size, or / (2 beam_size) guided) or below bq->n_utterances (queue), and everything the entry point of the same form refuses. */
+int cvx_t2s_beam_rules_steps(const cvx_t2s_decoder* dec, const cvx_t2s_beam* beam, const cvx_t2s_beam_queue* bq /* NULL: lock-step */,
+                             const cvx_t2s_rules* rules, int32_t n_steps, cvx_stream_t stream);
+
+/* cvx_t2s_beam_select_f32 under those rules, through the device code of cvx_t2s_beam_rules_steps: the history is given outright - history
+ * int32 [G * B][streams][hist_ld] (may be NULL when hist_ld == 0), hist_len int32 [G * B] (= pos of the hypothesis, clamped into
+ * [0, hist_ld]) - and table holds one 4-word row per GROUP ([2] n, clamped into [0, 8]; [3] m, clamped at 0 only: there is no max_len
+ * here).  Same outputs.  CVX_EINVAL (nothing is launched): what cvx_t2s_beam_select_f32 refuses, hist_ld outside [0, 4096]. */
+int cvx_t2s_beam_select_rules_f32(const float* logits, const float* scores_in, const uint8_t* finished_in, const int32_t* history,
+                                  const int32_t* hist_len, const void* table, int32_t groups, int32_t beam_size, int32_t streams, int32_t V,
+                                  int32_t hist_ld, int32_t* parents, int64_t* tokens, float* token_lp, float* scores_out,
+                                  uint8_t* finished_out, cvx_stream_t stream);
 
 /* The log-probability epilogue alone (the device function cvx_t2s_decode_steps_scored uses): out[r] = log_softmax(logits[r, :])[tokens[r]]
  * as defined above; logits [rows, V] fp32, tokens int64 [rows], out fp32 [rows].  One thread block per row.  A token outside [0, V) gives

@@ -245,7 +245,8 @@ class CoVoMixModel:
                                        prompt_mel=None, uniforms=None, generator=None, max_length=None, slots=64,
                                        filter_logits_fn="top_k", filter_fn_kwargs=None, return_logprobs=False, best_of=1,
                                        beam_size=10, length_penalty=1.0, prefix=None, best_of_temperatures=None, mixed_guidance=False,
-                                       guided_beam=False, repetition_penalty=1.0, repetition_window=0, no_repeat_ngram_size=0, min_length=0):
+                                       guided_beam=False, repetition_penalty=1.0, repetition_window=0, no_repeat_ngram_size=0, min_length=0,
+                                       beam_rules=False):
         """reference conditional_model.py:313-321 -> TextToSemanticWrapper.sample (text2semantic.py:1237-1251): the
         sampled semantic tokens as one flat int64 tensor (two-output models: stream 1 then stream 2) on the input's
         device.  (`temprature` is the reference's spelling.)  `uniforms` / `generator` (optional) fix the U(0,1) draws
@@ -282,7 +283,9 @@ class CoVoMixModel:
         history rules of the decode - a penalty on every id a stream has emitted in its last `repetition_window` tokens (0: all), no
         n-gram twice in a stream, no eos below min_length.  Scalars, or - with a list of texts - lists of the same length (per-utterance
         settings, as above).  All off by default: the call is then what it was.  Log-probs stay those of the model's unmodified rows.
-        None of these combines with beam search (ValueError)."""
+        None of these combines with beam search (ValueError) - unless beam_rules=True (default False): no_repeat_ngram_size and min_length,
+        scalars or lists as above, then run under beam search (t2s.generate_beam(beam_rules=True): candidates are removed along every
+        hypothesis' own ancestry, scores and log-probs stay the model's); a repetition_penalty other than 1 and a repetition_window other than 0 stay a ValueError."""
         if not self.is_text2semantic:
             raise TypeError("this checkpoint is an acoustic model: use synthesis_sample")
         ids = grapheme_token_ids
@@ -321,6 +324,22 @@ class CoVoMixModel:
         check_rules(None, 1, 1 << 30, **rule_kw)
         rule_kw = {k: v for k, v in rule_kw.items() if v != RULES_OFF[RULE_FIELDS.index(k)]}
         per = bool(lists) or prefix is not None or best_of_temperatures is not None
+        beam_kw = {}
+        if beam_search_decode and beam_rules:
+            # the two rules of the beam chain leave the per-utterance lists; t2s.check_beam_rules validates them and refuses a penalty
+            pens = lists.get("repetition_penalty") or [rule_kw.get("repetition_penalty", 1.0)]    # (a list of equal entries is its scalar)
+            if any(float(x) != 1.0 for x in pens):
+                raise ValueError("beam search takes no repetition_penalty (it would make the search score something other than the model's "
+                                 "log-probability): leave it at 1")
+            beam_kw = dict(beam_rules=True, no_repeat_ngram_size=lists.pop("no_repeat_ngram_size", rule_kw.get("no_repeat_ngram_size", 0)),
+                           min_length=lists.pop("min_length", rule_kw.get("min_length", 0)))
+            if any(int(x) != 0 for x in (lists.get("repetition_window") or [rule_kw.get("repetition_window", 0)])):
+                raise ValueError("beam search takes no repetition_window: it is the window of the repetition penalty, which beam search does "
+                                 "not run")
+            lists.pop("repetition_penalty", None)
+            lists.pop("repetition_window", None)       # (lists of 1s and 0s: off)
+            rule_kw = {}
+            per = bool(lists) or prefix is not None or best_of_temperatures is not None
         if beam_search_decode:
             if rule_kw or any(k in lists for k in RULE_FIELDS):
                 raise ValueError("beam search does not run the history rules (repetition_penalty, repetition_window, no_repeat_ngram_size, "
@@ -340,9 +359,9 @@ class CoVoMixModel:
                 if _dims(self.active_state_dict())["streams"] != 1:          # (from the weights: refused whatever the device)
                     raise NotImplementedError("guidance (cond_scale > 1) on a two-output model: the reference cannot run it")
                 res = self._get_t2s().generate_beam(list(ids) if many else ids, beam_size, max_length, float(length_penalty),
-                                                    cond_scale=float(cond_scale))
+                                                    cond_scale=float(cond_scale), **beam_kw)
             else:
-                res = self._get_t2s().generate_beam(list(ids) if many else ids, beam_size, max_length, float(length_penalty))
+                res = self._get_t2s().generate_beam(list(ids) if many else ids, beam_size, max_length, float(length_penalty), **beam_kw)
             pick = (lambda r, i: tuple(t.to(i.device) for t in r[:3])) if return_logprobs else (lambda r, i: r[0].to(i.device))
             return [pick(r, i) for r, i in zip(res, ids)] if many else pick(res, ids)
         if best_of_temperatures is not None:

@@ -49,6 +49,12 @@
 //                          records, the next input (one embedding row into both x rows) and the ancestry rows (text row from the parent's text
 //                          row, null row from its null row) for both halves; the queue form re-arms both halves of a refilled group.
 //                          The back-track kernels are shared: their rows are hypotheses either way.
+// BEAM SEARCH UNDER THE HISTORY RULES (cvx_t2s_beam_rules_steps: the four beam chains with no-repeat n-gram and minimum length):
+//   beam_shortlist_rules_kernel<QUEUE>, beam_shortlist_guided_rules_kernel<QUEUE>   the shortlists with the hypothesis' own history gathered
+//                          along the ancestry table into LDS (beam_history), rules_marks' ban marks over it, and the bans applied to the
+//                          log-softmax between the lp pass and the ranking (beam_shortlist<NT, RULES>);
+//   beam_merge_*_rules_kernel   beam_merge_step<QUEUE, GUIDED, RULES = true>: a banned shortlist entry (-inf) gives no candidate.
+// The same two launches per step; the kernels of the plain chains keep their instruction text.
 // ONE BODY PER STEP: the five sampling kernels instantiate sample_step, the four merge kernels beam_merge_step, the two back-track kernels
 // beam_backtrack_step.  What such sharing does to a kernel is read from the compiler (tools/kernel_text_diff.py against the parent's
 // assembly), not assumed: the default chain's kernels keep their instruction text (tests/test_t2s_code_objects.py holds their resources).
@@ -764,9 +770,10 @@ __device__ __forceinline__ Rules rules_row(const int* row, int cap)
 //   pen[t]  t occurs in h[max(0, pos - W), pos)  (W = 0: in all of h)
 //   ban[t]  t = h[e] for a position e in [n - 1, pos) whose n - 1 predecessors equal the last n - 1 tokens of h (n = 1: every id of h)
 // tid strides over the positions; an id outside [0, V) marks nothing.  The history was written by earlier launches on the stream (or by
-// the host): plain loads.  Synchronises before it returns.
-template <int NT>
-__device__ __forceinline__ void rules_marks(const int64_t* h, int pos, int V, const Rules& r, uint8_t* pen, uint8_t* ban)
+// the host): plain loads.  Synchronises before it returns.  T: int64_t - a token row in global memory (the sampled chains); int - the
+// history a beam hypothesis gathered into LDS along its ancestry (beam_history).
+template <int NT, class T = int64_t>
+__device__ __forceinline__ void rules_marks(const T* h, int pos, int V, const Rules& r, uint8_t* pen, uint8_t* ban)
 {
     const int tid = threadIdx.x;
     for (int i = tid; i < 1024; i += NT) { pen[i] = 0; ban[i] = 0; }
@@ -774,7 +781,7 @@ __device__ __forceinline__ void rules_marks(const int64_t* h, int pos, int V, co
     const int lo = r.W > 0 ? max(0, pos - r.W) : 0;
     const int n1 = r.n - 1;
     for (int e = tid; e < pos; e += NT) {
-        const int64_t t = h[e];
+        const T t = h[e];
         if (t < 0 || t >= V) continue;
         if (e >= lo) pen[t] = 1;
         if (r.n >= 1 && e >= n1) {
@@ -1194,8 +1201,12 @@ constexpr int BEAM_MAX = 16;
 // #{j: lp[j] > lp[i] or (lp[j] == lp[i] and j < i)} - a total order, so exactly K entries have a rank below K whatever the ties.
 // lp[j] = (lg[j] - m) - logf(sum) with row_logprob's m and sum: the same function of the row.  lg: the staged row (stage_row), ex: 1024
 // floats, bv: 16 floats, ls: one float of LDS; out_lp / out_tok [K]: LDS or global.  The caller synchronises before lg / ex are written again.
-template <int NT>
-__device__ __forceinline__ void beam_shortlist(const float* lg, int V, int K, float* ex, float* bv, float* ls, float* out_lp, int* out_tok)
+// RULES (cvx_t2s_beam_rules_steps): between the lp pass and the ranking the banned entries of lp become -inf - ban[i] (rules_marks) and,
+// with no_eos, entry V - 1.  When that leaves no un-banned entry (one block-uniform count) the marks of ban are void and the eos ban stays.
+// The ranking is the same total order, so a shortlist may hold entries of -inf: the merge gives them no candidate.
+template <int NT, bool RULES = false>
+__device__ __forceinline__ void beam_shortlist(const float* lg, int V, int K, float* ex, float* bv, float* ls, float* out_lp, int* out_tok,
+                                               const uint8_t* ban = nullptr, bool no_eos = false)
 {
     const int tid = threadIdx.x;
     float m;
@@ -1205,6 +1216,14 @@ __device__ __forceinline__ void beam_shortlist(const float* lg, int V, int K, fl
     const float l = *ls;
     for (int i = tid; i < 1024; i += NT) ex[i] = i < V ? (lg[i] - m) - l : -INFINITY;
     __syncthreads();
+    if constexpr (RULES) {
+        int open = 0;
+        for (int i = tid; i < V; i += NT) open |= (ban[i] || (no_eos && i == V - 1)) ? 0 : 1;
+        const bool marks = __syncthreads_or(open) != 0;        // (block-uniform) false: the n-gram bans of this step are void
+        for (int i = tid; i < V; i += NT)
+            if ((marks && ban[i]) || (no_eos && i == V - 1)) ex[i] = -INFINITY;
+        __syncthreads();
+    }
     for (int i = tid; i < V; i += NT) {
         const float me = ex[i];
         int cnt = 0;
@@ -1222,7 +1241,8 @@ __device__ __forceinline__ void beam_shortlist(const float* lg, int V, int K, fl
 // candidate q = p B B with its score unchanged; a p with score -inf has none.  Order: score descending, q ascending.  sel[r] = the r-th best
 // q, or -1 when fewer than r + 1 candidates exist.  sc / fin [B], sl_lp [B][S][BEAM_MAX]: LDS or global; bv / bi: 16 entries of LDS.
 // NT = 1024 threads hold the B^3 <= 4096 candidates four each; B rounds of a block-wide argmax.
-template <int NT>
+// RULES: a shortlist entry of -inf (banned) gives no candidate.
+template <int NT, bool RULES = false>
 __device__ __forceinline__ void beam_merge(const float* sc, const int* fin, const float* sl_lp, int B, int S, int K, float* bv, int* bi, int* sel)
 {
     static_assert(BEAM_MAX * BEAM_MAX * BEAM_MAX <= 4 * NT, "four candidates per thread");
@@ -1240,8 +1260,13 @@ __device__ __forceinline__ void beam_merge(const float* sc, const int* fin, cons
                 if (fin[p]) { if (a == 0 && b == 0) { ok |= 1u << k; cs[k] = c; } }
                 else if (a < K && (S == 2 ? b < K : b == 0)) {
                     const float l0 = sl_lp[(p * S) * BEAM_MAX + a];
-                    ok |= 1u << k;
-                    cs[k] = S == 2 ? c + (l0 + sl_lp[(p * S + 1) * BEAM_MAX + b]) : c + l0;
+                    if constexpr (RULES) {
+                        const float l1 = S == 2 ? sl_lp[(p * S + 1) * BEAM_MAX + b] : 0.f;
+                        if (l0 > -INFINITY && l1 > -INFINITY) { ok |= 1u << k; cs[k] = S == 2 ? c + (l0 + l1) : c + l0; }
+                    } else {
+                        ok |= 1u << k;
+                        cs[k] = S == 2 ? c + (l0 + sl_lp[(p * S + 1) * BEAM_MAX + b]) : c + l0;
+                    }
                 }
             }
         }
@@ -1308,7 +1333,26 @@ struct BeamSelectArgs {
     uint8_t* finished_out;
 };
 
-__global__ __launch_bounds__(1024) void beam_select_kernel(const BeamSelectArgs a)
+// what cvx_t2s_beam_select_rules_f32 adds: every hypothesis' history given outright, one rules row per group
+struct BeamSelectRulesArgs {
+    const int* history;      // [G * B][S][hist_ld]
+    const int* hist_len;     // [G * B]: pos, clamped into [0, hist_ld]
+    const int* table;        // [G][RULES_WORDS]
+    int hist_ld;
+};
+
+// The ban marks of one row of a beam hypothesis (RULES shortlists): h [pos] = its history, already in LDS.  Without an n-gram rule nothing
+// of h is read (pos 0: the marks are cleared only).  Returns whether the eos is banned at this position.
+__device__ __forceinline__ bool beam_marks(const int* h, int pos, int V, const Rules& r, uint8_t* pen, uint8_t* ban)
+{
+    Rules nb = r;
+    nb.theta = 1.f; nb.W = 0;                          // (beam search has no repetition penalty: pen is scratch)
+    rules_marks<1024, int>(h, r.n >= 1 ? pos : 0, V, nb, pen, ban);
+    return pos < r.m;
+}
+
+template <bool RULES>
+__device__ __forceinline__ void beam_select_step(const BeamSelectArgs& a, const BeamSelectRulesArgs& ra)
 {
     __shared__ __attribute__((aligned(16))) float lg[1024];
     __shared__ __attribute__((aligned(16))) float ex[1024];
@@ -1329,10 +1373,21 @@ __global__ __launch_bounds__(1024) void beam_select_kernel(const BeamSelectArgs 
         const int p = row / S;
         if (fin[p] || !(sc[p] > -INFINITY)) continue;                  // (block-uniform) no candidates from this row
         stage_row<1024>(a.logits + (base * S + row) * a.V, nullptr, 1.f, a.V, lg);
-        beam_shortlist<1024>(lg, a.V, K, ex, bv, &ls, sl_lp + row * BEAM_MAX, sl_tok + row * BEAM_MAX);
+        if constexpr (RULES) {
+            __shared__ int hrow[T2S_MAX_KEYS];
+            __shared__ uint8_t pen[1024], ban[1024];
+            const int pos = min(max(ra.hist_len[base + p], 0), ra.hist_ld);
+            const Rules r = rules_row(ra.table + RULES_WORDS * (int64_t)blockIdx.x, 0x7fffffff);
+            if (r.n >= 1)
+                for (int j = tid; j < pos; j += 1024) hrow[j] = ra.history[(base * S + row) * (int64_t)ra.hist_ld + j];     // (base: int64_t)
+            __syncthreads();
+            const bool no_eos = beam_marks(hrow, pos, a.V, r, pen, ban);
+            beam_shortlist<1024, true>(lg, a.V, K, ex, bv, &ls, sl_lp + row * BEAM_MAX, sl_tok + row * BEAM_MAX, ban, no_eos);
+        } else
+            beam_shortlist<1024>(lg, a.V, K, ex, bv, &ls, sl_lp + row * BEAM_MAX, sl_tok + row * BEAM_MAX);
         __syncthreads();
     }
-    beam_merge<1024>(sc, fin, sl_lp, B, S, K, bv, bi, sel);
+    beam_merge<1024, RULES>(sc, fin, sl_lp, B, S, K, bv, bi, sel);
     if (tid < B) {
         const BeamPick r = beam_pick(sel[tid], tid, sc, fin, sl_lp, sl_tok, B, S, a.V - 1);
         a.parents[base + tid] = r.parent;
@@ -1342,6 +1397,9 @@ __global__ __launch_bounds__(1024) void beam_select_kernel(const BeamSelectArgs 
         a.finished_out[base + tid] = (uint8_t)r.fin;
     }
 }
+
+__global__ __launch_bounds__(1024) void beam_select_kernel(const BeamSelectArgs a) { beam_select_step<false>(a, BeamSelectRulesArgs{}); }
+__global__ __launch_bounds__(1024) void beam_select_rules_kernel(const BeamSelectArgs a, const BeamSelectRulesArgs ra) { beam_select_step<true>(a, ra); }
 
 // the beam chain's selection: beam_shortlist_kernel (one block per live row) then beam_merge_kernel (one block per utterance)
 struct BeamArgs {
@@ -1413,6 +1471,72 @@ template <bool QUEUE> __device__ __forceinline__ int64_t beam_hist_index(const B
     return QUEUE ? ((int64_t)g * a.max_len + t) * a.B + i : (int64_t)t * a.batch + g * a.B + i;
 }
 
+// The shortlists under the history rules (cvx_t2s_beam_rules_steps): beam_shortlist_kernel / beam_shortlist_guided_kernel with the bans of
+// the hypothesis' OWN history between the lp pass and the ranking.  The history is not one row: it runs through the ancestry table.  At
+// position pos the hypothesis' ancestry row own = owner[pos & 1][slot] names in own[j + 1] the slot its ancestor sat in after step j - the
+// slot whose new hypothesis the merge of step j recorded in hist_tokens - so
+//   h_s[j] = hist_tokens[beam_hist_index(g, j, own[j + 1] / P - base)][s],  j in [0, pos)
+// (P slots per hypothesis: the text half's row in the guided chain), two dependent loads per position, strided over the block into LDS.
+// beam_merge_step wrote own[0..pos] (the parent's row, then the slot itself) and every named history entry in earlier launches: plain loads.
+// A re-armed group sits at position 0: an empty history.  The rules row: the group (lock-step) or its utterance (QUEUE), n and m alone.
+// hyp: the hypothesis (== the slot in the unguided chain); returns false for a row without candidates (block-uniform).
+template <bool QUEUE, int P>
+__device__ __forceinline__ bool beam_history(const BeamArgs& a, const BeamQueueArgs& qa, const RulesArgs& ru, int hyp, int s, int* hrow,
+                                             uint8_t* pen, uint8_t* ban, bool& no_eos)
+{
+    const int tid = threadIdx.x, B = a.B, S = a.streams;
+    const int slot = hyp * P;
+    const int pos = aloadi(a.state + SR * slot);
+    if (pos >= a.max_len || pos < 0) return false;                    // finished, ended or idle
+    const int u = hyp / B, base = u * B;
+    const int hg = QUEUE ? min(max(aloadi(a.groups + 4 * u + 3), 0), max(aloadi(qa.queue + 1) - 1, 0)) : u;
+    const Rules r = rules_row(ru.table + (int64_t)RULES_WORDS * min(ru.n_records - 1, hg), a.max_len);
+    if (r.n >= 1) {
+        const int* const own = a.owner + ((int64_t)(pos & 1) * a.batch * P + slot) * a.max_len;
+        const int* const hist_tok = QUEUE ? qa.hist_tok : a.hist_tok;
+        for (int j = tid; j < pos; j += 1024) {                       // (j + 1 <= pos < max_len)
+            const int i = min(max(aloadi(own + j + 1) / P - base, 0), B - 1);      // (a stray entry stays inside the group)
+            hrow[j] = hist_tok[beam_hist_index<QUEUE>(a, hg, j, i) * S + s];
+        }
+    }
+    __syncthreads();
+    no_eos = beam_marks(hrow, pos, a.V, r, pen, ban);
+    return true;
+}
+
+template <bool QUEUE>
+__global__ __launch_bounds__(1024) void beam_shortlist_rules_kernel(const BeamArgs a, const BeamQueueArgs qa, const RulesArgs ru)
+{
+    __shared__ __attribute__((aligned(16))) float lg[1024];
+    __shared__ __attribute__((aligned(16))) float ex[1024];
+    __shared__ float bv[16];
+    __shared__ float ls;
+    __shared__ int hrow[T2S_MAX_KEYS];
+    __shared__ uint8_t pen[1024], ban[1024];
+    const int row = blockIdx.x, slot = row / a.streams;
+    bool no_eos;
+    if (!beam_history<QUEUE, 1>(a, qa, ru, slot, row - slot * a.streams, hrow, pen, ban, no_eos)) return;
+    stage_row<1024>(a.logits + (int64_t)row * a.V, nullptr, 1.f, a.V, lg);
+    beam_shortlist<1024, true>(lg, a.V, min(a.B, a.V), ex, bv, &ls, a.short_lp + row * BEAM_MAX, a.short_tok + row * BEAM_MAX, ban, no_eos);
+}
+
+template <bool QUEUE>
+__global__ __launch_bounds__(1024) void beam_shortlist_guided_rules_kernel(const BeamArgs a, const BeamQueueArgs qa, const RulesArgs ru,
+                                                                          const float scale)
+{
+    __shared__ __attribute__((aligned(16))) float lg[1024];
+    __shared__ __attribute__((aligned(16))) float ex[1024];
+    __shared__ float bv[16];
+    __shared__ float ls;
+    __shared__ int hrow[T2S_MAX_KEYS];
+    __shared__ uint8_t pen[1024], ban[1024];
+    const int h = blockIdx.x;
+    bool no_eos;
+    if (!beam_history<QUEUE, 2>(a, qa, ru, h, 0, hrow, pen, ban, no_eos)) return;
+    stage_row<1024>(a.logits + (int64_t)(2 * h) * a.V, a.logits + (int64_t)(2 * h + 1) * a.V, scale, a.V, lg);
+    beam_shortlist<1024, true>(lg, a.V, min(a.B, a.V), ex, bv, &ls, a.short_lp + h * BEAM_MAX, a.short_tok + h * BEAM_MAX, ban, no_eos);
+}
+
 // One selection step of group u = blockIdx.x (1024 threads): the B best candidates, their back-pointers into the history, the scores and
 // slot records, then the next inputs and the next ancestry rows.  ONE body behind beam_merge_kernel and beam_merge_queue_kernel.  QUEUE: the
 // history is indexed by the group's utterance (group record [3]) and, when the utterance ends, the same launch writes its finals, status and
@@ -1423,7 +1547,9 @@ template <bool QUEUE> __device__ __forceinline__ int64_t beam_hist_index(const B
 // the slot records, the next input (the same embedding row) and the ancestry rows (the text row continues the parent's text row, the null
 // row the parent's null row).  A re-armed group gives the text half the utterance's context rows and kv_c row 2 * utterance, the null half one
 // context row (the learned null key / value) and kv_c row 2 * utterance + 1.
-template <bool QUEUE, bool GUIDED = false>
+// RULES (cvx_t2s_beam_rules_steps): the shortlists may hold banned entries (-inf), which give no candidate (beam_merge<.., RULES>); a new
+// slot left without one is a dead hypothesis as before.  Nothing else differs: the history the rules read is what this body records anyway.
+template <bool QUEUE, bool GUIDED = false, bool RULES = false>
 __device__ __forceinline__ void beam_merge_step(const BeamArgs& a, const BeamQueueArgs& qa)
 {
     constexpr int P = GUIDED ? 2 : 1;                   // slots per hypothesis
@@ -1449,7 +1575,7 @@ __device__ __forceinline__ void beam_merge_step(const BeamArgs& a, const BeamQue
     __syncthreads();
     const float* const sl_lp = a.short_lp + (int64_t)base * S * BEAM_MAX;
     const int* const sl_tok = a.short_tok + (int64_t)base * S * BEAM_MAX;
-    beam_merge<1024>(sc, fin, sl_lp, B, S, min(B, a.V), bv, bi, sel);
+    beam_merge<1024, RULES>(sc, fin, sl_lp, B, S, min(B, a.V), bv, bi, sel);
     BeamPick r;
     if (tid < B) {
         r = beam_pick(sel[tid], tid, sc, fin, sl_lp, sl_tok, B, S, a.V - 1);
@@ -1564,6 +1690,10 @@ __global__ __launch_bounds__(1024) void beam_merge_kernel(const BeamArgs a) { be
 __global__ __launch_bounds__(1024) void beam_merge_queue_kernel(const BeamArgs a, const BeamQueueArgs qa) { beam_merge_step<true>(a, qa); }
 __global__ __launch_bounds__(1024) void beam_merge_guided_kernel(const BeamArgs a) { beam_merge_step<false, true>(a, BeamQueueArgs{}); }
 __global__ __launch_bounds__(1024) void beam_merge_guided_queue_kernel(const BeamArgs a, const BeamQueueArgs qa) { beam_merge_step<true, true>(a, qa); }
+__global__ __launch_bounds__(1024) void beam_merge_rules_kernel(const BeamArgs a) { beam_merge_step<false, false, true>(a, BeamQueueArgs{}); }
+__global__ __launch_bounds__(1024) void beam_merge_queue_rules_kernel(const BeamArgs a, const BeamQueueArgs qa) { beam_merge_step<true, false, true>(a, qa); }
+__global__ __launch_bounds__(1024) void beam_merge_guided_rules_kernel(const BeamArgs a) { beam_merge_step<false, true, true>(a, BeamQueueArgs{}); }
+__global__ __launch_bounds__(1024) void beam_merge_guided_queue_rules_kernel(const BeamArgs a, const BeamQueueArgs qa) { beam_merge_step<true, true, true>(a, qa); }
 
 // tokens / logprobs [row][streams][max_len] from the back-pointers: one thread per row walks its ancestry.  A row is a slot of group g
 // (steps: group record [0]) or, with QUEUE, hypothesis row - g B of utterance g (steps: utterance record [4])
@@ -1744,7 +1874,8 @@ struct T2sSelect {
     } kind;
     float* logprobs;         // SAMPLE / PER / MIXED: non-NULL picks the scoring instantiation
     PerArgs per;             // PER / MIXED
-    RulesArgs rules;         // PER / MIXED: a table (cvx_t2s_decode_steps_rules) picks the kernels that apply the history rules
+    RulesArgs rules;         // PER / MIXED: a table (cvx_t2s_decode_steps_rules) picks the kernels that apply the history rules;
+                             // BEAM / BEAM_QUEUE: a table (cvx_t2s_beam_rules_steps) picks the rule-aware shortlist and merge kernels
     const cvx_t2s_beam* bm;  // BEAM / BEAM_QUEUE
     BeamQueueArgs bq;        // BEAM_QUEUE
     bool guided;             // BEAM / BEAM_QUEUE: cvx_t2s_beam_guided_steps / _queue_steps - a hypothesis is a slot pair, the shortlist reads the
@@ -1807,6 +1938,16 @@ static int t2s_decode_run(const cvx_t2s_decoder* d, int32_t n_steps, const T2sSe
         if (beam && sel.guided) {
             const BeamArgs ba = beam_args(d, sel.bm, true);
             const dim3 groups((unsigned)(ba.batch / sel.bm->beam_size));
+            if (sel.rules.table) {                      // cvx_t2s_beam_rules_steps: the same two launches
+                if (sel.kind == T2sSelect::BEAM_QUEUE) {
+                    hipLaunchKernelGGL(beam_shortlist_guided_rules_kernel<true>, dim3((unsigned)ba.batch), block, 0, st, ba, sel.bq, sel.rules, d->cfg_scale);
+                    hipLaunchKernelGGL(beam_merge_guided_queue_rules_kernel, groups, block, 0, st, ba, sel.bq);
+                } else {
+                    hipLaunchKernelGGL(beam_shortlist_guided_rules_kernel<false>, dim3((unsigned)ba.batch), block, 0, st, ba, sel.bq, sel.rules, d->cfg_scale);
+                    hipLaunchKernelGGL(beam_merge_guided_rules_kernel, groups, block, 0, st, ba);
+                }
+                continue;
+            }
             hipLaunchKernelGGL(beam_shortlist_guided_kernel, dim3((unsigned)ba.batch), block, 0, st, ba, d->cfg_scale);
             if (sel.kind == T2sSelect::BEAM_QUEUE) hipLaunchKernelGGL(beam_merge_guided_queue_kernel, groups, block, 0, st, ba, sel.bq);
             else hipLaunchKernelGGL(beam_merge_guided_kernel, groups, block, 0, st, ba);
@@ -1815,6 +1956,16 @@ static int t2s_decode_run(const cvx_t2s_decoder* d, int32_t n_steps, const T2sSe
         if (beam) {
             const BeamArgs ba = beam_args(d, sel.bm);
             const dim3 groups((unsigned)(nb / sel.bm->beam_size));
+            if (sel.rules.table) {
+                if (sel.kind == T2sSelect::BEAM_QUEUE) {
+                    hipLaunchKernelGGL(beam_shortlist_rules_kernel<true>, dim3((unsigned)(nb * d->streams)), block, 0, st, ba, sel.bq, sel.rules);
+                    hipLaunchKernelGGL(beam_merge_queue_rules_kernel, groups, block, 0, st, ba, sel.bq);
+                } else {
+                    hipLaunchKernelGGL(beam_shortlist_rules_kernel<false>, dim3((unsigned)(nb * d->streams)), block, 0, st, ba, sel.bq, sel.rules);
+                    hipLaunchKernelGGL(beam_merge_rules_kernel, groups, block, 0, st, ba);
+                }
+                continue;
+            }
             hipLaunchKernelGGL(beam_shortlist_kernel, dim3((unsigned)(nb * d->streams)), block, 0, st, ba);
             if (sel.kind == T2sSelect::BEAM_QUEUE) hipLaunchKernelGGL(beam_merge_queue_kernel, groups, block, 0, st, ba, sel.bq);
             else hipLaunchKernelGGL(beam_merge_kernel, groups, block, 0, st, ba);
@@ -1997,11 +2148,26 @@ extern "C" int cvx_t2s_rules_f32(const float* logits, const int64_t* history, co
 }
 
 // cvx_t2s_beam_steps and cvx_t2s_beam_guided_steps: the checks, the steps, the back-track (one thread per hypothesis)
-static int t2s_beam_steps(const char* who, const cvx_t2s_decoder* d, const cvx_t2s_beam* bm, int32_t n_steps, bool guided, cvx_stream_t s)
+// cvx_t2s_rules of cvx_t2s_beam_rules_steps (rules: whether the entry point takes one): a row per utterance - `rows` of them
+static int t2s_beam_rules_block(const char* who, const cvx_t2s_rules* ru, bool rules, int rows, T2sSelect& sel)
+{
+    if (!rules) return CVX_OK;
+    T2S_TRY(t2s_struct_size(who, "cvx_t2s_rules", ru));
+    CVX_REQUIRE(ru->table && ru->n_records >= 1 && ru->n_records >= rows, "%s: null rules table, or n_records = %d rows for %d utterances", who,
+                ru->n_records, rows);
+    sel.rules = RulesArgs{static_cast<const int*>(ru->table), ru->n_records};
+    return CVX_OK;
+}
+
+// (rules: the entry point is cvx_t2s_beam_rules_steps, which is guided by the descriptor's scale - read once t2s_validate has passed it)
+static int t2s_beam_steps(const char* who, const cvx_t2s_decoder* d, const cvx_t2s_beam* bm, int32_t n_steps, bool guided, cvx_stream_t s,
+                          const cvx_t2s_rules* ru = nullptr, bool rules = false)
 {
     T2sSelect sel{T2sSelect::BEAM};
     T2S_TRY(t2s_validate(d, n_steps));
+    if (rules) guided = d->cfg_scale > 1.f;
     T2S_TRY(t2s_beam_block(who, d, bm, sel, guided));
+    T2S_TRY(t2s_beam_rules_block(who, ru, rules, d->batch / ((guided ? 2 : 1) * bm->beam_size), sel));
     if (n_steps > 0) T2S_TRY(t2s_decode_run(d, n_steps, sel, s));
     if (bm->backtrack) {
         const BeamArgs ba = beam_args(d, bm, guided);
@@ -2023,15 +2189,17 @@ extern "C" int cvx_t2s_beam_guided_steps(const cvx_t2s_decoder* d, const cvx_t2s
 
 // cvx_t2s_beam_queue_steps and cvx_t2s_beam_guided_queue_steps
 static int t2s_beam_queue_steps(const char* who, const cvx_t2s_decoder* d, const cvx_t2s_beam* bm, const cvx_t2s_beam_queue* bq, int32_t n_steps,
-                                bool guided, cvx_stream_t s)
+                                bool guided, cvx_stream_t s, const cvx_t2s_rules* ru = nullptr, bool rules = false)
 {
     T2sSelect sel{T2sSelect::BEAM_QUEUE};
     T2S_TRY(t2s_validate(d, n_steps));
+    if (rules) guided = d->cfg_scale > 1.f;                    // (as in t2s_beam_steps)
     T2S_TRY(t2s_beam_block(who, d, bm, sel, guided));
     T2S_TRY(t2s_struct_size(who, "cvx_t2s_beam_queue", bq));
     CVX_REQUIRE(bq->n_utterances >= 1, "%s: n_utterances = %d", who, bq->n_utterances);
     CVX_REQUIRE(bq->queue && bq->utterances && bq->start && bq->parents && bq->hist_tokens && bq->hist_logprobs && bq->final_scores &&
                 bq->final_steps && bq->final_finished && bq->tokens && bq->logprobs, "%s: null pointer in cvx_t2s_beam_queue", who);
+    T2S_TRY(t2s_beam_rules_block(who, ru, rules, bq->n_utterances, sel));
     sel.bq = BeamQueueArgs{bq->queue, bq->utterances, bq->start, bq->parents, bq->hist_tokens, bq->hist_logprobs, bq->final_scores,
                            bq->final_steps, bq->final_finished, bq->tokens, bq->logprobs, bq->n_utterances, d->ctx_rows};
     if (n_steps > 0) T2S_TRY(t2s_decode_run(d, n_steps, sel, s));
@@ -2053,6 +2221,33 @@ extern "C" int cvx_t2s_beam_guided_queue_steps(const cvx_t2s_decoder* d, const c
                                                cvx_stream_t s)
 {
     return t2s_beam_queue_steps("t2s_beam_guided_queue_steps", d, bm, bq, n_steps, true, s);
+}
+
+// the four beam chains under the history rules: lock-step (bq == NULL) or refilled, guided when dec->cfg_scale > 1
+extern "C" int cvx_t2s_beam_rules_steps(const cvx_t2s_decoder* d, const cvx_t2s_beam* bm, const cvx_t2s_beam_queue* bq, const cvx_t2s_rules* ru,
+                                        int32_t n_steps, cvx_stream_t s)
+{
+    const char* const who = "t2s_beam_rules_steps";
+    if (bq) return t2s_beam_queue_steps(who, d, bm, bq, n_steps, false, s, ru, true);
+    return t2s_beam_steps(who, d, bm, n_steps, false, s, ru, true);
+}
+
+extern "C" int cvx_t2s_beam_select_rules_f32(const float* logits, const float* scores_in, const uint8_t* finished_in, const int32_t* history,
+                                             const int32_t* hist_len, const void* table, int32_t groups, int32_t beam_size, int32_t streams,
+                                             int32_t V, int32_t hist_ld, int32_t* parents, int64_t* tokens, float* token_lp, float* scores_out,
+                                             uint8_t* finished_out, cvx_stream_t s)
+{
+    CVX_REQUIRE(logits && scores_in && finished_in && hist_len && table && parents && tokens && token_lp && scores_out && finished_out &&
+                (history || hist_ld == 0), "t2s_beam_select_rules: null pointer");
+    CVX_REQUIRE(groups >= 0 && beam_size >= 1 && beam_size <= BEAM_MAX && (streams == 1 || streams == 2) && V >= 1 && V <= 1024 &&
+                hist_ld >= 0 && hist_ld <= T2S_MAX_KEYS,
+                "t2s_beam_select_rules: bad arguments (groups=%d beam_size=%d streams=%d V=%d hist_ld=%d)", groups, beam_size, streams, V, hist_ld);
+    if (groups == 0) return CVX_OK;
+    const BeamSelectArgs a{logits, scores_in, finished_in, beam_size, streams, V, parents, tokens, token_lp, scores_out, finished_out};
+    const BeamSelectRulesArgs ra{history, hist_len, static_cast<const int*>(table), hist_ld};
+    hipLaunchKernelGGL(beam_select_rules_kernel, dim3((unsigned)groups), dim3(1024), 0, cvx_hip_stream(s), a, ra);
+    CVX_CHECK_LAUNCH("cvx_t2s_beam_select_rules_f32");
+    return CVX_OK;
 }
 
 extern "C" int cvx_t2s_beam_select_f32(const float* logits, const float* scores_in, const uint8_t* finished_in, int32_t groups,

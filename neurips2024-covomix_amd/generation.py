@@ -111,6 +111,9 @@ def build_parser() -> ArgumentParser:
     p.add_argument("--t2s_beam_size", type=int, default=0, help="extension: beam search with this many hypotheses per turn (1..16) instead of "
                    "sampling - deterministic: no draws, temperature and filter unused; not together with --t2s_best_of > 1 or guidance "
                    "(0 = off: sampling, today's files)")
+    p.add_argument("--t2s_beam_rules", action="store_true", help="extension: lets --t2s_beam_size run under the history rules "
+                   "--t2s_no_repeat_ngram and --t2s_min_length (and those two keys of a turn's <name>.t2s.json): candidates are removed along "
+                   "every hypothesis' own history, scores stay the model's log-probabilities; --t2s_repetition_penalty stays refused")
     p.add_argument("--t2s_beam_guided", action="store_true", help="extension: lets --t2s_beam_size run under guidance (--t2s_cond_scale > 1): "
                    "every hypothesis takes a slot pair, so a wave holds half as many turns (one-output models)")
     p.add_argument("--gpus", type=int, default=1, help="extension: from a plain shell, start this many ranks (one per GPU, "
@@ -268,12 +271,15 @@ def t2s_sampling_kwargs(args) -> dict:
         kw["beam_search_decode"], kw["beam_size"] = True, beam
         if guided_beam:
             kw["guided_beam"] = True
+        if getattr(args, "t2s_beam_rules", False):
+            kw["beam_rules"] = True
     if getattr(args, "t2s_mixed_guidance", False):
         kw["mixed_guidance"] = True
     for flag, key, conv in T2S_RULE_FLAGS:
         if getattr(args, "t2s_" + flag, None) is not None:
-            if beam:
-                raise ValueError(f"--t2s_beam_size does not combine with the history rules (--t2s_{flag})")
+            if beam and not (kw.get("beam_rules") and flag in T2S_BEAM_RULE_FLAGS):
+                raise ValueError(f"--t2s_beam_size does not combine with the history rules (--t2s_{flag})" if not kw.get("beam_rules") else
+                                 f"--t2s_beam_size with --t2s_beam_rules runs --t2s_no_repeat_ngram and --t2s_min_length, not --t2s_{flag}")
             kw[key] = conv(getattr(args, "t2s_" + flag))
     return kw
 
@@ -282,6 +288,7 @@ def t2s_sampling_kwargs(args) -> dict:
 T2S_RULE_FLAGS = (("repetition_penalty", "repetition_penalty", float), ("repetition_window", "repetition_window", int),
                   ("no_repeat_ngram", "no_repeat_ngram_size", int), ("min_length", "min_length", int))
 T2S_RULE_KEYWORDS = tuple(key for _, key, _ in T2S_RULE_FLAGS)
+T2S_BEAM_RULE_FLAGS = ("no_repeat_ngram", "min_length")     # the history rules beam search runs (--t2s_beam_rules)
 
 
 def _candidate_salt(c: int) -> int:
@@ -384,7 +391,12 @@ def _predict_turns(work, t2s, device, seed: int, slots: int = 64, sampling=None,
         for w in range(0, len(todo), win):
             part = todo[w:w + win]
             if (sampling or {}).get("beam_search_decode"):          # --t2s_beam_size: no draws, lock-step waves of 64 // beam_size turns
-                toks = t2s.synthesis_sample_text2semantic([ids.to(device) for _, _, ids in part], **sampling)
+                bkw = dict(sampling)
+                if sampling.get("beam_rules"):                      # --t2s_beam_rules: the two rules per turn, side files over flags
+                    for flag, key, conv in T2S_RULE_FLAGS:
+                        if flag in T2S_BEAM_RULE_FLAGS:
+                            bkw[key] = [conv((side.get((name, k), (None, None))[0] or {}).get(flag, sampling.get(key, 0))) for name, k, _ in part]
+                toks = t2s.synthesis_sample_text2semantic([ids.to(device) for _, _, ids in part], **bkw)
                 for (name, k, _), t in zip(part, toks):
                     out[(name, k)] = t.cpu().numpy().astype(np.int64)
                 continue

@@ -875,6 +875,33 @@ def t2s_beam_select(logits: torch.Tensor, scores: torch.Tensor, finished: torch.
     return parents, tokens, lp, out_sc, out_fin
 
 
+def t2s_beam_select_rules(logits: torch.Tensor, scores: torch.Tensor, finished: torch.Tensor, beam_size: int, history: torch.Tensor,
+                          hist_len: torch.Tensor, table: torch.Tensor):
+    """t2s_beam_select under the history rules of beam search (cvx_t2s_beam_select_rules_f32; the definition: include/covomix_hip.h,
+    cvx_t2s_beam_rules_steps): history int32 [G * B, S, hist_ld] - what every hypothesis' ancestry took -, hist_len int32 [G * B], table
+    int32 [G, 4] (one rules row per group: [2] n-gram size, [3] minimum length).  Same outputs."""
+    _chk_f32(logits, scores)
+    assert logits.ndim == 3 and logits.is_contiguous() and scores.is_contiguous()
+    rows, S, V = logits.shape
+    B = int(beam_size)
+    assert B >= 1 and rows % B == 0 and scores.shape == (rows,) and finished.shape == (rows,) and finished.is_cuda
+    assert history.dtype == torch.int32 and history.ndim == 3 and history.shape[:2] == (rows, S) and history.is_contiguous() and history.is_cuda
+    assert hist_len.dtype == torch.int32 and hist_len.shape == (rows,) and hist_len.is_contiguous() and hist_len.is_cuda
+    assert table.dtype == torch.int32 and table.shape == (rows // B, _lib.T2S_RULES_WORDS) and table.is_contiguous() and table.is_cuda
+    fin = finished.to(torch.uint8).contiguous()
+    dev = logits.device
+    parents = torch.empty(rows, dtype=torch.int32, device=dev)
+    tokens = torch.empty(rows, S, dtype=torch.int64, device=dev)
+    lp = torch.empty(rows, S, dtype=torch.float32, device=dev)
+    out_sc = torch.empty(rows, dtype=torch.float32, device=dev)
+    out_fin = torch.empty(rows, dtype=torch.uint8, device=dev)
+    _lib.check(_lib.load().cvx_t2s_beam_select_rules_f32(logits.data_ptr(), scores.data_ptr(), fin.data_ptr(), history.data_ptr(),
+                                                         hist_len.data_ptr(), table.data_ptr(), rows // B, B, S, V, history.shape[2],
+                                                         parents.data_ptr(), tokens.data_ptr(), lp.data_ptr(), out_sc.data_ptr(),
+                                                         out_fin.data_ptr(), _stream()), "cvx_t2s_beam_select_rules_f32")
+    return parents, tokens, lp, out_sc, out_fin
+
+
 def dwconv31_gelu_res(x: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, out: torch.Tensor,
                       Bt: int, T: int, ragged: Optional[Ragged] = None) -> torch.Tensor:
     _chk_f32(x, w, bias, out)

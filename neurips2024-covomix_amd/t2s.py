@@ -10,7 +10,8 @@ any number of utterances through continuously refilled groups of beam_size slots
 decoding, no padded text batches.  Beside the tokens: the log-probability of every sampled token (return_logprobs), teacher-forced scoring of given tokens
 through the same decode slots (score_many) and the mean token log-probability best-of-N selects by (sequence_logprob).  And what looks at
 the tokens an utterance has ALREADY emitted: the history rules - repetition penalty, no-repeat n-gram, minimum length (check_rules;
-cvx_t2s_decode_steps_rules) - per utterance and per output stream, in every sampled schedule; off by default.
+cvx_t2s_decode_steps_rules) - per utterance and per output stream, in every sampled schedule; off by default.  Under beam search
+(beam_rules=True: check_beam_rules; cvx_t2s_beam_rules_steps) the last two remove candidates along every hypothesis' own ancestry.
 
   encoder  (source transformer, once per utterance): the full-sequence kernels of the acoustic path - fp32 GEMM with
            the RoPE epilogue, flash attention, RMSNorm - plus a GEGLU kernel;
@@ -345,6 +346,31 @@ def rules_rows(resolved) -> torch.Tensor:
     for c in (1, 2, 3):
         rows[:, c] = torch.tensor([int(r[c]) for r in resolved], dtype=torch.int32)
     return rows
+
+
+def check_beam_rules(n: int, max_length: int, repetition_penalty=1.0, repetition_window=0, no_repeat_ngram_size=0, min_length=0) -> list:
+    """The history rules of n utterances of a beam search under `beam_rules` (the definition: include/covomix_hip.h,
+    cvx_t2s_beam_rules_steps): no_repeat_ngram_size and min_length, each a scalar or one value per utterance, validated by `check_rules`
+    -> n tuples (1.0, 0, ngram, min_len) for `rules_rows`.  ValueError: what check_rules refuses, a list of another length than n, and a
+    repetition penalty other than 1 - it would make the search score something other than the model's log-probability - or a repetition
+    window other than 0, the window of a penalty there is none of.  Pure host code."""
+    per = {}
+    for name, v in (("no_repeat_ngram_size", no_repeat_ngram_size), ("min_length", min_length)):
+        if isinstance(v, (list, tuple)) or torch.is_tensor(v):
+            vals = v.tolist() if torch.is_tensor(v) else list(v)
+            if len(vals) != n:
+                raise ValueError(f"beam search: {len(vals)} values of {name} for {n} utterances")
+            per[name] = vals
+    scalar = lambda name, v: 0 if name in per else v
+    settings = [{k: vals[j] for k, vals in per.items()} for j in range(n)] if per else None
+    resolved = check_rules(settings, n, max_length, repetition_penalty, repetition_window, scalar("no_repeat_ngram_size", no_repeat_ngram_size),
+                           scalar("min_length", min_length))
+    if any(r[0] != 1.0 for r in resolved):
+        raise ValueError("beam search takes no repetition_penalty: a penalty would make the search score something other than the model's "
+                         "log-probability - leave it at 1 (no_repeat_ngram_size and min_length run under beam_rules)")
+    if any(r[1] != 0 for r in resolved):
+        raise ValueError("beam search takes no repetition_window: it is the window of the repetition penalty, which beam search does not run")
+    return [(1.0, 0, r[2], r[3]) for r in resolved]
 
 
 def mixed_records(kinds) -> list:
@@ -1262,11 +1288,11 @@ class TextToSemanticDecoder:
         return max(0, min(int(max_length or self.max_length), self.max_length))
 
     def _beam_rules(self, max_length, *rule_scalars) -> None:
-        """Beam search takes no history rules yet: a hypothesis' history runs through the ancestry table, not through one token row, and
-        blocking along it is a later change.  The scalars are validated (`check_rules`), and any rule switched on is a ValueError."""
+        """A beam search WITHOUT the `beam_rules` switch takes no history rules: the scalars are validated (`check_rules`), and any rule
+        switched on is a ValueError.  (With the switch: `check_beam_rules`, cvx_t2s_beam_rules_steps.)"""
         if rules_active(check_rules(None, 1, self._rule_bound(max_length), *rule_scalars)):
             raise ValueError("beam search does not run the history rules (repetition_penalty, no_repeat_ngram_size, min_length): a hypothesis' "
-                             "history lives in the ancestry table - sample instead, or leave them off")
+                             "history lives in the ancestry table - pass beam_rules=True (no_repeat_ngram_size, min_length), sample instead, or leave them off")
 
     def _ensure_beam(self) -> dict:
         """Device state of the beam chain (cvx_t2s_beam), for the decode buffers' current slot capacity: allocated on first use, and again
@@ -1278,17 +1304,23 @@ class TextToSemanticDecoder:
         f32 = lambda *s: torch.zeros(*s, dtype=torch.float32, device=dev)
         self._beam = dict(gen=self._gen, scores=f32(n), finished=torch.zeros(n, dtype=torch.uint8, device=dev), owner=i32(2 * n * L),
                           groups=i32(n, 4), parents=i32(L * n), hist_tokens=i32(L * n * S), hist_logprobs=f32(L * n * S),
-                          short_lp=f32(n * S * BEAM_MAX), short_tokens=i32(n * S * BEAM_MAX), logprobs=f32(n, S, L))
+                          short_lp=f32(n * S * BEAM_MAX), short_tokens=i32(n * S * BEAM_MAX), logprobs=f32(n, S, L),
+                          rules=i32(n, _lib.T2S_RULES_WORDS))     # (cvx_t2s_beam_rules_steps, lock-step: a row per group)
         return self._beam
 
-    def _launch_beam(self, batch: int, beam_size: int, n: int, backtrack: bool = False, scale: float = 1.0) -> None:
+    def _launch_beam(self, batch: int, beam_size: int, n: int, backtrack: bool = False, scale: float = 1.0, ruled: bool = False) -> None:
         """n steps of the beam chain (cvx_t2s_beam_steps) on the current stream; backtrack: then tokens / log-probs from the back-pointers.
-        scale > 1: the guided chain (cvx_t2s_beam_guided_steps) - `batch` slots are batch / 2 hypotheses."""
+        scale > 1: the guided chain (cvx_t2s_beam_guided_steps) - `batch` slots are batch / 2 hypotheses.  ruled: either chain under the
+        rules table of the beam state, a row per group (cvx_t2s_beam_rules_steps)."""
         bm = self._ensure_beam()
         dec = self._descriptor(1.0, batch, scale)
         bs = _lib.T2SBeam(C.sizeof(_lib.T2SBeam), beam_size, self.max_length, 1 if backtrack else 0,
                           *[bm[k].data_ptr() for k in ("scores", "finished", "owner", "groups", "parents", "hist_tokens", "hist_logprobs",
                                                       "short_lp", "short_tokens", "logprobs")])
+        if ruled:
+            ru = _lib.T2SRules(C.sizeof(_lib.T2SRules), bm["rules"].shape[0], bm["rules"].data_ptr())
+            _lib.check(_lib.load().cvx_t2s_beam_rules_steps(C.byref(dec), C.byref(bs), None, C.byref(ru), n, ops._stream()), "cvx_t2s_beam_rules_steps")
+            return
         if scale > 1.0:
             _lib.check(_lib.load().cvx_t2s_beam_guided_steps(C.byref(dec), C.byref(bs), n, ops._stream()), "cvx_t2s_beam_guided_steps")
             return
@@ -1301,13 +1333,16 @@ class TextToSemanticDecoder:
         g[:, 1] = 1
         self._ensure_beam()["groups"].copy_(g)
 
-    def _beam_graph(self, batch: int, beam_size: int, scale: float = 1.0):
+    def _beam_graph(self, batch: int, beam_size: int, scale: float = 1.0, ruled: bool = False):
         """The captured graph of CHUNK beam steps for this (batch, beam size, stream CU count), through `_capture` as `_graph`'s, under a key of its own shape.
-        The guided chain (scale > 1) has graphs of its own kind, "beamg", whose key carries the scale (a kernel argument)."""
+        The guided chain (scale > 1) has graphs of its own kind, "beamg", whose key carries the scale (a kernel argument).  ruled: the key
+        gains a "rules" marker, not the values - the table is device memory, so one graph serves every mix of rules."""
         self._ensure_beam()
         key = ("beamg", beam_size, batch, float(scale), ops.stream_cus(), self._gen) if scale > 1.0 else \
             ("beam", beam_size, batch, ops.stream_cus(), self._gen)
-        return self._capture(key, lambda: self._launch_beam(batch, beam_size, CHUNK, scale=scale), self._beam_idle)
+        if ruled:
+            key += ("rules",)
+        return self._capture(key, lambda: self._launch_beam(batch, beam_size, CHUNK, scale=scale, ruled=ruled), self._beam_idle)
 
     def _beam_slot_records(self, ctx, B: int, nb: int, guided: bool) -> torch.Tensor:
         """slot records [slots, SR] (CPU) of nb beam slots at position 0, the others idle (`_slot_records`); ctx: context rows per dialogue
@@ -1334,11 +1369,12 @@ class TextToSemanticDecoder:
                 self.last_beam[-1].update(status=status[u][0], group=status[u][1])
         return out
 
-    def _beam_wave(self, sources, B: int, max_len: int, length_penalty: float, scale: float = 1.0) -> list:
+    def _beam_wave(self, sources, B: int, max_len: int, length_penalty: float, scale: float = 1.0, rules=None) -> list:
         """One lock-step wave: utterance u in slots [u B, (u + 1) B).  -> per utterance the list of its B hypotheses, best first.
         scale > 1 (guided): hypothesis h is the slot pair (2h, 2h + 1) - text context / null context - and utterance u owns the kv_c rows
         2u (its context) and 2u + 1 (the null key / value alone), as in a guided generate_batch; everything kept per hypothesis (scores, history,
-        back-tracked rows) has nh = n B rows, everything per slot nb = 2 nh."""
+        back-tracked rows) has nh = n B rows, everything per slot nb = 2 nh.
+        rules: None, or the n tuples of `check_beam_rules` - the wave runs under them (cvx_t2s_beam_rules_steps), utterance u by row u."""
         d = self.d
         S, n = d["streams"], len(sources)
         guided = scale > 1.0
@@ -1346,7 +1382,11 @@ class TextToSemanticDecoder:
         nb = 2 * nh if guided else nh
         self._ensure(nb, nb, 0)
         bm = self._ensure_beam()
-        graph = self._beam_graph(nb, B, scale) if os.environ.get("CVX_GRAPH", "1") == "1" else None
+        ruled = rules is not None
+        graph = self._beam_graph(nb, B, scale, ruled) if os.environ.get("CVX_GRAPH", "1") == "1" else None
+        if ruled:
+            bm["rules"].zero_()
+            bm["rules"][:n].copy_(ops.h2d(rules_rows(rules), self.device))
         ctx = self._guided_contexts(sources) if guided else self._contexts(sources)
         self.buf["state"].copy_(self._beam_slot_records(ctx, B, nb, guided))
         self.buf["x"][:nb].copy_(self.start[None, :].expand(nb, -1))
@@ -1359,7 +1399,7 @@ class TextToSemanticDecoder:
         g[:, 1] = 1
         g[:n, 1], g[:n, 2] = 0, max_len
         bm["groups"].copy_(g)
-        self._chunks(graph.replay if graph is not None else lambda: self._launch_beam(nb, B, CHUNK, scale=scale), self.buf["state"], nb,
+        self._chunks(graph.replay if graph is not None else lambda: self._launch_beam(nb, B, CHUNK, scale=scale, ruled=ruled), self.buf["state"], nb,
                      lambda st: all(r[1] for r in st), (max_len + CHUNK - 1) // CHUNK)
         self._launch_beam(nb, B, 0, backtrack=True, scale=scale)
         st = self._read_state(nb)[::2 if guided else 1]    # (per hypothesis: the text half's record)
@@ -1373,7 +1413,7 @@ class TextToSemanticDecoder:
     @torch.no_grad()
     def generate_beam(self, sources, beam_size: int = 10, max_length: Optional[int] = None, length_penalty: float = 1.0,
                       return_beams: bool = False, cond_scale: float = 1.0, repetition_penalty: float = 1.0, repetition_window: int = 0,
-                      no_repeat_ngram_size: int = 0, min_length: int = 0):
+                      no_repeat_ngram_size=0, min_length=0, beam_rules: bool = False):
         """Beam search (the algorithm: include/covomix_hip.h, cvx_t2s_beam_steps): deterministic, no draws - temperature, logit filter and
         uniforms play no part.  Every step keeps the beam_size hypotheses with the largest cumulative log-probability (fp32); a hypothesis
         that takes an eos in any stream is finished and competes with its score unchanged; the utterance ends when all are finished or after
@@ -1391,19 +1431,28 @@ class TextToSemanticDecoder:
         slot pair (text context, null context), the search ranks by the log-softmax of null + (cond - null) * cond_scale, and logprobs
         equal, bit for bit, score_many(..., cond_scale=cond_scale); waves hold MAX_BATCH // (2 * beam_size) utterances.  Return values and
         `last_beam` have the same shape.  ValueError for cond_scale < 1, NotImplementedError for a two-output model.
-        The history rules (generate_batch) do not run under beam search: any of them switched on is a ValueError (`_beam_rules`)."""
-        self._beam_rules(max_length, repetition_penalty, repetition_window, no_repeat_ngram_size, min_length)
-        B = check_beam_size(beam_size)
-        scale = self._beam_scale(cond_scale)
+        Without beam_rules the history rules (generate_batch) do not run under beam search: any of them switched on is a ValueError
+        (`_beam_rules`).  beam_rules=True: no_repeat_ngram_size and min_length - each a scalar or one value per utterance
+        (`check_beam_rules`) - remove candidates along every hypothesis' own ancestry (cvx_t2s_beam_rules_steps: the bans act on the
+        log-softmax, so scores and logprobs stay the model's and still equal score_many bit for bit); with both off for everyone the plain
+        chain runs.  A repetition_penalty other than 1 stays a ValueError."""
         one = torch.is_tensor(sources)
         srcs = [sources] if one else list(sources)
+        rules = None
+        if beam_rules:
+            rules = check_beam_rules(len(srcs), self._rule_bound(max_length), repetition_penalty, repetition_window, no_repeat_ngram_size, min_length)
+            rules = rules if rules_active(rules) else None
+        else:
+            self._beam_rules(max_length, repetition_penalty, repetition_window, no_repeat_ngram_size, min_length)
+        B = check_beam_size(beam_size)
+        scale = self._beam_scale(cond_scale)
         max_len = min(int(max_length or self.max_length), self.max_length)
         if max_len < 1:
             raise ValueError("generate_beam needs at least one step")
         self.last_beam = []
         per, out = MAX_BATCH // (2 * B if scale > 1.0 else B), []
         for w in range(0, len(srcs), per):
-            out += self._beam_wave(srcs[w:w + per], B, max_len, float(length_penalty), scale)
+            out += self._beam_wave(srcs[w:w + per], B, max_len, float(length_penalty), scale, rules[w:w + per] if rules else None)
         res = out if return_beams else [h[0] for h in out]
         return res[0] if one else res
 
@@ -1424,13 +1473,16 @@ class TextToSemanticDecoder:
                            hist_logprobs=f32(R * L * S), final_scores=f32(R), final_steps=i32(R),
                            final_finished=torch.zeros(R, dtype=torch.uint8, device=dev),
                            tokens=torch.zeros(R, S, L, dtype=torch.int64, device=dev), logprobs=f32(R, S, L),
+                           rules=i32(R, _lib.T2S_RULES_WORDS),   # (cvx_t2s_beam_rules_steps, queue form: a row per utterance)
                            owner=torch.arange(n, dtype=torch.int32, device=dev)[None, :, None].expand(2, -1, L).contiguous(),
                            slot_ids=torch.arange(n, dtype=torch.int32, device=dev))
         return self._beamq
 
-    def _launch_beam_queue(self, batch: int, beam_size: int, n_utt: int, n: int, backtrack: bool = False, scale: float = 1.0) -> None:
+    def _launch_beam_queue(self, batch: int, beam_size: int, n_utt: int, n: int, backtrack: bool = False, scale: float = 1.0,
+                           ruled: bool = False) -> None:
         """n steps of the refilled beam chain (cvx_t2s_beam_queue_steps) on the current stream; backtrack: then tokens / log-probs of every
-        (utterance, hypothesis) from the per-utterance back-pointers.  scale > 1: cvx_t2s_beam_guided_queue_steps."""
+        (utterance, hypothesis) from the per-utterance back-pointers.  scale > 1: cvx_t2s_beam_guided_queue_steps.  ruled: either under
+        the rules table of the queue state, a row per utterance (cvx_t2s_beam_rules_steps)."""
         bm, bq = self._ensure_beam(), self._beamq
         dec = self._descriptor(1.0, batch, scale)
         bs = _lib.T2SBeam(C.sizeof(_lib.T2SBeam), beam_size, self.max_length, 1 if backtrack else 0, bm["scores"].data_ptr(),
@@ -1439,20 +1491,27 @@ class TextToSemanticDecoder:
         qs = _lib.T2SBeamQueue(C.sizeof(_lib.T2SBeamQueue), n_utt, bq["queue"].data_ptr(), bq["utterances"].data_ptr(), self.start.data_ptr(),
                                *[bq[k].data_ptr() for k in ("parents", "hist_tokens", "hist_logprobs", "final_scores", "final_steps",
                                                            "final_finished", "tokens", "logprobs")])
+        if ruled:
+            ru = _lib.T2SRules(C.sizeof(_lib.T2SRules), bq["rules"].shape[0], bq["rules"].data_ptr())
+            _lib.check(_lib.load().cvx_t2s_beam_rules_steps(C.byref(dec), C.byref(bs), C.byref(qs), C.byref(ru), n, ops._stream()),
+                       "cvx_t2s_beam_rules_steps")
+            return
         if scale > 1.0:
             _lib.check(_lib.load().cvx_t2s_beam_guided_queue_steps(C.byref(dec), C.byref(bs), C.byref(qs), n, ops._stream()),
                        "cvx_t2s_beam_guided_queue_steps")
             return
         _lib.check(_lib.load().cvx_t2s_beam_queue_steps(C.byref(dec), C.byref(bs), C.byref(qs), n, ops._stream()), "cvx_t2s_beam_queue_steps")
 
-    def _beam_queue_graph(self, batch: int, beam_size: int, scale: float = 1.0):
+    def _beam_queue_graph(self, batch: int, beam_size: int, scale: float = 1.0, ruled: bool = False):
         """The captured graph of CHUNK steps of the refilled beam chain (`_capture`).  (The number of utterances sizes the
         back-track launch only, which is not part of the graph: the steps read the device-side queue.)  Guided: kind "beamqg", with the scale."""
         key = ("beamqg", beam_size, batch, float(scale), ops.stream_cus(), self._gen) if scale > 1.0 else \
             ("beamq", beam_size, batch, ops.stream_cus(), self._gen)
-        return self._capture(key, lambda: self._launch_beam_queue(batch, beam_size, 1, CHUNK, scale=scale), self._beam_idle)
+        if ruled:                                          # (a marker, not the values: one graph serves every mix)
+            key += ("rules",)
+        return self._capture(key, lambda: self._launch_beam_queue(batch, beam_size, 1, CHUNK, scale=scale, ruled=ruled), self._beam_idle)
 
-    def _beam_queue_window(self, sources, B: int, lim: list, length_penalty: float, slots: int, scale: float = 1.0) -> list:
+    def _beam_queue_window(self, sources, B: int, lim: list, length_penalty: float, slots: int, scale: float = 1.0, rules=None) -> list:
         """One window of generate_beam_many: its utterances' contexts resident, the groups refilled on the device until all have ended.
         scale > 1 (guided): a group is 2 B slots - the pairs of _beam_wave - and utterance j owns the kv_c rows 2j and 2j + 1."""
         d = self.d
@@ -1463,7 +1522,11 @@ class TextToSemanticDecoder:
         nb = G * B * P                                     # (the buffers hold whole 8-slot kernel groups: _ensure)
         self._ensure(nb, n * P, 0)
         bm, bq = self._ensure_beam(), self._ensure_beam_queue(max(n * B, WINDOW))
-        graph = self._beam_queue_graph(nb, B, scale) if os.environ.get("CVX_GRAPH", "1") == "1" else None
+        ruled = rules is not None                          # (the n tuples of check_beam_rules: utterance j by row j)
+        graph = self._beam_queue_graph(nb, B, scale, ruled) if os.environ.get("CVX_GRAPH", "1") == "1" else None
+        if ruled:
+            bq["rules"].zero_()
+            bq["rules"][:n].copy_(ops.h2d(rules_rows(rules), self.device))
         ctx = self._guided_contexts(sources) if guided else self._contexts(sources)
         self.buf["state"].copy_(self._beam_slot_records(ctx, B, nb, guided))
         self.buf["x"][:nb].copy_(self.start[None, :].expand(nb, -1))
@@ -1482,7 +1545,7 @@ class TextToSemanticDecoder:
         bq["queue"].copy_(torch.tensor([G, n], dtype=torch.int32))
         done = lambda r: all(row[3] >= 2 for row in r)
         cap = (sum(lim) + CHUNK - 1) // CHUNK + 4          # (one group decoding everything: cannot be reached)
-        i, rec = self._chunks(graph.replay if graph is not None else lambda: self._launch_beam_queue(nb, B, n, CHUNK, scale=scale), bq["utterances"], n, done, cap)
+        i, rec = self._chunks(graph.replay if graph is not None else lambda: self._launch_beam_queue(nb, B, n, CHUNK, scale=scale, ruled=ruled), bq["utterances"], n, done, cap)
         if not done(rec):
             raise RuntimeError(f"text2semantic refilled beam decode: {sum(1 for row in rec if row[3] < 2)} of {n} utterances did not finish in {i} chunks")
         self._launch_beam_queue(nb, B, n, 0, backtrack=True, scale=scale)
@@ -1495,7 +1558,7 @@ class TextToSemanticDecoder:
     @torch.no_grad()
     def generate_beam_many(self, sources, beam_size: int = 10, max_length: Optional[int] = None, length_penalty: float = 1.0,
                            return_beams: bool = False, slots: int = 64, limits=None, cond_scale: float = 1.0, repetition_penalty: float = 1.0,
-                           repetition_window: int = 0, no_repeat_ngram_size: int = 0, min_length: int = 0):
+                           repetition_window: int = 0, no_repeat_ngram_size=0, min_length=0, beam_rules: bool = False):
         """generate_beam for ANY number of utterances through continuously refilled slot GROUPS (cvx_t2s_beam_queue_steps): slots // beam_size
         groups (at most MAX_BATCH // beam_size) of beam_size neighbouring slots; a group whose utterance has ended - all hypotheses finished,
         or its step limit - takes the next pending utterance inside the selection kernel of that very step, as generate_many's slots do.
@@ -1506,13 +1569,21 @@ class TextToSemanticDecoder:
         cond_scale > 1 (one-output models): the guided search of generate_beam(cond_scale=...) through slots // (2 * beam_size) groups of
         slot pairs (cvx_t2s_beam_guided_queue_steps); every utterance again equals generate_beam(cond_scale=...) alone, bit for bit.
         ValueError (before any device work): beam_size outside 1..16, slots that hold no group (slots < beam_size, or < 2 * beam_size under
-        guidance), cond_scale < 1, limits of another length than sources, any history rule switched on (`_beam_rules`).
-        NotImplementedError: guidance on a two-output model."""
-        self._beam_rules(max_length, repetition_penalty, repetition_window, no_repeat_ngram_size, min_length)
-        B = check_beam_size(beam_size)
-        scale = self._beam_scale(cond_scale)
+        guidance), cond_scale < 1, limits of another length than sources, any history rule switched on without beam_rules (`_beam_rules`).
+        NotImplementedError: guidance on a two-output model.
+        beam_rules=True: no_repeat_ngram_size / min_length as in generate_beam, a scalar or one value per utterance; an utterance's history
+        is its own ancestry, so a refilled group is not affected by its predecessor, and every utterance equals generate_beam alone with its
+        own values, bit for bit."""
         srcs = list(sources)
         n = len(srcs)
+        rules = None
+        if beam_rules:
+            rules = check_beam_rules(n, self._rule_bound(max_length), repetition_penalty, repetition_window, no_repeat_ngram_size, min_length)
+            rules = rules if rules_active(rules) else None
+        else:
+            self._beam_rules(max_length, repetition_penalty, repetition_window, no_repeat_ngram_size, min_length)
+        B = check_beam_size(beam_size)
+        scale = self._beam_scale(cond_scale)
         if int(slots) < (2 * B if scale > 1.0 else B):
             raise ValueError(f"generate_beam_many: slots = {slots} hold no {'guided ' if scale > 1.0 else ''}group of beam_size = {B}")
         if limits is not None and len(limits) != n:
@@ -1524,7 +1595,8 @@ class TextToSemanticDecoder:
         self.last_beam = []
         out, win = [], max(1, WINDOW // B)
         for w in range(0, n, win):
-            out += self._beam_queue_window(srcs[w:w + win], B, lim[w:w + win], float(length_penalty), int(slots), scale)
+            out += self._beam_queue_window(srcs[w:w + win], B, lim[w:w + win], float(length_penalty), int(slots), scale,
+                                           rules[w:w + win] if rules else None)
         return out if return_beams else [h[0] for h in out]
 
     def score_many(self, sources, targets, cond_scale=1.0, slots: int = 64, mixed_guidance: bool = False):

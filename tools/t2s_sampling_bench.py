@@ -22,6 +22,13 @@
       128 utterances that end at different steps (limits 100 ... 608: the set of config5.decode_ragged) for CoMix and CoSingle:
       generate_beam_many (continuously refilled groups) against generate_beam in lock-step waves of 64 // beam_size utterances, each wave
       as long as its longest utterance; in turns, five rounds, utterances per second.
+  python tools/t2s_sampling_bench.py beamrules [--beam-size 10] [--root OTHER_CHECKOUT]
+      beam search under the history rules (generate_beam(beam_rules=True): no 3-gram twice, minimum length 40, every utterance) against
+      the plain beam chain, 60 slots: CoMix and CoSingle with 6 utterances, CoSingle under guidance (cond_scale 1.5) with 3.  The eos
+      embedding row is zeroed (no hypothesis finishes: every call runs all its steps).  us per step over positions 256 .. 512 - the
+      histories the rule kernels gather - = (wall time of 512 steps - wall time of 256 steps) / 256, sides alternating, five rounds, with the
+      effective shader clock.  A checkout without beam_rules (--root, the parent commit) times the plain chain alone: run fresh
+      processes of both in turns.
 """
 import argparse
 import json
@@ -32,7 +39,7 @@ import time
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("what", choices=["steps", "guided", "score", "bestof", "beam", "beamq"])
+    ap.add_argument("what", choices=["steps", "guided", "score", "bestof", "beam", "beamq", "beamrules"])
     ap.add_argument("--logprobs", action="store_true")
     ap.add_argument("--root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     ap.add_argument("--top-p", type=float, default=None)
@@ -83,6 +90,38 @@ def main():
                 done = min(r["steps"] for r in m.last_beam)               # (an utterance whose hypotheses all finish ends early)
                 print(json.dumps({"tag": args.tag, "model": name, "beam_size": B, "utterances": n, "slots": n * B, "steps": args.steps,
                                   "steps_of_the_shortest": done, "us_per_step": round(t / args.steps * 1e6, 1)}), flush=True)
+    elif args.what == "beamrules":
+        import inspect
+        import statistics
+        from covomix_amd import ops
+        B = args.beam_size
+        ruled = "beam_rules" in inspect.signature(TextToSemanticDecoder.generate_beam).parameters
+        for name, scale, n in (("comix", 1.0, 60 // B), ("cosingle", 1.0, 60 // B), ("cosingle", 1.5, 60 // (2 * B))):
+            sd = {k: torch.from_numpy(v) for k, v in syn.t2s_state_dict(syn.t2s_param_shapes(**shapes[name]), seed=0).items()}
+            sd["semantic_token_emb.weight"][-1] = 0.0         # the eos logit is 0 at every step, far below the shortlists
+            m = TextToSemanticDecoder(sd, dev, max_length=512)
+            srcs = [torch.randint(1, 30000, (1, 64), generator=g) for _ in range(n)]
+            sides = [("plain", {})] + ([("rules", dict(beam_rules=True, no_repeat_ngram_size=3, min_length=40))] if ruled else [])
+            run = lambda kw, steps: m.generate_beam(srcs, beam_size=B, max_length=steps, cond_scale=scale, **kw)
+            for _, kw in sides:
+                run(kw, 64)                                   # graph + buffers of the timed shape (min_length 40 fits)
+            t = {k: [] for k, _ in sides}
+            c0 = ops.clock_stamps()
+            for r in range(5):
+                for k, kw in (sides if r % 2 == 0 else sides[::-1]):
+                    t256 = timed(lambda: run(kw, 256))
+                    t512 = timed(lambda: run(kw, 512))
+                    assert all(rec["steps"] == 512 for rec in m.last_beam), "a search ended early"
+                    t[k].append((t512 - t256) / 256 * 1e6)
+            clk = ops.clock_from_stamps(c0, ops.clock_stamps())
+            out = {"tag": args.tag, "model": name, "cond_scale": scale, "beam_size": B, "utterances": n, "slots": n * B * (2 if scale > 1 else 1),
+                   "positions": "256..512", "clock_mhz": round(clk["mhz"]) if clk else None}
+            for k, _ in sides:
+                out[k + "_us_per_step"] = [round(x, 1) for x in t[k]]
+                out[k + "_median"] = round(statistics.median(t[k]), 1)
+            if ruled:
+                out["rules_minus_plain"] = round(out["rules_median"] - out["plain_median"], 1)
+            print(json.dumps(out), flush=True)
     elif args.what == "beamq":
         B, n, tokens = args.beam_size, 128, 608
         per = 64 // B
