@@ -1096,6 +1096,51 @@ int cvx_t2s_beam_select_rules_f32(const float* logits, const float* scores_in, c
  * its row a NaN.  CVX_EINVAL (nothing is launched) for V < 1, V > 1024, rows < 0 or a NULL pointer. */
 int cvx_t2s_logprob_f32(const float* logits, const int64_t* tokens, int64_t rows, int32_t V, float* out, cvx_stream_t stream);
 
+/* PREFILL: the attention of one causal full-sequence pass of the target transformer over tokens that are already known (a forced
+ * dialogue, a forced prefix) - csrc/t2s_prefill.hip.  Still ABI 113: symbols and a struct added.
+ * The pass (neurips2024-covomix_amd/t2s.py, _prefill): a packed batch of n sequences; sequence i has L_i input rows at positions
+ * 0 .. L_i - 1 (row 0 = start_token, row p > 0 = the embeddings of its tokens at p - 1, stream after stream) and runs the decoder
+ * layers in the order of cvx_t2s_decode_steps on all rows at once: the row-local parts on the full-sequence kernels (fp32 GEMM with the
+ * half-split RoPE epilogue at the row's position, RMSNorm, GEGLU), the two attentions through this entry.  Logits row p is the pre-filter
+ * row of decode step p; the rows are fp32-class, not bit-identical to the step chain (a GEMM and a GEMV round differently).
+ * One call, both modes.  Query row r of sequence i (cu[i] <= r < cu[i + 1]), at index p = r - cu[i], head h:
+ *     out[r][h] = softmax_j(scale * q[r][h] . K[kbase[i] + j][h]) . V[kbase[i] + j][h]     over j < (causal ? p + 1 : nk[i])
+ *   q   [rows][ldq], k / v [*][ldkv] (one shared row stride), out [rows][heads * 64], all fp32, heads of 64 columns side by side;
+ *   cu int32 [n + 1] (cu[0] = 0, cu[n] = rows), kbase int32 [n] (first key row of sequence i), nk int32 [n] (its key count, >= 1;
+ *   not read - may be NULL - when causal), all on the device; max_q = the largest cu[i + 1] - cu[i] (the host's copy: it sizes the grid).
+ *   Self-attention of the pass: the packed q | k | v buffer itself - k = qkv + inner, v = qkv + 2 inner, ldq = ldkv = 3 inner,
+ *   kbase = cu, causal = 1.  Cross-attention: the decode's kv_c records directly - v = k + inner, ldkv = 2 inner,
+ *   kbase[i] = record * ctx_rows, nk[i] = context rows (row 0 is the null key / value), causal = 0; no RoPE, no mask but the count.
+ * Flash-style online softmax in the exp2 domain; nothing rows x keys reaches memory.  A key is SELECTED by its index, not masked by
+ * adding a large number: key rows at or past a sequence's count (causal: past its last row) are never read and may hold anything, NaN
+ * included.  (Causal: the rows of the sequence itself that lie behind a query's position share its tiles - their scores are not
+ * selected, their weights are exactly 0, and their v must be finite, as rows of one pass are.)  A block works on one sequence only, and
+ * a query's result does not depend on the other sequences of the call nor - causal - on any row behind its position.  No scratch.
+ * CVX_EINVAL, nothing launched: p NULL, struct_size != sizeof(cvx_t2s_prefill_attention), n < 1, heads < 1, rows < 0, max_q outside
+ * [0, rows]; with rows > 0: a NULL pointer (nk only when not causal), max_q < 1, a stride below heads * 64 or not a multiple of 4, a
+ * pointer off 16 bytes.  rows == 0 is a no-op returning 0. */
+typedef struct cvx_t2s_prefill_attention {
+    uint32_t struct_size;
+    int32_t n, heads, causal, max_q;
+    float scale;
+    int64_t rows;
+    const float* q;
+    int64_t ldq;
+    const float *k, *v;
+    int64_t ldkv;
+    float* out;
+    const int32_t *cu, *kbase, *nk;
+} cvx_t2s_prefill_attention;
+
+int cvx_t2s_prefill_attention_f32(const cvx_t2s_prefill_attention* p, cvx_stream_t stream);
+
+/* Guidance on the logits rows of a pass: for r < rows with null_row[r] >= 0,  l[r][c] = n + (l[r][c] - n) * scale[r]  with
+ * n = l[null_row[r]][c] - the operation order of the guided decode step, no contraction; a row with null_row[r] < 0 is left alone.
+ * logits fp32 [>= rows][width] (the null rows lie behind `rows` and are only read), null_row int32 [rows], scale fp32 [rows], on the
+ * device.  CVX_EINVAL (nothing is launched): a NULL pointer, rows < 0, width < 1. */
+int cvx_t2s_prefill_guidance_f32(float* logits, const int32_t* null_row, const float* scale, int64_t rows, int32_t width,
+                                 cvx_stream_t stream);
+
 /* The filter + sampling of one decode step alone (the device function cvx_t2s_decode_steps samples with; no slot state, no queue, no
  * embedding write): tokens[r] = argmax_i (kept(r, i) ? logits[r, i] / max(temperature, 1e-10) + gumbel(uniforms[r, i]) : -inf), lowest
  * index on ties, gumbel(u) = -log(-log(u)) with both logarithms clamped at 1e-20 (text2semantic.py:105-113).  logits, uniforms

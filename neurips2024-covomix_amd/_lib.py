@@ -183,6 +183,13 @@ T2S_RULES_WORDS = 4                              # 32-bit words per row of that 
 T2S_RULES_MAX_NGRAM = 8
 
 
+class T2SPrefillAttention(C.Structure):
+    """cvx_t2s_prefill_attention: struct_size = sizeof(this); the packed attention of a prefill pass (include/covomix_hip.h)"""
+    _fields_ = [("struct_size", C.c_uint32), ("n", C.c_int32), ("heads", C.c_int32), ("causal", C.c_int32), ("max_q", C.c_int32),
+                ("scale", C.c_float), ("rows", C.c_int64), ("q", C.c_void_p), ("ldq", C.c_int64), ("k", C.c_void_p), ("v", C.c_void_p),
+                ("ldkv", C.c_int64), ("out", C.c_void_p), ("cu", C.c_void_p), ("kbase", C.c_void_p), ("nk", C.c_void_p)]
+
+
 class T2SBeam(C.Structure):
     """cvx_t2s_beam: struct_size = sizeof(this); device state of the beam chain (include/covomix_hip.h)"""
     _fields_ = [("struct_size", C.c_uint32), ("beam_size", C.c_int32), ("hist_len", C.c_int32), ("backtrack", C.c_int32)] + \
@@ -262,6 +269,8 @@ SIGNATURES = {
                                                 C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                 C.c_void_p]),
     "cvx_t2s_logprob_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]),
+    "cvx_t2s_prefill_attention_f32": (C.c_int, [C.POINTER(T2SPrefillAttention), C.c_void_p]),
+    "cvx_t2s_prefill_guidance_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]),
     "cvx_t2s_sample_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float,
                                      C.c_void_p, C.c_void_p, C.c_void_p]),
     "cvx_geglu_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_void_p]),

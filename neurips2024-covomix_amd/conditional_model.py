@@ -246,7 +246,7 @@ class CoVoMixModel:
                                        filter_logits_fn="top_k", filter_fn_kwargs=None, return_logprobs=False, best_of=1,
                                        beam_size=10, length_penalty=1.0, prefix=None, best_of_temperatures=None, mixed_guidance=False,
                                        guided_beam=False, repetition_penalty=1.0, repetition_window=0, no_repeat_ngram_size=0, min_length=0,
-                                       beam_rules=False):
+                                       beam_rules=False, prefill=False):
         """reference conditional_model.py:313-321 -> TextToSemanticWrapper.sample (text2semantic.py:1237-1251): the
         sampled semantic tokens as one flat int64 tensor (two-output models: stream 1 then stream 2) on the input's
         device.  (`temprature` is the reference's spelling.)  `uniforms` / `generator` (optional) fix the U(0,1) draws
@@ -276,7 +276,10 @@ class CoVoMixModel:
         False): a list of cond_scale values may then hold 1 (unguided) beside values > 1 (guided), and all of them run through one slot
         pool in one call (t2s.generate_many(mixed_guidance=True)) with the results they get one by one.
         prefix (extension): int64 [S, P] tokens the decode continues from (a list, None where an utterance has none, for a list of texts):
-        the result starts with them (t2s.generate_many(prefixes=...)).
+        the result starts with them (t2s.generate_many(prefixes=...)).  prefill=True (default False; without a prefix it changes nothing):
+        the prefix positions come from one causal full-sequence pass instead of one decode step per token
+        (t2s.generate_many(prefill=True): fp32-class, not bit-identical to the steps; windows of as many utterances as the slots hold;
+        a ValueError with mixed_guidance).
         best_of_temperatures (extension): a sequence of N temperatures - best_of = N with candidate c of every utterance decoded at
         temperature c, all in the one generate_many call of best_of; a best_of other than 1 or N is a ValueError.
         repetition_penalty / repetition_window / no_repeat_ngram_size / min_length (extension; t2s.generate_batch, t2s.check_rules): the
@@ -398,7 +401,8 @@ class CoVoMixModel:
                                           filter_logits_fn="top_k" if "filter_logits_fn" in lists else filter_logits_fn,
                                           filter_fn_kwargs=None if "filter_logits_fn" in lists or "filter_fn_kwargs" in lists else filter_fn_kwargs,
                                           return_logprobs=bool(return_logprobs) or N > 1, settings=sets, prefixes=pres,
-                                          **({"mixed_guidance": True} if mixed_guidance else {}), **rule_kw)
+                                          **({"mixed_guidance": True} if mixed_guidance else {}), **({"prefill": True} if prefill else {}),
+                                          **rule_kw)
             eos = self._t2s.d["vocab"] - 1
             out = []
             for j, i in enumerate(ids_l):
@@ -443,12 +447,14 @@ class CoVoMixModel:
 
     @ops.gated
     @torch.no_grad()
-    def score_text2semantic(self, grapheme_token_ids, streams, cond_scale=1.0, mixed_guidance=False):
+    def score_text2semantic(self, grapheme_token_ids, streams, cond_scale=1.0, mixed_guidance=False, prefill=False):
         """Teacher-forced scoring (extension; what the reference's evaluate_text2semantic measures through
         TextToSemantic.forward(..., return_loss=True)): the log-probability of every token of `streams` - int64 [S, L], the streams a
         sampling call returned - under the text: float32 [S, L] (t2s.score_many).  One utterance, or LISTS of texts and streams (-> a
         list).  cond_scale > 1 scores under the guidance-combined logits and needs what sampling with it needs.  mixed_guidance=True with
-        lists: cond_scale may be a list as long as the texts, 1 (unguided) beside values > 1 (guided), scored in one call."""
+        lists: cond_scale may be a list as long as the texts, 1 (unguided) beside values > 1 (guided), scored in one call.
+        prefill=True (default False): the log-probs come from causal full-sequence passes over the streams instead of one decode step per
+        token (t2s.score_many(prefill=True)): much faster for few utterances, fp32-class, not bit-identical to the default."""
         if not self.is_text2semantic:
             raise TypeError("this checkpoint is an acoustic model")
         scales = [float(c) for c in cond_scale] if isinstance(cond_scale, (list, tuple)) else [float(cond_scale)]
@@ -466,8 +472,9 @@ class CoVoMixModel:
             if isinstance(cond_scale, (list, tuple)) and (not many or len(scales) != len(grapheme_token_ids)):
                 raise ValueError("score_text2semantic: a list of cond_scale values goes with a list of texts of the same length")
             res = dec.score_many(list(grapheme_token_ids) if many else [grapheme_token_ids], list(streams) if many else [streams],
-                                 cond_scale=scales if isinstance(cond_scale, (list, tuple)) else scales[0], mixed_guidance=True)
+                                 cond_scale=scales if isinstance(cond_scale, (list, tuple)) else scales[0], mixed_guidance=True,
+                                 **({"prefill": True} if prefill else {}))
             return res if many else res[0]
         res = dec.score_many(list(grapheme_token_ids) if many else [grapheme_token_ids], list(streams) if many else [streams],
-                             cond_scale=float(cond_scale))
+                             cond_scale=float(cond_scale), **({"prefill": True} if prefill else {}))
         return res if many else res[0]

@@ -108,6 +108,9 @@ def build_parser() -> ArgumentParser:
                    "candidate: candidate c of every turn is decoded at temperature c (implies --t2s_best_of = their number)")
     p.add_argument("--t2s_mixed_guidance", action="store_true", help="extension: turns whose side files make some of them guided and "
                    "others not are decoded in ONE call through one slot pool instead of two calls (the same files either way)")
+    p.add_argument("--t2s_prefill", action="store_true", help="extension: turns with a <name>.prefix.semantic.npy take their prefix through one "
+                   "causal full-sequence pass instead of one decode step per prefix token (fp32-class, not bit-identical to the steps; such "
+                   "turns decode in windows of as many turns as the slots hold; not with --t2s_mixed_guidance); other turns are unaffected")
     p.add_argument("--t2s_beam_size", type=int, default=0, help="extension: beam search with this many hypotheses per turn (1..16) instead of "
                    "sampling - deterministic: no draws, temperature and filter unused; not together with --t2s_best_of > 1 or guidance "
                    "(0 = off: sampling, today's files)")
@@ -275,6 +278,10 @@ def t2s_sampling_kwargs(args) -> dict:
             kw["beam_rules"] = True
     if getattr(args, "t2s_mixed_guidance", False):
         kw["mixed_guidance"] = True
+    if getattr(args, "t2s_prefill", False):
+        if kw.get("mixed_guidance"):
+            raise ValueError("--t2s_prefill does not combine with --t2s_mixed_guidance (the mixed pool's slots are armed on the device)")
+        kw["prefill"] = True
     for flag, key, conv in T2S_RULE_FLAGS:
         if getattr(args, "t2s_" + flag, None) is not None:
             if beam and not (kw.get("beam_rules") and flag in T2S_BEAM_RULE_FLAGS):

@@ -831,6 +831,43 @@ def t2s_logprob(logits: torch.Tensor, tokens: torch.Tensor) -> torch.Tensor:
     return out
 
 
+def t2s_prefill_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Tensor, cu: torch.Tensor, kbase: torch.Tensor,
+                          nk: Optional[torch.Tensor], max_q: int, heads: int, scale: float, causal: bool) -> torch.Tensor:
+    """The packed attention of a text2semantic prefill pass (cvx_t2s_prefill_attention_f32; the definition: include/covomix_hip.h):
+    query row r of sequence i, at index p = r - cu[i], attends to the key rows kbase[i] + j for j < (p + 1 if causal else nk[i]).
+    q [rows, >= heads * 64] and k, v [*, >= heads * 64] are 2-D fp32 views with unit inner stride (column slices of a packed q | k | v
+    or k | v buffer; k and v share their row stride); out [rows, heads * 64] contiguous; cu int32 [n + 1], kbase int32 [>= n], nk int32 [n]
+    (None when causal) on the device; max_q: the longest sequence (the host's copy of max(cu[i + 1] - cu[i]))."""
+    _chk_f32(q, k, v, out)
+    I = heads * 64
+    rows, n = q.shape[0], cu.numel() - 1
+    assert q.ndim == 2 and k.ndim == 2 and v.ndim == 2 and q.stride(1) == 1 and k.stride(1) == 1 and v.stride(1) == 1
+    assert q.shape[1] == I and k.shape[1] == I and v.shape[1] == I and k.stride(0) == v.stride(0)
+    assert out.is_contiguous() and out.shape == (rows, I)
+    for t in (cu, kbase, nk):
+        assert t is None or (t.is_cuda and t.dtype == torch.int32 and t.is_contiguous())
+    assert kbase.numel() >= n and (nk is None or nk.numel() >= n)
+    a = _lib.T2SPrefillAttention()
+    a.struct_size, a.n, a.heads, a.causal, a.max_q = C.sizeof(_lib.T2SPrefillAttention), n, heads, 1 if causal else 0, int(max_q)
+    a.scale, a.rows = float(scale), rows
+    a.q, a.ldq, a.k, a.v, a.ldkv, a.out = _p(q), q.stride(0), _p(k), _p(v), k.stride(0), _p(out)
+    a.cu, a.kbase, a.nk = _p(cu), _p(kbase), _p(nk)
+    _lib.check(_lib.load().cvx_t2s_prefill_attention_f32(C.byref(a), _stream()), "cvx_t2s_prefill_attention_f32")
+    return out
+
+
+def t2s_prefill_guidance(logits: torch.Tensor, null_row: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
+    """In place on the first null_row.numel() rows of logits [R, width]: l[r] = n + (l[r] - n) * scale[r] with n = l[null_row[r]], the
+    guided decode step's operation order (cvx_t2s_prefill_guidance_f32); rows with null_row[r] < 0 are left alone."""
+    _chk_f32(logits, scale)
+    assert logits.ndim == 2 and logits.is_contiguous() and null_row.is_cuda and null_row.dtype == torch.int32 and null_row.is_contiguous()
+    rows = null_row.numel()
+    assert scale.is_contiguous() and scale.numel() == rows and rows <= logits.shape[0]
+    _lib.check(_lib.load().cvx_t2s_prefill_guidance_f32(logits.data_ptr(), null_row.data_ptr(), scale.data_ptr(), rows, logits.shape[1],
+                                                        _stream()), "cvx_t2s_prefill_guidance_f32")
+    return logits
+
+
 def t2s_rules(logits: torch.Tensor, history: torch.Tensor, hist_len: torch.Tensor, table: torch.Tensor, eos_id: int,
               out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """The history rules of the text2semantic decode alone (cvx_t2s_rules_f32; the definition: include/covomix_hip.h,

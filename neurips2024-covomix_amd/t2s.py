@@ -12,6 +12,8 @@ through the same decode slots (score_many) and the mean token log-probability be
 the tokens an utterance has ALREADY emitted: the history rules - repetition penalty, no-repeat n-gram, minimum length (check_rules;
 cvx_t2s_decode_steps_rules) - per utterance and per output stream, in every sampled schedule; off by default.  Under beam search
 (beam_rules=True: check_beam_rules; cvx_t2s_beam_rules_steps) the last two remove candidates along every hypothesis' own ancestry.
+Tokens that are already KNOWN - the targets of score_many, a forced prefix of generate_many - can take ONE causal full-sequence pass
+instead of one decode step each (prefill=True, off by default: prefill_rows, _prefill; csrc/t2s_prefill.hip, cvx_t2s_prefill_attention_f32).
 
   encoder  (source transformer, once per utterance): the full-sequence kernels of the acoustic path - fp32 GEMM with
            the RoPE epilogue, flash attention, RMSNorm - plus a GEGLU kernel;
@@ -463,6 +465,68 @@ def check_prefixes(prefixes, n: int, streams: int, vocab: int, limits, forced=No
         if bool((t == vocab - 1).any()):
             raise ValueError(f"prefix {j}: holds an eos (token {vocab - 1}); continuing past an end is not defined")
         out[j] = t
+    return out
+
+
+PREFILL_ROWS = 32768           # packed rows of one prefill pass (its buffers: [M, 3 inner], [M, 2 ff], [M, S, V])
+
+
+def prefill_rows(seqs, streams: int, max_length: int, ctx_rows: int) -> dict:
+    """The packed tables of ONE prefill pass (TextToSemanticDecoder._prefill; the definition: include/covomix_hip.h,
+    cvx_t2s_prefill_attention_f32).  seqs: one entry per sequence, (tokens int64 [S, L], record, ctx, slot): the L >= 1 given tokens
+    (sequence i then has L input rows at positions 0 .. L - 1: row 0 is the start token, row p > 0 the embeddings of tokens[:, p - 1]),
+    the dialogue record whose kv_c rows [0, ctx) its cross-attention reads (ctx = 1: the null half of a guided pair) and the decode slot
+    whose caches take its rotated keys and values - None for all sequences or for none.  -> host tensors:
+      cu int32 [n + 1]       packed rows per sequence            positions int64 [M]   position of every row (the RoPE rows)
+      gather int64 [M, S]    embedding row per (row, stream); 0 on a sequence's first row, which `starts` int64 [n] names
+      targets int64 [M, S]   tokens[:, p]: the token row p's logits are scored at
+      kbase, nk int32 [n]    first kv_c row (record * ctx_rows) and key count (ctx) of the cross-attention
+      cache int64 [M]        flat cache row slot * max_length + position (None without slots)
+    and rows = M, max_q = the longest sequence.  ValueError: no sequence, a shape other than [S, L], L outside [1, max_length], ctx
+    outside [1, ctx_rows], a negative record or slot, slots for some sequences only.  Pure host code."""
+    seqs = list(seqs)
+    if not seqs:
+        raise ValueError("prefill_rows: no sequence")
+    cu, pos, gather, targets, kbase, nk, cache = [0], [], [], [], [], [], []
+    with_slots = seqs[0][3] is not None
+    for i, (tok, record, ctx, slot) in enumerate(seqs):
+        tok = torch.as_tensor(tok).detach().cpu().to(torch.int64)
+        if tok.ndim != 2 or tok.shape[0] != streams or not 1 <= tok.shape[1] <= max_length:
+            raise ValueError(f"prefill_rows: sequence {i}: [S = {streams}, 1 <= L <= {max_length}] tokens expected, got {tuple(tok.shape)}")
+        if not 1 <= int(ctx) <= ctx_rows or int(record) < 0:
+            raise ValueError(f"prefill_rows: sequence {i}: record {record} with {ctx} context rows (1..{ctx_rows})")
+        if (slot is not None) != with_slots or (with_slots and int(slot) < 0):
+            raise ValueError("prefill_rows: a decode slot for every sequence or for none")
+        L = tok.shape[1]
+        p = torch.arange(L, dtype=torch.int64)
+        cu.append(cu[-1] + L)
+        pos.append(p)
+        gather.append(torch.cat((torch.zeros(1, streams, dtype=torch.int64), tok[:, :L - 1].T), dim=0))
+        targets.append(tok.T)
+        kbase.append(int(record) * ctx_rows)
+        nk.append(int(ctx))
+        if with_slots:
+            cache.append(p + int(slot) * max_length)
+    i32 = lambda xs: torch.tensor(xs, dtype=torch.int32)
+    return dict(cu=i32(cu), positions=torch.cat(pos), gather=torch.cat(gather).contiguous(), starts=torch.tensor(cu[:-1], dtype=torch.int64),
+                targets=torch.cat(targets).contiguous(), kbase=i32(kbase), nk=i32(nk), cache=torch.cat(cache) if with_slots else None,
+                rows=cu[-1], max_q=max(b - a for a, b in zip(cu, cu[1:])))
+
+
+def prefill_windows(rows, cap: int = PREFILL_ROWS, records=None, window: int = WINDOW) -> list:
+    """Utterance ranges [(begin, end), ...] of the prefill passes of a call: rows[j] = the packed rows utterance j brings (both halves of a
+    guided one), at most `cap` per pass - and, with records[j] = its dialogue records, at most `window` of those.  An utterance is never
+    cut: a range ends where the next one would not fit whole, and one that exceeds the cap alone is a pass of its own."""
+    out, begin, used, recs = [], 0, 0, 0
+    for j, r in enumerate(rows):
+        need = 0 if records is None else int(records[j])
+        if j > begin and (used + int(r) > cap or recs + need > window):
+            out.append((begin, j))
+            begin, used, recs = j, 0, 0
+        used += int(r)
+        recs += need
+    if begin < len(rows):
+        out.append((begin, len(rows)))
     return out
 
 
@@ -1060,7 +1124,7 @@ class TextToSemanticDecoder:
                       generator: Optional[torch.Generator] = None, slots: int = 32, ignore_eos: bool = False, limits=None, on_done=None,
                       cond_scale: float = 1.0, filter_logits_fn="top_k", filter_fn_kwargs=None, return_logprobs: bool = False, forced=None,
                       settings=None, prefixes=None, mixed_guidance: bool = False, repetition_penalty: float = 1.0, repetition_window: int = 0,
-                      no_repeat_ngram_size: int = 0, min_length: int = 0):
+                      no_repeat_ngram_size: int = 0, min_length: int = 0, prefill: bool = False):
         """Decode ANY number of utterances through `slots` decode slots with continuous batching: every utterance runs the
         reference's loop (text2semantic.py:749-848) from position 0 to its first eos (:803-818) or its step limit, and the slot it
         ran in takes the next pending utterance in the sampling kernel of that very step (cvx_t2s_decoder.queue) - utterances end
@@ -1108,7 +1172,18 @@ class TextToSemanticDecoder:
         graph for graph.  With any on, the call runs the per-dialogue (or mixed) chain under a rules table
         (cvx_t2s_decode_steps_rules) and ONE graph serves every mix; an utterance's history is its own token row, so a refilled slot
         inherits nothing and every utterance still gets, bit for bit, what it gets alone with its rules.  A prefix counts as history;
-        given steps (prefix, forced) are not subject to the rules."""
+        given steps (prefix, forced) are not subject to the rules.
+        prefill (default False; with no prefix in the call it changes nothing, graph for graph): the first P positions of every prefixed
+        utterance come from ONE causal full-sequence pass (`_prefill`; include/covomix_hip.h, cvx_t2s_prefill_attention_f32) instead of P
+        decode steps: the pass fills the caches of the utterance's slot(s) - both of a guided pair - for positions 0 .. P - 1, its slot
+        record starts at position P with the embedding of the prefix' last tokens as input, its token row holds the prefix (history rules
+        and `streams` as ever), and under return_logprobs the positions below P hold the pass' log-probs.  The device-side refill always
+        starts a dialogue at position 0 with an empty cache, so such a call is cut into windows of at most (armed slots / slots per
+        utterance) utterances, each an ordinary queue call in which the host arms every slot - nothing is refilled: MANY SHORT prefixes
+        may be better off without prefill.  The prefix positions are fp32-class, not bit-identical to the step chain (score_many).
+        ValueError with mixed_guidance, and for a model whose widths the full-sequence kernels do not admit (`_prefill_check`)."""
+        if prefill and mixed_guidance:
+            raise ValueError("generate_many: prefill=True does not run with mixed_guidance=True (the mixed pool's slots are armed on the device)")
         rule_kw = dict(repetition_penalty=repetition_penalty, repetition_window=repetition_window, no_repeat_ngram_size=no_repeat_ngram_size,
                        min_length=min_length)
         if mixed_guidance:
@@ -1137,6 +1212,10 @@ class TextToSemanticDecoder:
         if n == 0:
             return []
         win = WINDOW // P
+        use_prefill = bool(prefill) and prefixes is not None and any(p_ is not None for p_ in prefixes)
+        if use_prefill:           # (the host arms every slot of such a window: as many utterances as slots hold)
+            self._prefill_check()
+            win = max(1, min(int(slots) // P, MAX_BATCH // P))
         if n > win:               # (the context k/v, uniforms and token rows of every queued utterance are resident: bounded windows)
             out = []
             for w in range(0, n, win):
@@ -1146,7 +1225,7 @@ class TextToSemanticDecoder:
                                           cond_scale, filter_logits_fn, filter_fn_kwargs, return_logprobs,
                                           None if forced is None else forced[w:w + win],
                                           None if settings is None else list(settings)[w:w + win],
-                                          None if prefixes is None else list(prefixes)[w:w + win], **rule_kw)
+                                          None if prefixes is None else list(prefixes)[w:w + win], **rule_kw, prefill=prefill)
             return out
         nb = P * max(1, min(int(slots) // P, MAX_BATCH // P, n))
         nb = nb if nb in (1, 2, 4) else min((nb + 7) // 8 * 8, MAX_BATCH)      # whole kernel groups (idle slots cost nothing)
@@ -1188,10 +1267,35 @@ class TextToSemanticDecoder:
         slot = self._slot_records(ctx[:first]).clone()
         for r in range(first):
             slot[r, 5], slot[r, 6] = lim[r // P], flags[r // P]
-        b["state"].copy_(slot)
         b["x"][:first].copy_(self.start[None, :].expand(first, -1))
+        if use_prefill:           # (first == nrec: every record sits in the slot of its own number)
+            self._prefill_slots(pre, text, ctx, [r[2] for r in resolved], P, slot, scored)
+        b["state"].copy_(slot)
         return self._queue_chunks(lambda: self._run_chunk(temperature, nb, cond_scale, True, filt, nrec, scored, per, None, ruled), nrec, text, lim,
                                   span, scored, on_done, lambda records: records[0::P])
+
+    def _prefill_slots(self, pre, text, ctx, scales, P: int, slot: torch.Tensor, scored: bool) -> None:
+        """generate_many(prefill=True), one window whose slots the host arms (record r in slot r): the prefixes `pre` (None: none) of the
+        utterances in records text[j] (P = 2: the null half in text[j] + 1) run as prefill passes of at most PREFILL_ROWS rows that fill
+        the slots' caches; the slot records `slot` (host) then start at the prefix length, the slots' x rows hold the embedding of the
+        prefix' last tokens and, scored, the log-prob rows of the text records hold the passes' log-probs below it."""
+        b, dev = self.buf, self.device
+        idx = [j for j, p_ in enumerate(pre) if p_ is not None]
+        for w0, w1 in prefill_windows([pre[j].shape[1] * P for j in idx]):
+            js = idx[w0:w1]
+            seqs, nulls = self._prefill_pairs([pre[j] for j in js], [text[j] for j in js], [ctx[text[j]] for j in js],
+                                              [scales[j] if P == 2 else 1.0 for j in js], True)
+            lps = self._prefill(seqs, nulls, [scales[j] for j in js], cache=True)
+            for j, lp in zip(js, lps):
+                if scored:
+                    b["logprobs"][text[j], :, :lp.shape[1]].copy_(lp)
+        last = ops.h2d(torch.stack([pre[j][:, -1] for j in idx]).reshape(-1), dev)        # [len(idx) * S] token ids
+        xs = self.emb.index_select(0, last).view(len(idx), self.d["dim_target"])
+        for h in range(P):
+            rows = [text[j] + h for j in idx]
+            b["x"].index_copy_(0, ops.h2d(torch.tensor(rows, dtype=torch.int64), dev), xs)
+            for j in idx:
+                slot[text[j] + h, 0] = pre[j].shape[1]
 
     def _generate_many_mixed(self, sources, uniforms, max_length, temperature, generator, slots, ignore_eos, limits, on_done, cond_scale,
                              filter_logits_fn, filter_fn_kwargs, return_logprobs, forced, settings, prefixes, rule_kw=None):
@@ -1599,7 +1703,118 @@ class TextToSemanticDecoder:
                                            rules[w:w + win] if rules else None)
         return out if return_beams else [h[0] for h in out]
 
-    def score_many(self, sources, targets, cond_scale=1.0, slots: int = 64, mixed_guidance: bool = False):
+    # ------------------------------------------------------------------ prefill: one causal full-sequence pass over given tokens
+    def _prefill_check(self) -> None:
+        """The widths the full-sequence kernels admit: the fp32 GEMM reads rows in 16-byte pieces (K, lda % 4 == 0), and the logits GEMM of
+        stream s starts at column s * dim_emb of the normed rows.  ValueError otherwise - the step chain takes any width."""
+        d = self.d
+        if d["dim_target"] % 4 or d["dim_emb"] % 4:
+            raise ValueError(f"prefill=True: the full-sequence GEMMs need dim_target ({d['dim_target']}) and the semantic embedding width "
+                             f"({d['dim_emb']}) to be multiples of 4; run this model without prefill")
+
+    def _prefill(self, seqs, nulls=None, scales=None, cache: bool = False, return_logits: bool = False):
+        """ONE pass of the target transformer over the packed rows of `seqs` (`prefill_rows`: (tokens [S, L], record, ctx, slot) each; the
+        kv_c rows of the records are in place - `_contexts`), layer by layer in the decode's order on the full-sequence kernels: RMSNorm,
+        the fp32 GEMMs (to_qkv with the RoPE epilogue at every row's position), GEGLU, and the two attentions on
+        ops.t2s_prefill_attention - causal over the pass' own q | k | v rows, then over [0, ctx) of the record's kv_c.
+        nulls / scales (guidance): the first len(nulls) sequences are the ones scored; nulls[j] >= 0 names the sequence that ran the same
+        tokens with ctx = 1, and the scored rows become null + (cond - null) * scales[j] (ops.t2s_prefill_guidance); -1: unguided.
+        Default: every sequence is scored as it is.  cache: the rotated keys and the values of every layer go into k_cache / v_cache of
+        the sequences' slots, positions 0 .. L - 1.
+        -> per scored sequence the log-probs float32 [S, L] of its tokens (cvx_t2s_logprob_f32: the decode's summation order) on the
+        device; with return_logits (tests) also its logits [L, S, V], the rows the log-probs were taken from."""
+        self._prefill_check()
+        d, dev = self.d, self.device
+        S, V, I, H, D, E, F_ = d["streams"], d["vocab"], d["inner"], d["heads"], d["dim_target"], d["dim_emb"], d["ff_tgt"]
+        t = prefill_rows(seqs, S, self.max_length, self.max_source + 2)
+        M, n, cu_host = t["rows"], len(seqs), t["cu"].tolist()
+        n_out = n if nulls is None else len(nulls)
+        Mc = cu_host[n_out]
+        if cache and max(s_[3] for s_ in seqs) >= self._slots:
+            raise ValueError("prefill: a cache slot beyond the decode buffers")
+        cu, kbase, nk = (ops.h2d(t[k], dev) for k in ("cu", "kbase", "nk"))
+        pos, starts = ops.h2d(t["positions"], dev), ops.h2d(t["starts"], dev)
+        f = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
+        x = self.emb.index_select(0, ops.h2d(t["gather"].reshape(-1), dev)).view(M, D)
+        x.index_copy_(0, starts, self.start[None, :].expand(n, -1))
+        rope = (self.rope[0].index_select(0, pos), self.rope[1].index_select(0, pos))        # per-row tables (rope_T = M)
+        normed, qkv, att, qc, h2, hg = f(M, D), f(M, 3 * I), f(M, I), f(M, I), f(M, 2 * F_), f(M, self.Fp)
+        dst = ops.h2d(t["cache"], dev) if cache else None
+        scale = 64 ** -0.5
+        for L in self.dec:
+            ops.adarmsnorm(x, L["gamma_s"], None, normed)
+            ops.gemm(normed, L["wqkv_s"], qkv, rope=rope, rope_cols=2 * I)
+            ops.t2s_prefill_attention(qkv[:, :I], qkv[:, I:2 * I], qkv[:, 2 * I:], att, cu, cu, None, t["max_q"], H, scale, True)
+            if cache:
+                L["k_cache"].view(-1, I).index_copy_(0, dst, qkv[:, I:2 * I])
+                L["v_cache"].view(-1, I).index_copy_(0, dst, qkv[:, 2 * I:])
+            ops.gemm(att, L["wo_s"], x, residual=x)
+            ops.adarmsnorm(x, L["gamma_c"], None, normed)
+            ops.gemm(normed, L["wq_c"], qc)
+            kv = L["kv_c"].view(-1, 2 * I)
+            ops.t2s_prefill_attention(qc, kv[:, :I], kv[:, I:], att, cu, kbase, nk, t["max_q"], H, scale, False)
+            ops.gemm(att, L["wo_c"], x, residual=x)
+            ops.adarmsnorm(x, L["gamma_f"], None, normed)
+            ops.gemm(normed, L["w1"], h2, bias=L["b1"])
+            ops.geglu(h2, hg, F_)
+            ops.gemm(hg, L["w2"], x, bias=L["b2"], residual=x)
+        ops.adarmsnorm(x, self.dec_final, None, normed)
+        logits = f(M, S, V)
+        for s_ in range(S):
+            ops.gemm(normed[:, s_ * E:(s_ + 1) * E], self.emb, logits[:, s_, :])
+        if nulls is not None and any(k >= 0 for k in nulls):                                 # (guidance: one-output models, S = 1)
+            null_row = torch.full((Mc,), -1, dtype=torch.int32)
+            row_scale = torch.ones(Mc, dtype=torch.float32)
+            for j, k in enumerate(nulls):
+                if k >= 0:
+                    null_row[cu_host[j]:cu_host[j + 1]] = torch.arange(cu_host[k], cu_host[k + 1], dtype=torch.int32)
+                    row_scale[cu_host[j]:cu_host[j + 1]] = float(scales[j])
+            ops.t2s_prefill_guidance(logits.view(M * S, V), ops.h2d(null_row, dev), ops.h2d(row_scale, dev))
+        lp = ops.t2s_logprob(logits[:Mc].view(Mc * S, V), ops.h2d(t["targets"][:Mc].reshape(-1), dev)).view(Mc, S)
+        out = [lp[cu_host[j]:cu_host[j + 1]].T.contiguous() for j in range(n_out)]
+        if return_logits:
+            return out, [logits[cu_host[j]:cu_host[j + 1]] for j in range(n_out)]
+        return out
+
+    def _prefill_pairs(self, tokens, text, ctx_text, scales, slots: bool):
+        """The sequences of a pass over `tokens` (int64 [S, L] each; utterance j sits in record text[j] with ctx_text[j] context rows, the
+        null half of a guided one - scales[j] > 1 - in record text[j] + 1): the text halves first, then the null halves.
+        slots: every record's caches are those of the slot of the same number.  -> (seqs, nulls) for `_prefill`."""
+        seqs = [(tokens[j], text[j], ctx_text[j], text[j] if slots else None) for j in range(len(tokens))]
+        nulls = [-1] * len(tokens)
+        for j in range(len(tokens)):
+            if scales[j] > 1.0:
+                nulls[j] = len(seqs)
+                seqs.append((tokens[j], text[j] + 1, 1, text[j] + 1 if slots else None))
+        return seqs, nulls
+
+    @ops.gated
+    @torch.no_grad()
+    def _score_prefill(self, sources, tg, scales, return_logits: bool = False):
+        """score_many(prefill=True): windows of at most PREFILL_ROWS packed rows and WINDOW dialogue records, each one encoder pass
+        (`_contexts` into the records of `mixed_records`) and one `_prefill` pass.  No decode slot, no queue, no graph."""
+        self._prefill_check()
+        kinds = [c > 1.0 for c in scales]
+        out, lgs = [], []
+        for w0, w1 in prefill_windows([t.shape[1] * (2 if g else 1) for t, g in zip(tg, kinds)], PREFILL_ROWS, [2 if g else 1 for g in kinds]):
+            first = mixed_records(kinds[w0:w1])
+            text = first[:-1]
+            self._ensure(0, first[-1], 0)
+            ctx_text = self._contexts(sources[w0:w1], text)
+            nulls = [text[j] + 1 for j in range(w1 - w0) if kinds[w0 + j]]
+            if nulls:              # the null half: the learned null key / value row only
+                ni = ops.h2d(torch.tensor(nulls, dtype=torch.int64), self.device)
+                for L in self.dec:
+                    L["kv_c"][:, 0].index_copy_(0, ni, L["null"][None, :].expand(len(nulls), -1))
+            seqs, null_of = self._prefill_pairs(tg[w0:w1], text, ctx_text, scales[w0:w1], False)
+            res = self._prefill(seqs, null_of, scales[w0:w1], return_logits=return_logits)
+            if return_logits:
+                lgs += [x.cpu() for x in res[1]]
+                res = res[0]
+            out += [x.cpu() for x in res]
+        return (out, lgs) if return_logits else out
+
+    def score_many(self, sources, targets, cond_scale=1.0, slots: int = 64, mixed_guidance: bool = False, prefill: bool = False):
         """Teacher-forced scoring: the log-probability the model gives every token of targets[j] under the text sources[j] - what the
         reference's TextToSemantic.forward(..., return_loss=True) averages (text2semantic.py), position by position.  targets[j]: int64
         [S, L_j], the `streams` that `generate` returns; -> list of float32 [S, L_j] host tensors: entry [s, t] is the log-softmax, at
@@ -1609,7 +1824,14 @@ class TextToSemanticDecoder:
         `generate(return_logprobs=True)` returned when it sampled those tokens.  ValueError for L_j < 1, L_j > max_length or a token
         outside [0, vocab); NotImplementedError for guidance on a two-output model.
         mixed_guidance: cond_scale may be a list, one scale per utterance - 1 (unguided) or > 1 (guided) - and all of them are scored in
-        one generate_many(mixed_guidance=True) call."""
+        one generate_many(mixed_guidance=True) call.
+        prefill (default False: the call as above): the log-probs come from causal full-sequence PASSES over the targets (`_prefill`;
+        include/covomix_hip.h, cvx_t2s_prefill_attention_f32) instead of one decode step per token - no decode slot, no queue, no graph;
+        `slots` is not looked at.  Same return type and shapes; cond_scale > 1 and mixed_guidance as above (a guided utterance is two
+        sequences of a pass).  The values are fp32-class and inside the oracle bound of the step chain, but NOT bit-identical to it (a GEMM
+        and a GEMV round differently), and an utterance's bits may depend on how many rows its pass holds; the
+        same call twice gives the same bits.  ValueError for a model whose widths the full-sequence kernels do not admit
+        (`_prefill_check`)."""
         sources, targets = list(sources), list(targets)
         if len(sources) != len(targets):
             raise ValueError(f"score_many: {len(sources)} sources, {len(targets)} targets")
@@ -1621,6 +1843,8 @@ class TextToSemanticDecoder:
             tg = check_targets(targets, self.d["streams"], self.d["vocab"], self.max_length)
             if not tg:
                 return []
+            if prefill:
+                return self._score_prefill(sources, tg, scales)
             res = self.generate_many(sources, None, max(t.shape[1] for t in tg), 1.0, None, slots, return_logprobs=True, forced=tg,
                                      settings=[{"cond_scale": c} for c in scales], mixed_guidance=True)
             return [r[2] for r in res]
@@ -1629,6 +1853,8 @@ class TextToSemanticDecoder:
         tg = check_targets(targets, self.d["streams"], self.d["vocab"], self.max_length)
         if not tg:
             return []
+        if prefill:
+            return self._score_prefill(sources, tg, [float(cond_scale)] * len(tg))
         res = self.generate_many(sources, None, max(t.shape[1] for t in tg), 1.0, None, slots, cond_scale=cond_scale,
                                  return_logprobs=True, forced=tg)
         return [r[2] for r in res]
