@@ -78,7 +78,9 @@ typedef const cvx_ctx* cvx_stream_t;
  * cvx_t2s_beam_guided_queue_steps - beam search under classifier-free guidance, on the structs of the unguided entry points.  Still 113
  * (two symbols and a struct added): cvx_t2s_decode_steps_rules with cvx_t2s_rules, cvx_t2s_rules_f32 - repetition penalty, no-repeat
  * n-gram and minimum length per dialogue; cvx_t2s_per_dialogue and its rows are untouched.  Still 113 (two symbols added, no struct
- * changed): cvx_t2s_beam_rules_steps and cvx_t2s_beam_select_rules_f32 - no-repeat n-gram and minimum length under beam search. */
+ * changed): cvx_t2s_beam_rules_steps and cvx_t2s_beam_select_rules_f32 - no-repeat n-gram and minimum length under beam search.  Still 113
+ * (six symbols added, no struct changed): cvx_mel_items_words / _fill, cvx_mel_pack_f32, cvx_mel_log_gather_f32,
+ * cvx_mel_workspace_bytes_many and cvx_mel_spectrogram_many_f32 - the prompt mel of many wav prompts in one call. */
 #define CVX_ABI_VERSION 113
 int         cvx_version(void);
 const char* cvx_last_error_string(void);
@@ -662,6 +664,55 @@ int cvx_amax_pow2_scale_f32(const float* x, int64_t n, float target, float* scal
  */
 int cvx_mel_magnitude_f32(const float* spec, float* mag, int64_t T, int32_t nb, int32_t nbp, cvx_stream_t s);
 int cvx_mel_log_transpose_f32(const float* x, float* y, int64_t T, int32_t n_mels, cvx_stream_t s);
+
+/* MANY PROMPTS IN ONE CALL (ragged batch; opt-in - the two entry points above and the one-prompt path built on them are unchanged).
+ * Geometry: n_fft % 4 == 0, hop % 4 == 0, hop <= n_fft, (n_fft - hop) % 2 == 0, pad = (n_fft - hop) / 2, window = n_fft, no centring.
+ * The prompts are PACKED into one buffer of reflect-padded signals: item b has n_b samples at the target rate (n_b = n_raw for a stored
+ * signal, ceil(up * n_raw / down) for one that names a resample bank), its padded signal of n_b + 2 * pad samples starts at float
+ * S_b = slot_b * hop and takes ceil((n_b + 2 * pad) / hop) hop-sized slots; the next item starts at the next slot; the slack behind an
+ * item and the n_fft - hop floats behind the last slot are ZERO.  Frame t of item b is row slot_b + t of ONE [R, n_fft] view with row
+ * stride hop over the whole buffer (R = all slots), T_b = (n_b + 2 * pad - n_fft) / hop + 1 frames (0 when the padded item is shorter
+ * than n_fft).  A valid row reads only its own item's padded samples; the rows that straddle into the next item are computed and never
+ * gathered.  The DFT and the mel projection are then ONE fp32 GEMM each over all R rows, and an item's mel is bit for bit what the
+ * one-prompt path gives it alone (every form of the fp32 GEMM contracts an element's products in one order whatever M is).
+ *
+ * ITEM TABLE: int32 words, filled on the HOST by cvx_mel_items_fill (cvx_mel_items_words of them); the caller uploads a copy and
+ * passes both with their word count.
+ *   header[16]      magic, n_items, n_fft, hop, pad, R, M = sum T_b, max T_b, packed floats (R * hop + n_fft - hop, rounded up to 4),
+ *                   raw floats, n_banks, bank floats, 0 ...
+ *   item[n][8]      raw offset (floats into `raw`: the items' stored samples one after the other, every start rounded up to 4), n_raw,
+ *                   n_b, slot_b, T_b, cu_b (frames of the items before), bank (-1: none), 0
+ *   bank[n_banks][4]  up, down, width, offset (floats into `banks`) of a polyphase filter bank [up][2 * width + down] as
+ *                   cvx_resample_fir_f32 takes it (covomix_amd.hubert.sinc_resample_kernel); the banks lie one after the other
+ * bank_geom = n_banks triples (up, down, width) in host memory, at most 16 banks.  cvx_mel_items_fill returns CVX_EINVAL and
+ * cvx_mel_items_words -1 (nothing is launched, here and in every call that takes a table) when n_items <= 0, the geometry breaks the
+ * constraints above, an item has n_b <= pad (its reflection is undefined), names no bank of the call or has n_raw < 0, or the packed
+ * buffer, the raw samples or the banks do not fit int32 or the frames reach 2^24.  T_b = 0 is legal.
+ * Every call that takes a table re-derives the host copy from its own n_raw / bank words and compares it word by word, then reads the
+ * device copy back (one small blocking copy on the context's stream: these calls are NOT graph-capturable) and compares it with the
+ * host copy - before anything is launched.  Nothing is allocated and nothing is copied from the host.
+ *
+ * cvx_mel_pack_f32: ONE launch writes every word of packed[header[8]]: position p of item b takes the stored sample at the reflected
+ * index of p - pad, or - for an item with a bank - the polyphase FIR output at that index (the loop of cvx_resample_fir_f32: same taps,
+ * same fmaf order, zero outside [0, n_raw)), clamped to [-1, 1]; slack and tail are written as zero.  raw and packed 16-byte aligned.
+ * cvx_mel_log_gather_f32: out[n_mels * cu_b + m * T_b + t] = log(max(proj[(slot_b + t) * n_mels + m], 1e-5)): item b's [n_mels, T_b]
+ * block is contiguous in the packed output of n_mels * M floats; proj = [R, n_mels].
+ * cvx_mel_spectrogram_many_f32: the whole call - pack, DFT GEMM (A = the packed buffer, lda = hop; dft = [2 * nb, n_fft], the windowed
+ * cos | sin basis, nb = n_fft / 2 + 1), cvx_mel_magnitude_f32, mel GEMM (basis = [n_mels, nbp], nbp = nb rounded up to 4, zero in the
+ * padding), log-gather.  workspace: 256-byte aligned device memory of cvx_mel_workspace_bytes_many bytes (-1 for an illegal table); it
+ * needs no initialisation - every word that is read was written by the call. */
+int64_t cvx_mel_items_words(int32_t n_fft, int32_t hop, const int64_t* n_raw, const int32_t* bank, const int32_t* bank_geom,
+                            int32_t n_banks, int32_t n_items);
+int cvx_mel_items_fill(int32_t n_fft, int32_t hop, const int64_t* n_raw, const int32_t* bank, const int32_t* bank_geom, int32_t n_banks,
+                       int32_t n_items, int32_t* table, int64_t table_words);
+int cvx_mel_pack_f32(const float* raw, const float* banks, const int32_t* items_host, const int32_t* items_dev, int64_t items_words,
+                     int32_t n_items, float* packed, cvx_stream_t s);
+int cvx_mel_log_gather_f32(const float* proj, const int32_t* items_host, const int32_t* items_dev, int64_t items_words, int32_t n_items,
+                           int32_t n_mels, float* out, cvx_stream_t s);
+int64_t cvx_mel_workspace_bytes_many(const int32_t* items_host, int64_t items_words, int32_t n_items, int32_t n_mels);
+int cvx_mel_spectrogram_many_f32(const float* raw, const float* banks, const float* dft, const float* basis, int32_t n_mels,
+                                 const int32_t* items_host, const int32_t* items_dev, int64_t items_words, int32_t n_items,
+                                 float* out, void* workspace, int64_t workspace_bytes, cvx_stream_t s);
 
 /* pcm[i] = (int16) trunc( wav[i] * 32768 )   mel_decode_to_wav tail (monologue_generation.py:55-57),
  * numpy astype('int16') semantics for in-range values (C truncation toward zero). */

@@ -247,6 +247,13 @@ SIGNATURES = {
                                                  C.c_int32, C.c_void_p]),
     "cvx_mel_magnitude_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p]),
     "cvx_mel_log_transpose_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]),
+    "cvx_mel_items_words": (C.c_int64, [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32]),
+    "cvx_mel_items_fill": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64]),
+    "cvx_mel_pack_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]),
+    "cvx_mel_log_gather_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "cvx_mel_workspace_bytes_many": (C.c_int64, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32]),
+    "cvx_mel_spectrogram_many_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64,
+                                               C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "cvx_t2s_decode_steps": (C.c_int, [C.POINTER(T2SDecoder), C.c_int32, C.c_void_p]),
     "cvx_t2s_decode_steps_scored": (C.c_int, [C.POINTER(T2SDecoder), C.POINTER(T2SScoring), C.c_int32, C.c_void_p]),
     "cvx_t2s_decode_steps_per_dialogue": (C.c_int, [C.POINTER(T2SDecoder), C.POINTER(T2SScoring), C.POINTER(T2SPerDialogue), C.c_int32,

@@ -12,7 +12,8 @@ Upstream stages:
       this repo does not ship) is decoded on the GPU; otherwise `<text_dir>/<name>.semantic.npy` holds already
       predicted tokens (covosingle / covosinx: int array [n]; covomix: [2, n] or flat [2n], split at half).
   * prompt mel extraction (N3, built: mel.py): `<prompt_dir>/<name>.mel.npy` ([80, T] log-mel) if present, else the
-      log-mel of `<prompt_dir>/<name>.wav` (8 kHz) computed on the GPU
+      log-mel of `<prompt_dir>/<name>.wav` (8 kHz) computed on the GPU (--mel_batch N > 1: all such prompts of the run
+      up front, N per ragged call, instead of one call per prompt; the same mels bit for bit)
   * prompt tokens (N4, built: hubert.py): `<prompt_dir>/<name>.hubert_code.npy` if present (what
       fairseq-hubert/get_fisher_semantic_tokens.py wrote offline), else, with --hubert_ckpt and --km_path, the HuBERT
       layer-12 + k-means codes of `<prompt_dir>/<name>.wav` computed on the GPU (resampled to the checkpoint's rate;
@@ -73,6 +74,9 @@ def build_parser() -> ArgumentParser:
     p.add_argument("--km_path", type=str, default=None, help="k-means model (joblib) for --hubert_ckpt")
     p.add_argument("--hubert_batch", type=int, default=1, help="with --hubert_ckpt: N > 1 tokenises the run's wav prompts up front, N per "
                    "ragged call (HubertTokenizer.wav2code_many; 16 is the measured recommendation); 1 = one call per prompt as it is needed")
+    p.add_argument("--mel_batch", type=int, default=1, help="extension: N > 1 extracts the mels of the run's wav prompts that have no "
+                   "<name>.mel.npy up front, N per ragged call (mel.extract_mel_many; bit-identical mels); 1 = one extract_mel call per "
+                   "prompt as it is needed")
     p.add_argument("--nfe", type=int, default=32, help="extension: CFG-combined field evaluations of the midpoint solver (32 = the "
                    "reference's ode_step_size 0.0625, acoustic.py:586-591; 64 = BASELINE config 5's 64-step setting)")
     p.add_argument("--ode_method", type=str, default="midpoint", help="extension: the fixed-grid solver (the reference's "
@@ -127,6 +131,7 @@ def build_parser() -> ArgumentParser:
 HEAD_START = 16     # utterances read before the first launch of a large directory (generation.run, --pipeline off)
 _HUBERT = None      # HubertTokenizer, built by main() when --hubert_ckpt / --km_path are given
 _HUBERT_CODES: dict = {}   # (prompt_dir, prompt name) -> code string, filled by the --hubert_batch pre-pass
+_PROMPT_MELS: dict = {}    # (prompt_dir, prompt name) -> [80, T] log-mel, filled by the --mel_batch pre-pass
 
 
 def _load_prompt(prompt_dir: str, name: str):
@@ -140,6 +145,8 @@ def _load_prompt(prompt_dir: str, name: str):
     npy = os.path.join(prompt_dir, name + ".mel.npy")
     if os.path.isfile(npy):
         mel = torch.from_numpy(np.load(npy).astype(np.float32))
+    elif (prompt_dir, name) in _PROMPT_MELS:               # extracted by the --mel_batch pre-pass
+        mel = _PROMPT_MELS[(prompt_dir, name)]
     else:                                                  # extract_mel(prompt wav), monologue_generation.py:62-74 (row N3)
         from .mel import extract_mel
         mel = extract_mel(os.path.join(prompt_dir, name + ".wav"))
@@ -159,6 +166,18 @@ def pretokenise_prompts(prompt_dir: str, names, batch: int) -> int:
         group = todo[i:i + batch]
         for n, code in zip(group, _HUBERT.wav2code_many([os.path.join(prompt_dir, n + ".wav") for n in group], 1)):
             _HUBERT_CODES[(prompt_dir, n)] = code
+    return len(todo)
+
+
+def preextract_prompt_mels(prompt_dir: str, names, batch: int) -> int:
+    """--mel_batch N > 1: extract the mel of every prompt of the run that has no <name>.mel.npy in groups of N (mel.extract_mel_many:
+    what extract_mel returns for the file, bit for bit) and keep them for `_load_prompt`.  -> number of prompts extracted."""
+    from .mel import extract_mel_many
+    todo = [n for n in dict.fromkeys(names) if not os.path.isfile(os.path.join(prompt_dir, n + ".mel.npy"))]
+    for i in range(0, len(todo), batch):
+        group = todo[i:i + batch]
+        for n, mel in zip(group, extract_mel_many([os.path.join(prompt_dir, n + ".wav") for n in group])):
+            _PROMPT_MELS[(prompt_dir, n)] = mel
     return len(todo)
 
 
@@ -591,6 +610,12 @@ def run(dialogue: bool, argv=None) -> int:
         t_pre = time.perf_counter()
         pretokenise_prompts(args.prompt_dir, prompt_names(mine, dialogue), int(args.hubert_batch))
         prepass_s = time.perf_counter() - t_pre
+    _PROMPT_MELS.clear()
+    mel_prepass_s = 0.0                                           # (the same for the --mel_batch pre-pass)
+    if args.mel_batch > 1:
+        t_pre = time.perf_counter()
+        preextract_prompt_mels(args.prompt_dir, prompt_names(mine, dialogue), int(args.mel_batch))
+        mel_prepass_s = time.perf_counter() - t_pre
     work = [(n, k, s) for n in mine for k, s in enumerate(sources[n])]
     to_decode = sum(1 for _, _, (kind, _) in work if kind != "sem")
     mode = args.pipeline
@@ -774,7 +799,7 @@ def run(dialogue: bool, argv=None) -> int:
         frames = sum(nfr)
     drain()
     torch.cuda.synchronize()
-    elapsed = time.perf_counter() - t0 + prepass_s                # (--hubert_batch 1 tokenises inside the loop: both forms are counted)
+    elapsed = time.perf_counter() - t0 + prepass_s + mel_prepass_s     # (--hubert_batch 1 / --mel_batch 1 work inside the loop: both forms are counted)
     for n in mine:
         if not segments[n]:
             continue
@@ -788,7 +813,9 @@ def run(dialogue: bool, argv=None) -> int:
             json.dump({n: [segs[k] for k in sorted(segs)] for n, segs in sorted(solve_errors.items())}, f, indent=1)
     print(f"rank {rank}: {done} utterances, {frames} generated frames in {elapsed:.3f} s ({frames / max(elapsed, 1e-9):.1f} frames/s, "
           f"{'text2semantic + ' if mode != 'off' else ''}sampling + vocoder, excluding model load; --pipeline {mode}"
-          + (f"; of that {prepass_s:.3f} s in the --hubert_batch pre-pass" if prepass_s else "") + ")")
+          + (f"; of that {prepass_s:.3f} s in the --hubert_batch pre-pass" if prepass_s else "")
+          + (f"; of that {mel_prepass_s:.3f} s in the --mel_batch pre-pass" if mel_prepass_s else "") + ")")
     run.last_stats = dict(utterances=done, frames=frames, seconds=elapsed, pipeline=mode, load_seconds=load_s, batches=batch_log,
-                          max_frames=max_frames, head_start=bool(head_start), hubert_prepass_seconds=prepass_s)
+                          max_frames=max_frames, head_start=bool(head_start), hubert_prepass_seconds=prepass_s,
+                          mel_prepass_seconds=mel_prepass_s)
     return done
