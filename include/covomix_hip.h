@@ -1192,6 +1192,27 @@ int cvx_t2s_prefill_attention_f32(const cvx_t2s_prefill_attention* p, cvx_stream
 int cvx_t2s_prefill_guidance_f32(float* logits, const int32_t* null_row, const float* scale, int64_t rows, int32_t width,
                                  cvx_stream_t stream);
 
+/* EDIT DISTANCE of many pairs of token sequences in one launch - csrc/edit_distance.hip.  Still ABI 113: one symbol and one constant added.
+ * What consensus (minimum-Bayes-risk) selection among the candidates of best-of-N and the reference's validation metric of
+ * text2semantic (covomix/util/inference.py:287-358: jiwer.wer over token strings) are counted with.
+ *   out[p] = the unit-cost Levenshtein distance between items a_p and b_p: the fewest substitutions, insertions and deletions (1 each)
+ *            that turn one into the other.
+ * tokens int64 [n_tokens] on the device; an ITEM is tokens[offset : offset + length), 0 <= length <= CVX_EDIT_MAX_LEN; items may overlap,
+ * touch or repeat.  items = int32 [n_items][2] (offset, length), pairs = int32 [n_pairs][2] (item a, item b), each given twice: the
+ * HOST copy is validated before anything is launched and sizes the launch, the DEVICE copy is what the kernel reads (the caller uploads
+ * it; nothing is copied or allocated here, no host synchronisation, graph-capturable).  out int32 [n_pairs] on the device.
+ * Tokens are compared by their low 32 bits (the kernel narrows them; every vocabulary here is far below 2^31).  A zero-length item gives
+ * the other item's length; a pair may name one item twice (0) and pairs may repeat; a pair's result depends on its two items alone, not
+ * on its place in the table or on its neighbours.  One block per pair, ONE store per pair, int32 arithmetic, no global scratch, no
+ * atomics, no token behind an item's length read.
+ * CVX_EINVAL, nothing launched and out untouched: a negative count; an item with offset < 0, length outside [0, CVX_EDIT_MAX_LEN] or
+ * offset + length > n_tokens; a pair index outside [0, n_items); a NULL table; with n_pairs > 0 a NULL device pointer.  n_pairs == 0 is
+ * a successful call without a launch.  A block whose DEVICE rows break these bounds (the device copy is not the host copy) reads no
+ * token and stores -1. */
+#define CVX_EDIT_MAX_LEN 4096           /* tokens per item: two streams of the largest max_length */
+int cvx_edit_distance_i64(const int64_t* tokens_dev, int64_t n_tokens, const int32_t* items_host, const int32_t* items_dev, int32_t n_items,
+                          const int32_t* pairs_host, const int32_t* pairs_dev, int32_t n_pairs, int32_t* out_dev, cvx_stream_t s);
+
 /* The filter + sampling of one decode step alone (the device function cvx_t2s_decode_steps samples with; no slot state, no queue, no
  * embedding write): tokens[r] = argmax_i (kept(r, i) ? logits[r, i] / max(temperature, 1e-10) + gumbel(uniforms[r, i]) : -inf), lowest
  * index on ties, gumbel(u) = -log(-log(u)) with both logarithms clamped at 1e-20 (text2semantic.py:105-113).  logits, uniforms

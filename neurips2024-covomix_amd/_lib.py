@@ -181,6 +181,7 @@ class T2SRules(C.Structure):
 
 T2S_RULES_WORDS = 4                              # 32-bit words per row of that table
 T2S_RULES_MAX_NGRAM = 8
+EDIT_MAX_LEN = 4096                              # CVX_EDIT_MAX_LEN: tokens per item of cvx_edit_distance_i64
 
 
 class T2SPrefillAttention(C.Structure):
@@ -278,6 +279,8 @@ SIGNATURES = {
     "cvx_t2s_logprob_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]),
     "cvx_t2s_prefill_attention_f32": (C.c_int, [C.POINTER(T2SPrefillAttention), C.c_void_p]),
     "cvx_t2s_prefill_guidance_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]),
+    "cvx_edit_distance_i64": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
+                                        C.c_void_p]),
     "cvx_t2s_sample_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float,
                                      C.c_void_p, C.c_void_p, C.c_void_p]),
     "cvx_geglu_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_void_p]),

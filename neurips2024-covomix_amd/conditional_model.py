@@ -246,7 +246,7 @@ class CoVoMixModel:
                                        filter_logits_fn="top_k", filter_fn_kwargs=None, return_logprobs=False, best_of=1,
                                        beam_size=10, length_penalty=1.0, prefix=None, best_of_temperatures=None, mixed_guidance=False,
                                        guided_beam=False, repetition_penalty=1.0, repetition_window=0, no_repeat_ngram_size=0, min_length=0,
-                                       beam_rules=False, prefill=False):
+                                       beam_rules=False, prefill=False, best_of_select="logprob"):
         """reference conditional_model.py:313-321 -> TextToSemanticWrapper.sample (text2semantic.py:1237-1251): the
         sampled semantic tokens as one flat int64 tensor (two-output models: stream 1 then stream 2) on the input's
         device.  (`temprature` is the reference's spelling.)  `uniforms` / `generator` (optional) fix the U(0,1) draws
@@ -288,9 +288,21 @@ class CoVoMixModel:
         settings, as above).  All off by default: the call is then what it was.  Log-probs stay those of the model's unmodified rows.
         None of these combines with beam search (ValueError) - unless beam_rules=True (default False): no_repeat_ngram_size and min_length,
         scalars or lists as above, then run under beam search (t2s.generate_beam(beam_rules=True): candidates are removed along every
-        hypothesis' own ancestry, scores and log-probs stay the model's); a repetition_penalty other than 1 and a repetition_window other than 0 stay a ValueError."""
+        hypothesis' own ancestry, scores and log-probs stay the model's); a repetition_penalty other than 1 and a repetition_window other than 0 stay a ValueError.
+        best_of_select (extension): the rule best_of keeps a candidate by.  "logprob" (default: the call as it was, no edit-distance call is
+        made) - the largest sequence_logprob.  "mbr" - consensus (minimum Bayes risk): the candidate with the smallest total edit distance to
+        the utterance's other candidates over the counted tokens of every stream (t2s.consensus_risks: all utterances of the call in one
+        ops.edit_distance launch), ties to the larger sequence_logprob, then to the lowest index (t2s.consensus_candidate).  "mbr" without
+        best_of > 1 or best_of_temperatures, with beam search, or an unknown name: ValueError."""
         if not self.is_text2semantic:
             raise TypeError("this checkpoint is an acoustic model: use synthesis_sample")
+        if best_of_select not in ("logprob", "mbr"):
+            raise ValueError(f"best_of_select must be 'logprob' or 'mbr', got {best_of_select!r}")
+        if best_of_select == "mbr":
+            if beam_search_decode:
+                raise ValueError("best_of_select='mbr' does not combine with beam search (consensus is over sampled candidates)")
+            if best_of_temperatures is None and not (isinstance(best_of, int) and not isinstance(best_of, bool) and best_of > 1):
+                raise ValueError("best_of_select='mbr' needs candidates to choose among: best_of > 1 or best_of_temperatures")
         ids = grapheme_token_ids
         many = isinstance(ids, (list, tuple))
         lists = {k: list(v) for k, v in (("temperature", temprature), ("cond_scale", cond_scale), ("filter_logits_fn", filter_logits_fn),
@@ -322,7 +334,7 @@ class CoVoMixModel:
         for k in list(rule_kw):
             if lists.get(k) and all(x == lists[k][0] for x in lists[k]):
                 rule_kw[k] = lists.pop(k)[0]
-        from .t2s import RULE_FIELDS, RULES_OFF, best_candidate, check_beam_size, check_best_of, check_rules, sequence_logprob
+        from .t2s import RULE_FIELDS, RULES_OFF, check_beam_size, check_best_of, check_rules
         rule_kw = {k: v for k, v in rule_kw.items() if k not in lists}
         check_rules(None, 1, 1 << 30, **rule_kw)
         rule_kw = {k: v for k, v in rule_kw.items() if v != RULES_OFF[RULE_FIELDS.index(k)]}
@@ -404,10 +416,10 @@ class CoVoMixModel:
                                           **({"mixed_guidance": True} if mixed_guidance else {}), **({"prefill": True} if prefill else {}),
                                           **rule_kw)
             eos = self._t2s.d["vocab"] - 1
+            chosen = self._select_candidates(res, N, eos, best_of_select) if N > 1 else [0] * n
             out = []
             for j, i in enumerate(ids_l):
-                cand = res[j * N:(j + 1) * N]
-                r = cand[best_candidate([sequence_logprob(c[2], c[1], eos) for c in cand])] if N > 1 else cand[0]
+                r = res[j * N + chosen[j]]
                 out.append(tuple(t.to(i.device) for t in r) if return_logprobs else r[0].to(i.device))
             return out if many else out[0]
         if best_of > 1:
@@ -420,10 +432,10 @@ class CoVoMixModel:
                                           cond_scale=float(cond_scale), filter_logits_fn=filter_logits_fn, filter_fn_kwargs=filter_fn_kwargs,
                                           return_logprobs=True, **rule_kw)
             eos = self._t2s.d["vocab"] - 1
+            chosen = self._select_candidates(res, N, eos, best_of_select)
             out = []
             for j, i in enumerate(ids_l):
-                cand = res[j * N:(j + 1) * N]
-                r = cand[best_candidate([sequence_logprob(c[2], c[1], eos) for c in cand])]
+                r = res[j * N + chosen[j]]
                 out.append(tuple(t.to(i.device) for t in r) if return_logprobs else r[0].to(i.device))
             return out if many else out[0]
         if many:                                    # extension: several utterances decoded together (bit-identical tokens)
@@ -444,6 +456,38 @@ class CoVoMixModel:
         out = self._t2s.generate(ids, uniforms=uniforms, max_length=max_length, temperature=float(temprature), generator=generator,
                                  cond_scale=float(cond_scale), filter_logits_fn=filter_logits_fn, filter_fn_kwargs=filter_fn_kwargs, **rule_kw)
         return out.to(ids.device) if ids.device != out.device else out
+
+    @staticmethod
+    def _select_candidates(res, N: int, eos: int, select: str) -> list:
+        """Per utterance the index best-of-N keeps among its N candidates res[j * N : (j + 1) * N] ((flat, streams, logprobs) tuples)."""
+        from .t2s import best_candidate, consensus_candidate, consensus_risks, sequence_logprob
+        groups = [res[j:j + N] for j in range(0, len(res), N)]
+        scores = [[sequence_logprob(c[2], c[1], eos) for c in cand] for cand in groups]
+        if select == "logprob":
+            return [best_candidate(sc) for sc in scores]
+        return [consensus_candidate(r, sc) for r, sc in zip(consensus_risks(groups, eos), scores)]
+
+    @ops.gated
+    @torch.no_grad()
+    def evaluate_text2semantic(self, grapheme_token_ids, gt_tokens, **sampling_kw):
+        """reference covomix/util/inference.py:287-358 (evaluate_text2semantic) on texts and ground-truth tokens that are already loaded:
+        LISTS of id tensors and of 1-D int64 token tensors -> (0.0, mean token error rate) - the reference's return shape, its accuracy
+        being the constant 0.  Every text is decoded through t2s.generate_many (synthesis_sample_text2semantic with a list;
+        **sampling_kw are its keywords); a two-output model's prediction is the first half of the flat result (len // 2, as the
+        reference cuts it); t2s.token_error_rate runs all pairs in one launch and the mean is taken in fp64 on the host."""
+        from .t2s import _dims, token_error_rate
+        if not self.is_text2semantic:
+            raise TypeError("this checkpoint is an acoustic model")
+        if not isinstance(grapheme_token_ids, (list, tuple)) or not isinstance(gt_tokens, (list, tuple)) or \
+                len(grapheme_token_ids) != len(gt_tokens) or not grapheme_token_ids:
+            raise ValueError("evaluate_text2semantic: a non-empty list of texts and an equally long list of ground-truth token tensors")
+        if sampling_kw.get("return_logprobs"):
+            raise ValueError("evaluate_text2semantic: return_logprobs is not a sampling setting of the metric")
+        preds = self.synthesis_sample_text2semantic(list(grapheme_token_ids), **sampling_kw)
+        if _dims(self.active_state_dict())["streams"] == 2:
+            preds = [p[:p.shape[0] // 2] for p in preds]
+        rates = token_error_rate([p.reshape(-1) for p in preds], [torch.as_tensor(g).reshape(-1) for g in gt_tokens])
+        return 0.0, float(torch.tensor(rates, dtype=torch.float64).mean())
 
     @ops.gated
     @torch.no_grad()

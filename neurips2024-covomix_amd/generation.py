@@ -108,6 +108,10 @@ def build_parser() -> ArgumentParser:
                    "steps")
     p.add_argument("--t2s_best_of", type=int, default=1, help="extension: decode this many candidates per turn through the continuously "
                    "refilled slots and keep the one the model finds most likely (largest mean token log-probability; 1 = off: today's files)")
+    p.add_argument("--t2s_best_of_select", choices=("logprob", "mbr"), default="logprob", help="extension: the rule --t2s_best_of keeps a "
+                   "candidate by - logprob: the largest mean token log-probability (today's files); mbr: consensus (minimum Bayes risk) - the "
+                   "candidate with the smallest total edit distance to the turn's other candidates, ties to the larger log-probability; "
+                   "needs --t2s_best_of > 1 or --t2s_best_of_temperatures")
     p.add_argument("--t2s_best_of_temperatures", type=str, default=None, help="extension: T1,T2,... - --t2s_best_of with one temperature per "
                    "candidate: candidate c of every turn is decoded at temperature c (implies --t2s_best_of = their number)")
     p.add_argument("--t2s_mixed_guidance", action="store_true", help="extension: turns whose side files make some of them guided and "
@@ -282,7 +286,16 @@ def t2s_sampling_kwargs(args) -> dict:
             raise ValueError(f"--t2s_best_of {best_of} disagrees with the {len(temps)} --t2s_best_of_temperatures")
         kw["best_of_temperatures"] = temps
         best_of = len(temps)
+    select = getattr(args, "t2s_best_of_select", None) or "logprob"
+    if select not in ("logprob", "mbr"):
+        raise ValueError(f"--t2s_best_of_select {select}: logprob or mbr")
     beam = int(getattr(args, "t2s_beam_size", 0))
+    if select == "mbr":
+        if beam:
+            raise ValueError("--t2s_best_of_select mbr does not combine with --t2s_beam_size (consensus is over sampled candidates)")
+        if best_of < 2:
+            raise ValueError("--t2s_best_of_select mbr needs candidates to choose among: --t2s_best_of > 1 or --t2s_best_of_temperatures")
+        kw["best_of_select"] = "mbr"
     if beam:
         if not 1 <= beam <= 16:
             raise ValueError(f"--t2s_beam_size {beam}: 0 (sampling) or 1..16")

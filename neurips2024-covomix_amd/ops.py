@@ -1571,3 +1571,73 @@ def kmeans_argmin(x: torch.Tensor, dots: torch.Tensor, cnorm: torch.Tensor, with
     _lib.check(_lib.load().cvx_kmeans_argmin_f32(x.data_ptr(), dots.data_ptr(), cnorm.data_ptr(), labels.data_ptr(),
                                                  _p(margin), T, D, K, _stream()), "cvx_kmeans_argmin_f32")
     return (labels, margin) if with_margin else labels
+
+
+EDIT_MAX_LEN = _lib.EDIT_MAX_LEN      # tokens per sequence of edit_distance (CVX_EDIT_MAX_LEN)
+
+
+def edit_distance_tables(lengths: Sequence[int], pairs) -> tuple:
+    """The two host tables of cvx_edit_distance_i64 for sequences packed back to back: items int32 [n, 2] (offset, length) and pairs
+    int32 [P, 2] (item a, item b).  ValueError for a length outside [0, EDIT_MAX_LEN], a pair that is no (i, j) of two sequence indices,
+    or a pool of 2^31 tokens or more."""
+    lens = [int(x) for x in lengths]
+    for i, n in enumerate(lens):
+        if not 0 <= n <= EDIT_MAX_LEN:
+            raise ValueError(f"edit_distance: sequence {i} has {n} tokens (0 ... {EDIT_MAX_LEN})")
+    if sum(lens) >= 1 << 31:
+        raise ValueError(f"edit_distance: {sum(lens)} tokens in one call (fewer than 2^31)")
+    offs, off = [], 0
+    for n in lens:
+        offs.append(off)
+        off += n
+    items = torch.tensor(list(zip(offs, lens)), dtype=torch.int32).reshape(-1, 2)
+    rows = []
+    for p, pr in enumerate(pairs):
+        if not isinstance(pr, (tuple, list)) or len(pr) != 2 or any(isinstance(x, bool) or not isinstance(x, int) for x in pr):
+            raise ValueError(f"edit_distance: pair {p} = {pr!r} is no (i, j) of two sequence indices")
+        if not (0 <= pr[0] < len(lens) and 0 <= pr[1] < len(lens)):
+            raise ValueError(f"edit_distance: pair {p} = {tuple(pr)} names a sequence outside the {len(lens)} of the call")
+        rows.append((pr[0], pr[1]))
+    return items, torch.tensor(rows, dtype=torch.int32).reshape(-1, 2)
+
+
+def edit_distance(sequences, pairs, device=None) -> torch.Tensor:
+    """Unit-cost Levenshtein distances (substitution, insertion, deletion: 1 each) between token sequences: out[p] = the distance between
+    sequences[i] and sequences[j] of pairs[p] = (i, j); int32 [len(pairs)] on the HOST.  sequences: 1-D int64 tensors of 0 ...
+    EDIT_MAX_LEN tokens, on the host or the device; pairs may repeat and may name one sequence twice.  One pooled upload (tokens and
+    both tables in one buffer), one launch (cvx_edit_distance_i64: a block per pair), one download.  Tokens are compared by their low 32
+    bits; host sequences with a value outside int32 are a ValueError.  No pairs: an empty result and no launch."""
+    seqs = list(sequences)
+    for i, q in enumerate(seqs):
+        if not isinstance(q, torch.Tensor) or q.dtype != torch.int64 or q.dim() != 1:
+            raise TypeError(f"edit_distance: sequence {i} must be a 1-D int64 tensor")
+    items, prs = edit_distance_tables([q.numel() for q in seqs], pairs)
+    if prs.shape[0] == 0:
+        return torch.zeros(0, dtype=torch.int32)
+    on_dev = [q for q in seqs if q.is_cuda]
+    if device is None:
+        device = on_dev[0].device if on_dev else torch.device("cuda")
+    device = torch.device(device)
+    if device.type != "cuda" or not torch.cuda.is_available():
+        raise _lib.CovomixHipError("edit_distance needs a GPU: covomix_amd has no CPU path")
+    lib = _lib.load()
+    n_tok, n_items, n_pairs = int(items[:, 1].sum()), items.shape[0], prs.shape[0]
+    tables = torch.cat((items.reshape(-1), prs.reshape(-1)))
+    with torch.cuda.device(device):
+        if not on_dev:
+            # tokens (int64) then the tables (int32 words) in ONE pinned buffer: one copy
+            pool = torch.empty(n_tok + (tables.numel() + 1) // 2, dtype=torch.int64).pin_memory()
+            if n_tok:
+                torch.cat(seqs, out=pool[:n_tok])
+                if int(pool[:n_tok].min()) < -(1 << 31) or int(pool[:n_tok].max()) >= 1 << 31:
+                    raise ValueError("edit_distance: token values outside int32")
+            pool[n_tok:].view(torch.int32)[:tables.numel()] = tables
+            pool_dev = pool.to(device, non_blocking=True)
+            tok_dev, tab_dev = pool_dev[:n_tok], pool_dev[n_tok:].view(torch.int32)
+        else:
+            tok_dev = torch.cat([q.to(device) for q in seqs]) if n_tok else torch.zeros(0, dtype=torch.int64, device=device)
+            tab_dev = h2d(tables, device)
+        out = torch.empty(n_pairs, dtype=torch.int32, device=device)
+        _lib.check(lib.cvx_edit_distance_i64(tok_dev.data_ptr(), n_tok, items.data_ptr(), tab_dev.data_ptr(), n_items, prs.data_ptr(),
+                                             tab_dev.data_ptr() + 8 * n_items, n_pairs, out.data_ptr(), _stream()), "cvx_edit_distance_i64")
+        return out.cpu()

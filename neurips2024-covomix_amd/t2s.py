@@ -8,7 +8,9 @@ filter_fn_kwargs, text2semantic.py:118-132, :796) - in every decode schedule bel
 reference's generate accepts without a body, text2semantic.py:673-677 - the algorithm is defined in include/covomix_hip.h; `generate_beam_many`:
 any number of utterances through continuously refilled groups of beam_size slots); no speculative
 decoding, no padded text batches.  Beside the tokens: the log-probability of every sampled token (return_logprobs), teacher-forced scoring of given tokens
-through the same decode slots (score_many) and the mean token log-probability best-of-N selects by (sequence_logprob).  And what looks at
+through the same decode slots (score_many) and the mean token log-probability best-of-N selects by (sequence_logprob).  What is counted from
+the edit distances between decoded token sequences (ops.edit_distance, csrc/edit_distance.hip): consensus selection among the candidates of
+best-of-N (consensus_risks, consensus_candidate) and the reference's validation metric (token_error_rate).  And what looks at
 the tokens an utterance has ALREADY emitted: the history rules - repetition penalty, no-repeat n-gram, minimum length (check_rules;
 cvx_t2s_decode_steps_rules) - per utterance and per output stream, in every sampled schedule; off by default.  Under beam search
 (beam_rules=True: check_beam_rules; cvx_t2s_beam_rules_steps) the last two remove candidates along every hypothesis' own ancestry.
@@ -91,9 +93,100 @@ def sequence_logprob(logprobs: torch.Tensor, streams: torch.Tensor, eos: int) ->
     if lp.shape != st.shape or lp.numel() == 0 or lp.ndim not in (1, 2):
         raise ValueError(f"sequence_logprob: logprobs {tuple(lp.shape)} and streams {tuple(st.shape)} must be the same non-empty [S, L]")
     lp, st = lp.reshape(-1, lp.shape[-1]), st.reshape(-1, st.shape[-1])
-    after = (st == eos).cumsum(dim=-1) > 0
-    counted = ~torch.nn.functional.pad(after, (1, -1), value=False)
+    counted = counted_mask(st, eos)
     return float(lp[counted].sum() / int(counted.sum()))
+
+
+def counted_mask(streams: torch.Tensor, eos: int) -> torch.Tensor:
+    """bool [S, L]: per stream the positions up to AND INCLUDING its first eos, all of them when it has none - the positions
+    sequence_logprob counts and counted_tokens returns."""
+    after = (streams == eos).cumsum(dim=-1) > 0
+    return ~torch.nn.functional.pad(after, (1, -1), value=False)
+
+
+def counted_tokens(streams, eos: int) -> list:
+    """Per stream of `streams` (int64 [S, L] or [L]) its counted tokens as a 1-D host tensor: the positions up to and including the first
+    eos, all positions when the stream has none (counted_mask: the set sequence_logprob averages over)."""
+    st = torch.as_tensor(streams).detach().cpu()
+    if st.ndim not in (1, 2) or st.dtype != torch.int64:
+        raise ValueError(f"counted_tokens: streams {tuple(st.shape)} {st.dtype} must be int64 [S, L] or [L]")
+    st = st.reshape(-1, st.shape[-1])
+    mask = counted_mask(st, eos)
+    return [row[m] for row, m in zip(st, mask)]
+
+
+def consensus_pairs(n_candidates: int, streams: int) -> list:
+    """The S N (N - 1) / 2 unordered pairs one utterance's risks are counted from, over its items in the order candidate-major,
+    stream-minor (item c * S + s): (c, c', s) for c < c'."""
+    return [(c * streams + s, c2 * streams + s) for c in range(n_candidates) for c2 in range(c + 1, n_candidates) for s in range(streams)]
+
+
+def consensus_risks(candidates, eos: int):
+    """Consensus (minimum-Bayes-risk) risks of the candidates of best-of-N: risk[c] = sum over the other candidates c' and the streams s
+    of the edit distance between counted_tokens(c)[s] and counted_tokens(c')[s].  `candidates`: the (flat, streams[, logprobs]) tuples of
+    ONE utterance -> list of N ints; or a LIST of such lists (utterances, which may differ in N) -> a list of lists, with the pairs of all
+    utterances in ONE ops.edit_distance launch.  The distance is symmetric, so every unordered pair is computed once."""
+    cands = list(candidates)
+    one = bool(cands) and isinstance(cands[0], tuple)
+    utts = [cands] if one else [list(u) for u in cands]
+    seqs, pairs, spans = [], [], []
+    for u in utts:
+        if not u:
+            raise ValueError("consensus_risks: an utterance without candidates")
+        toks = [counted_tokens(c[1], eos) for c in u]
+        S = len(toks[0])
+        if any(len(t) != S for t in toks):
+            raise ValueError("consensus_risks: the candidates of an utterance differ in their number of streams")
+        base = len(seqs)
+        seqs += [t for cand in toks for t in cand]
+        here = consensus_pairs(len(u), S)
+        spans.append((len(pairs), here, S))
+        pairs += [(base + a, base + b) for a, b in here]
+    dist = ops.edit_distance(seqs, pairs).tolist() if pairs else []
+    out = []
+    for u, (at, here, S) in zip(utts, spans):
+        risk = [0] * len(u)
+        for k, (a, b) in enumerate(here):
+            risk[a // S] += dist[at + k]
+            risk[b // S] += dist[at + k]
+        out.append(risk)
+    return out[0] if one else out
+
+
+def consensus_candidate(risks, scores) -> int:
+    """The index consensus selection keeps: the smallest risk; among equal risks the larger score under best_candidate's rule (a NaN
+    never wins against a number); among those the lowest index."""
+    risks, scores = [int(r) for r in risks], [float(x) for x in scores]
+    if not risks or len(risks) != len(scores):
+        raise ValueError(f"consensus_candidate: {len(risks)} risks and {len(scores)} scores")
+    low = min(risks)
+    tied = [c for c, r in enumerate(risks) if r == low]
+    return tied[best_candidate([scores[c] for c in tied])]
+
+
+def token_error_rate(pred, ref, pad: int = 501):
+    """The reference's validation metric of text2semantic (covomix/util/inference.py:287-358: jiwer.wer over the token strings after both
+    were padded with 501 to the longer length): edit distance(pred + pads, ref + pads) / padded length; two empty inputs give 0.0.
+    pred, ref: 1-D int64 tensors -> float; or lists of them (equally long) -> a list of floats from ONE ops.edit_distance launch (the
+    mean is the caller's)."""
+    one = isinstance(pred, torch.Tensor)
+    if one != isinstance(ref, torch.Tensor):
+        raise ValueError("token_error_rate: one prediction and one reference, or a list of each")
+    preds, refs = ([pred], [ref]) if one else (list(pred), list(ref))
+    if len(preds) != len(refs):
+        raise ValueError(f"token_error_rate: {len(preds)} predictions and {len(refs)} references")
+    seqs, lens = [], []
+    for p_, r_ in zip(preds, refs):
+        p_, r_ = (torch.as_tensor(x).detach().cpu().reshape(-1).to(torch.int64) for x in (p_, r_))
+        L = max(p_.numel(), r_.numel())
+        seqs += [torch.nn.functional.pad(x, (0, L - x.numel()), value=pad) for x in (p_, r_)]
+        lens.append(L)
+    live = [k for k, L in enumerate(lens) if L > 0]
+    dist = ops.edit_distance(seqs, [(2 * k, 2 * k + 1) for k in live]).tolist() if live else []
+    out = [0.0] * len(lens)
+    for k, d in zip(live, dist):
+        out[k] = d / lens[k]
+    return out[0] if one else out
 
 
 def best_candidate(scores) -> int:
