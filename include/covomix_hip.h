@@ -1213,6 +1213,40 @@ int cvx_t2s_prefill_guidance_f32(float* logits, const int32_t* null_row, const f
 int cvx_edit_distance_i64(const int64_t* tokens_dev, int64_t n_tokens, const int32_t* items_host, const int32_t* items_dev, int32_t n_items,
                           const int32_t* pairs_host, const int32_t* pairs_dev, int32_t n_pairs, int32_t* out_dev, cvx_stream_t s);
 
+/* DTW: dynamic time warping of many pairs of feature sequences in one launch - csrc/dtw.hip.
+ * Still ABI 113: one symbol and two constants added.  What the mel-cepstral distortion of the acoustic model's output against a target of another timing is counted with
+ * (metrics.py; the reference validates the acoustic model by a frame-wise F.mse_loss, covomix/util/inference.py:32-75, :151-227, which
+ * needs equal timing).
+ *   cost_dev[p], steps_dev[p] = the cost and the length (cells) of the best warping path between items a_p and b_p.
+ * frames fp32 [n_rows][ld] on the device; an ITEM is rows [first row, first row + frames), 0 <= frames <= CVX_DTW_MAX_FRAMES; items may
+ * overlap or repeat.  1 <= dim <= CVX_DTW_MAX_DIM, ld >= dim, ld % 4 == 0, frames_dev 16-byte aligned.  Columns [dim, ld) and rows outside
+ * every item may hold anything (NaN included): they are not read into a result.  items = int32 [n_items][2] (first row, frames), pairs =
+ * int32 [n_pairs][2] (item a, item b), each given twice as for cvx_edit_distance_i64: the HOST copy is validated before anything is
+ * launched and sizes the launch, the DEVICE copy is what the kernel reads; nothing is copied or allocated here, no host
+ * synchronisation, graph-capturable.
+ * The definition, fixed to the bit:
+ *   frame distance  c(i, j) = sqrt(sum_d (x_i[d] - y_j[d])^2), d ascending, the sum starting from +0, every subtraction, product, sum and
+ *                   the square root an individually rounded fp32 operation (no contraction).  Dimensions an instance pads behind dim
+ *                   add (0 - 0)^2 = +0, which changes no bit.
+ *   path            steps (i-1, j-1), (i-1, j), (i, j-1), unit weights, no window.  A cell carries (cost, steps):
+ *                   cost(i, j) = c(i, j) + the smallest cost among its predecessors (one rounded fp32 sum), steps(i, j) = 1 + the
+ *                   SMALLEST steps among the predecessors of that cost - a lexicographic minimum on (cost, steps).  Cell (0, 0) is
+ *                   (c(0, 0), 1).  The rule is symmetric: a pair and its swap give the same bits.
+ *   result          the last cell; (0.0f, 0) if either item has no frame.  Non-finite features leave that pair's result unspecified
+ *                   (no other pair's, and nothing is read out of bounds).
+ * A pair's result depends on its two items alone: not on its place in the table, its neighbours, or the width dim is padded to.
+ * One block per pair, TWO stores per pair, no global scratch, no atomics, no private segment.
+ * CVX_EINVAL, nothing launched and the outputs untouched: a negative count; dim outside [1, CVX_DTW_MAX_DIM]; ld < dim or ld % 4 != 0;
+ * frames_dev not 16-byte aligned; an item with first row < 0, frames outside [0, CVX_DTW_MAX_FRAMES] or first row + frames > n_rows; a
+ * pair index outside [0, n_items); a NULL table; with n_pairs > 0 a NULL device pointer.  n_pairs == 0 is a successful call without a
+ * launch.  A block whose DEVICE rows break these bounds (the device copy is not the host copy) reads no frame and stores (NaN, -1). */
+#define CVX_DTW_MAX_FRAMES 4096
+#define CVX_DTW_MAX_DIM 80
+int cvx_dtw_f32(const float* frames_dev, int64_t n_rows, int64_t ld, int32_t dim,
+                const int32_t* items_host, const int32_t* items_dev, int32_t n_items,
+                const int32_t* pairs_host, const int32_t* pairs_dev, int32_t n_pairs,
+                float* cost_dev, int32_t* steps_dev, cvx_stream_t s);
+
 /* The filter + sampling of one decode step alone (the device function cvx_t2s_decode_steps samples with; no slot state, no queue, no
  * embedding write): tokens[r] = argmax_i (kept(r, i) ? logits[r, i] / max(temperature, 1e-10) + gumbel(uniforms[r, i]) : -inf), lowest
  * index on ties, gumbel(u) = -log(-log(u)) with both logarithms clamped at 1e-20 (text2semantic.py:105-113).  logits, uniforms

@@ -182,6 +182,8 @@ class T2SRules(C.Structure):
 T2S_RULES_WORDS = 4                              # 32-bit words per row of that table
 T2S_RULES_MAX_NGRAM = 8
 EDIT_MAX_LEN = 4096                              # CVX_EDIT_MAX_LEN: tokens per item of cvx_edit_distance_i64
+DTW_MAX_FRAMES = 4096                            # CVX_DTW_MAX_FRAMES: frames per item of cvx_dtw_f32
+DTW_MAX_DIM = 80                                 # CVX_DTW_MAX_DIM: features per frame
 
 
 class T2SPrefillAttention(C.Structure):
@@ -281,6 +283,8 @@ SIGNATURES = {
     "cvx_t2s_prefill_guidance_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]),
     "cvx_edit_distance_i64": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
                                         C.c_void_p]),
+    "cvx_dtw_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,
+                              C.c_void_p, C.c_void_p, C.c_void_p]),
     "cvx_t2s_sample_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float,
                                      C.c_void_p, C.c_void_p, C.c_void_p]),
     "cvx_geglu_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_void_p]),

@@ -491,6 +491,49 @@ class CoVoMixModel:
 
     @ops.gated
     @torch.no_grad()
+    def evaluate_acoustic(self, phoneme_ids, cond_mels, gt_mels=None, region=("head", 0.7), cond_scale=0.7, y0=None, mcd=False):
+        """reference covomix/util/inference.py:32-75 (evaluate_acoustic_predictor_hubert) and :151-227 (..._2input_1output, without
+        repeat_prompt) on utterances that are already loaded: LISTS of token tensors [T_i(, streams)], of conditioning mels [T_i, C] and
+        (optional; default = cond_mels) of ground-truth mels [T_i, dim_out], of any lengths -> (0.0, mean MSE) - the reference's return
+        shape, its accuracy being the constant 0.  The split index of an utterance is int(T_i * fraction), as the reference computes it.
+        region = ("head", f): the first part is generated and the rest stays as the prompt (:55-68, f = 0.7); ("tail", f): the rest
+        is generated and the first part stays (:191-220, f = 0.5, gt_mels = the mix mel).  The conditioning is the mel with the
+        generated part zeroed; ONE ragged synthesis_sample call runs all utterances (y0, a list, is passed through); the MSE of an
+        utterance is F.mse_loss over its generated part, the mean over utterances is taken in fp64 on the host.  mcd=True: a third
+        value, the per-utterance mel-cepstral distortion of the generated part without alignment (float64 [n] in dB,
+        metrics.mel_cepstral_distortion(align="none"): this project's definition, see metrics.py)."""
+        from .metrics import mel_cepstral_distortion, mel_mse
+        if self.is_text2semantic:
+            raise TypeError("this checkpoint is a text2semantic model")
+        lists = [phoneme_ids, cond_mels] + ([gt_mels] if gt_mels is not None else []) + ([y0] if y0 is not None else [])
+        if not all(isinstance(x, (list, tuple)) for x in lists) or len(set(len(x) for x in lists)) != 1 or not phoneme_ids:
+            raise ValueError("evaluate_acoustic: non-empty, equally long lists of token tensors, conditioning mels (and ground-truth mels, y0)")
+        if not (isinstance(region, (list, tuple)) and len(region) == 2 and region[0] in ("head", "tail") and 0.0 <= float(region[1]) <= 1.0):
+            raise ValueError(f"evaluate_acoustic: region = {region!r} (('head' | 'tail', a fraction in [0, 1]))")
+        head, frac = region[0] == "head", float(region[1])
+        gts = list(cond_mels) if gt_mels is None else list(gt_mels)
+        conds, parts = [], []
+        for i, (ids, c, g) in enumerate(zip(phoneme_ids, cond_mels, gts)):
+            if c.shape[0] != ids.shape[0] or g.shape[0] != ids.shape[0]:
+                raise ValueError(f"evaluate_acoustic: utterance {i} has {ids.shape[0]} tokens, {c.shape[0]} and {g.shape[0]} mel frames")
+            k = int(len(ids) * frac)
+            parts.append(slice(0, k) if head else slice(k, ids.shape[0]))
+            c = c.clone()
+            c[parts[-1]] = 0
+            conds.append(c.to(self.device))
+        preds = self.synthesis_sample([p.to(self.device) for p in phoneme_ids], conds, None, cond_scale, y0=y0)
+        gen = [p[s] for p, s in zip(preds, parts)]
+        want = [g[s].to(p.device) for g, p, s in zip(gts, preds, parts)]
+        for i, (a, b) in enumerate(zip(gen, want)):
+            if a.shape != b.shape:
+                raise ValueError(f"evaluate_acoustic: utterance {i} generates {tuple(a.shape)} against a ground truth of {tuple(b.shape)}")
+        mse = float(torch.stack([m.double().cpu() for m in mel_mse(gen, want)]).mean())
+        if not mcd:
+            return 0.0, mse
+        return 0.0, mse, mel_cepstral_distortion([a.contiguous() for a in gen], [b.contiguous() for b in want], align="none")[0]
+
+    @ops.gated
+    @torch.no_grad()
     def score_text2semantic(self, grapheme_token_ids, streams, cond_scale=1.0, mixed_guidance=False, prefill=False):
         """Teacher-forced scoring (extension; what the reference's evaluate_text2semantic measures through
         TextToSemantic.forward(..., return_loss=True)): the log-probability of every token of `streams` - int64 [S, L], the streams a

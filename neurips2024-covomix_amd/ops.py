@@ -1641,3 +1641,90 @@ def edit_distance(sequences, pairs, device=None) -> torch.Tensor:
         _lib.check(lib.cvx_edit_distance_i64(tok_dev.data_ptr(), n_tok, items.data_ptr(), tab_dev.data_ptr(), n_items, prs.data_ptr(),
                                              tab_dev.data_ptr() + 8 * n_items, n_pairs, out.data_ptr(), _stream()), "cvx_edit_distance_i64")
         return out.cpu()
+
+
+DTW_MAX_FRAMES = _lib.DTW_MAX_FRAMES  # frames per sequence of dtw (CVX_DTW_MAX_FRAMES)
+DTW_MAX_DIM = _lib.DTW_MAX_DIM        # features per frame (CVX_DTW_MAX_DIM)
+
+
+def dtw_tables(lengths: Sequence[int], pairs) -> tuple:
+    """The two host tables of cvx_dtw_f32 for feature sequences packed back to back: items int32 [n, 2] (first row, frames) and pairs
+    int32 [P, 2] (item a, item b).  ValueError for a length outside [0, DTW_MAX_FRAMES], a pair that is no (i, j) of two sequence
+    indices, or a pool of 2^31 rows or more."""
+    lens = [int(x) for x in lengths]
+    for i, n in enumerate(lens):
+        if not 0 <= n <= DTW_MAX_FRAMES:
+            raise ValueError(f"dtw: sequence {i} has {n} frames (0 ... {DTW_MAX_FRAMES})")
+    if sum(lens) >= 1 << 31:
+        raise ValueError(f"dtw: {sum(lens)} frames in one call (fewer than 2^31)")
+    rows, row = [], 0
+    for n in lens:
+        rows.append(row)
+        row += n
+    items = torch.tensor(list(zip(rows, lens)), dtype=torch.int32).reshape(-1, 2)
+    out = []
+    for p, pr in enumerate(pairs):
+        if not isinstance(pr, (tuple, list)) or len(pr) != 2 or any(isinstance(x, bool) or not isinstance(x, int) for x in pr):
+            raise ValueError(f"dtw: pair {p} = {pr!r} is no (i, j) of two sequence indices")
+        if not (0 <= pr[0] < len(lens) and 0 <= pr[1] < len(lens)):
+            raise ValueError(f"dtw: pair {p} = {tuple(pr)} names a sequence outside the {len(lens)} of the call")
+        out.append((pr[0], pr[1]))
+    return items, torch.tensor(out, dtype=torch.int32).reshape(-1, 2)
+
+
+def dtw(features, pairs, device=None) -> tuple:
+    """Dynamic time warping between feature sequences: for pairs[p] = (i, j) the cost (sum of the Euclidean frame distances) and the
+    length in cells of the best warping path between features[i] and features[j], steps (i-1, j-1), (i-1, j), (i, j-1) at unit weight,
+    no window; among the paths of the smallest cost the shortest one is counted.  -> (cost float32 [P], steps int32 [P]) on the HOST.
+    The arithmetic is fixed to the bit (include/covomix_hip.h, "DTW").  features: 2-D fp32 tensors [T_i, D] of one D, 1 <= D <=
+    DTW_MAX_DIM, 0 <= T_i <= DTW_MAX_FRAMES, on the host or the device; pairs may repeat and may name one sequence twice; a sequence
+    without frames gives (0, 0).  One pooled upload (the frames, rows padded to a multiple of 4 floats, and both tables in one buffer),
+    one launch (cvx_dtw_f32: a block per pair), one download.  TypeError / ValueError: a wrong dtype or rank, mixed D, a D or a length
+    outside the limits, a bad pair, a non-finite value in a HOST feature (device features are not looked at: their pair's result is
+    unspecified).  No pairs: empty results and no launch."""
+    feats = list(features)
+    for i, f in enumerate(feats):
+        if not isinstance(f, torch.Tensor) or f.dtype != torch.float32 or f.dim() != 2:
+            raise TypeError(f"dtw: sequence {i} must be a 2-D float32 tensor [frames, D]")
+    dims = sorted(set(f.shape[1] for f in feats))
+    if len(dims) > 1:
+        raise ValueError(f"dtw: sequences of different feature sizes {dims} in one call")
+    if dims and not 1 <= dims[0] <= DTW_MAX_DIM:
+        raise ValueError(f"dtw: {dims[0]} features per frame (1 ... {DTW_MAX_DIM})")
+    items, prs = dtw_tables([f.shape[0] for f in feats], pairs)
+    for i, f in enumerate(feats):
+        if not f.is_cuda and f.numel() and not bool(torch.isfinite(f).all()):
+            raise ValueError(f"dtw: sequence {i} holds a non-finite value")
+    if prs.shape[0] == 0:
+        return torch.zeros(0, dtype=torch.float32), torch.zeros(0, dtype=torch.int32)
+    on_dev = [f for f in feats if f.is_cuda]
+    if device is None:
+        device = on_dev[0].device if on_dev else torch.device("cuda")
+    device = torch.device(device)
+    if device.type != "cuda" or not torch.cuda.is_available():
+        raise _lib.CovomixHipError("dtw needs a GPU: covomix_amd has no CPU path")
+    lib = _lib.load()
+    D = dims[0]
+    ld = (D + 3) // 4 * 4
+    n_rows, n_items, n_pairs = int(items[:, 1].sum()), items.shape[0], prs.shape[0]
+    tables = torch.cat((items.reshape(-1), prs.reshape(-1)))
+    with torch.cuda.device(device):
+        if not on_dev:
+            # the frames (fp32, rows of ld floats) then the tables (int32 words) in ONE pinned buffer: one copy
+            pool = torch.zeros(n_rows * ld + tables.numel(), dtype=torch.float32).pin_memory()
+            if n_rows:
+                pool[:n_rows * ld].view(n_rows, ld)[:, :D].copy_(torch.cat(feats))
+            pool[n_rows * ld:].view(torch.int32).copy_(tables)
+            pool_dev = pool.to(device, non_blocking=True)
+            frames_dev, tab_dev = pool_dev[:n_rows * ld], pool_dev[n_rows * ld:].view(torch.int32)
+        else:
+            frames_dev = torch.zeros(max(n_rows, 1), ld, dtype=torch.float32, device=device)
+            if n_rows:
+                frames_dev[:n_rows, :D] = torch.cat([f.to(device) for f in feats])
+            tab_dev = h2d(tables, device)
+        out = torch.empty(2 * n_pairs, dtype=torch.int32, device=device)         # cost (fp32 bits) then steps: one download
+        _lib.check(lib.cvx_dtw_f32(frames_dev.data_ptr(), n_rows, ld, D, items.data_ptr(), tab_dev.data_ptr(), n_items, prs.data_ptr(),
+                                   tab_dev.data_ptr() + 8 * n_items, n_pairs, out.data_ptr(), out.data_ptr() + 4 * n_pairs, _stream()),
+                   "cvx_dtw_f32")
+        host = out.cpu()
+        return host[:n_pairs].view(torch.float32).clone(), host[n_pairs:].clone()
