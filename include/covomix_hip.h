@@ -1247,6 +1247,51 @@ int cvx_dtw_f32(const float* frames_dev, int64_t n_rows, int64_t ld, int32_t dim
                 const int32_t* pairs_host, const int32_t* pairs_dev, int32_t n_pairs,
                 float* cost_dev, int32_t* steps_dev, cvx_stream_t s);
 
+/* ONE NETWORK EVALUATION WITH A TIME PER SEQUENCE, and the flow-matching loss on it - csrc/flow_loss.hip.
+ * Still ABI 113: three symbols and one constant added.  The conditional-flow-matching loss of held-out mels (reference acoustic.py:732-791 on
+ * CoVoMix.forward(..., target = flow), :430-538) evaluates the network once with a different time for every utterance of a PACKED
+ * batch (sequence i owns rows [cu[i], cu[i + 1]) of every [rows, width] tensor).  cu = int32 [n_seq + 1], given twice as the tables of
+ * cvx_dtw_f32 are: the HOST copy is validated before anything is launched and sizes the launches, the DEVICE copy is what the kernels
+ * search; 1 <= n_seq <= CVX_SEQ_NORM_MAX_SEQS, 0 <= cu[0], cu non-decreasing (a sequence may be empty), cu[n_seq] <= rows < 2^31.  Rows
+ * outside [cu[0], cu[n_seq]) are neither read nor written.  A kernel whose DEVICE copy differs from the host copy still touches only
+ * rows of that range and table rows [0, n_seq).  No copy, no allocation, no host synchronisation: graph-capturable.  All three are
+ * row-local streaming kernels (one wavefront per row, the row's sequence from a wave-uniform binary search): no private segment, no
+ * global scratch, no atomics (the saturation commit of a split-pair store apart).
+ * CVX_EINVAL, nothing launched and every output untouched: a NULL pointer that is not optional, a bad shape, a table that breaks the
+ * rules above, or what the individual entries name. */
+#define CVX_SEQ_NORM_MAX_SEQS 4096
+/* cvx_adarmsnorm_scaled_f32 with ONE GAMMA / BETA ROW PER SEQUENCE: row r of sequence g is normalised with gamma + g * group_stride
+ * (and beta + g * group_stride; beta may be NULL) - group_stride >= D, a multiple of 4 floats, so that an [n_seq, depth, 4, D] table of
+ * adaptive-norm rows is read in place.  The arithmetic per row, the fp32 output, the plain and the interleaved (y_lo == y_hi + 32,
+ * D % 32 == 0) split outputs, split_scale_dev and the saturation flag are those of cvx_adarmsnorm_scaled_f32, operation for operation: a
+ * sequence's rows are BIT-IDENTICAL to that entry called on the sequence's slice with its own gamma / beta row.  x, gamma, beta, y
+ * 16-byte aligned, D % 4 == 0. */
+int cvx_adarmsnorm_seq_f32(const float* x, const float* gamma, const float* beta, float* y, uint16_t* y_hi, uint16_t* y_lo,
+                           int64_t rows, int32_t D, const int32_t* cu_host, const int32_t* cu_dev, int32_t n_seq, int64_t group_stride,
+                           float scale, float eps, const float* split_scale_dev, cvx_stream_t s);
+/* The inputs of the loss evaluation in one launch: with t = times_dev[g] for a row of sequence g and m = mask[row] (uint8, != 0: a
+ * frame the loss counts, whose conditioning is hidden),
+ *   w       [rows, dim_out]  = (1 - (1 - sigma) t) x0 + t x1       acoustic.py:773
+ *   flow    [rows, dim_out]  = x1 - (1 - sigma) x0                  :775
+ *   cond_in [rows, dim_cond] = m ? +0 : cond                        :469 (cond * ~mask)
+ * every operation an individually rounded fp32 operation in exactly that order: a = 1 - sigma; b = a t; c = 1 - b; w = c x0 + t x1 (two
+ * products, one sum); flow = x1 - a x0.  No contraction.  dim_out and dim_cond positive multiples of 4, the six row tensors 16-byte
+ * aligned, 0 <= sigma <= 1.  w may be a buffer of the network (the field's input). */
+int cvx_cfm_inputs_f32(const float* x1, const float* x0, const float* cond, const uint8_t* mask, const float* times_dev,
+                       const int32_t* cu_host, const int32_t* cu_dev, int32_t n_seq, int64_t rows, int32_t dim_out, int32_t dim_cond,
+                       float sigma, float* w, float* flow, float* cond_in, cvx_stream_t s);
+/* The masked mean-squared error per sequence (acoustic.py:527-536), two launches:
+ *   err_rows[r] = (sum_d (pred[r, d] - flow[r, d])^2) / dim_out       for every row of the range.  One wavefront per row: lane l sums
+ *                 d = l, l + 64, ... in that order from +0, then the xor butterfly over 32, 16, 8, 4, 2, 1.
+ *   num[s]      = sum of err_rows over the rows of s with mask != 0   one block per sequence: thread t sums the rows t, t + 256, ...
+ *                 COUNTED FROM THE SEQUENCE'S FIRST ROW in that order from +0 (an unmasked row adds +0, whatever it holds), the
+ *                 butterfly, then the four wave sums as (w0 + w1) + (w2 + w3): ceil(T / 256) + 8 additions above any term.
+ *   count[s]    = the number of those rows;   loss[s] = num[s] / max((float)count[s], 1e-5f)      (an empty mask: 0)
+ * All individually rounded fp32 operations, no contraction.  A sequence's loss depends on its own rows alone - not on where it sits
+ * in the pool or on its neighbours.  loss fp32 [n_seq], count int32 [n_seq], err_rows fp32 [rows]. */
+int cvx_masked_mse_f32(const float* pred, const float* flow, const uint8_t* mask, const int32_t* cu_host, const int32_t* cu_dev,
+                       int32_t n_seq, int64_t rows, int32_t dim_out, float* err_rows, float* loss, int32_t* count, cvx_stream_t s);
+
 /* The filter + sampling of one decode step alone (the device function cvx_t2s_decode_steps samples with; no slot state, no queue, no
  * embedding write): tokens[r] = argmax_i (kept(r, i) ? logits[r, i] / max(temperature, 1e-10) + gumbel(uniforms[r, i]) : -inf), lowest
  * index on ties, gumbel(u) = -log(-log(u)) with both logarithms clamped at 1e-20 (text2semantic.py:105-113).  logits, uniforms

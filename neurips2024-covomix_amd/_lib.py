@@ -184,6 +184,7 @@ T2S_RULES_MAX_NGRAM = 8
 EDIT_MAX_LEN = 4096                              # CVX_EDIT_MAX_LEN: tokens per item of cvx_edit_distance_i64
 DTW_MAX_FRAMES = 4096                            # CVX_DTW_MAX_FRAMES: frames per item of cvx_dtw_f32
 DTW_MAX_DIM = 80                                 # CVX_DTW_MAX_DIM: features per frame
+SEQ_NORM_MAX_SEQS = 4096                         # CVX_SEQ_NORM_MAX_SEQS: sequences of a packed batch with a time per sequence
 
 
 class T2SPrefillAttention(C.Structure):
@@ -285,6 +286,12 @@ SIGNATURES = {
                                         C.c_void_p]),
     "cvx_dtw_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,
                               C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cvx_adarmsnorm_seq_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p,
+                                         C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_float, C.c_void_p, C.c_void_p]),
+    "cvx_cfm_inputs_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64,
+                                     C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cvx_masked_mse_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.c_void_p]),
     "cvx_t2s_sample_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float,
                                      C.c_void_p, C.c_void_p, C.c_void_p]),
     "cvx_geglu_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_void_p]),

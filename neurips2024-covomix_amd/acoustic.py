@@ -18,6 +18,7 @@ Python here only sequences kernel launches on torch's current stream and owns de
 """
 from __future__ import annotations
 
+import dataclasses
 from dataclasses import dataclass, field
 from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple, Union
 
@@ -79,6 +80,13 @@ def route(M: int, dim: int, precision: str, ragged_rows: Optional[int] = None) -
     q = VectorField.RAGGED_ROW_QUANTUM
     return Route(split_io, interleaved, split_io and M < FUSE_NORM_BELOW_ROWS, split_io and M <= ops.SPLITK_SCRATCH_MAX_ROWS, deferred,
                  graph, None if ragged_rows is None else (ragged_rows + q - 1) // q * q)
+
+
+def route_seq_times(M: int, dim: int, precision: str, ragged_rows: Optional[int] = None) -> Route:
+    """The route of ONE evaluation with a time per sequence (VectorField.evaluate_seq_times): route()'s record with the three forms off
+    that need one gamma / beta row for all rows (fuse_norm: the fused-norm GEMMs take one row), per-time weight copies (deferred: gamma(t)
+    is baked into them) or a replay that would pay for itself (graph: one evaluation is launched once).  Pure, like route()."""
+    return dataclasses.replace(route(M, dim, precision, ragged_rows), fuse_norm=False, deferred=False, graph=False)
 
 
 class _Linear(NamedTuple):
@@ -317,12 +325,17 @@ class VectorField:
 
     # ------------------------------------------------------------------ per-call setup
     def prepare(self, phoneme_ids: torch.Tensor, cond: torch.Tensor, times: torch.Tensor, use_null: bool,
-                lengths: Optional[List[int]] = None, times_key=None) -> dict:
+                lengths: Optional[List[int]] = None, times_key=None, seq_times: bool = False) -> dict:
         """Everything that does not depend on the ODE state x:
         time MLP + adaptive-norm tables for every evaluation time (_time_tables: computed once per solver grid `times_key` and
         model), and the step-invariant part of to_embed.
         lengths: ragged batch - phoneme_ids [M1(, S)] and cond [M1, C] hold the utterances back to back (M1 = sum(lengths));
-        the null-branch rows repeat the same sequence structure behind them."""
+        the null-branch rows repeat the same sequence structure behind them.
+        seq_times: `times` holds one time PER UTTERANCE of a ragged batch for ONE evaluation (evaluate(ctx, 0)) instead of one per
+        evaluation: the route is route_seq_times', the tables are built for these times and not cached, ctx["seq"] (the batch's
+        Ragged) makes the layer walkers take every adaptive norm's gamma / beta row per sequence (_norm), and the activation
+        pre-scales - one scalar per (layer, kind) for the whole evaluation - are the smallest over the utterances' times: the
+        largest modelled RMS (H takes the maximum already)."""
         d, sd = self.d, self.sd
         rg = None
         if lengths is not None:
@@ -334,6 +347,9 @@ class VectorField:
             M1 = B * T
         Bt, M = (2 * B, 2 * M1) if use_null else (B, M1)
         r = self.route(M, ragged_rows=None if rg is None else M)   # from the real row count: read here, by _workspace and by evaluate()
+        if seq_times:
+            assert rg is not None and times.numel() == B, "a time per utterance goes with a packed batch and one time for each"
+            r = route_seq_times(M, d["dim"], self.precision, M)
         if rg is not None:
             full = self._workspace(0, 0, M, r)
             ws = self._ws_cut(full, 0, M, vt=None)               # row views of the capacity-sized buffers; V^T stays whole
@@ -341,7 +357,13 @@ class VectorField:
             ws["rope"] = self._rope_tables(rg.positions())       # per-ROW tables: the to_qkv epilogue then runs with rope_T = M
         else:
             ws = self._workspace(Bt, T, r=r)
-        tt = self._time_tables(times, times_key)
+        tt = self._time_tables(times, None if seq_times else times_key)
+        if seq_times:
+            tt = dict(tt, table=tt["table"].repeat(2, 1) if use_null else tt["table"])      # the null-branch sequences repeat the times
+            if "S" in tt:
+                S = tt["S"].amin(dim=0, keepdim=True).contiguous()
+                p0, K = S.data_ptr(), self.N_KINDS
+                tt.update(S=S, sp=[[[p0 + 4 * (i * K + k) for k in range(K)] for i in range(d["depth"])]])
         # step-invariant to_embed columns: rows [0, M1) conditional, rows [M1, 2*M1) null branch
         g = ws["gathered"]
         ids = phoneme_ids.to(torch.int64).contiguous()
@@ -352,7 +374,7 @@ class VectorField:
                              d["null_id"], g[M1:], M1)
         rest = self.embed_rest
         ops.gemm(g, rest.w, ws["base"], bias=rest.bias, w_split=rest.split)
-        ctx = dict(ws=ws, table=tt["table"], B=B, T=T, Bt=Bt, M1=M1, use_null=use_null, M=M, ragged=rg, route=r)
+        ctx = dict(ws=ws, table=tt["table"], B=B, T=T, Bt=Bt, M1=M1, use_null=use_null, M=M, ragged=rg, route=r, seq=rg if seq_times else None)
         if "S" in tt:
             ctx["scales"], ctx["h_scale"] = tt["S"], tt["H"]                   # keep the tensors alive as long as the pointers
             ctx["sp"], ctx["hp"] = tt["sp"], tt["H"].data_ptr()
@@ -542,6 +564,48 @@ class VectorField:
             return self._head(ctx, self._layers_pair_stream(ctx, step, h, twin, free), False)
         return self._head(ctx, *self._layers_split(ctx, step, h, twin, free, r.fuse_norm))
 
+    def _norm_rows(self, ctx: dict, step: int) -> torch.Tensor:
+        """The adaptive-norm rows of evaluation #step as [depth, 4, ...]: [dim] each - or, with a time per sequence (ctx["seq"]),
+        [n sequences, dim] views of the [n, depth, 4, dim] table, a sequence's rows depth * 4 * dim floats apart."""
+        d = self.d
+        if ctx.get("seq") is None:
+            return ctx["table"][step].view(d["depth"], 4, d["dim"])
+        assert step == 0
+        return ctx["table"].view(-1, d["depth"], 4, d["dim"]).permute(1, 2, 0, 3)
+
+    @staticmethod
+    def _norm(ctx: dict, h: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, out, **kw):
+        """One adaptive norm of the layer walkers: one gamma / beta row for all rows, or one per sequence (ctx["seq"], _norm_rows)."""
+        if ctx.get("seq") is None:
+            return ops.adarmsnorm(h, gamma, beta, out, **kw)
+        return ops.adarmsnorm_seq(h, gamma, beta, out, ctx["seq"], **kw)
+
+    def xin_rows(self, lengths: Sequence[int], use_null: bool = False) -> torch.Tensor:
+        """The conditional rows [sum(lengths), dim_out] of the input buffer evaluate_seq_times will run this batch on: a producer
+        (ops.cfm_inputs) that writes them there saves the copy."""
+        M1 = int(sum(lengths))
+        M = 2 * M1 if use_null else M1
+        return self._workspace(0, 0, M, route_seq_times(M, self.d["dim"], self.precision, M))["xin"][:M1]
+
+    def evaluate_seq_times(self, phoneme_ids: torch.Tensor, cond: torch.Tensor, x: torch.Tensor, times: torch.Tensor, lengths: Sequence[int],
+                           use_null: bool = False) -> torch.Tensor:
+        """ONE evaluation of the network on a packed batch with a TIME PER UTTERANCE (what the flow-matching loss and the reference's
+        sample_regression need, acoustic.py:768, :716): phoneme_ids [M1(, S)], cond [M1, C], x [M1, dim_out] hold the utterances back to
+        back (an equal-length batch is a packed one), times fp32 [len(lengths)] on the device.  use_null: the null-conditioning branch
+        runs behind the conditional rows at the same times.  Returns the workspace's pred [M1 or 2 M1, dim_out] (valid until the next
+        call on this field).  Route: route_seq_times - stand-alone norms (ops.adarmsnorm_seq), never deferred, never captured."""
+        lengths = [int(t) for t in lengths]
+        if not 1 <= len(lengths) * (2 if use_null else 1) <= ops.SEQ_NORM_MAX_SEQS:
+            raise ValueError(f"evaluate_seq_times: {len(lengths)} utterances{' and their null-branch twins' if use_null else ''} in one evaluation "
+                             f"(1 ... {ops.SEQ_NORM_MAX_SEQS} sequences)")
+        ctx = self.prepare(phoneme_ids, cond, times, use_null, lengths=lengths, seq_times=True)
+        xin, M1 = ctx["ws"]["xin"], ctx["M1"]
+        if x.data_ptr() != xin.data_ptr():
+            xin[:M1].copy_(x.reshape(M1, -1))
+        if use_null:
+            xin[M1:].copy_(xin[:M1])
+        return self.evaluate(ctx, 0)
+
     def _head(self, ctx: dict, h: torch.Tensor, normed_ahead: bool) -> torch.Tensor:
         """The final RMSNorm and to_pred.  normed_ahead: the last ff2 wrote the normed pair already (fuse_norm)."""
         ws = ctx["ws"]
@@ -557,7 +621,7 @@ class VectorField:
     def _layers_fp32(self, ctx: dict, step: int, h: torch.Tensor, free: list) -> torch.Tensor:
         """The layers on the fp32 residual stream with fp32 activations (no split I/O: up to SPLIT_IO_ABOVE_ROWS rows, 'fp32', odd widths)."""
         d, ws, Bt, T, rg = self.d, ctx["ws"], ctx["Bt"], ctx["T"], ctx["ragged"]
-        tab = ctx["table"][step].view(d["depth"], 4, d["dim"])
+        tab = self._norm_rows(ctx, step)
         skips: List[torch.Tensor] = []
         for i, (cb, qkv, out, ff1, ff2) in enumerate(self.layers):
             g_attn, b_attn, g_ff, b_ff = tab[i].unbind(0)
@@ -569,12 +633,12 @@ class VectorField:
                 ops.gemm(h, cb.w, comb, bias=cb.bias, w_split=cb.plain, a2=s)
                 free += [h, s]
                 h = comb
-            ops.adarmsnorm(h, g_attn, b_attn, ws["normed"])
+            self._norm(ctx, h, g_attn, b_attn, ws["normed"])
             ops.gemm(ws["normed"], qkv.w, ws["qkv"], w_split=qkv.plain, rope=ws["rope"], rope_cols=2 * d["heads"] * 64)
             ops.attention(ws["qkv"], ws["att"], Bt, T, d["heads"], 64 ** -0.5, ragged=rg)
             h_in, h = h, (free.pop() if keep_input else h)
             ops.gemm(ws["att"], out.w, h, w_split=out.plain, residual=h_in)
-            ops.adarmsnorm(h, g_ff, b_ff, ws["normed"])
+            self._norm(ctx, h, g_ff, b_ff, ws["normed"])
             ops.gemm(ws["normed"], ff1.w, ws["ff"], bias=ff1.bias, w_split=ff1.plain, act=ops.ACT_GELU)
             ops.gemm(ws["ff"], ff2.w, h, bias=ff2.bias, w_split=ff2.plain, residual=h)
         return h
@@ -585,7 +649,7 @@ class VectorField:
         that problems on the split-K path (one utterance) normalise inside the reduction (FUSE_NORM_BELOW_ROWS rows and more never
         split K: the call would run the same two kernels, so it stays two calls there)."""
         d, ws, Bt, T, rg = self.d, ctx["ws"], ctx["Bt"], ctx["T"], ctx["ragged"]
-        tab = ctx["table"][step].view(d["depth"], 4, d["dim"])
+        tab = self._norm_rows(ctx, step)
         sp_step, hp, pp = ctx["sp"][step], ctx["hp"], self.pred_scale.data_ptr()
         n16, a16, f16 = ws["normed16"], ws["att16"], ws["ff16"]
         normed_ahead = False                 # the attention norm of the layer about to start was produced by the previous GEMM
@@ -605,7 +669,7 @@ class VectorField:
                 free += [h, s]
                 h = comb
             if not normed_ahead:
-                ops.adarmsnorm(h, g_attn, b_attn, None, out_split=n16, split_scale=s_na)
+                self._norm(ctx, h, g_attn, b_attn, None, out_split=n16, split_scale=s_na)
             # q | k split row-major, v split + transposed, straight into the f16x3 attention (any T: sequences whose
             # length is not a multiple of 4 store their v columns 2 bytes at a time)
             ops.gemm(ws["normed"], qkv.w, ws["qkv"], w_split=qkv.split, w_il=qkv.il, rope=ws["rope"], rope_cols=2 * d["heads"] * 64, a_split=n16,
@@ -616,7 +680,7 @@ class VectorField:
             ops.gemm(ws["att"], out.w, h, w_split=out.split, w_il=out.il, residual=h_in, a_split=a16, a_scale=s_at,
                      norm=dict(gamma=g_ff, beta=b_ff, out_split=n16, scale=s_nf) if fuse_norm else None)
             if not fuse_norm:
-                ops.adarmsnorm(h, g_ff, b_ff, None, out_split=n16, split_scale=s_nf)
+                self._norm(ctx, h, g_ff, b_ff, None, out_split=n16, split_scale=s_nf)
             ops.gemm(ws["normed"], ff1.w, ws["ff"], bias=ff1.bias, w_split=ff1.split, w_il=ff1.il, act=ops.ACT_GELU, a_split=n16, out_split=f16,
                      write_f32=False, a_scale=s_nf, c_scale=s_ff)
             last = i + 1 == d["depth"]

@@ -532,6 +532,141 @@ class CoVoMixModel:
             return 0.0, mse
         return 0.0, mse, mel_cepstral_distortion([a.contiguous() for a in gen], [b.contiguous() for b in want], align="none")[0]
 
+    def _acoustic_dims(self) -> dict:
+        from .acoustic import _dims_from_state
+        if self.is_text2semantic:
+            raise TypeError("this checkpoint is a text2semantic model")
+        return _dims_from_state(self.active_state_dict())
+
+    def _run_unsaturated(self, run):
+        """run(field) under the saturation contract of synthesis_sample: one flag read per call; a flagged call on a split-precision field is
+        repeated on the exact-fp32 field (or raises: CVX_ON_SATURATION=raise) - run must be repeatable with the same draws."""
+        field = self._get_field()
+        checked = field.precision != "fp32" and ops.saturation_checked()
+        if checked:
+            ops.saturation_reset()
+        out = run(field)
+        if checked and ops.saturation_query():
+            out = run(self._saturated(field.precision))
+        return out
+
+    @ops.gated
+    @torch.no_grad()
+    def flow_matching_loss(self, phoneme_ids, mels, cond_mels=None, masks=None, times=None, x0=None, cond_drop=None, sigma=0.0, seed=None,
+                           max_rows=8192, return_pred=False):
+        """The conditional-flow-matching loss of held-out mels: the reference's `valid_loss` (conditional_model.py:229-271 ->
+        ConditionalFlowMatcherWrapper.forward, acoustic.py:732-791, on CoVoMix.forward(..., target = flow), :430-538) - ONE network
+        evaluation per utterance, at a time of its own.  LISTS of per-utterance tensors of any lengths: phoneme_ids[i] [T_i(, streams)],
+        mels[i] [T_i, dim_out] (x1), cond_mels[i] [T_i, dim_cond] (default: mels, as VoSingle trains), masks[i] bool [T_i] (True: the frame
+        is hidden from the conditioning and counted by the loss), times [n] in [0, 1], x0[i] [T_i, dim_out] (the noise), cond_drop [n] bools
+        (True: the utterance runs on the null phoneme id and null_cond, acoustic.py:473-494; default none - the reference's default
+        cond_drop_prob is 0), sigma (the wrapper's, default 0).  -> flow_loss.FlowLoss.
+        PER-UTTERANCE semantics: every utterance gets the reference's result at B = 1 (acoustic.py:527-538: the masked mean over its own
+        frames) and `loss` is the mean of those in fp64 - the reference pads a batch to its longest item without a padding mask, which
+        this project reproduces nowhere.  The caller's order is cut into packed launches of at most max_rows rows; per launch
+        ops.cfm_inputs, one VectorField.evaluate_seq_times and ops.masked_mse.
+        What is not passed is drawn from a CPU torch.Generator seeded with `seed`, utterance by utterance: time ~ U[0, 1), x0 ~ N(0, 1),
+        the mask of acoustic.py:460-465 (flow_loss.draw documents the order) - the reference's distributions, not its device RNG stream.
+        A mask without a True frame is no error: that utterance's loss is 0 through the clamp, as in the reference.
+        Saturation: as synthesis_sample - a flagged call on a split-precision field is repeated on the fp32 field with the same draws.
+        ValueError: unequal list lengths, an empty list, token / mel / mask / x0 shapes that disagree, a time outside [0, 1];
+        TypeError: a text2semantic checkpoint."""
+        from . import flow_loss as fl
+        d = self._acoustic_dims()
+        chk = fl.check_inputs(d, phoneme_ids, mels, cond_mels, masks, times, x0, cond_drop, sigma)
+        n, lengths, drop = chk["n"], chk["lengths"], chk["drop"]
+        launches = fl.cut_launches(lengths, max_rows, ops.SEQ_NORM_MAX_SEQS)
+        drawn = fl.draw(lengths, d["dim_out"], seed, need_times=times is None, need_x0=x0 is None, need_masks=masks is None)
+        tv = chk["times"] if times is not None else torch.tensor(drawn["times"], dtype=torch.float32)
+        x0 = list(x0) if x0 is not None else drawn["x0"]
+        masks = [m.cpu() for m in masks] if masks is not None else drawn["masks"]
+        f32 = lambda ts: torch.cat([t.detach().to(dtype=torch.float32).cpu().reshape(t.shape[0], -1) for t in ts]).contiguous()
+
+        def run(field):
+            dev = field.device
+            res = []
+            for rng in launches:
+                lens = [lengths[i] for i in rng]
+                ids = torch.cat([torch.full_like(phoneme_ids[i].cpu(), d["null_id"]) if drop[i] else phoneme_ids[i].cpu() for i in rng])
+                x1_d, x0_d, c_d = (ops.h2d(f32([src[i] for i in rng]), dev) for src in (mels, x0, chk["conds"]))
+                m_d = ops.h2d(torch.cat([masks[i] for i in rng]).to(torch.uint8), dev)
+                t_d = ops.h2d(tv[rng.start:rng.stop].contiguous(), dev)
+                rg = ops.Ragged(lens, dev)
+                _, flow, cond_in = ops.cfm_inputs(x1_d, x0_d, c_d, m_d, t_d, rg, float(sigma), field.xin_rows(lens))
+                for k, i in enumerate(rng):              # the null conditioning replaces the (already masked) one, acoustic.py:476
+                    if drop[i]:
+                        cond_in[rg.cu_host[k]:rg.cu_host[k + 1]] = field.sd["null_cond"]
+                pred = field.evaluate_seq_times(ops.h2d(ids.to(torch.int64), dev), cond_in, field.xin_rows(lens), t_d, lens)
+                loss, count, err = ops.masked_mse(pred, flow, m_d, rg)
+                res.append((loss.cpu(), count.cpu(), err.cpu(), pred.cpu() if return_pred else None, lens))
+            return res
+        res = self._run_unsaturated(run)
+        per = torch.cat([r[0] for r in res]).double()
+        err_rows, preds = [], []
+        for _, _, err, pred, lens in res:
+            err_rows += list(torch.split(err, lens))
+            if return_pred:
+                preds += list(torch.split(pred, lens))
+        return fl.FlowLoss(loss=float(per.mean()), per_utterance=per, frames=torch.cat([r[1] for r in res]).to(torch.int64), times=tv,
+                           masks=masks, err_rows=err_rows, pred=preds if return_pred else None)
+
+    @ops.gated
+    @torch.no_grad()
+    def synthesis_regression_duration(self, phoneme_ids, cond, mask, cond_scale, y0=None, times=None):
+        """The reference's one-shot regression sample (conditional_model.py synthesis_regression_duration ->
+        ConditionalFlowMatcherWrapper.sample_regression, acoustic.py:690-727): ONE guided evaluation f_c (1 + s) - s f_null of the network
+        on noise at a random time per utterance.  A batch (phoneme_ids [B, T(, streams)], cond [B, T, C]; -> [B, T, dim_out]) or LISTS of
+        per-utterance tensors of any lengths (-> a list); `mask` is accepted and unused, as in the reference.  y0 (the noise, default
+        randn) and times ([B] in [0, 1], default U[0, 1)) fix the draws; parity is defined given them.  One call holds at most
+        ops.SEQ_NORM_MAX_SEQS utterances, half as many under guidance (ValueError).  cond_scale == 1 runs the
+        conditional branch alone (acoustic.py:423).  One VectorField.evaluate_seq_times call on the packed batch, the branches combined
+        by the solve's combine kernel."""
+        d = self._acoustic_dims()
+        many = isinstance(cond, (list, tuple))
+        conds = list(cond) if many else list(cond.unbind(0))
+        idsl = list(phoneme_ids) if many else list(phoneme_ids.unbind(0))
+        n = len(conds)
+        if n == 0 or len(idsl) != n:
+            raise ValueError("synthesis_regression_duration: a non-empty batch of tokens and conditioning mels of the same size")
+        lengths = [int(c.shape[0]) for c in conds]
+        for i in range(n):
+            if conds[i].dim() != 2 or conds[i].shape[1] != d["dim_cond"] or lengths[i] < 1:
+                raise ValueError(f"synthesis_regression_duration: cond[{i}] must be [T >= 1, {d['dim_cond']}], got {tuple(conds[i].shape)}")
+            expect = (lengths[i],) + ((d["streams"],) if d["streams"] > 1 else ())
+            if tuple(idsl[i].shape) != expect:
+                raise ValueError(f"synthesis_regression_duration: phoneme_ids[{i}] must be {expect}, got {tuple(idsl[i].shape)}")
+        if y0 is None:
+            y0l = [torch.randn(T, d["dim_out"]) for T in lengths]
+        else:
+            y0l = list(y0) if many else list(y0.unbind(0))
+            if len(y0l) != n or any(tuple(y.shape) != (T, d["dim_out"]) for y, T in zip(y0l, lengths)):
+                raise ValueError(f"synthesis_regression_duration: y0 must hold one [T, {d['dim_out']}] per utterance")
+        tv = torch.rand(n) if times is None else torch.tensor([float(t) for t in times], dtype=torch.float64).to(torch.float32)
+        if tv.numel() != n or not bool(((tv >= 0) & (tv <= 1)).all()):
+            raise ValueError("synthesis_regression_duration: one time in [0, 1] per utterance")
+        s = float(cond_scale)
+        use_null = s != 1.0
+        if n * (2 if use_null else 1) > ops.SEQ_NORM_MAX_SEQS:      # (the null branch doubles the sequences of the one evaluation)
+            raise ValueError(f"synthesis_regression_duration: {n} utterances in one call, at most {ops.SEQ_NORM_MAX_SEQS // (2 if use_null else 1)}"
+                             f"{' under guidance (cond_scale != 1)' if use_null else ''}")
+
+        def run(field):
+            dev = field.device
+            ids_p = torch.cat([p.to(device=dev, dtype=torch.int64) for p in idsl]).contiguous()
+            cond_p = torch.cat([c.to(device=dev, dtype=torch.float32) for c in conds]).contiguous()
+            y = torch.cat([t.to(device=dev, dtype=torch.float32) for t in y0l]).contiguous()
+            pred = field.evaluate_seq_times(ids_p, cond_p, y, ops.h2d(tv, dev), lengths, use_null=use_null)
+            M1 = y.shape[0]
+            if not use_null:
+                return pred[:M1].clone()
+            out = torch.empty_like(y)
+            ops.cfg_combine_axpy(pred[:M1], pred[M1:], torch.zeros_like(y), s, 1.0, out)      # 0 + 1 * (f_c (1 + s) - s f_null)
+            return out
+        out = self._run_unsaturated(run)
+        ref = conds[0]
+        outs = [o.to(ref.device) if ref.device != o.device else o for o in torch.split(out, lengths)]
+        return outs if many else torch.stack(outs)
+
     @ops.gated
     @torch.no_grad()
     def score_text2semantic(self, grapheme_token_ids, streams, cond_scale=1.0, mixed_guidance=False, prefill=False):

@@ -706,7 +706,8 @@ class Ragged:
         for t in self.lengths:
             cu.append(cu[-1] + t)
         self.cu_host = cu
-        self.cu = h2d(torch.tensor(cu, dtype=torch.int32), device)
+        self.cu_host_i32 = torch.tensor(cu, dtype=torch.int32)      # the host table of the entry points that validate one (adarmsnorm_seq, ...)
+        self.cu = h2d(self.cu_host_i32, device)
 
     def positions(self) -> torch.Tensor:
         """Position of every packed row inside its own sequence (fp32, on the device)."""
@@ -1728,3 +1729,164 @@ def dtw(features, pairs, device=None) -> tuple:
                    "cvx_dtw_f32")
         host = out.cpu()
         return host[:n_pairs].view(torch.float32).clone(), host[n_pairs:].clone()
+
+
+SEQ_NORM_MAX_SEQS = _lib.SEQ_NORM_MAX_SEQS      # sequences of a packed batch with a time per sequence (CVX_SEQ_NORM_MAX_SEQS)
+MASKED_MSE_BLOCK = 256                          # rows one thread of cvx_masked_mse_f32's sequence block strides by
+
+
+def masked_mse_tree_depth(T: int) -> int:
+    """Rounded additions above any term of a sequence sum of masked_mse: ceil(T / 256) in a thread, 6 in the wave, 2 across the waves."""
+    return (max(int(T), 1) + MASKED_MSE_BLOCK - 1) // MASKED_MSE_BLOCK + 8
+
+
+def seq_offsets(seqs, rows: int, what: str = "seq_offsets") -> tuple:
+    """The host table of the per-sequence kernels: `seqs` is a Ragged or a sequence of n + 1 row offsets -> (int32 tensor [n + 1], n).
+    ValueError: fewer than one or more than SEQ_NORM_MAX_SEQS sequences, a negative or decreasing offset, an end behind `rows`."""
+    cu = list(seqs.cu_host) if isinstance(seqs, Ragged) else [x for x in seqs]
+    if any(isinstance(x, bool) or not isinstance(x, int) for x in cu):
+        raise ValueError(f"{what}: row offsets must be python ints")
+    n = len(cu) - 1
+    if not 1 <= n <= SEQ_NORM_MAX_SEQS:
+        raise ValueError(f"{what}: {n} sequences (1 ... {SEQ_NORM_MAX_SEQS})")
+    if cu[0] < 0 or any(b < a for a, b in zip(cu, cu[1:])):
+        raise ValueError(f"{what}: row offsets must start at 0 or above and never decrease")
+    if cu[-1] > rows or rows >= 1 << 31:
+        raise ValueError(f"{what}: the sequences end at row {cu[-1]} of {rows} (fewer than 2^31)")
+    return torch.tensor(cu, dtype=torch.int32), n
+
+
+def _seq_host(seqs, rows: int, what: str) -> tuple:
+    """(host int32 [n + 1], n) of a Ragged (its own table) or of n + 1 offsets, validated against `rows`"""
+    if not isinstance(seqs, Ragged):
+        return seq_offsets(seqs, rows, what)
+    if not 1 <= seqs.n <= SEQ_NORM_MAX_SEQS:
+        raise ValueError(f"{what}: {seqs.n} sequences (1 ... {SEQ_NORM_MAX_SEQS})")
+    if seqs.cu_host[-1] > rows or rows >= 1 << 31:
+        raise ValueError(f"{what}: the sequences end at row {seqs.cu_host[-1]} of {rows} (fewer than 2^31)")
+    return seqs.cu_host_i32, seqs.n
+
+
+def _seq_dev(seqs, host: torch.Tensor, device, what: str) -> torch.Tensor:
+    """the device copy of the table (a Ragged brings its own, which must live with the rows); called last, when every check has passed"""
+    if torch.device(device).type != "cuda" or not torch.cuda.is_available():
+        raise _lib.CovomixHipError(f"{what} needs a GPU: covomix_amd has no CPU path")
+    if not isinstance(seqs, Ragged):
+        return h2d(host, device)
+    if seqs.cu.device != torch.device(device):
+        raise ValueError(f"{what}: the Ragged's offsets are on {seqs.cu.device}, the rows on {device}")
+    return seqs.cu
+
+
+def _rows_f32(t, what: str, width=None):
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 2 or not t.is_contiguous():
+        raise TypeError(f"{what} must be a contiguous 2-D float32 tensor")
+    if width is not None and t.shape[1] != width:
+        raise ValueError(f"{what} has {t.shape[1]} columns, {width} are needed")
+    if t.data_ptr() % 16:
+        raise ValueError(f"{what} must be 16-byte aligned")
+    return t
+
+
+def adarmsnorm_seq(x: torch.Tensor, gamma: torch.Tensor, beta: Optional[torch.Tensor], out: Optional[torch.Tensor], seqs,
+                   eps: float = 1e-12, out_split=None, split_scale=None):
+    """ops.adarmsnorm with ONE gamma / beta row PER SEQUENCE of a packed batch (cvx_adarmsnorm_seq_f32): x [rows, D]; `seqs` a Ragged
+    or n + 1 row offsets; gamma, beta [n, D] fp32 with unit column stride and ANY row stride >= D that is a multiple of 4 (both the
+    same: views into one [n, depth, 4, D] table).  Rows outside the sequences are not touched.  A sequence's rows are bit-identical to
+    adarmsnorm on its slice with its row.  TypeError / ValueError before anything is launched, the outputs untouched."""
+    _rows_f32(x, "adarmsnorm_seq: x")
+    rows, D = x.shape
+    if D % 4:
+        raise ValueError(f"adarmsnorm_seq: D = {D} is no multiple of 4")
+    host, n = _seq_host(seqs, rows, "adarmsnorm_seq")
+    for name, t in (("gamma", gamma), ("beta", beta)):
+        if t is None and name == "beta":
+            continue
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 2 or tuple(t.shape) != (n, D) or t.stride(1) != 1:
+            raise ValueError(f"adarmsnorm_seq: {name} must be float32 [{n}, {D}] with unit column stride")
+        if t.data_ptr() % 16 or (n > 1 and (t.stride(0) < D or t.stride(0) % 4)):
+            raise ValueError(f"adarmsnorm_seq: {name} must be 16-byte aligned with a row stride >= D that is a multiple of 4")
+    stride = gamma.stride(0) if n > 1 else D
+    if beta is not None and n > 1 and beta.stride(0) != stride:
+        raise ValueError("adarmsnorm_seq: gamma and beta must have the same row stride")
+    if out is None and out_split is None:
+        raise ValueError("adarmsnorm_seq: no output")
+    if out is not None:
+        _rows_f32(out, "adarmsnorm_seq: out", D)
+        if out.shape[0] != rows:
+            raise ValueError("adarmsnorm_seq: out must have the rows of x")
+    dev = _seq_dev(seqs, host, x.device, "adarmsnorm_seq")
+    oh, ol = (None, None)
+    if out_split is not None:
+        ensure_saturation_bound()
+        oh, ol, ld = _pair(out_split, rows if isinstance(out_split, SplitIL) else None, D)
+        assert isinstance(out_split, SplitIL) or (out_split[0].is_contiguous() and out_split[0].numel() == x.numel())
+        assert not isinstance(out_split, SplitIL) or ld == 2 * D, "adarmsnorm_seq: no row stride (a SplitIL view into a wider buffer)"
+    _lib.check(_lib.load().cvx_adarmsnorm_seq_f32(x.data_ptr(), gamma.data_ptr(), _p(beta), _p(out), oh, ol, rows, D, host.data_ptr(),
+                                                  dev.data_ptr(), n, stride, float(D) ** 0.5, eps, _sp(split_scale), _stream()),
+               "cvx_adarmsnorm_seq_f32")
+    return out if out is not None else out_split
+
+
+def cfm_inputs(x1: torch.Tensor, x0: torch.Tensor, cond: torch.Tensor, mask: torch.Tensor, times: torch.Tensor, seqs, sigma: float,
+               w: torch.Tensor, flow: Optional[torch.Tensor] = None, cond_in: Optional[torch.Tensor] = None) -> tuple:
+    """The inputs of the flow-matching loss evaluation in one launch (cvx_cfm_inputs_f32): with t = times[sequence of the row],
+    w = (1 - (1 - sigma) t) x0 + t x1, flow = x1 - (1 - sigma) x0, cond_in = cond with the rows of mask zeroed - individually rounded
+    fp32 operations in that order.  x1, x0, w, flow [rows, dim_out]; cond, cond_in [rows, C]; mask bool / uint8 [rows]; times fp32 [n]
+    on the device.  -> (w, flow, cond_in).  TypeError / ValueError before anything is launched, the outputs untouched."""
+    _rows_f32(x1, "cfm_inputs: x1")
+    rows, dim_out = x1.shape
+    _rows_f32(x0, "cfm_inputs: x0", dim_out), _rows_f32(cond, "cfm_inputs: cond"), _rows_f32(w, "cfm_inputs: w", dim_out)
+    C = cond.shape[1]
+    if dim_out % 4 or C % 4 or dim_out < 4 or C < 4:
+        raise ValueError(f"cfm_inputs: widths {dim_out} and {C} must be positive multiples of 4")
+    if not isinstance(mask, torch.Tensor) or mask.dtype not in (torch.bool, torch.uint8) or mask.dim() != 1 or not mask.is_contiguous():
+        raise TypeError("cfm_inputs: mask must be a contiguous bool or uint8 tensor [rows]")
+    if not isinstance(times, torch.Tensor) or times.dtype != torch.float32 or times.dim() != 1 or not times.is_contiguous():
+        raise TypeError("cfm_inputs: times must be a contiguous float32 tensor [sequences]")
+    if not (isinstance(sigma, (int, float)) and 0.0 <= float(sigma) <= 1.0):
+        raise ValueError(f"cfm_inputs: sigma = {sigma!r} outside [0, 1]")
+    host, n = _seq_host(seqs, rows, "cfm_inputs")
+    if times.shape[0] != n:
+        raise ValueError(f"cfm_inputs: {times.shape[0]} times for {n} sequences")
+    if any(t.shape[0] != rows for t in (x0, cond, w, mask)):
+        raise ValueError("cfm_inputs: x0, cond, mask and w must have the rows of x1")
+    flow = torch.empty_like(x1) if flow is None else _rows_f32(flow, "cfm_inputs: flow", dim_out)
+    cond_in = torch.empty_like(cond) if cond_in is None else _rows_f32(cond_in, "cfm_inputs: cond_in", C)
+    if flow.shape[0] != rows or cond_in.shape[0] != rows:
+        raise ValueError("cfm_inputs: flow and cond_in must have the rows of x1")
+    if len({t.device for t in (x1, x0, cond, mask, times, w, flow, cond_in)}) != 1:
+        raise ValueError("cfm_inputs: every tensor must be on the same device")
+    dev = _seq_dev(seqs, host, x1.device, "cfm_inputs")
+    _lib.check(_lib.load().cvx_cfm_inputs_f32(x1.data_ptr(), x0.data_ptr(), cond.data_ptr(), mask.data_ptr(), times.data_ptr(), host.data_ptr(),
+                                              dev.data_ptr(), n, rows, dim_out, C, float(sigma), w.data_ptr(), flow.data_ptr(),
+                                              cond_in.data_ptr(), _stream()), "cvx_cfm_inputs_f32")
+    return w, flow, cond_in
+
+
+def masked_mse(pred: torch.Tensor, flow: torch.Tensor, mask: torch.Tensor, seqs, err_rows: Optional[torch.Tensor] = None) -> tuple:
+    """The masked mean-squared error per sequence (cvx_masked_mse_f32; reference acoustic.py:527-536): err_rows[r] = mean_d (pred - flow)^2,
+    loss[s] = (sum of err_rows over the sequence's masked rows) / max(count[s], 1e-5), count[s] = its masked rows; fixed summation
+    orders (masked_mse_tree_depth).  pred, flow [rows, dim_out]; mask bool / uint8 [rows].  -> (loss fp32 [n], count int32 [n],
+    err_rows fp32 [rows]) on the device; err_rows is written for the rows of the sequences only (a fresh one is zero elsewhere).
+    TypeError / ValueError before anything is launched."""
+    _rows_f32(pred, "masked_mse: pred")
+    rows, dim_out = pred.shape
+    _rows_f32(flow, "masked_mse: flow", dim_out)
+    if not isinstance(mask, torch.Tensor) or mask.dtype not in (torch.bool, torch.uint8) or mask.dim() != 1 or not mask.is_contiguous():
+        raise TypeError("masked_mse: mask must be a contiguous bool or uint8 tensor [rows]")
+    if flow.shape[0] != rows or mask.shape[0] != rows:
+        raise ValueError("masked_mse: flow and mask must have the rows of pred")
+    host, n = _seq_host(seqs, rows, "masked_mse")
+    if err_rows is None:
+        err_rows = torch.zeros(rows, dtype=torch.float32, device=pred.device)
+    elif not isinstance(err_rows, torch.Tensor) or err_rows.dtype != torch.float32 or tuple(err_rows.shape) != (rows,) or not err_rows.is_contiguous():
+        raise ValueError("masked_mse: err_rows must be a contiguous float32 tensor [rows]")
+    if len({t.device for t in (pred, flow, mask, err_rows)}) != 1:
+        raise ValueError("masked_mse: every tensor must be on the same device")
+    dev = _seq_dev(seqs, host, pred.device, "masked_mse")
+    loss = torch.empty(n, dtype=torch.float32, device=pred.device)
+    count = torch.empty(n, dtype=torch.int32, device=pred.device)
+    _lib.check(_lib.load().cvx_masked_mse_f32(pred.data_ptr(), flow.data_ptr(), mask.data_ptr(), host.data_ptr(), dev.data_ptr(), n, rows, dim_out,
+                                              err_rows.data_ptr(), loss.data_ptr(), count.data_ptr(), _stream()), "cvx_masked_mse_f32")
+    return loss, count, err_rows
